@@ -8,16 +8,22 @@
 
 One step = forward + backward + (RCCL gradient all-reduce) + TF-Adam of train_deep_sentiment on a
 synthetic batch resident in HBM: 224x224x3 images + 32-token posts, Inception-v1 + 300-d embedding +
-LSTM-512, batch 256 per GPU (BASELINE cfg3; weak scaling under data parallelism -- a multi-rank run ALSO times the
+LSTM-512, batch 256 per GPU (BASELINE cfg3; weak scaling under data parallelism -- with --full a multi-rank run ALSO times the
 strong-scaling point BASELINE configs[3] names, global batch 256 split over the ranks, and reports it in the same JSON line
 as `strong_scaling`), fp32 arithmetic
 (the precision the 1e-3 parity gate is stated in), dropout and BatchNorm in train mode, reference
 freeze (conv weights below Mixed_5c frozen, every BatchNorm beta trainable).
 
-Prints ONE JSON line (rank 0) carrying `roofline` for the dominant kernel (the implicit-GEMM fp32
-MFMA conv/GEMM kernel, timed live with HIP events around every launch on its stream, in a second pass
-of the same K steps so that the event records do not slow the headline pass) and
-`cpu_baseline` (the PyTorch-CPU oracle timed on this box's host cores on a bounded sample; N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and reports the headline
+(`value`, `ms_per_step`); everything else it can measure is taken only with --full:
+`roofline` for the dominant kernel (the implicit-GEMM fp32 MFMA conv/GEMM kernel, timed live with HIP events around
+every launch on its stream, in a second pass of the same K steps so that the event records do not slow the headline
+pass), `gather` (embedding-gather bandwidth), `cpu_baseline` (the PyTorch-CPU oracle timed on the host cores on a
+bounded sample; N=1 only), and with data parallelism the `dp` overlap report and the `strong_scaling` point.
+
+--dump-outputs DIR writes what the last timed step computed (logits, loss, the trainable variables after the update,
+the BatchNorm moving statistics) as DIR/<name>.npy, so that two builds can be compared output for output on the same
+seeded inputs.
 """
 import argparse
 import json
@@ -314,6 +320,43 @@ def pmc_traffic(args):
     return round(d["hbm_bytes_per_launch"]), os.path.relpath(files[-1], ROOT)
 
 
+DUMP_LIMIT_BYTES = (64 << 20) - (64 << 10)       # 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(out_dir, net, ce, total_loss):
+    """What a caller of the timed step receives after the last timed step, as <out_dir>/<name>.npy:
+      logits        [B, classes] float32 (this rank's shard)
+      loss          [1] float32, the cross entropy train_step returned; total_loss [1] float64, CE + L2 (final_loss)
+      trainable     float32, every trainable variable after the Adam update, TF names in sorted order, concatenated
+      moving_stats  float32, every BatchNorm moving mean / variance after the step, same order (image tower only)
+    Under the reference freeze this is about 14 MB; should an array not fit the 64 MB left to it, a fixed seeded sample of
+    its elements (ascending indices, RandomState(0)) is written instead."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sd = net.state_dict()
+    trainable = set()
+    for e in net.store.entries.values():
+        if e.trainable:
+            trainable.update([n for (n, _, _) in e.columns] if e.columns else [e.name])
+    names = sorted(sd)
+    stats = [n for n in names if n.endswith(("/moving_mean", "/moving_variance"))]
+    arrays = [
+        ("logits", net.logits.detach().float().cpu().numpy()),
+        ("loss", np.asarray([float(ce.detach())], np.float32)),
+        ("total_loss", np.asarray([total_loss], np.float64)),
+        ("trainable", np.concatenate([sd[n].reshape(-1) for n in names if n in trainable]).astype(np.float32)),
+    ]
+    if stats:
+        arrays.append(("moving_stats", np.concatenate([sd[n].reshape(-1) for n in stats]).astype(np.float32)))
+    left = DUMP_LIMIT_BYTES
+    for name, a in sorted(arrays, key=lambda kv: kv[1].nbytes):
+        if a.nbytes > left:
+            k = left // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -371,11 +414,17 @@ def main():
                     help="A/B aid: text tower on the main stream instead of concurrently with the image tower")
     ap.add_argument("--rccl-world1", action="store_true",
                     help="--gpus 1 only: initialise the nccl (= RCCL) backend with ONE rank and take the bucketed all-reduce path "
-                         "(early bucket 1 on the side stream, async work handle) exactly as a multi-GPU run does; prints the `dp` "
-                         "block.  What a 1-GPU box can show of the 8-GPU code path")
+                         "(early bucket 1 on the side stream, async work handle) exactly as a multi-GPU run does; with --full "
+                         "prints the `dp` block.  What a 1-GPU box can show of the 8-GPU code path")
     ap.add_argument("--no-overlap-comm", action="store_true",
                     help="data parallel A/B: both gradient buckets all-reduced after the backward pass on the main stream "
                          "(default: bucket 1 launched early on a side stream, under the Inception backward)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements after the headline: the roofline timing pass (with live "
+                         "rocprofv3 traffic), the gather bandwidth, the CPU baseline and, with data parallelism, the overlap "
+                         "report and the strong-scaling point (the --no-* options below switch single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--cpu-warmup", type=int, default=3)
@@ -384,6 +433,8 @@ def main():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic from the committed profile instead of two rocprofv3 --pmc sub-runs (about 40 s)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N` (how the driver starts the N = 1 bench): become the N-rank job
@@ -487,7 +538,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        net.train_step(batch, lr)
+        ce = net.train_step(batch, lr)
     t_enq = time.perf_counter() - t0          # host time to ENQUEUE the K steps (the GPU runs behind it)
     barrier()
     dt = time.perf_counter() - t0
@@ -496,8 +547,10 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     loss = net.total_loss_value()
+    if args.dump_outputs and rank == 0:      # before any --full pass steps the model further
+        dump_outputs(args.dump_outputs, net, ce, loss)
     dp_report = None
-    if world > 1 or force_dp:          # two more steps with event pairs around the early bucket-1 reduce (not in the timed region)
+    if args.full and (world > 1 or force_dp):          # two more steps with event pairs around the early bucket-1 reduce (not in the timed region)
         net.reducer.timing = True
         for _ in range(2):
             net.train_step(batch, lr)
@@ -515,7 +568,7 @@ def main():
     if graphed:
         net.release_graph()      # the roofline passes time individual launches: eager
     in_situ = None
-    if not args.no_conv_timing:
+    if args.full and not args.no_conv_timing:
         # Event-bracketed launch times are a kernel's own duration only when nothing else is queued beside it: the
         # timing pass therefore issues the Mixed-block branches on ONE stream (the headline pass runs Branch_2 /
         # Branch_3 on side streams, where a launch's bracket also contains the time it waited for CUs).  The
@@ -558,14 +611,14 @@ def main():
         net.text_stream = side
         n2, ms2, fl2 = t2.summary()
         isolated = round(fl2 / (ms2 * 1e-3) / 1e12, 2)
-    if not args.no_conv_timing and net.image is not None and not args.no_branch_streams:
+    if args.full and not args.no_conv_timing and net.image is not None and not args.no_branch_streams:
         net.image.branch_streams = True
 
     # BASELINE configs[3] names a GLOBAL batch of 256 split over the GPUs (strong scaling); the headline above keeps 256 per
-    # GPU (weak scaling, the contract's `value`).  A multi-rank run therefore times BOTH in one invocation: the same model
+    # GPU (weak scaling, the contract's `value`).  With --full a multi-rank run therefore times BOTH in one invocation: the same model
     # re-allocated at 256 / world samples per rank, W warm-up + K timed steps bracketed like the headline, its own `dp` block.
     strong_block = None
-    if world > 1 and not strong and 256 % world == 0 and os.environ.get("DS_BENCH_NO_STRONG") != "1":
+    if args.full and world > 1 and not strong and 256 % world == 0 and os.environ.get("DS_BENCH_NO_STRONG") != "1":
         sb_n = 256 // world
         sbatch = to_device(synthetic_batch_numpy(256, T, V, 15, seed=0, with_images=args.mode != "text"), "cuda", rank, world)
         for _ in range(args.warmup):
@@ -658,9 +711,9 @@ def main():
             "conv_arithmetic": conv_arithmetic(net),
             "dp": dp_report,
             "strong_scaling": strong_block,
-            "gather": gather_bandwidth() if (args.mode != "image" and not args.no_gather) else None,
+            "gather": gather_bandwidth() if (args.full and args.mode != "image" and not args.no_gather) else None,
         }
-        if world == 1 and not args.no_cpu_baseline and args.mode == "joint" and not args.train_all:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "joint" and not args.train_all:
             out["cpu_baseline"] = cpu_baseline(T, V, D, H, args.cpu_warmup, args.cpu_steps)
         else:
             out["cpu_baseline"] = None
