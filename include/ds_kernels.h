@@ -274,6 +274,13 @@ int ds_conv_stem_pool(const float *x, const float *w, float *zmax, float *stats,
 /* ... of ds_conv_stem_bf16 (the 16-bit configurations: operands rounded to bf16, bf16 MFMA; zmax and the sums stay fp32) */
 int ds_conv_stem_pool_bf16(const float *x, const float *w, float *zmax, float *stats, const float *pivot, int32_t N, int32_t H,
                            int32_t W, int32_t cin_store, int32_t Cout, int32_t ldz, void *stream);
+/* Conv2DBackpropInput of Conv2d_1a_7x7: dx [N, H, W, 3] (packed like the images) = the gradient of the stem's input from
+ * dz [N, OH, OW, 64] (pixel stride ldx: a multiple of 4, 16-byte aligned pixels), w = the same HWIO store as ds_conv_stem
+ * (cin_store 3 or 4; the 4th channel is never read), TF SAME geometry as the forward.  fp32, one lane per dx element: the
+ * result is bit-reproducible.  ds_conv_stem_dgrad_supported(H, W): 1 for every image size the forward accepts.       */
+int ds_conv_stem_dgrad_supported(int32_t H, int32_t W);
+int ds_conv_stem_dgrad(const float *dz, const float *w, float *dx, int32_t N, int32_t H, int32_t W, int32_t cin_store,
+                       int32_t ldx, void *stream);
 /* ds_conv_stem for the 16-bit configurations: x and w rounded to bf16 (RNE) as they are packed, v_mfma_f32_32x32x16_bf16 with fp32
  * accumulation (two kernel rows per three MFMAs: 11 instead of 84 per accumulator); same arguments and layout; stats as
  * float[2][64][ds_conv_stem_bf16_partials(N, OH, OW)]. */
@@ -351,7 +358,7 @@ int ds_conv_wino4_bf16x2_x16(const void *x16, const void *u2, float *z, float *s
  * calls.  The family-level entry points above stay exported for kernel tests and tuning scripts; the engine of this
  * build calls only these (tests/test_abi_cpu.py checks that).
  *   ds_conv_plan             fills a caller-owned plan (plain data, no allocation): role DS_CONV_FWD or DS_CONV_DGRAD
- *                            (stride-1 SAME convs), arithmetic DS_ARITH_*, N / H / W of the layer INPUT, the filter's own
+ *                            (stride-1 SAME convs, and the stride-2 stem with DS_PLAN_PACKED_RGB), arithmetic DS_ARITH_*, N / H / W of the layer INPUT, the filter's own
  *                            channel counts and size k, pixel strides of x and z, epilogue flags (DS_EPI_*).
  *   ds_conv_plan_set_flags   changes the epilogue flags of a plan, returns its new partial count
  *   ds_conv_plan_enable_bnsums   dgrad whose result feeds a BatchNorm + ReLU backward: adds DS_EPI_BNSUMS (y with pixel
@@ -384,6 +391,8 @@ int ds_conv_wino4_bf16x2_x16(const void *x16, const void *u2, float *z, float *s
 #define DS_FAM_F32X3 6
 #define DS_FAM_WINO4H 7        /* ds_conv_wino4_bf16x2: F(4x4, 3x3) of the bf16-rounded operands on the bf16 matrix cores */
 #define DS_FAM_STEM_POOL 8     /* ds_conv_stem_pool: the stem with MaxPool_2a inside (z of ds_conv_run = the pooled maxima)  */
+#define DS_FAM_STEM_DGRAD 9    /* ds_conv_stem_dgrad: the stem's input gradient (DS_CONV_DGRAD | DS_PLAN_PACKED_RGB, stride 2,
+                                  fp32, no epilogue; x of ds_conv_run = dz with pixel stride ldx, z = dx with ldz 3)          */
 #define DS_PLAN_NO_WINO 1u          /* A/B: implicit GEMM for every 3x3 layer                                           */
 #define DS_PLAN_NO_WINO4 2u         /* A/B: F(2x2) wherever Winograd applies                                            */
 #define DS_PLAN_NO_STEM_DIRECT 4u   /* A/B: the stem through the generic kernel on a 4-channel copy of the batch        */

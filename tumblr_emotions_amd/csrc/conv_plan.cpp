@@ -68,10 +68,36 @@ extern "C" int ds_conv_plan(ds_conv_layer_plan *out, int32_t role, int32_t arith
     PLAN_REQUIRE(role == DS_CONV_FWD || role == DS_CONV_DGRAD, "ds_conv_plan: role %d", role);
     PLAN_REQUIRE(arith >= DS_ARITH_F32 && arith <= DS_ARITH_F32X3, "ds_conv_plan: arithmetic %d", arith);
     PLAN_REQUIRE(N > 0 && H > 0 && W > 0 && w_cin > 0 && w_cout > 0 && k > 0 && stride > 0, "ds_conv_plan: geometry");
-    PLAN_REQUIRE(role == DS_CONV_FWD || stride == 1, "ds_conv_plan: Conv2DBackpropInput is built for stride-1 SAME convs");
     const bool stem = (options & DS_PLAN_PACKED_RGB) != 0;      // Conv2d_1a_7x7: x is the packed [N, H, W, 3] batch
-    PLAN_REQUIRE(!stem || (role == DS_CONV_FWD && k == 7 && (w_cin == 3 || w_cin == 4)),
+    PLAN_REQUIRE(role == DS_CONV_FWD || stride == 1 || stem,
+                 "ds_conv_plan: Conv2DBackpropInput is built for stride-1 SAME convs and the packed-RGB stem");
+    PLAN_REQUIRE(!stem || (k == 7 && (w_cin == 3 || w_cin == 4)),
                  "ds_conv_plan: DS_PLAN_PACKED_RGB is the 7x7 stem (filter stored with 3 or 4 input channels)");
+    if (stem && role == DS_CONV_DGRAD) {
+        // the stem's input gradient dx [N, H, W, 3] (packed like the images) from dz [N, OH, OW, 64] with pixel stride ldx:
+        // ds_conv_stem_dgrad, fp32 only, no epilogue; it reads the HWIO filter in place
+        PLAN_REQUIRE(stride == 2 && w_cout == 64 && arith == DS_ARITH_F32 && flags == 0 && ds_conv_stem_dgrad_supported(H, W),
+                     "ds_conv_plan: the stem's Conv2DBackpropInput is the fp32 7x7 / 2 conv into 64 channels, no epilogue");
+        memset(out, 0, sizeof(*out));
+        out->role = role;
+        out->arith = arith;
+        out->k = k;
+        out->w_cin = w_cin;
+        out->w_cout = w_cout;
+        out->family = DS_FAM_STEM_DGRAD;
+        out->splitk = 1;
+        ds_conv_desc &d = out->d;
+        d.N = N; d.H = H; d.W = W;
+        d.stride = stride;
+        d.Cin = w_cout; d.Cout = 3; d.KH = 7; d.KW = 7; d.flip = 1;
+        d.ldx = ldx; d.ldz = ldz;
+        d.splits = 1;
+        d.dtype = DS_DTYPE_F32;
+        same_pad(H, 7, stride, &d.OH, &d.pad_t);
+        same_pad(W, 7, stride, &d.OW, &d.pad_l);
+        out->alg_flops = 2.0 * N * d.OH * d.OW * w_cout * 147.0;      // the forward's
+        return DS_OK;
+    }
     memset(out, 0, sizeof(*out));
     out->role = role;
     out->arith = arith;
@@ -313,6 +339,9 @@ extern "C" int ds_conv_run(const ds_conv_layer_plan *p, const void *x, const voi
         return (d.dtype == DS_DTYPE_BF16 ? ds_conv_stem_pool_bf16 : ds_conv_stem_pool)(
             (const float *)x, (const float *)w, z, (d.flags & DS_EPI_STATS) ? io->stats : nullptr, io->pivot, d.N, d.H, d.W, p->w_cin,
             d.Cout, d.ldz, stream);
+    case DS_FAM_STEM_DGRAD:
+        PLAN_REQUIRE(d.ldz == 3, "ds_conv_run: the stem's input gradient is written packed (ldz 3)");
+        return ds_conv_stem_dgrad((const float *)x, (const float *)w, z, d.N, d.H, d.W, p->w_cin, d.ldx, stream);
     case DS_FAM_BF16D: return ds_conv_bf16(&d, x, w, z, io->mask, io->stats, io->pivot, stream);
     case DS_FAM_F32X3: return ds_conv_f32x3(&d, (const float *)x, w, z, io->mask, io->stats, io->pivot, stream);
     case DS_FAM_FP8D:

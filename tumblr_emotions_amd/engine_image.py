@@ -325,9 +325,16 @@ class ConvBN:
     def make_dgrad(self, lddx, allow_z16=False):
         """Conv2DBackpropInput as a forward conv over dz with flipped taps (stride-1 SAME convs only); the library picks
         the kernel family for the swapped shape.  allow_z16: the caller's forward / backward use of this layer's z goes through
-        ds_bn_apply_relu / ds_bn_bwd_reduce / ds_bn_bwd_apply only (the plain layers of a Mixed block), so z may live in bf16."""
-        assert self.stride == 1
+        ds_bn_apply_relu / ds_bn_bwd_reduce / ds_bn_bwd_apply only (the plain layers of a Mixed block), so z may live in bf16.
+        The stem (input gradients only, InceptionV1Engine.input_backward): the gradient of the packed RGB images, fp32."""
         eng = self.eng
+        if self.fold:
+            if eng.dtype != "f32":
+                raise NotImplementedError("input gradients are implemented for the fp32 configuration only")
+            self.dgrad = ops.LayerPlan(ops.DS_CONV_DGRAD, ops.DS_ARITH_F32, ops.DS_PLAN_PACKED_RGB, self.B, self.H, self.W, 4,
+                                       self.cout, self.k, self.stride, self.ldz, lddx, 0)
+            return
+        assert self.stride == 1
         self.dgrad = ops.LayerPlan(ops.DS_CONV_DGRAD, eng.arith, eng.plan_options(), self.B, self.H, self.W, self.cin,
                                    self.cout, self.k, 1, self.ldz, lddx, 0)
         self.dgrad.alloc_weights(eng.device)
@@ -548,6 +555,7 @@ class InputStage(Stage):
 
     def alloc(self, B):
         self.out = torch.zeros(B, self.H, self.W, 4, device=self.eng.device)
+        self.dout = None          # InceptionV1Engine.input_backward: the caller's [B, H, W, 3] image gradient
 
 
 class ConvStage(Stage):
@@ -568,9 +576,7 @@ class ConvStage(Stage):
         nxt = getattr(self, "next", None)
         # Conv2d_1a_7x7 -> MaxPool_2a_3x3 in one kernel (ds_conv_stem_pool / _bf16): a frozen stem whose BatchNorm + ReLU run
         # behind the pool anyway (fuse_bn_pool); its backward sums come from the pooled tensors (PoolStage.alloc)
-        self.layer.pool_inside = bool(self.layer.fold and eng.stem_pool and eng.stem_direct and eng.fuse_bn_pool
-                                      and not eng.mul3 and not self.layer.trainable
-                                      and isinstance(nxt, PoolStage) and nxt.k == 3 and nxt.stride == 2)
+        self.layer.pool_inside = self.pool_inside_wanted()
         self.layer.alloc(B)
         self.out16 = self.eng.act16 and not self.layer.fold       # Conv2d_2b / 2c (the stem's output is read by hip tests only)
         self.out = torch.empty(B, self.H, self.W, self.C, device=dev, dtype=torch.bfloat16 if self.out16 else torch.float32)
@@ -605,6 +611,14 @@ class ConvStage(Stage):
                     stem.part_sums[0] = (src[0], src[1], 0, self.prev.C)
                     stem._sum_segs = None
 
+    def pool_inside_wanted(self):
+        """The stem with MaxPool_2a inside its kernel -- not while input gradients are wanted: BatchNorm's backward then needs
+        the full-resolution z (its mean terms make dz dense), which only the unpooled stem writes."""
+        eng, nxt = self.eng, getattr(self, "next", None)
+        return bool(self.layer.fold and eng.stem_pool and eng.stem_direct and eng.fuse_bn_pool and not eng.input_grad
+                    and not eng.mul3 and not self.layer.trainable
+                    and isinstance(nxt, PoolStage) and nxt.k == 3 and nxt.stride == 2)
+
     def forward(self):
         # fused_into_pool: this conv feeds nothing but the next max pool, which then reads z and applies BN + ReLU
         # after pooling (a quarter of the elements); `out` is not produced
@@ -612,7 +626,7 @@ class ConvStage(Stage):
                            ops.act_dtype(self.prev.out), getattr(self.prev, "out_amax", None))
 
     def backward(self, need_dx):
-        need_dx = need_dx and not self.layer.fold
+        need_dx = need_dx and (not self.layer.fold or self.eng.input_grad)      # (the stem: the image gradient, input_backward)
         dx = ops._p(self.prev.dout) if need_dx else None
         if self.fused_into_pool and self.pool.stride == 2:
             self.layer.backward_pooled(self.pool, ops._p(self.prev.out), self.prev.C, dx, need_dx)
@@ -1208,6 +1222,11 @@ class InceptionV1Engine:
         self.text_gate = int(e) if e else None
         self.text_gate_event = None
         self.weights_version = 0     # bumped by SentimentNet.after_load(): frozen layers redo their G g G^T
+        # input gradients wanted (forward(input_grad=True) .. the next plain forward): the stem runs unpooled (ConvStage.alloc);
+        # _pivots keeps the statistics pivots of the training state that was left, so the next training step is unchanged
+        self.input_grad = False
+        self._pivots = None
+        self._restore_pivots = None
         self._stats_n = self._bwdp_n = self._ws_bytes = 0
         self.B = None
         self.input = InputStage(self, image_size)
@@ -1377,11 +1396,38 @@ class InceptionV1Engine:
         self.gb_fc = st.grad_view(self.lg + "/biases")
 
     # ------------------------------------------------------------------------------------------
-    def forward(self, images, dropout_mask=None, seed=0):
+    def _set_input_grad(self, on):
+        """Enter / leave the input-gradient layout.  Entering keeps the BatchNorm statistics pivots (each layer's `mean`: the
+        last training batch's means) and re-allocates if the stem has to leave the pooled kernel; leaving re-allocates (the
+        training layout, as a net that never left it would have it) and puts the pivots back if the batch size is theirs."""
+        if on == self.input_grad:
+            return
+        if on:
+            self._pivots = (self.B, [l.mean.clone() for l in self.layers]) if self.B is not None else None
+            self.input_grad = True
+            if self.B is not None and self.stages[0].layer.pool_inside:
+                self.B = None
+        else:
+            self.input_grad = False
+            self._restore_pivots, self._pivots = self._pivots, None
+            self.B = None
+
+    def forward(self, images, dropout_mask=None, seed=0, input_grad=False):
         """images: [B,224,224,3] fp32 NHWC in [-1,1] (preprocess_for_eval range).  Returns the
-        internal logits buffer [B,num_classes]."""
+        internal logits buffer [B,num_classes].  input_grad: the pass input_backward() differentiates (unpooled stem)."""
         B = images.shape[0]
+        self._set_input_grad(input_grad)
         self.alloc(B)
+        if self._restore_pivots is not None:
+            pB, pivots = self._restore_pivots
+            self._restore_pivots = None
+            if pB == B:
+                for l, m in zip(self.layers, pivots):
+                    l.mean.copy_(m)
+        if input_grad:      # every input-gradient pass from the same pivots: a function of the state and its arguments only
+            saved = self._pivots if self._pivots is not None and self._pivots[0] == B else None
+            for i, l in enumerate(self.layers):
+                l.mean.copy_(saved[1][i] if saved is not None else l.mm)
         for a, b in zip(self.stages[:-1], self.stages[1:]):
             if isinstance(a, ConvStage):
                 a.fused_into_pool = self.fuse_bn_pool and isinstance(b, PoolStage) and b.k == 3
@@ -1439,3 +1485,33 @@ class InceptionV1Engine:
             torch.cuda.current_stream().wait_stream(self.wgrad_stream)
         if self.reducer is not None and self.train_all:
             self.reducer.stage_done(TRAINABLE_ENDPOINTS[0])      # whole tower trainable: bucket 1 closes with the stem
+
+    def input_backward(self, dlogits, dimages):
+        """d(sum dlogits * logits) / d(images) of the last forward(input_grad=True) into dimages [B, H, W, 3] (fp32, packed):
+        the backward pass down to the stem's Conv2DBackpropInput, BatchNorm with its batch-statistics terms.  No weight or
+        beta gradient is formed (every layer runs as a frozen one without a beta gradient for the pass), nothing is handed to
+        the gradient reducer: this rank's own gradient."""
+        if not self.input_grad:
+            raise RuntimeError("input_backward needs a forward pass with input_grad=True")
+        B, F = self.B, self.feat
+        if tuple(dimages.shape) != (B, self.input.H, self.input.W, 3) or dimages.dtype != torch.float32 or not dimages.is_contiguous():
+            raise ValueError("dimages must be a contiguous float32 [%d, %d, %d, 3] tensor" % (B, self.input.H, self.input.W))
+        last = self.last
+        self.fc_dgrad.run(ops._p(dlogits), self.w_fc, ops._p(self.dpooled))
+        ops.avgpool_dropout_bwd(self.dpooled, self.mask, B, last.H * last.W, F, self.keep, last.dout)
+        stem = self.stages[0].layer
+        if stem.dgrad is None:
+            stem.make_dgrad(3)
+        saved = [(l.trainable, l.gbeta) for l in self.layers]
+        self.input.dout = dimages
+        try:
+            for l in self.layers:
+                l.trainable, l.gbeta = False, None
+            self.wgrad_stream, self.wgrad_pending = None, False
+            for s in reversed(self.stages):
+                s.backward(need_dx=True)
+        finally:
+            for l, (tr, gb) in zip(self.layers, saved):
+                l.trainable, l.gbeta = tr, gb
+            self.input.dout = None
+        return dimages

@@ -265,6 +265,12 @@ class JointHeadEngine:
             self.reducer.stage_done("head")
         return self.d_im, self.d_tx
 
+    def input_backward(self, dlogits):
+        """d_im alone (SentimentNet.input_gradient): the text features are constants, no weight gradient is formed."""
+        self.sm_dgrad.run(ops._p(dlogits), self.w_sm, ops._p(self.ddense), mask=ops._p(self.dense))      # ReluGrad fused
+        self.im_dgrad.run(ops._p(self.ddense), self.w_im, ops._p(self.d_im))
+        return self.d_im
+
 
 class TextHeadEngine:
     """logits = h_last . W_softmax + b_softmax   (text_model/text_embedding.py:84-86)"""

@@ -185,3 +185,75 @@ def word_most_relevant(top_words, num_classes, checkpoint_dir, *, config=None, o
     scores = np.vstack(scores) if scores else np.zeros((0, model.dataset.num_classes), np.float32)
     _save(out_dir, top_words_scores=scores, top_words=top_words)
     return scores, vocabulary, word_to_id
+
+
+# ---- class visualisation: gradient ascent on the input image (im_text_rnn_model.py:209-339) ------------
+
+def deprocess_image(np_image):
+    """(:209-210), formula verbatim."""
+    return (np_image - 0.5) / 2.0
+
+
+def _gaussian_filter1d(a, sigma, axis, truncate=4.0):
+    """scipy.ndimage.gaussian_filter1d(a, sigma, axis) (order 0, mode 'reflect' = edge sample repeated, truncate 4.0):
+    correlation with the normalised kernel exp(-x^2 / (2 sigma^2)), |x| <= int(truncate * sigma + 0.5), in float64."""
+    radius = int(truncate * float(sigma) + 0.5)
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    k = np.exp(-0.5 / (float(sigma) ** 2) * x ** 2)
+    k /= k.sum()
+    a64 = np.asarray(a, dtype=np.float64)
+    n = a64.shape[axis]
+    pad = [(0, 0)] * a64.ndim
+    pad[axis] = (radius, radius)
+    p = np.pad(a64, pad, mode='symmetric')
+    out = np.zeros_like(a64)
+    for i, w in enumerate(k):
+        out += w * np.take(p, np.arange(i, i + n), axis=axis)
+    return out.astype(np.asarray(a).dtype, copy=False)
+
+
+def blur_image(np_image, sigma=1):
+    """(:212-215): Gaussian blur along axes 1 and 2 (H and W of a [B, H, W, C] batch), scipy-free."""
+    np_image = _gaussian_filter1d(np_image, sigma, axis=1)
+    np_image = _gaussian_filter1d(np_image, sigma, axis=2)
+    return np_image
+
+
+def class_visualisation(label, learning_rate, checkpoint_dir, *, config=None, num_iterations=500, seed=0, out_dir='data'):
+    """Visualise class `label` by gradient ascent on the input image (:217-339) through the newest checkpoint of
+    `checkpoint_dir`: the joint model at B = 1 with batch statistics and a fresh dropout draw per iteration, next to a post
+    of `post_size` unknown words (the zero embedding row).  J = logit[label] - 0.001 ||x||^2; the step is lr * dJ/dx / ||dJ/dx||
+    under a random jitter of up to 16 pixels, then the pixels below the 20th percentile are zeroed and every 10th iteration
+    the image is blurred (sigma 0.5).  dlogit/dx comes from SentimentNet.input_gradient (HIP); the post-processing runs in
+    NumPy as in the reference.  The start image is preprocess_image of np.random.RandomState(seed).standard_normal((224,
+    224, 3)); the jitters are the next draws of that generator.  Writes class_visualisation_<label>.npy to `out_dir` (the
+    reference shows the image with matplotlib instead) and returns the final [224, 224, 3] image.
+    Deviation: the reference builds an older joint graph (mean-of-embeddings text branch, 128 image features, 6 classes)
+    that no checkpoint of its own training path restores; this runs the model that train_deep_sentiment trains."""
+    from ..preprocessing.inception_preprocessing import preprocess_image
+    import os
+    model = _restored_validation_model(checkpoint_dir, config)
+    net = model.net
+    dev = net.device
+    size, post = 224, net.text.T
+    blur_every, max_jitter, clip_percentile, l2_reg = 10, 16, 20, 0.001
+    rng = np.random.RandomState(seed)
+    np_image = preprocess_image(rng.standard_normal((size, size, 3)).astype(np.float32), size, size, is_training=False)[None]
+    batch = {"texts": torch.full((1, post), net.text.V - 1, dtype=torch.int64, device=dev),
+             "seq_lens": torch.full((1,), post, dtype=torch.int64, device=dev)}
+    for i in range(num_iterations):
+        ox, oy = rng.randint(-max_jitter, max_jitter + 1, 2)
+        np_image = np.roll(np.roll(np_image, ox, 1), oy, 2)
+        batch["images"] = torch.from_numpy(np.ascontiguousarray(np_image, dtype=np.float32)).to(dev)
+        _, dimg = net.input_gradient(batch, int(label), seed=seed * 1000003 + i)
+        grad = dimg.cpu().numpy().astype(np.float32) - np.float32(2.0 * l2_reg) * np_image
+        grad = grad / np.linalg.norm(grad)
+        np_image = np_image + np.float32(learning_rate) * grad
+        np_image = np.roll(np.roll(np_image, -ox, 1), -oy, 2)
+        min_norm = np.percentile(np_image, clip_percentile)
+        np_image[np_image < min_norm] = 0.0
+        if i % blur_every == 0:
+            np_image = blur_image(np_image, sigma=0.5)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "class_visualisation_%d.npy" % int(label)), np_image[0])
+    return np_image[0]

@@ -236,6 +236,52 @@ class SentimentNet:
             if self.image is not None:
                 self.image.training, self.image.update_moving = True, True
 
+    def input_gradient(self, batch, target, *, is_training=True, dropout_mask=None, seed=None):
+        """(logits, dimages): the forward pass of predict(is_training=True) and the exact gradient of
+        J = sum_b sum_k target[b, k] logits[b, k] with respect to batch['images'] ([B, H, W, 3], BatchNorm's batch-statistics
+        terms included: what tf.gradients gives in the reference's class_visualisation, im_text_rnn_model.py:217-339).
+        target: an int label (every sample), a [B] int64 label tensor (one-hot) or a [B, nb_emotions] float tensor.  In the
+        joint model the text tower runs forward only: its features are constants of J.  Variables, moving statistics, Adam
+        slots and `step` are not touched; no weight gradient is formed and nothing is all-reduced (this rank's gradient)."""
+        if self.image is None:
+            raise ValueError("input_gradient needs the image tower (mode 'image' or 'joint'), not mode %r" % self.mode)
+        if self.dtype != "f32":
+            raise NotImplementedError("input_gradient is implemented for the fp32 configuration, not %r" % self.dtype)
+        if not is_training:
+            raise NotImplementedError("input_gradient differentiates batch-statistics BatchNorm (is_training=True) only")
+        images = batch["images"]
+        B, nc = images.shape[0], self.nb_emotions
+        if isinstance(target, (int, np.integer)):
+            target = torch.full((B,), int(target), dtype=torch.int64, device=self.device)
+        target = torch.as_tensor(target, device=self.device)
+        if target.dtype in (torch.int32, torch.int64) and target.dim() == 1 and target.shape[0] == B:
+            if bool(((target < 0) | (target >= nc)).any()):
+                raise ValueError("target labels must lie in [0, %d)" % nc)
+            target = torch.nn.functional.one_hot(target.long(), nc).float()
+        elif target.is_floating_point() and tuple(target.shape) == (B, nc):
+            target = target.float().contiguous()
+        else:
+            raise ValueError("target must be an int, a [B] label tensor or a [B, %d] float tensor" % nc)
+        self._input_grad_calls = getattr(self, "_input_grad_calls", 0) + 1
+        seed = (1 << 41) + self._input_grad_calls if seed is None else seed
+        eng = self.image
+        sync = eng.sync_bn
+        eng.training, eng.update_moving, eng.sync_bn = True, False, False
+        try:
+            with torch.no_grad():
+                im = eng.forward(images, dropout_mask, self._rank_seed(seed), input_grad=True)
+                if self.mode == "image":
+                    logits = im.clone()
+                    dimg = eng.input_backward(target, torch.empty(images.shape, device=self.device))
+                else:
+                    tx = self.text.forward(batch["texts"], batch["seq_lens"])
+                    logits = self.head.forward(im, tx).clone()
+                    d_im = self.head.input_backward(target)
+                    dimg = eng.input_backward(d_im, torch.empty(images.shape, device=self.device))
+        finally:
+            eng.training, eng.update_moving, eng.sync_bn = True, True, sync
+        return logits, dimg
+
     def cross_entropy(self, logits, labels):
         if self.dlogits is None or self.dlogits.shape != logits.shape:
             self.dlogits = torch.empty(logits.shape, device=self.device)
