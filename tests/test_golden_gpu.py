@@ -9,6 +9,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+MAX_FLIPS = 2          # dense ReLU decisions the full-size step may take the other way (measured: 1 joint, 0 image)
+
 
 def test_joint_step_matches_committed_golden_vector():
     from oracle import tf_semantics as S
@@ -140,6 +142,10 @@ def test_full_size_step_matches_committed_golden_vector(which):
             assert (int(b), int(j)) in units, "dense unit (%d, %d): ReLU decision differs from the oracle's, whose pre-activation " \
                 "is not within 1e-4 of zero" % (b, j)
             flipped.append(units.index((int(b), int(j))))
+    # ... and only a few of them: a systematic forward bias would flip many of the near-zero units at once.  Measured on the
+    # MI355X: one of the 131 072 units of the joint step (pre-activation -2.1e-6), none of the image-only step
+    print("%s: %d dense unit(s) decided the other way" % (which, len(flipped)))
+    assert len(flipped) <= MAX_FLIPS, "%d dense units decided the other way (at most %d expected)" % (len(flipped), MAX_FLIPS)
     report = []
     for n in names:
         ref = g["grad/" + n].astype(np.float64)
