@@ -743,6 +743,24 @@ int ds_copy2d(const float *src, int32_t lds, float *dst, int32_t ldd, int64_t ro
 int ds_pad_channels(const float *src, int32_t cs, float *dst, int32_t cd, int64_t pixels, void *stream);
 int ds_fill(float *dst, int64_t n, float value, void *stream);
 
+/* Eval-time image preprocessing for a ragged batch (preprocess_for_eval, slim/preprocessing/inception_preprocessing.py:237-275,
+ * called per image by load_batch_with_text, image_model/im_model.py:78-116): one launch turns B decoded, ALREADY CENTRALLY
+ * CROPPED uint8 RGB images (HWC, 3 bytes per pixel, back to back in `bytes`) into the packed fp32 batch
+ * out[B][out_h][out_w][3] the stem kernels read:  v / 255 (through `lut`, 256 floats built by the caller as
+ * float(i) / 255.f)  ->  TF-1 legacy bilinear resize (src = dst * scale, align_corners = False)  ->  (x - 0.5) * 2.
+ * Per element, every step one fp32 rounding, no contraction:  src = float(o) * scale; lo = floor(src);
+ * hi = min(lo + 1, n - 1); f = src - lo; top = a + (b - a) * fx; bot = c + (d - c) * fx; r = top + (bot - top) * fy.
+ * The crop geometry and the scales (float(n_in / n_out), the division in double) are the caller's: image i occupies
+ * bytes [offset, offset + height * width * 3).  `bytes` must be 4-byte aligned and hold `nbytes` bytes; the caller
+ * guarantees that every descriptor lies inside it (the launch cannot report a bad descriptor). */
+typedef struct ds_preprocess_desc {
+    int64_t offset;            /* first byte of the cropped image in `bytes`                  */
+    int32_t height, width;     /* cropped size in pixels (>= 1)                               */
+    float scale_y, scale_x;    /* float(height / out_h), float(width / out_w)                 */
+} ds_preprocess_desc;
+int ds_preprocess_eval(const uint8_t *bytes, int64_t nbytes, const ds_preprocess_desc *desc, int32_t batch, const float *lut,
+                       float *out, int32_t out_h, int32_t out_w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

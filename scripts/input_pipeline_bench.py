@@ -1,0 +1,189 @@
+#!/usr/bin/env python
+"""The input pipelines, measured on one dataset in one session ("Real-data input pipeline").
+
+    input_pipeline_bench.py [--out DIR] [--images 4096] [--seconds 5] [--json FILE] [parts ...]
+
+Writes a seeded dataset of 500 x 375 JPEGs (quality 90, smooth content) under DIR, then, per part:
+  loader   loader-only images/s at batch 256: the host pipeline against the device pipeline at 1, 2, 4, 8, 16 workers,
+           alternating host and device windows of >= `seconds` each, every loader after a warm-up epoch
+  train    joint fp32 training samples/s at batch 256 from that dataset, host against device at 8 workers, and the same
+           step on a resident batch (the step time the kernel's share is taken of)
+  kernel   ds_preprocess_eval at B = 256 (device events), the bytes it must move; run this part alone under
+           `rocprofv3 --kernel-trace --stats` for the profiler's figure and pass the stats file back with --kernel-stats
+One JSON line per measurement on stdout; everything is merged into FILE (default DIR/input_pipeline.json)."""
+import argparse
+import concurrent.futures
+import csv
+import io
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+B, H, W, OUT = 256, 375, 500, 224
+V, D, RNN = 10000, 300, 512
+
+
+def make_dataset(root, n, shards=8, seed=0):
+    from PIL import Image
+    from tumblr_emotions_amd.datasets import convert_to_dataset as cd
+    from tumblr_emotions_amd.datasets import dataset_utils as du
+    from tumblr_emotions_amd.datasets import tfrecord as T
+    if os.path.exists(os.path.join(root, "photos", cd._TRAIN_VALID_FILENAME)):
+        return cd.get_split_with_text("train", root)
+    os.makedirs(os.path.join(root, "photos"))
+    os.makedirs(os.path.join(root, "tfrecords"))
+    du.write_label_file({i: "emotion%d" % i for i in range(15)}, root, "photos")
+    with open(os.path.join(root, "photos", cd._TRAIN_VALID_FILENAME), "w") as f:
+        f.write("train:%d\nvalidation:0\n" % n)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+
+    def one(i):
+        r = np.random.RandomState(seed * 100003 + i)
+        a, b, c, d = r.uniform(20, 90, size=4)
+        p = r.uniform(0, 6.28, size=3)
+        img = np.stack([128 + 110 * np.sin(yy / a + p[0]) * np.cos(xx / b), 128 + 110 * np.sin((xx + yy) / c + p[1]),
+                        128 + 110 * np.cos(xx / d + p[2])], axis=2) + r.normal(0, 3, size=(H, W, 3))
+        buf = io.BytesIO()
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(buf, format="JPEG", quality=90)
+        text = r.randint(0, V, size=50).tolist()
+        return du.image_to_tfexample_with_text(buf.getvalue(), b'jpg', H, W, text, int(r.randint(5, 51)), int(r.randint(15)),
+                                               i, i % 7)
+
+    with concurrent.futures.ThreadPoolExecutor(16) as ex:
+        recs = list(ex.map(one, range(n)))
+    for s in range(shards):
+        T.write_records(cd.dataset_filename(root, "tfrecords", "train", s, shards), recs[s::shards])
+    return cd.get_split_with_text("train", root)
+
+
+def emit(results, **kw):
+    results.append(kw)
+    print(json.dumps(kw), flush=True)
+
+
+def _window(it, seconds):
+    import torch
+    torch.cuda.synchronize()
+    t0, n = time.perf_counter(), 0
+    while time.perf_counter() - t0 < seconds:
+        b = next(it)
+        n += int(b["labels"].shape[0])
+    torch.cuda.synchronize()               # the last batch's preprocessing has finished, too
+    return n / (time.perf_counter() - t0)
+
+
+def part_loader(ds, args, results):
+    from tumblr_emotions_amd.image_model.im_model import load_batch_with_text
+    kw = dict(batch_size=B, height=OUT, width=OUT, max_token_id=V, num_classes=15)
+    epoch = ds.num_samples // B
+    host = load_batch_with_text(ds, pipeline='host', **kw)
+    for _ in range(epoch):
+        next(host)
+    for workers in (1, 2, 4, 8, 16):
+        h = _window(host, args.seconds)
+        dev = load_batch_with_text(ds, pipeline='device', workers=workers, **kw)
+        for _ in range(epoch):
+            next(dev)
+        d = _window(dev, args.seconds)
+        dev.close()
+        emit(results, what="loader", workers=workers, host_images_per_s=round(h, 1), device_images_per_s=round(d, 1),
+             ratio=round(d / h, 2))
+
+
+def part_train(ds, args, results):
+    import torch
+    from tumblr_emotions_amd.image_model.im_model import load_batch_with_text
+    from tumblr_emotions_amd.net import SentimentNet
+    net = SentimentNet(mode="joint", nb_emotions=15, im_features_size=256, rnn_size=RNN, fc_size=512, vocab_size=V,
+                       embedding_dim=D, post_size=50, dropout_keep_prob=0.8)
+    net.initialize(seed=1)
+    kw = dict(batch_size=B, height=OUT, width=OUT, max_token_id=V, num_classes=15)
+
+    def run(it, seconds, warm):
+        for _ in range(warm):
+            net.train_step(next(it), 1e-3)
+        torch.cuda.synchronize()
+        t0, n = time.perf_counter(), 0
+        while time.perf_counter() - t0 < seconds:
+            net.train_step(next(it), 1e-3)
+            n += B
+        torch.cuda.synchronize()
+        return n / (time.perf_counter() - t0)
+
+    dev = load_batch_with_text(ds, pipeline='device', workers=8, **kw)
+    resident = next(dev)
+    for _ in range(10):
+        net.train_step(resident, 1e-3)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(50):
+        net.train_step(resident, 1e-3)
+    torch.cuda.synchronize()
+    step_ms = (time.perf_counter() - t0) / 50 * 1e3
+    emit(results, what="step_resident_batch", ms=round(step_ms, 3), samples_per_s=round(B / step_ms * 1e3, 1))
+    d = run(dev, args.seconds, ds.num_samples // B)
+    dev.close()
+    host = load_batch_with_text(ds, pipeline='host', **kw)
+    h = run(host, args.seconds, 2)
+    emit(results, what="train_joint_fp32", batch=B, host_samples_per_s=round(h, 1), device8_samples_per_s=round(d, 1),
+         ratio=round(d / h, 2))
+
+
+def part_kernel(ds, args, results):
+    import torch
+    from tumblr_emotions_amd import input_pipeline as P
+    from tumblr_emotions_amd import ops
+    rng = np.random.RandomState(0)
+    y0, x0, ch, cw = P.crop_box(H, W)
+    images = [rng.randint(0, 256, size=(ch, cw, 3)).astype(np.uint8) for _ in range(B)]
+    buf, desc, used = P.pack_ragged(images, OUT, OUT)
+    dbytes = torch.from_numpy(buf[:used]).cuda()
+    ddesc = torch.from_numpy(desc.view(np.uint8)).cuda()
+    out = torch.empty(B, OUT, OUT, 3, device="cuda")
+    for _ in range(5):
+        ops.preprocess_eval(dbytes, desc, OUT, OUT, desc_dev=ddesc, out=out)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(50):
+        ops.preprocess_eval(dbytes, desc, OUT, OUT, desc_dev=ddesc, out=out)
+    e1.record()
+    torch.cuda.synchronize()
+    us = e0.elapsed_time(e1) / 50 * 1e3
+    moved = used + out.numel() * 4
+    emit(results, what="ds_preprocess_eval", B=B, crop="%dx%d" % (ch, cw), read_bytes=used, write_bytes=out.numel() * 4,
+         us_events=round(us, 1), tb_per_s=round(moved / us / 1e6, 3))
+
+
+def kernel_stats(path, results):
+    """Average duration of preprocess_eval_kernel from a rocprofv3 --kernel-trace --stats csv (Name, Calls, ..., AverageNs)."""
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            if "preprocess_eval_kernel" in row.get("Name", ""):
+                emit(results, what="ds_preprocess_eval_rocprofv3", calls=int(row["Calls"]),
+                     us_average=round(float(row["AverageNs"]) / 1e3, 1))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="bench_outputs/input_pipeline")
+    ap.add_argument("--images", type=int, default=4096)
+    ap.add_argument("--seconds", type=float, default=5.0)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("parts", nargs="*", default=["loader", "train", "kernel"])
+    args = ap.parse_args()
+    os.makedirs(args.out, exist_ok=True)
+    path = args.json or os.path.join(args.out, "input_pipeline.json")
+    results = json.load(open(path)) if os.path.exists(path) else []
+    if args.kernel_stats:
+        kernel_stats(args.kernel_stats, results)
+    else:
+        ds = make_dataset(os.path.join(args.out, "dataset"), args.images)
+        for p in args.parts:
+            {"loader": part_loader, "train": part_train, "kernel": part_kernel}[p](ds, args, results)
+    with open(path, "w") as f:
+        json.dump(results, f, indent=1)

@@ -90,6 +90,11 @@ class SumSegments(C.Structure):
                 ("s2", C.c_void_p * 4), ("q2", C.c_void_p * 4)]
 
 
+class PreprocessDesc(C.Structure):
+    """ds_preprocess_desc"""
+    _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32), ("scale_y", C.c_float), ("scale_x", C.c_float)]
+
+
 _P = C.c_void_p
 _i32, _i64, _f32, _u64 = C.c_int32, C.c_int64, C.c_float, C.c_uint64
 _CD = C.POINTER(ConvDesc)
@@ -207,6 +212,7 @@ SIGNATURES = {
     "ds_copy2d": (C.c_int, [_P, _i32, _P, _i32, _i64, _i32, _P]),
     "ds_pad_channels": (C.c_int, [_P, _i32, _P, _i32, _i64, _P]),
     "ds_fill": (C.c_int, [_P, _i64, _f32, _P]),
+    "ds_preprocess_eval": (C.c_int, [_P, _i64, _P, _i32, _P, _P, _i32, _i32, _P]),
 }
 
 _lib = None

@@ -83,7 +83,8 @@ def evaluate_image_model(checkpoint_dir, log_dir, mode, num_evals, *, config=Non
 
 
 def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False,
-                         device="cuda", rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None):
+                         device="cuda", rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None,
+                         pipeline='host', workers=8, prefetch=2, decode_images=True):
     """Generator of training batches from a `datasets.convert_to_dataset.Dataset` -- the role of
     load_batch_with_text + tf.train.batch in the reference (im_model.py:78-116): decode the JPEG, apply the
     EVAL preprocessing (is_training=False is what every reference call site uses, :78,102), batch.
@@ -92,18 +93,35 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
     rank, rank+world, ... (disjoint shards of one global order; the others are skipped BEFORE the JPEG is
     decoded).  max_token_id / num_classes: a record whose token ids exceed the embedding table (ids index the
     vocabulary the dataset was converted with; id == vocabulary size is '<ukn>') or whose label is out of
-    range raises -- the gather would otherwise read zero rows / the loss kernel out of bounds."""
+    range raises -- the gather would otherwise read zero rows / the loss kernel out of bounds.
+    pipeline: 'host' (this generator: PIL decode + NumPy preprocessing on one thread, blocking uploads) or 'device'
+    (input_pipeline.DeviceLoader: the same batches bit for bit and in the same order, decode on `workers` threads (at most
+    16), preprocessing in ds_preprocess_eval, `prefetch` batches uploaded ahead on a copy stream).  decode_images=False
+    (text-only models): the JPEGs are neither decoded nor preprocessed and the batches carry no 'images'."""
+    if pipeline == 'device':
+        from ..input_pipeline import DeviceLoader
+        return DeviceLoader(dataset, batch_size, shuffle, height, width, is_training, device, rank, world, seed, loop,
+                            max_token_id, num_classes, workers=workers, prefetch=prefetch, decode_images=decode_images)
+    if pipeline != 'host':
+        raise ValueError("pipeline must be 'host' or 'device', not %r" % (pipeline,))
+    return _host_batches(dataset, batch_size, shuffle, height, width, is_training, device, rank, world, seed, loop,
+                         max_token_id, num_classes, decode_images)
+
+
+def _host_batches(dataset, batch_size, shuffle, height, width, is_training, device, rank, world, seed, loop, max_token_id,
+                  num_classes, decode_images):
+    """The host pipeline of load_batch_with_text (a generator)."""
     import torch
     from ..preprocessing.inception_preprocessing import preprocess_image
     rng = np.random.RandomState(seed)
-    buf = {k: [] for k in ("images", "texts", "seq_lens", "labels", "post_ids", "days")}
+    buf = {k: [] for k in ("images", "texts", "seq_lens", "labels", "post_ids", "days") if decode_images or k != "images"}
     while True:
         sources = list(dataset.data_sources)
         if shuffle:
             rng.shuffle(sources)
         view = type(dataset)(sources, dataset.num_samples, dataset.num_classes, dataset.labels_to_names)
         n = 0
-        for i, ex in enumerate(view.examples(decode_image=lambda idx: idx % world == rank)):
+        for i, ex in enumerate(view.examples(decode_image=lambda idx: decode_images and idx % world == rank)):
             if i % world != rank:
                 continue
             n += 1
@@ -112,14 +130,15 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
                                  "dataset was converted with a different vocabulary" % (int(np.max(ex["text"])), max_token_id))
             if num_classes is not None and not 0 <= int(ex["label"]) < num_classes:
                 raise ValueError("label %d outside [0, %d)" % (int(ex["label"]), num_classes))
-            buf["images"].append(preprocess_image(ex["image"], height, width, is_training=is_training))
+            if decode_images:
+                buf["images"].append(preprocess_image(ex["image"], height, width, is_training=is_training))
             buf["texts"].append(ex["text"])
             for k, s in (("seq_lens", "seq_len"), ("labels", "label"), ("post_ids", "post_id"), ("days", "day")):
                 buf[k].append(ex[s])
             if len(buf["labels"]) == batch_size:
                 order = rng.permutation(batch_size) if shuffle else np.arange(batch_size)
-                out = {"images": torch.from_numpy(np.stack(buf["images"])[order]).to(device),
-                       "texts": torch.from_numpy(np.stack(buf["texts"])[order]).to(device)}
+                out = {"images": torch.from_numpy(np.stack(buf["images"])[order]).to(device)} if decode_images else {}
+                out["texts"] = torch.from_numpy(np.stack(buf["texts"])[order]).to(device)
                 for k in ("seq_lens", "labels", "post_ids", "days"):
                     out[k] = torch.from_numpy(np.asarray(buf[k], np.int64)[order]).to(device)
                 buf = {k: [] for k in buf}

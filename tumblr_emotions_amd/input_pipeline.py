@@ -1,0 +1,401 @@
+"""Device input pipeline: the batches of `image_model.im_model.load_batch_with_text`, bit for bit and in the same order,
+with the eval preprocessing on the GPU (ds_preprocess_eval), the JPEG decode on a bounded pool of worker threads, and
+the upload + preprocessing of the next batches overlapped with the training step.
+
+    records (main feeder thread, file order)         raw TFRecord payloads of THIS rank only
+      -> OrderedPool (<= 16 daemon threads)          decode_example + PIL decode + central crop   (GIL released in PIL / NumPy)
+      -> feeder, in submission order                 checks, ragged packing into a pinned staging set, descriptor table
+      -> copy stream                                 non_blocking uploads, ds_preprocess_eval behind them, an event
+      -> DeviceLoader.__next__                       the consumer's stream waits for the event and takes the tensors
+
+The crop offsets / extents and the resize scales are computed with the very expressions of
+preprocessing/inception_preprocessing.py (Python doubles, then np.float32), so the kernel repeats no double arithmetic.
+Source shuffling, the in-batch permutation and the ragged tail draw from one RandomState in the host generator's
+sequence.  Staging sets are filled by the feeder (not by the workers: an image's offset in the ragged buffer is known
+only once every earlier image of the batch has been decoded) and are reused only after the event of their last upload
+has completed.
+"""
+import io
+import queue
+import threading
+import weakref
+
+import numpy as np
+
+MAX_WORKERS = 16
+CENTRAL_FRACTION = 0.875              # preprocess_for_eval's default, the only value the reference uses
+_FIELDS = (("seq_lens", "seq_len"), ("labels", "label"), ("post_ids", "post_id"), ("days", "day"))
+
+
+# ---- geometry: the host half of preprocess_for_eval -------------------------------------------------------------------------
+def crop_box(h, w, central_fraction=CENTRAL_FRACTION):
+    """(y0, x0, crop_h, crop_w) of central_crop for an h x w image -- its own expressions, in Python doubles."""
+    if not central_fraction:
+        return 0, 0, h, w
+    h0 = int((h - h * central_fraction) / 2)
+    w0 = int((w - w * central_fraction) / 2)
+    return h0, w0, h - 2 * h0, w - 2 * w0
+
+
+def resize_scale(n_in, n_out):
+    """The fp32 scale of resize_bilinear's axis(): np.float32(n_in / n_out), the division in double."""
+    return np.float32(n_in / n_out)
+
+
+def clamp_workers(workers):
+    """1 <= workers <= 16, whatever the machine has (never sized from os.cpu_count())."""
+    return max(1, min(int(workers), MAX_WORKERS))
+
+
+def pack_ragged(images, out_h, out_w, out=None, desc=None, align=4):
+    """Lay cropped uint8 HWC images back to back (each start rounded up to `align` bytes) and describe them.
+    images: list of [h, w, 3] uint8 arrays; out: uint8 buffer to fill (a new one when None; ValueError when too small);
+    desc: descriptor array to fill (first len(images) records).  Returns (buffer, descriptors, bytes used)."""
+    from .ops import preprocess_desc_dtype
+    n = len(images)
+    if desc is None:
+        desc = np.zeros(n, preprocess_desc_dtype())
+    offsets, pos = [], 0
+    for im in images:
+        if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError("pack_ragged: images must be non-empty uint8 [h, w, 3] arrays")
+        offsets.append(pos)
+        pos = -(-(pos + im.size) // align) * align
+    if out is None:
+        out = np.zeros(max(pos, align), np.uint8)
+    if out.size < pos:
+        raise ValueError("pack_ragged: %d bytes do not fit a buffer of %d" % (pos, out.size))
+    for i, (im, off) in enumerate(zip(images, offsets)):
+        out[off:off + im.size].reshape(im.shape)[...] = im
+        desc[i] = (off, im.shape[0], im.shape[1], resize_scale(im.shape[0], out_h), resize_scale(im.shape[1], out_w))
+    return out, desc[:n], pos
+
+
+# ---- decode pool ------------------------------------------------------------------------------------------------------------
+class _Slot:
+    __slots__ = ("done", "value", "error")
+
+    def __init__(self):
+        self.done, self.value, self.error = threading.Event(), None, None
+
+    def result(self):
+        self.done.wait()
+        if self.error is not None:
+            raise self.error
+        return self.value
+
+
+def _pool_worker(tasks):
+    while True:
+        item = tasks.get()
+        if item is None:
+            return
+        slot, fn, args = item
+        try:
+            slot.value = fn(*args)
+        except BaseException as e:          # handed to the consumer, raised at this item's position in the order
+            slot.error = e
+        slot.done.set()
+
+
+class OrderedPool:
+    """At most 16 daemon threads; submit() returns a slot whose result() blocks -- callers consume slots in submission
+    order, so a slow early item delays but never reorders the stream.  close() joins every thread."""
+
+    def __init__(self, workers):
+        self.workers = clamp_workers(workers)
+        self._tasks = queue.SimpleQueue()
+        self._threads = [threading.Thread(target=_pool_worker, args=(self._tasks,), daemon=True,
+                                          name="ds-input-decode-%d" % i) for i in range(self.workers)]
+        for t in self._threads:
+            t.start()
+
+    def submit(self, fn, *args):
+        slot = _Slot()
+        self._tasks.put((slot, fn, args))
+        return slot
+
+    def close(self):
+        try:                                   # queued items nobody will consume any more are dropped, not decoded
+            while True:
+                self._tasks.get_nowait()
+        except queue.Empty:
+            pass
+        for _ in self._threads:
+            self._tasks.put(None)
+        for t in self._threads:
+            t.join()
+        self._threads = []
+
+
+def decode_record(rec, decode_image=True):
+    """One TFRecord payload -> (cropped uint8 image or None, text int64[50], seq_len, label, post_id, day): the work of
+    Dataset.examples for one record plus central_crop (only the cropped region is ever uploaded)."""
+    from .datasets.convert_to_dataset import _POST_SIZE
+    from .datasets.tfrecord import decode_example
+    ex = decode_example(rec)
+    img = None
+    if decode_image:
+        from PIL import Image
+        img = np.asarray(Image.open(io.BytesIO(ex['image/encoded'][0])).convert('RGB'))
+        y0, x0, ch, cw = crop_box(img.shape[0], img.shape[1])
+        img = np.ascontiguousarray(img[y0:y0 + ch, x0:x0 + cw])
+    text = np.zeros(_POST_SIZE, np.int64)
+    t = ex.get('text', [])
+    text[:len(t)] = t
+    return (img, text, int(ex.get('seq_len', [0])[0]), int(ex.get('image/class/label', [0])[0]),
+            int(ex.get('post_id', [0])[0]), int(ex.get('day', [0])[0]))
+
+
+# ---- staging ----------------------------------------------------------------------------------------------------------------
+class _Staging:
+    """One pinned staging set: ragged image bytes + descriptor table + the int64 fields, with the device byte buffer and
+    descriptor table they are uploaded into and the event of the last upload."""
+
+    def __init__(self, batch_size, post_size, device, cuda):
+        import torch
+        from .ops import preprocess_desc_dtype
+        self.torch, self.device, self.cuda = torch, device, cuda
+        self.event = None
+        self.ints = self._host(batch_size * (post_size + len(_FIELDS)), torch.int64)
+        self.desc = self._host(batch_size * preprocess_desc_dtype().itemsize, torch.uint8)
+        self.desc_np = self.desc.numpy().view(preprocess_desc_dtype())
+        self.desc_dev = torch.empty(self.desc.numel(), dtype=torch.uint8, device=device) if cuda else None
+        self.bytes = self.bytes_dev = None
+        self.reserve(1 << 20)
+
+    def _host(self, n, dtype):
+        return self.torch.empty(n, dtype=dtype, pin_memory=self.cuda)
+
+    def reserve(self, nbytes):
+        if self.bytes is None or self.bytes.numel() < nbytes:
+            cap = -(-int(nbytes * 1.25) // 4096) * 4096
+            self.bytes = self._host(cap, self.torch.uint8)
+            self.bytes_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device) if self.cuda else None
+
+    def wait_free(self):
+        if self.event is not None:
+            self.event.synchronize()
+            self.event = None
+
+
+class _State:
+    """Everything the feeder thread touches (the DeviceLoader itself is not referenced from the thread, so dropping the
+    loader lets its finalizer stop the thread)."""
+
+    def __init__(self):
+        self.stop = threading.Event()
+        self.out = None
+        self.thread = None
+        self.pool = None
+
+
+def _put(state, item):
+    while not state.stop.is_set():
+        try:
+            state.out.put(item, timeout=0.05)
+            return True
+        except queue.Full:
+            pass
+    return False
+
+
+_EPOCH = object()
+
+
+def _record_stream(dataset, shuffle, rng, rank, world, loop):
+    """Raw records of this rank in the host generator's order, _EPOCH between passes.  The source shuffle of a pass is
+    drawn when the first record of that pass is asked for, never earlier."""
+    from .datasets.tfrecord import read_records
+    while True:
+        sources = list(dataset.data_sources)
+        if shuffle:
+            rng.shuffle(sources)
+        idx, n = -1, 0
+        for path in sources:
+            for rec in read_records(path):
+                idx += 1
+                if idx % world != rank:
+                    continue                   # other ranks' records: never parsed, never decoded
+                n += 1
+                yield rec
+        if not loop or n == 0:
+            return
+        yield _EPOCH
+
+
+def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, world, seed, loop, max_token_id,
+            num_classes, decode_images, prefetch, inflight):
+    import collections
+    try:
+        import torch
+        from . import ops
+        dev = torch.device(device)
+        cuda = dev.type == "cuda"
+        if decode_images and not cuda:
+            raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
+        post_size = None
+        stream = None
+        if cuda:
+            torch.cuda.set_device(dev)
+            stream = torch.cuda.Stream(device=dev)
+        rng = np.random.RandomState(seed)
+        stagings, turn = [], 0
+        pending = collections.deque()
+        records = _record_stream(dataset, shuffle, rng, rank, world, loop)
+        exhausted = boundary = False
+        buf = []
+        while not state.stop.is_set():
+            # Read ahead, but keep the RandomState's sequence equal to the host generator's: within a pass the only draws
+            # are the batch permutations (made below as batches complete); the next draw after the last record of a pass is
+            # the next pass's source shuffle.  So with shuffling on, the next pass starts only once every record of the
+            # finished one has been consumed (a short bubble per epoch); without shuffling nothing is drawn at all.
+            while not exhausted and len(pending) < inflight:
+                if boundary and shuffle and pending:
+                    break
+                boundary = False
+                rec = next(records, None)
+                if rec is None:
+                    exhausted = True
+                elif rec is _EPOCH:
+                    boundary = True
+                else:
+                    pending.append(state.pool.submit(decode_record, rec, decode_images))
+            if not pending:
+                break
+            img, text, seq_len, label, post_id, day = pending.popleft().result()
+            if max_token_id is not None and int(np.max(text)) > max_token_id:
+                raise ValueError("token id %d in the dataset exceeds the embedding table (%d rows + <ukn>): the "
+                                 "dataset was converted with a different vocabulary" % (int(np.max(text)), max_token_id))
+            if num_classes is not None and not 0 <= label < num_classes:
+                raise ValueError("label %d outside [0, %d)" % (label, num_classes))
+            buf.append((img, text, seq_len, label, post_id, day))
+            if len(buf) < batch_size:
+                continue
+            order = rng.permutation(batch_size) if shuffle else np.arange(batch_size)
+            if post_size is None:
+                post_size = len(buf[0][1])
+                stagings = [_Staging(batch_size, post_size, dev, cuda) for _ in range(max(2, prefetch + 1))]
+            st = stagings[turn]
+            turn = (turn + 1) % len(stagings)
+            st.wait_free()
+            ints = st.ints.numpy()
+            nt = batch_size * post_size
+            ints[:nt].reshape(batch_size, post_size)[...] = np.stack([b[1] for b in buf])[order]
+            for k in range(len(_FIELDS)):
+                ints[nt + k * batch_size:nt + (k + 1) * batch_size] = np.asarray([b[2 + k] for b in buf], np.int64)[order]
+            used = 0
+            if decode_images:
+                images = [buf[j][0] for j in order]          # descriptor j = output slot j: the permutation costs nothing
+                st.reserve(sum(-(-im.size // 4) * 4 for im in images))
+                _, _, used = pack_ragged(images, height, width, out=st.bytes.numpy(), desc=st.desc_np)
+                ops.check_preprocess_descs(st.desc_np[:batch_size], used)
+            buf = []
+            out = {}
+            if cuda:
+                with torch.cuda.stream(stream):
+                    if decode_images:
+                        st.bytes_dev[:used].copy_(st.bytes[:used], non_blocking=True)
+                        st.desc_dev.copy_(st.desc, non_blocking=True)
+                        out["images"] = ops.preprocess_eval(st.bytes_dev[:used], st.desc_np[:batch_size], height, width,
+                                                            desc_dev=st.desc_dev)
+                    ints_dev = st.ints.to(dev, non_blocking=True)
+                    st.event = torch.cuda.Event()
+                    st.event.record(stream)
+                event = st.event
+            else:
+                ints_dev, event = st.ints.clone(), None
+            out["texts"] = ints_dev[:nt].view(batch_size, post_size)
+            for k, (name, _) in enumerate(_FIELDS):
+                out[name] = ints_dev[nt + k * batch_size:nt + (k + 1) * batch_size]
+            if not _put(state, ("batch", out, event, stream)):
+                return
+        _put(state, ("end",))
+    except BaseException as e:
+        _put(state, ("error", e))
+
+
+
+
+def _shutdown(state):
+    state.stop.set()
+    if state.thread is not None and state.thread is not threading.current_thread():
+        state.thread.join()
+    if state.pool is not None:
+        state.pool.close()
+    try:                                       # drop queued batches (device tensors, events)
+        while True:
+            state.out.get_nowait()
+    except queue.Empty:
+        pass
+
+
+class DeviceLoader:
+    """Iterator over the batches of load_batch_with_text(pipeline='device').  `next(loader)` makes the current stream
+    wait for the batch's upload + preprocessing (an event; the host is not blocked by the device) and returns the dict.
+    close() -- also run by the context manager, by garbage collection of the loader and at interpreter exit -- stops the
+    feeder and joins every worker; a closed or exhausted loader raises StopIteration."""
+
+    def __init__(self, dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False, device="cuda",
+                 rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None, workers=8, prefetch=2,
+                 decode_images=True):
+        if is_training:
+            raise NotImplementedError("the reference's training path never uses the train-time augmentation")
+        if batch_size < 1 or height < 1 or width < 1 or world < 1 or not 0 <= rank < world:
+            raise ValueError("DeviceLoader: bad batch_size / height / width / rank / world")
+        self.workers = clamp_workers(workers)
+        self.prefetch = max(1, int(prefetch))
+        self.decode_images = bool(decode_images)
+        self._done = False
+        import torch
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None and torch.cuda.is_available():
+            device = torch.device("cuda", torch.cuda.current_device())      # the caller's current device, not the feeder thread's
+        st = self._state = _State()
+        st.out = queue.Queue(maxsize=self.prefetch)
+        st.pool = OrderedPool(self.workers)
+        inflight = max(4 * self.workers, min(int(batch_size), 256))
+        st.thread = threading.Thread(target=_feeder, name="ds-input-feeder", daemon=True,
+                                     args=(st, dataset, int(batch_size), bool(shuffle), int(height), int(width), device, rank,
+                                           world, seed, bool(loop), max_token_id, num_classes, self.decode_images,
+                                           self.prefetch, inflight))
+        self._finalizer = weakref.finalize(self, _shutdown, st)
+        st.thread.start()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._done:
+            raise StopIteration
+        item = self._state.out.get()
+        if item[0] == "batch":
+            _, out, event, stream = item
+            if event is not None:
+                import torch
+                cur = torch.cuda.current_stream(stream.device)
+                cur.wait_event(event)
+                for t in out.values():          # allocated on the copy stream, consumed (and later freed) on this one
+                    t.record_stream(cur)
+            return out
+        self.close()
+        if item[0] == "error":
+            raise item[1]
+        raise StopIteration
+
+    def close(self):
+        self._done = True
+        self._finalizer()
+
+    def threads(self):
+        """The loader's live threads (feeder + decode workers); empty after close()."""
+        st = self._state
+        ts = ([st.thread] if st.thread is not None else []) + list(st.pool._threads)
+        return [t for t in ts if t.is_alive()]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -866,3 +866,70 @@ def pad_channels(src, cs, dst, cd, pixels):
 
 def fill(dst, n, value):
     _lib.check(_lib.load().ds_fill(_p(dst), n, value, _stream()), "ds_fill")
+
+
+# ---- eval-time image preprocessing (ds_preprocess_eval) ---------------------------------------------------------------------
+def preprocess_desc_dtype():
+    """NumPy view of ds_preprocess_desc (24 bytes): one record per image of a ragged uint8 batch."""
+    import numpy as np
+    return np.dtype([("offset", np.int64), ("height", np.int32), ("width", np.int32),
+                     ("scale_y", np.float32), ("scale_x", np.float32)], align=True)
+
+
+def check_preprocess_descs(desc, nbytes):
+    """Every image of the descriptor table lies inside a byte buffer of `nbytes` bytes (the kernel cannot check): raises
+    ValueError before anything is launched."""
+    import numpy as np
+    desc = np.asarray(desc)
+    if desc.dtype != preprocess_desc_dtype() or desc.ndim != 1 or desc.size == 0:
+        raise ValueError("preprocess_eval: descriptors must be a non-empty 1-D array of ops.preprocess_desc_dtype()")
+    h, w, off = desc["height"].astype(np.int64), desc["width"].astype(np.int64), desc["offset"]
+    bad = (h < 1) | (w < 1) | (off < 0) | (off + h * w * 3 > int(nbytes))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError("preprocess_eval: descriptor %d (offset %d, %d x %d pixels) does not fit the byte buffer of %d bytes"
+                         % (i, int(off[i]), int(h[i]), int(w[i]), int(nbytes)))
+    if not (np.isfinite(desc["scale_y"]).all() and np.isfinite(desc["scale_x"]).all()
+            and (desc["scale_y"] > 0).all() and (desc["scale_x"] > 0).all()):
+        raise ValueError("preprocess_eval: scales must be finite and positive")
+
+
+_preprocess_lut = {}
+
+
+def preprocess_lut(device):
+    """The 256-entry uint8 -> [0, 1] table of convert_image_dtype, np.arange(256, f32) / f32(255), on `device` (cached)."""
+    import numpy as np
+    dev = torch.device(device)
+    key = torch.cuda.current_device() if dev.index is None else dev.index
+    if key not in _preprocess_lut:
+        lut = np.arange(256, dtype=np.float32) / np.float32(255)
+        _preprocess_lut[key] = torch.from_numpy(lut).to(torch.device("cuda", key))
+    return _preprocess_lut[key]
+
+
+def preprocess_eval(image_bytes, desc, out_h, out_w, desc_dev=None, out=None):
+    """preprocess_for_eval of a ragged batch in one launch.  image_bytes: device uint8 tensor holding the centrally cropped
+    HWC images back to back; desc: HOST array of ops.preprocess_desc_dtype() records (checked against the buffer's size
+    here, before the launch); desc_dev: the same table already on the device (uploaded here when None); out: fp32
+    [B, out_h, out_w, 3] (allocated when None).  Returns out."""
+    import numpy as np
+    if not image_bytes.is_cuda:
+        raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
+    if image_bytes.dtype != torch.uint8 or not image_bytes.is_contiguous():
+        raise ValueError("preprocess_eval: image_bytes must be a contiguous uint8 tensor")
+    if out_h < 1 or out_w < 1:
+        raise ValueError("preprocess_eval: out_h and out_w must be positive")
+    check_preprocess_descs(desc, image_bytes.numel())
+    B = int(np.asarray(desc).size)
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8)).to(image_bytes.device)
+    if desc_dev.numel() * desc_dev.element_size() < B * preprocess_desc_dtype().itemsize or not desc_dev.is_contiguous():
+        raise ValueError("preprocess_eval: desc_dev is smaller than the descriptor table")
+    if out is None:
+        out = torch.empty((B, out_h, out_w, 3), dtype=torch.float32, device=image_bytes.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * out_h * out_w * 3:
+        raise ValueError("preprocess_eval: out must be a contiguous fp32 [B, out_h, out_w, 3] tensor")
+    _lib.check(_lib.load().ds_preprocess_eval(_p(image_bytes), image_bytes.numel(), _p(desc_dev), B, _p(preprocess_lut(image_bytes.device)),
+                                              _p(out), out_h, out_w, _stream()), "ds_preprocess_eval")
+    return out

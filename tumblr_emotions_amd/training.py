@@ -132,7 +132,9 @@ def run_evaluation(model, checkpoint_dir, log_dir, mode, num_evals, batch_fn=Non
 class SyntheticInput:
     """Mixin: the input side of the reference's model constructors.  If `config['dataset_dir']` holds a
     converted dataset (photos/train_valid_split.txt + tfrecords/tumblr_<mode>_*.tfrecord, the layout of
-    datasets/convert_to_dataset.py:117-198) batches are read from it; otherwise they are synthetic."""
+    datasets/convert_to_dataset.py:117-198) batches are read from it; otherwise they are synthetic.
+    config['input_pipeline']: 'host' (default) or 'device' (input_pipeline.DeviceLoader: parallel decode on
+    config['input_workers'] threads, default 8, preprocessing on the GPU; the same batches bit for bit)."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
@@ -158,10 +160,11 @@ class SyntheticInput:
                 from .image_model.im_model import load_batch_with_text
                 self._records = load_batch_with_text(self.dataset, self.config["batch_size"], height=224, width=224,
                                                      device=device, rank=rank, world=world, max_token_id=vocab,
-                                                     num_classes=getattr(self.dataset, "num_classes", nb))
+                                                     num_classes=getattr(self.dataset, "num_classes", nb),
+                                                     pipeline=self.config.get("input_pipeline", "host"),
+                                                     workers=self.config.get("input_workers", 8),
+                                                     decode_images=with_images)     # text-only: no JPEG is decoded
             b = next(self._records)
-            if not with_images:
-                b.pop("images")
         else:
             gb = self.config["batch_size"] * world
             b = synthetic_batch_numpy(gb, post_size, vocab, nb, seed=step, with_images=with_images)
