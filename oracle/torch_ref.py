@@ -242,6 +242,10 @@ class DeepSentimentRef:
         # scopes whose conv output the build stores as bf16(z - pivot) (InceptionV1Engine.z16, 16-bit labels): set by the tests
         # from the build's own plan; the first step's pivot is the moving mean (ConvBN.bind)
         self.z_storage_bf16 = None
+        # {scope: [C] pivot} about which those scopes' stored z is centred in THIS step: from the second step on the build's
+        # pivot is the layer's previous batch mean (ConvBN.forward), which a free-running test reads from the build before
+        # the step.  None, or a scope left out: the moving mean, i.e. the first step after a load
+        self.z_pivots = None
 
     @staticmethod
     def _is_trainable(name, trainable_bn_beta):
@@ -275,7 +279,10 @@ class DeepSentimentRef:
         beta = self.p[scope + "/BatchNorm/beta"]
         if self.is_training:
             if self.z_storage_bf16 and scope in self.z_storage_bf16:
-                y, mean, var = batch_norm_train_stored(z, self.p[scope + "/BatchNorm/moving_mean"], beta)
+                pivot = None if self.z_pivots is None else self.z_pivots.get(scope)
+                if pivot is None:
+                    pivot = self.p[scope + "/BatchNorm/moving_mean"]
+                y, mean, var = batch_norm_train_stored(z, torch.as_tensor(pivot, dtype=z.dtype), beta)
             else:
                 y, mean, var = batch_norm_train(z, beta)
             self.bn_batch_stats[scope] = (mean.detach(), var.detach())
