@@ -761,6 +761,30 @@ typedef struct ds_preprocess_desc {
 int ds_preprocess_eval(const uint8_t *bytes, int64_t nbytes, const ds_preprocess_desc *desc, int32_t batch, const float *lut,
                        float *out, int32_t out_h, int32_t out_w, void *stream);
 
+/* Train-time image preprocessing for a ragged batch (preprocess_for_train, slim/preprocessing/inception_preprocessing.py:156-234
+ * with fast_mode = True and no caller-supplied box): the sibling of ds_preprocess_eval.  The caller has drawn every random
+ * choice and sliced the sampled crop; one launch turns B decoded, ALREADY CROPPED uint8 RGB images into out[B][out_h][out_w][3]:
+ *   v / 255 (through `lut`)  ->  bilinear resize as in ds_preprocess_eval  ->  left-right flip of the resized image
+ *   ->  brightness (x + delta) and saturation (RGB -> HSV, S = clamp(S * factor, 0, 1), HSV -> RGB) in the image's order
+ *   ->  clip to [0, 1]  ->  (x - 0.5) * 2,
+ * per pixel, every step one fp32 rounding without contraction, divisions correctly rounded, in the order of
+ * preprocessing/inception_preprocessing.py (adjust_saturation, distort_color_fast), which it matches bit for bit.
+ * Same buffer rules as ds_preprocess_eval; the caller additionally guarantees finite delta and factor, factor >= 0, no
+ * flag bits beyond the two below and reserved == 0. */
+#define DS_PREPROCESS_FLIP 1u                  /* mirror the resized image along x                        */
+#define DS_PREPROCESS_SATURATION_FIRST 2u      /* saturation then brightness (otherwise brightness first) */
+typedef struct ds_preprocess_train_desc {
+    int64_t offset;            /* first byte of the cropped image in `bytes`                  */
+    int32_t height, width;     /* cropped size in pixels (>= 1)                               */
+    float scale_y, scale_x;    /* float(height / out_h), float(width / out_w)                 */
+    float delta;               /* brightness delta, added to every channel                    */
+    float factor;              /* saturation factor (>= 0)                                    */
+    uint32_t flags;            /* DS_PREPROCESS_FLIP | DS_PREPROCESS_SATURATION_FIRST         */
+    uint32_t reserved;         /* 0                                                           */
+} ds_preprocess_train_desc;
+int ds_preprocess_train(const uint8_t *bytes, int64_t nbytes, const ds_preprocess_train_desc *desc, int32_t batch,
+                        const float *lut, float *out, int32_t out_h, int32_t out_w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,11 @@ Writes a seeded dataset of 500 x 375 JPEGs (quality 90, smooth content) under DI
            step on a resident batch (the step time the kernel's share is taken of)
   kernel   ds_preprocess_eval at B = 256 (device events), the bytes it must move; run this part alone under
            `rocprofv3 --kernel-trace --stats` for the profiler's figure and pass the stats file back with --kernel-stats
+  kernel_train   ds_preprocess_train at B = 256 on crops drawn by sample_train_params from 375 x 500 sources, beside
+           ds_preprocess_eval on the SAME packed crops (same bytes in and out: the eval kernel is the baseline); the part to run
+           under `rocprofv3 --kernel-trace --stats`
+  augment  device pipeline at 8 workers, alternating windows without and with is_training=True; the cost of
+           record_rng + sample_train_params per image on one thread (ordinary and 100-attempt sizes)
 One JSON line per measurement on stdout; everything is merged into FILE (default DIR/input_pipeline.json)."""
 import argparse
 import concurrent.futures
@@ -158,13 +163,72 @@ def part_kernel(ds, args, results):
          us_events=round(us, 1), tb_per_s=round(moved / us / 1e6, 3))
 
 
+def part_kernel_train(ds, args, results):
+    import torch
+    from tumblr_emotions_amd import input_pipeline as P
+    from tumblr_emotions_amd import ops
+    from tumblr_emotions_amd.preprocessing import inception_preprocessing as ip
+    rng = np.random.RandomState(0)
+    params = [ip.sample_train_params(H, W, ip.record_rng(0, 0, i)) for i in range(B)]
+    images = [rng.randint(0, 256, size=(p.crop_h, p.crop_w, 3)).astype(np.uint8) for p in params]
+    buf, tdesc, used = P.pack_ragged(images, OUT, OUT, params=params)
+    _, edesc, _ = P.pack_ragged(images, OUT, OUT)
+    dbytes = torch.from_numpy(buf[:used]).cuda()
+    out = torch.empty(B, OUT, OUT, 3, device="cuda")
+    moved = used + out.numel() * 4
+    for what, fn, desc in (("ds_preprocess_eval_on_train_crops", ops.preprocess_eval, edesc),
+                           ("ds_preprocess_train", ops.preprocess_train, tdesc)):
+        ddesc = torch.from_numpy(desc.view(np.uint8)).cuda()
+        for _ in range(5):
+            fn(dbytes, desc, OUT, OUT, desc_dev=ddesc, out=out)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(50):
+            fn(dbytes, desc, OUT, OUT, desc_dev=ddesc, out=out)
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) / 50 * 1e3
+        emit(results, what=what, B=B, source="%dx%d" % (H, W), mean_crop_pixels=int(np.mean([im.size // 3 for im in images])),
+             read_bytes=used, write_bytes=out.numel() * 4, us_events=round(us, 1), tb_per_s=round(moved / us / 1e6, 3))
+
+
+def part_augment(ds, args, results):
+    from tumblr_emotions_amd.image_model.im_model import load_batch_with_text
+    from tumblr_emotions_amd.preprocessing import inception_preprocessing as ip
+    for name, (h, w) in (("ordinary_375x500", (H, W)), ("fallback_50x1000", (50, 1000))):
+        n = 20000 if name.startswith("ordinary") else 2000
+        t0 = time.perf_counter()
+        for i in range(n):
+            ip.sample_train_params(h, w, ip.record_rng(0, 0, i))
+        emit(results, what="sample_train_params", size=name, us_per_image=round((time.perf_counter() - t0) / n * 1e6, 1))
+    kw = dict(batch_size=B, height=OUT, width=OUT, max_token_id=V, num_classes=15, pipeline='device', workers=8)
+    epoch = ds.num_samples // B
+    plain = load_batch_with_text(ds, **kw)
+    aug = load_batch_with_text(ds, is_training=True, **kw)
+    for it in (plain, aug):
+        for _ in range(epoch):
+            next(it)
+    rates = {"eval": [], "augment": []}
+    for _ in range(args.windows):
+        rates["eval"].append(_window(plain, args.seconds))
+        rates["augment"].append(_window(aug, args.seconds))
+    plain.close()
+    aug.close()
+    e, a = rates["eval"], rates["augment"]
+    emit(results, what="device_pipeline_augment", workers=8, windows=args.windows, seconds=args.seconds,
+         eval_images_per_s=[round(x, 1) for x in e], augment_images_per_s=[round(x, 1) for x in a],
+         eval_mean=round(float(np.mean(e)), 1), augment_mean=round(float(np.mean(a)), 1),
+         eval_spread=round(float(max(e) - min(e)), 1), ratio=round(float(np.mean(a) / np.mean(e)), 3))
+
+
 def kernel_stats(path, results):
-    """Average duration of preprocess_eval_kernel from a rocprofv3 --kernel-trace --stats csv (Name, Calls, ..., AverageNs)."""
+    """Average duration of the preprocessing kernels from a rocprofv3 --kernel-trace --stats csv (Name, Calls, ..., AverageNs)."""
     with open(path) as f:
         for row in csv.DictReader(f):
-            if "preprocess_eval_kernel" in row.get("Name", ""):
-                emit(results, what="ds_preprocess_eval_rocprofv3", calls=int(row["Calls"]),
-                     us_average=round(float(row["AverageNs"]) / 1e3, 1))
+            for k in ("preprocess_eval_kernel", "preprocess_train_kernel"):
+                if k in row.get("Name", ""):
+                    emit(results, what="ds_%s_rocprofv3" % k[:-len("_kernel")], calls=int(row["Calls"]),
+                         us_average=round(float(row["AverageNs"]) / 1e3, 1))
 
 
 if __name__ == "__main__":
@@ -172,6 +236,7 @@ if __name__ == "__main__":
     ap.add_argument("--out", default="bench_outputs/input_pipeline")
     ap.add_argument("--images", type=int, default=4096)
     ap.add_argument("--seconds", type=float, default=5.0)
+    ap.add_argument("--windows", type=int, default=4)
     ap.add_argument("--json", default=None)
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("parts", nargs="*", default=["loader", "train", "kernel"])
@@ -184,6 +249,7 @@ if __name__ == "__main__":
     else:
         ds = make_dataset(os.path.join(args.out, "dataset"), args.images)
         for p in args.parts:
-            {"loader": part_loader, "train": part_train, "kernel": part_kernel}[p](ds, args, results)
+            {"loader": part_loader, "train": part_train, "kernel": part_kernel, "kernel_train": part_kernel_train,
+             "augment": part_augment}[p](ds, args, results)
     with open(path, "w") as f:
         json.dump(results, f, indent=1)

@@ -27,6 +27,7 @@ DS_FAM_STEM_DGRAD = 9
 DS_PLAN_NO_WINO, DS_PLAN_NO_WINO4, DS_PLAN_NO_STEM_DIRECT, DS_PLAN_NO_BF16_DIRECT, DS_PLAN_ACT16, DS_PLAN_PACKED_RGB = 1, 2, 4, 8, 16, 32
 DS_PLAN_FP8_EVERYWHERE, DS_PLAN_FP8_WIDE_RULE, DS_PLAN_NO_WINO4H, DS_PLAN_STEM_POOL = 64, 128, 256, 512
 DS_PLAN_NO_SPLITK = 1024
+DS_PREPROCESS_FLIP, DS_PREPROCESS_SATURATION_FIRST = 1, 2
 
 
 class ConvDesc(C.Structure):
@@ -93,6 +94,12 @@ class SumSegments(C.Structure):
 class PreprocessDesc(C.Structure):
     """ds_preprocess_desc"""
     _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32), ("scale_y", C.c_float), ("scale_x", C.c_float)]
+
+
+class PreprocessTrainDesc(C.Structure):
+    """ds_preprocess_train_desc"""
+    _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32), ("scale_y", C.c_float), ("scale_x", C.c_float),
+                ("delta", C.c_float), ("factor", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 _P = C.c_void_p
@@ -213,6 +220,7 @@ SIGNATURES = {
     "ds_pad_channels": (C.c_int, [_P, _i32, _P, _i32, _i64, _P]),
     "ds_fill": (C.c_int, [_P, _i64, _f32, _P]),
     "ds_preprocess_eval": (C.c_int, [_P, _i64, _P, _i32, _P, _P, _i32, _i32, _P]),
+    "ds_preprocess_train": (C.c_int, [_P, _i64, _P, _i32, _P, _P, _i32, _i32, _P]),
 }
 
 _lib = None

@@ -68,6 +68,7 @@ class ImageModel(SyntheticInput):
 def train_image_model(checkpoints_dir, train_dir, num_steps, *, config=None, quiet=False):
     """Fine tune the Image model, retraining Mixed_5c (im_model.py:166-225)."""
     model = ImageModel(dict(_CONFIG, **(config or {})))
+    model.use_augmentation()
     init_fn = get_init_fn(checkpoints_dir)
     if init_fn is not None:
         init_fn(model.net)
@@ -87,7 +88,10 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
                          pipeline='host', workers=8, prefetch=2, decode_images=True):
     """Generator of training batches from a `datasets.convert_to_dataset.Dataset` -- the role of
     load_batch_with_text + tf.train.batch in the reference (im_model.py:78-116): decode the JPEG, apply the
-    EVAL preprocessing (is_training=False is what every reference call site uses, :78,102), batch.
+    EVAL preprocessing (is_training=False is what every reference call site uses, :78,102), batch.  is_training=True:
+    the train-time augmentation instead (preprocess_for_train: random crop, flip, brightness and saturation), each record's
+    draws taken from record_rng(seed, pass, global record index) -- the same in both pipelines, for any worker count and
+    world size; the order of the records and every other field are what they are with is_training=False.
     Yields dicts of device tensors: images [B,height,width,3] f32 in [-1,1], texts [B,50] i64, seq_lens,
     labels, post_ids, days.  Under data parallelism every rank reads the same stream and keeps examples
     rank, rank+world, ... (disjoint shards of one global order; the others are skipped BEFORE the JPEG is
@@ -96,7 +100,7 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
     range raises -- the gather would otherwise read zero rows / the loss kernel out of bounds.
     pipeline: 'host' (this generator: PIL decode + NumPy preprocessing on one thread, blocking uploads) or 'device'
     (input_pipeline.DeviceLoader: the same batches bit for bit and in the same order, decode on `workers` threads (at most
-    16), preprocessing in ds_preprocess_eval, `prefetch` batches uploaded ahead on a copy stream).  decode_images=False
+    16), preprocessing in ds_preprocess_eval / ds_preprocess_train, `prefetch` batches uploaded ahead on a copy stream).  decode_images=False
     (text-only models): the JPEGs are neither decoded nor preprocessed and the batches carry no 'images'."""
     if pipeline == 'device':
         from ..input_pipeline import DeviceLoader
@@ -112,10 +116,12 @@ def _host_batches(dataset, batch_size, shuffle, height, width, is_training, devi
                   num_classes, decode_images):
     """The host pipeline of load_batch_with_text (a generator)."""
     import torch
-    from ..preprocessing.inception_preprocessing import preprocess_image
+    from ..preprocessing.inception_preprocessing import preprocess_image, record_rng
     rng = np.random.RandomState(seed)
+    pass_no = -1
     buf = {k: [] for k in ("images", "texts", "seq_lens", "labels", "post_ids", "days") if decode_images or k != "images"}
     while True:
+        pass_no += 1
         sources = list(dataset.data_sources)
         if shuffle:
             rng.shuffle(sources)
@@ -131,7 +137,8 @@ def _host_batches(dataset, batch_size, shuffle, height, width, is_training, devi
             if num_classes is not None and not 0 <= int(ex["label"]) < num_classes:
                 raise ValueError("label %d outside [0, %d)" % (int(ex["label"]), num_classes))
             if decode_images:
-                buf["images"].append(preprocess_image(ex["image"], height, width, is_training=is_training))
+                buf["images"].append(preprocess_image(ex["image"], height, width, is_training=is_training,
+                                                      rng=record_rng(seed, pass_no, i) if is_training else None))
             buf["texts"].append(ex["text"])
             for k, s in (("seq_lens", "seq_len"), ("labels", "label"), ("post_ids", "post_id"), ("days", "day")):
                 buf[k].append(ex[s])

@@ -62,6 +62,7 @@ class DeepSentiment(SyntheticInput):
 def train_deep_sentiment(checkpoints_dir, train_dir, num_steps, *, config=None, quiet=False):
     """Fine tune the inception model, retraining the last layer (im_text_rnn_model.py:107-169)."""
     model = DeepSentiment(dict(_CONFIG, **(config or {})))
+    model.use_augmentation()
     init_fn = get_init_fn(checkpoints_dir)
     if init_fn is not None:
         init_fn(model.net)

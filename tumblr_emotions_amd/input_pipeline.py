@@ -1,5 +1,5 @@
 """Device input pipeline: the batches of `image_model.im_model.load_batch_with_text`, bit for bit and in the same order,
-with the eval preprocessing on the GPU (ds_preprocess_eval), the JPEG decode on a bounded pool of worker threads, and
+with the preprocessing on the GPU (ds_preprocess_eval; ds_preprocess_train with is_training=True), the JPEG decode on a bounded pool of worker threads, and
 the upload + preprocessing of the next batches overlapped with the training step.
 
     records (main feeder thread, file order)         raw TFRecord payloads of THIS rank only
@@ -10,6 +10,9 @@ the upload + preprocessing of the next batches overlapped with the training step
 
 The crop offsets / extents and the resize scales are computed with the very expressions of
 preprocessing/inception_preprocessing.py (Python doubles, then np.float32), so the kernel repeats no double arithmetic.
+With is_training=True a worker draws the record's augmentation parameters after the decode (the image size is known only
+then) from record_rng(seed, pass, global record index) -- the host generator's stream, so the batches stay equal whatever
+the worker count -- and slices the sampled crop instead of the central one; the feeder fills ds_preprocess_train_desc records.
 Source shuffling, the in-batch permutation and the ragged tail draw from one RandomState in the host generator's
 sequence.  Staging sets are filled by the feeder (not by the workers: an image's offset in the ragged buffer is known
 only once every earlier image of the batch has been decoded) and are reused only after the event of their last upload
@@ -47,14 +50,18 @@ def clamp_workers(workers):
     return max(1, min(int(workers), MAX_WORKERS))
 
 
-def pack_ragged(images, out_h, out_w, out=None, desc=None, align=4):
+def pack_ragged(images, out_h, out_w, out=None, desc=None, align=4, params=None):
     """Lay cropped uint8 HWC images back to back (each start rounded up to `align` bytes) and describe them.
     images: list of [h, w, 3] uint8 arrays; out: uint8 buffer to fill (a new one when None; ValueError when too small);
-    desc: descriptor array to fill (first len(images) records).  Returns (buffer, descriptors, bytes used)."""
-    from .ops import preprocess_desc_dtype
+    desc: descriptor array to fill (first len(images) records); params: one TrainParams per image (the images are their
+    sampled crops) -- the descriptors are then ds_preprocess_train_desc records.  Returns (buffer, descriptors, bytes used)."""
+    from .ops import preprocess_desc_dtype, preprocess_train_desc_dtype
+    from ._lib import DS_PREPROCESS_FLIP, DS_PREPROCESS_SATURATION_FIRST
     n = len(images)
+    if params is not None and len(params) != n:
+        raise ValueError("pack_ragged: one parameter set per image")
     if desc is None:
-        desc = np.zeros(n, preprocess_desc_dtype())
+        desc = np.zeros(n, preprocess_desc_dtype() if params is None else preprocess_train_desc_dtype())
     offsets, pos = [], 0
     for im in images:
         if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
@@ -67,7 +74,15 @@ def pack_ragged(images, out_h, out_w, out=None, desc=None, align=4):
         raise ValueError("pack_ragged: %d bytes do not fit a buffer of %d" % (pos, out.size))
     for i, (im, off) in enumerate(zip(images, offsets)):
         out[off:off + im.size].reshape(im.shape)[...] = im
-        desc[i] = (off, im.shape[0], im.shape[1], resize_scale(im.shape[0], out_h), resize_scale(im.shape[1], out_w))
+        geom = (off, im.shape[0], im.shape[1], resize_scale(im.shape[0], out_h), resize_scale(im.shape[1], out_w))
+        if params is None:
+            desc[i] = geom
+        else:
+            p = params[i]
+            if (p.crop_h, p.crop_w) != im.shape[:2]:
+                raise ValueError("pack_ragged: image %d is not the crop its parameters describe" % i)
+            flags = (DS_PREPROCESS_FLIP if p.flip else 0) | (DS_PREPROCESS_SATURATION_FIRST if p.saturation_first else 0)
+            desc[i] = geom + (p.delta, p.factor, flags, 0)
     return out, desc[:n], pos
 
 
@@ -128,9 +143,11 @@ class OrderedPool:
         self._threads = []
 
 
-def decode_record(rec, decode_image=True):
+def decode_record(rec, decode_image=True, train_key=None):
     """One TFRecord payload -> (cropped uint8 image or None, text int64[50], seq_len, label, post_id, day): the work of
-    Dataset.examples for one record plus central_crop (only the cropped region is ever uploaded)."""
+    Dataset.examples for one record plus central_crop (only the cropped region is ever uploaded).  train_key = (seed, pass,
+    global record index): the crop is the one sample_train_params draws from record_rng(*train_key), and the first item
+    is (crop, TrainParams)."""
     from .datasets.convert_to_dataset import _POST_SIZE
     from .datasets.tfrecord import decode_example
     ex = decode_example(rec)
@@ -138,8 +155,13 @@ def decode_record(rec, decode_image=True):
     if decode_image:
         from PIL import Image
         img = np.asarray(Image.open(io.BytesIO(ex['image/encoded'][0])).convert('RGB'))
-        y0, x0, ch, cw = crop_box(img.shape[0], img.shape[1])
-        img = np.ascontiguousarray(img[y0:y0 + ch, x0:x0 + cw])
+        if train_key is None:
+            y0, x0, ch, cw = crop_box(img.shape[0], img.shape[1])
+            img = np.ascontiguousarray(img[y0:y0 + ch, x0:x0 + cw])
+        else:
+            from .preprocessing.inception_preprocessing import record_rng, sample_train_params
+            p = sample_train_params(img.shape[0], img.shape[1], record_rng(*train_key))
+            img = (np.ascontiguousarray(img[p.y0:p.y0 + p.crop_h, p.x0:p.x0 + p.crop_w]), p)
     text = np.zeros(_POST_SIZE, np.int64)
     t = ex.get('text', [])
     text[:len(t)] = t
@@ -152,9 +174,10 @@ class _Staging:
     """One pinned staging set: ragged image bytes + descriptor table + the int64 fields, with the device byte buffer and
     descriptor table they are uploaded into and the event of the last upload."""
 
-    def __init__(self, batch_size, post_size, device, cuda):
+    def __init__(self, batch_size, post_size, device, cuda, train=False):
         import torch
-        from .ops import preprocess_desc_dtype
+        from . import ops
+        preprocess_desc_dtype = ops.preprocess_train_desc_dtype if train else ops.preprocess_desc_dtype
         self.torch, self.device, self.cuda = torch, device, cuda
         self.event = None
         self.ints = self._host(batch_size * (post_size + len(_FIELDS)), torch.int64)
@@ -204,10 +227,13 @@ _EPOCH = object()
 
 
 def _record_stream(dataset, shuffle, rng, rank, world, loop):
-    """Raw records of this rank in the host generator's order, _EPOCH between passes.  The source shuffle of a pass is
-    drawn when the first record of that pass is asked for, never earlier."""
+    """(pass number, global index within the pass, raw record) for the records of this rank in the host generator's order,
+    _EPOCH between passes.  The source shuffle of a pass is drawn when the first record of that pass is asked for, never
+    earlier."""
     from .datasets.tfrecord import read_records
+    pass_no = -1
     while True:
+        pass_no += 1
         sources = list(dataset.data_sources)
         if shuffle:
             rng.shuffle(sources)
@@ -218,14 +244,14 @@ def _record_stream(dataset, shuffle, rng, rank, world, loop):
                 if idx % world != rank:
                     continue                   # other ranks' records: never parsed, never decoded
                 n += 1
-                yield rec
+                yield pass_no, idx, rec
         if not loop or n == 0:
             return
         yield _EPOCH
 
 
 def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, world, seed, loop, max_token_id,
-            num_classes, decode_images, prefetch, inflight):
+            num_classes, decode_images, prefetch, inflight, train=False):
     import collections
     try:
         import torch
@@ -260,7 +286,9 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                 elif rec is _EPOCH:
                     boundary = True
                 else:
-                    pending.append(state.pool.submit(decode_record, rec, decode_images))
+                    pass_no, idx, payload = rec
+                    pending.append(state.pool.submit(decode_record, payload, decode_images,
+                                                     (seed, pass_no, idx) if train and decode_images else None))
             if not pending:
                 break
             img, text, seq_len, label, post_id, day = pending.popleft().result()
@@ -275,7 +303,7 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             order = rng.permutation(batch_size) if shuffle else np.arange(batch_size)
             if post_size is None:
                 post_size = len(buf[0][1])
-                stagings = [_Staging(batch_size, post_size, dev, cuda) for _ in range(max(2, prefetch + 1))]
+                stagings = [_Staging(batch_size, post_size, dev, cuda, train and decode_images) for _ in range(max(2, prefetch + 1))]
             st = stagings[turn]
             turn = (turn + 1) % len(stagings)
             st.wait_free()
@@ -287,9 +315,12 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             used = 0
             if decode_images:
                 images = [buf[j][0] for j in order]          # descriptor j = output slot j: the permutation costs nothing
+                params = None
+                if train:
+                    images, params = [im for im, _ in images], [p for _, p in images]
                 st.reserve(sum(-(-im.size // 4) * 4 for im in images))
-                _, _, used = pack_ragged(images, height, width, out=st.bytes.numpy(), desc=st.desc_np)
-                ops.check_preprocess_descs(st.desc_np[:batch_size], used)
+                _, _, used = pack_ragged(images, height, width, out=st.bytes.numpy(), desc=st.desc_np, params=params)
+                (ops.check_preprocess_train_descs if train else ops.check_preprocess_descs)(st.desc_np[:batch_size], used)
             buf = []
             out = {}
             if cuda:
@@ -297,8 +328,8 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                     if decode_images:
                         st.bytes_dev[:used].copy_(st.bytes[:used], non_blocking=True)
                         st.desc_dev.copy_(st.desc, non_blocking=True)
-                        out["images"] = ops.preprocess_eval(st.bytes_dev[:used], st.desc_np[:batch_size], height, width,
-                                                            desc_dev=st.desc_dev)
+                        run = ops.preprocess_train if train else ops.preprocess_eval
+                        out["images"] = run(st.bytes_dev[:used], st.desc_np[:batch_size], height, width, desc_dev=st.desc_dev)
                     ints_dev = st.ints.to(dev, non_blocking=True)
                     st.event = torch.cuda.Event()
                     st.event.record(stream)
@@ -334,13 +365,12 @@ class DeviceLoader:
     """Iterator over the batches of load_batch_with_text(pipeline='device').  `next(loader)` makes the current stream
     wait for the batch's upload + preprocessing (an event; the host is not blocked by the device) and returns the dict.
     close() -- also run by the context manager, by garbage collection of the loader and at interpreter exit -- stops the
-    feeder and joins every worker; a closed or exhausted loader raises StopIteration."""
+    feeder and joins every worker; a closed or exhausted loader raises StopIteration.  is_training=True: the train-time
+    augmentation (ds_preprocess_train) instead of the eval chain; ignored with decode_images=False."""
 
     def __init__(self, dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False, device="cuda",
                  rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None, workers=8, prefetch=2,
                  decode_images=True):
-        if is_training:
-            raise NotImplementedError("the reference's training path never uses the train-time augmentation")
         if batch_size < 1 or height < 1 or width < 1 or world < 1 or not 0 <= rank < world:
             raise ValueError("DeviceLoader: bad batch_size / height / width / rank / world")
         self.workers = clamp_workers(workers)
@@ -358,7 +388,7 @@ class DeviceLoader:
         st.thread = threading.Thread(target=_feeder, name="ds-input-feeder", daemon=True,
                                      args=(st, dataset, int(batch_size), bool(shuffle), int(height), int(width), device, rank,
                                            world, seed, bool(loop), max_token_id, num_classes, self.decode_images,
-                                           self.prefetch, inflight))
+                                           self.prefetch, inflight, bool(is_training)))
         self._finalizer = weakref.finalize(self, _shutdown, st)
         st.thread.start()
 

@@ -876,22 +876,49 @@ def preprocess_desc_dtype():
                      ("scale_y", np.float32), ("scale_x", np.float32)], align=True)
 
 
-def check_preprocess_descs(desc, nbytes):
-    """Every image of the descriptor table lies inside a byte buffer of `nbytes` bytes (the kernel cannot check): raises
-    ValueError before anything is launched."""
+def preprocess_train_desc_dtype():
+    """NumPy view of ds_preprocess_train_desc (40 bytes): the eval record + brightness delta, saturation factor, flags
+    (_lib.DS_PREPROCESS_FLIP | _lib.DS_PREPROCESS_SATURATION_FIRST) and a reserved word that stays 0."""
+    import numpy as np
+    return np.dtype([("offset", np.int64), ("height", np.int32), ("width", np.int32),
+                     ("scale_y", np.float32), ("scale_x", np.float32), ("delta", np.float32), ("factor", np.float32),
+                     ("flags", np.uint32), ("reserved", np.uint32)], align=True)
+
+
+def _check_descs(desc, nbytes, dtype, what):
     import numpy as np
     desc = np.asarray(desc)
-    if desc.dtype != preprocess_desc_dtype() or desc.ndim != 1 or desc.size == 0:
-        raise ValueError("preprocess_eval: descriptors must be a non-empty 1-D array of ops.preprocess_desc_dtype()")
+    if desc.dtype != dtype or desc.ndim != 1 or desc.size == 0:
+        raise ValueError("%s: descriptors must be a non-empty 1-D array of ops.%s()"
+                         % (what, "preprocess_train_desc_dtype" if what == "preprocess_train" else "preprocess_desc_dtype"))
     h, w, off = desc["height"].astype(np.int64), desc["width"].astype(np.int64), desc["offset"]
     bad = (h < 1) | (w < 1) | (off < 0) | (off + h * w * 3 > int(nbytes))
     if bad.any():
         i = int(np.flatnonzero(bad)[0])
-        raise ValueError("preprocess_eval: descriptor %d (offset %d, %d x %d pixels) does not fit the byte buffer of %d bytes"
-                         % (i, int(off[i]), int(h[i]), int(w[i]), int(nbytes)))
+        raise ValueError("%s: descriptor %d (offset %d, %d x %d pixels) does not fit the byte buffer of %d bytes"
+                         % (what, i, int(off[i]), int(h[i]), int(w[i]), int(nbytes)))
     if not (np.isfinite(desc["scale_y"]).all() and np.isfinite(desc["scale_x"]).all()
             and (desc["scale_y"] > 0).all() and (desc["scale_x"] > 0).all()):
-        raise ValueError("preprocess_eval: scales must be finite and positive")
+        raise ValueError("%s: scales must be finite and positive" % what)
+    return desc
+
+
+def check_preprocess_descs(desc, nbytes):
+    """Every image of the descriptor table lies inside a byte buffer of `nbytes` bytes (the kernel cannot check): raises
+    ValueError before anything is launched."""
+    _check_descs(desc, nbytes, preprocess_desc_dtype(), "preprocess_eval")
+
+
+def check_preprocess_train_descs(desc, nbytes):
+    """check_preprocess_descs for ds_preprocess_train_desc records; additionally delta and factor are finite, factor >= 0,
+    no unknown flag bit is set and the reserved word is 0."""
+    import numpy as np
+    desc = _check_descs(desc, nbytes, preprocess_train_desc_dtype(), "preprocess_train")
+    if not (np.isfinite(desc["delta"]).all() and np.isfinite(desc["factor"]).all() and (desc["factor"] >= 0).all()):
+        raise ValueError("preprocess_train: delta and factor must be finite and factor >= 0")
+    known = _lib.DS_PREPROCESS_FLIP | _lib.DS_PREPROCESS_SATURATION_FIRST
+    if (desc["flags"] & ~np.uint32(known)).any() or desc["reserved"].any():
+        raise ValueError("preprocess_train: unknown flag bits (or a non-zero reserved word)")
 
 
 _preprocess_lut = {}
@@ -908,28 +935,42 @@ def preprocess_lut(device):
     return _preprocess_lut[key]
 
 
+def _preprocess(what, check, itemsize, image_bytes, desc, out_h, out_w, desc_dev, out):
+    import numpy as np
+    if not image_bytes.is_cuda:
+        raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
+    if image_bytes.dtype != torch.uint8 or not image_bytes.is_contiguous():
+        raise ValueError("%s: image_bytes must be a contiguous uint8 tensor" % what)
+    if out_h < 1 or out_w < 1:
+        raise ValueError("%s: out_h and out_w must be positive" % what)
+    check(desc, image_bytes.numel())
+    B = int(np.asarray(desc).size)
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8)).to(image_bytes.device)
+    if desc_dev.numel() * desc_dev.element_size() < B * itemsize or not desc_dev.is_contiguous():
+        raise ValueError("%s: desc_dev is smaller than the descriptor table" % what)
+    if out is None:
+        out = torch.empty((B, out_h, out_w, 3), dtype=torch.float32, device=image_bytes.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * out_h * out_w * 3:
+        raise ValueError("%s: out must be a contiguous fp32 [B, out_h, out_w, 3] tensor" % what)
+    fn = getattr(_lib.load(), "ds_" + what)
+    _lib.check(fn(_p(image_bytes), image_bytes.numel(), _p(desc_dev), B, _p(preprocess_lut(image_bytes.device)),
+                  _p(out), out_h, out_w, _stream()), "ds_" + what)
+    return out
+
+
 def preprocess_eval(image_bytes, desc, out_h, out_w, desc_dev=None, out=None):
     """preprocess_for_eval of a ragged batch in one launch.  image_bytes: device uint8 tensor holding the centrally cropped
     HWC images back to back; desc: HOST array of ops.preprocess_desc_dtype() records (checked against the buffer's size
     here, before the launch); desc_dev: the same table already on the device (uploaded here when None); out: fp32
     [B, out_h, out_w, 3] (allocated when None).  Returns out."""
-    import numpy as np
-    if not image_bytes.is_cuda:
-        raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
-    if image_bytes.dtype != torch.uint8 or not image_bytes.is_contiguous():
-        raise ValueError("preprocess_eval: image_bytes must be a contiguous uint8 tensor")
-    if out_h < 1 or out_w < 1:
-        raise ValueError("preprocess_eval: out_h and out_w must be positive")
-    check_preprocess_descs(desc, image_bytes.numel())
-    B = int(np.asarray(desc).size)
-    if desc_dev is None:
-        desc_dev = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8)).to(image_bytes.device)
-    if desc_dev.numel() * desc_dev.element_size() < B * preprocess_desc_dtype().itemsize or not desc_dev.is_contiguous():
-        raise ValueError("preprocess_eval: desc_dev is smaller than the descriptor table")
-    if out is None:
-        out = torch.empty((B, out_h, out_w, 3), dtype=torch.float32, device=image_bytes.device)
-    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * out_h * out_w * 3:
-        raise ValueError("preprocess_eval: out must be a contiguous fp32 [B, out_h, out_w, 3] tensor")
-    _lib.check(_lib.load().ds_preprocess_eval(_p(image_bytes), image_bytes.numel(), _p(desc_dev), B, _p(preprocess_lut(image_bytes.device)),
-                                              _p(out), out_h, out_w, _stream()), "ds_preprocess_eval")
-    return out
+    return _preprocess("preprocess_eval", check_preprocess_descs, preprocess_desc_dtype().itemsize, image_bytes, desc,
+                       out_h, out_w, desc_dev, out)
+
+
+def preprocess_train(image_bytes, desc, out_h, out_w, desc_dev=None, out=None):
+    """preprocess_for_train of a ragged batch in one launch (ds_preprocess_train): as preprocess_eval, with the sampled
+    crops in image_bytes and ops.preprocess_train_desc_dtype() records, which also carry each image's flip, colour order,
+    brightness delta and saturation factor."""
+    return _preprocess("preprocess_train", check_preprocess_train_descs, preprocess_train_desc_dtype().itemsize,
+                       image_bytes, desc, out_h, out_w, desc_dev, out)

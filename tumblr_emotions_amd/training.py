@@ -134,13 +134,20 @@ class SyntheticInput:
     converted dataset (photos/train_valid_split.txt + tfrecords/tumblr_<mode>_*.tfrecord, the layout of
     datasets/convert_to_dataset.py:117-198) batches are read from it; otherwise they are synthetic.
     config['input_pipeline']: 'host' (default) or 'device' (input_pipeline.DeviceLoader: parallel decode on
-    config['input_workers'] threads, default 8, preprocessing on the GPU; the same batches bit for bit)."""
+    config['input_workers'] threads, default 8, preprocessing on the GPU; the same batches bit for bit).
+    config['augment'] (default False): the train-time augmentation of preprocess_for_train (load_batch_with_text's
+    is_training=True) on a real dataset -- honoured only once a trainer has called use_augmentation() (train_image_model,
+    train_deep_sentiment); evaluate_*, the analyses and class_visualisation always read eval-chain batches, as in the
+    reference (im_text_rnn_model.py:291,602).  With config['synthetic'] the key is a ValueError: there is no JPEG to augment."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
         self._in = (post_size, vocab_size, nb_emotions, with_images, device)
         self.post_ids = self.days = self.labels = None
         self._records = None
+        self._augment = False
+        if config.get("augment", False) and config.get("synthetic", False):
+            raise ValueError("config['augment'] needs a real dataset: synthetic batches have no JPEG to augment")
         ddir = config.get("dataset_dir")
         split = os.path.join(ddir or "", "photos", "train_valid_split.txt")
         if config.get("synthetic", False):
@@ -152,6 +159,12 @@ class SyntheticInput:
             raise IOError("no converted dataset under config['dataset_dir'] = %r (expected %s).  Set "
                           "config['synthetic'] = True for synthetic batches" % (ddir, split))
 
+    def use_augmentation(self):
+        """Called by the trainers of the models that read images, before the first batch: config['augment'] takes effect."""
+        if self._records is not None:
+            raise RuntimeError("use_augmentation() must precede the first batch")
+        self._augment = bool(self.config.get("augment", False))
+
     def next_batch(self, step):
         post_size, vocab, nb, with_images, device = self._in
         rank, world = _rank_world()
@@ -159,7 +172,7 @@ class SyntheticInput:
             if self._records is None:
                 from .image_model.im_model import load_batch_with_text
                 self._records = load_batch_with_text(self.dataset, self.config["batch_size"], height=224, width=224,
-                                                     device=device, rank=rank, world=world, max_token_id=vocab,
+                                                     is_training=self._augment, device=device, rank=rank, world=world, max_token_id=vocab,
                                                      num_classes=getattr(self.dataset, "num_classes", nb),
                                                      pipeline=self.config.get("input_pipeline", "host"),
                                                      workers=self.config.get("input_workers", 8),
