@@ -46,6 +46,12 @@ extern "C" {
                            /* + col] = the forward activation relu(bn(z)) of the layer that consumes dy.  They */
                            /* replace that layer's ds_bn_bwd_reduce pass over z and dy (ds_bn_bwd_finalize_segs,*/
                            /* kind 1).  Layout float[2][Cout][P] like DS_EPI_STATS; excludes STATS and MASK.     */
+#define DS_EPI_BN_RELU 64  /* inference forward (slim.batch_norm is_training=False + tf.nn.relu inside the conv): */
+                           /* y[row, col] = fmaxf(fmaf(acc, scale[col], shift[col]), 0) is stored at z (pixel      */
+                           /* stride ldz) and NOTHING else is written -- no z, no statistics.  scale / shift =     */
+                           /* ds_conv_io.scale / .shift (what ds_bn_infer_prepare* produce); bit-identical to the  */
+                           /* plain launch followed by ds_bn_apply_relu.  ds_conv_run only (fp32 forward plans,    */
+                           /* ds_conv_plan_enable_bn_relu); excludes STATS, BNSUMS, MASK, ACCUM, BIAS and RELU.    */
 
 int ds_version(void);
 const char *ds_last_error(void);
@@ -370,6 +376,12 @@ int ds_conv_wino4_bf16x2_x16(const void *x16, const void *u2, float *z, float *s
  *                            formed on load (d.pool_argmax = the winners' bytes, what ds_maxpool_fwd would record) and
  *                            plan.partials is recomputed; returns 1, or 0 when the chosen kernel cannot (the plan is unchanged
  *                            and the caller keeps the separate pool pass)
+ *   ds_conv_plan_enable_bn_relu   forward fp32 plan of an inference pass: replaces the plan's flags by DS_EPI_BN_RELU (the
+ *                            launch stores relu(acc * io.scale + io.shift) at z and nothing else) and returns 1 where the chosen
+ *                            family carries that epilogue -- implicit GEMM / wide 1x1 (also behind enable_pool3), F(2x2), F(4x4)
+ *                            and its split-K form (applied where the slices are combined); returns 0 and leaves the plan
+ *                            untouched for a dgrad, a plan that carries another epilogue, the stem and the 16-bit families.  It judges
+ *                            the plan's CURRENT plan.d.ldz (the stride of the tensor that receives y): set it first
  *   ds_conv_prepare_weights  plan.w_bytes > 0: converts the HWIO filter into the form the family reads (G g G^T, bf16 /
  *                            fp8 / three-piece K-loop order); redo whenever the filter changes.  fp8: wscale =
  *                            float[plan.wscale_floats]
@@ -429,6 +441,8 @@ typedef struct ds_conv_io {
     const ds_bn_finalize_in_launch *fin;   /* nullable: ds_bn_finalize inside the launch (ds_conv_plan_finalize_tickets > 0)   */
     void *ws;                /* plan.ws_bytes > 0: scratch of at least that many bytes (16-byte aligned), private to the stream  */
     size_t ws_bytes;
+    const float *scale;      /* DS_EPI_BN_RELU: per-column multiplier (rstd) and addend (shift), plan.d.Cout floats each,       */
+    const float *shift;      /* 16-byte aligned; ds_conv_run fails with DS_ERR_ARG before any launch when either is NULL         */
 } ds_conv_io;
 int ds_conv_plan(ds_conv_layer_plan *plan, int32_t role, int32_t arith, uint32_t options, int32_t N, int32_t H, int32_t W,
                  int32_t w_cin, int32_t w_cout, int32_t k, int32_t stride, int32_t ldx, int32_t ldz, int32_t flags);
@@ -437,6 +451,7 @@ int ds_conv_plan_enable_bnsums(ds_conv_layer_plan *plan, int32_t ldy);
 int ds_conv_plan_norm_supported(const ds_conv_layer_plan *plan);
 int ds_conv_plan_bnb_supported(const ds_conv_layer_plan *plan);      /* would ds_conv_run take plan.d.bnb?                 */
 int ds_conv_plan_enable_pool3(ds_conv_layer_plan *plan, uint8_t *argmax);
+int ds_conv_plan_enable_bn_relu(ds_conv_layer_plan *plan);
 int ds_conv_plan_finalize_tickets(const ds_conv_layer_plan *plan);      /* > 0: ds_conv_run honours io.fin (that many ticket words) */
 int ds_conv_prepare_weights(const ds_conv_layer_plan *plan, const float *w_hwio, void *w_prepared, float *wscale,
                             void *stream);
@@ -514,6 +529,14 @@ int ds_bn_apply_relu_z16(const void *z16, int64_t M, int32_t C, const float *rst
  * rstd = rsqrt(moving_variance + eps), shift = beta - moving_mean*rstd, then ds_bn_apply_relu.  */
 int ds_bn_infer_prepare(const float *beta, const float *moving_mean, const float *moving_var, float eps,
                         int32_t C, float *rstd, float *shift, void *stream);
+/* The same for every BatchNorm layer of a net in ONE launch (the inference forward prepares its 57 layers once per weight
+ * version instead of once per layer and call).  Per channel the arithmetic is ds_bn_infer_prepare's: bit-identical.        */
+typedef struct ds_bn_infer_job {
+    const float *beta, *moving_mean, *moving_var;      /* C floats each */
+    int32_t C;
+    float *rstd, *shift;                               /* out, C floats each */
+} ds_bn_infer_job;
+int ds_bn_infer_prepare_multi(const ds_bn_infer_job *jobs, int32_t njobs, float eps, void *stream);
 
 /* BatchNorm(train)+ReLU backward: g = dy*(y>0); dbeta = sum g; dz = rstd*(g - mean(g) - xhat*mean(g*xhat)).
  * dy is gathered from the same segments the forward scattered to.                          */

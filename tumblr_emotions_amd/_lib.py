@@ -17,6 +17,7 @@ def tuning_env(name, default=None):
 
 
 DS_EPI_BIAS, DS_EPI_RELU, DS_EPI_ACCUM, DS_EPI_STATS, DS_EPI_MASK, DS_EPI_BNSUMS = 1, 2, 4, 8, 16, 32
+DS_EPI_BN_RELU = 64
 DS_DTYPE_F32, DS_DTYPE_BF16 = 0, 1
 DS_FP8_E4M3, DS_FP8_E5M2 = 0, 1
 DS_CONV_FWD, DS_CONV_DGRAD = 0, 1
@@ -69,7 +70,8 @@ class LayerPlanStruct(C.Structure):
 class ConvIO(C.Structure):
     """ds_conv_io"""
     _fields_ = [("bias", C.c_void_p), ("mask", C.c_void_p), ("stats", C.c_void_p), ("pivot", C.c_void_p),
-                ("x_amax", C.c_void_p), ("wscale", C.c_void_p), ("fin", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+                ("x_amax", C.c_void_p), ("wscale", C.c_void_p), ("fin", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+                ("scale", C.c_void_p), ("shift", C.c_void_p)]
 
 
 class Segments(C.Structure):
@@ -83,6 +85,12 @@ class BnFinalizeJob(C.Structure):
     _fields_ = [("stats", C.c_void_p), ("P", C.c_int32), ("C", C.c_int32), ("count", C.c_int64), ("beta", C.c_void_p),
                 ("pivot", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("shift", C.c_void_p),
                 ("moving_mean", C.c_void_p), ("moving_var", C.c_void_p)]
+
+
+class BnInferJob(C.Structure):
+    """ds_bn_infer_job"""
+    _fields_ = [("beta", C.c_void_p), ("moving_mean", C.c_void_p), ("moving_var", C.c_void_p), ("C", C.c_int32),
+                ("rstd", C.c_void_p), ("shift", C.c_void_p)]
 
 
 class SumSegments(C.Structure):
@@ -168,6 +176,7 @@ SIGNATURES = {
     "ds_conv_plan_norm_supported": (C.c_int, [_LP]),
     "ds_conv_plan_bnb_supported": (C.c_int, [_LP]),
     "ds_conv_plan_enable_pool3": (C.c_int, [_LP, C.c_void_p]),
+    "ds_conv_plan_enable_bn_relu": (C.c_int, [_LP]),
     "ds_conv_plan_finalize_tickets": (C.c_int, [_LP]),
     "ds_conv_prepare_weights": (C.c_int, [_LP, _P, _P, _P, _P]),
     "ds_conv_run": (C.c_int, [_LP, _P, _P, _P, _IO, _P]),
@@ -179,6 +188,7 @@ SIGNATURES = {
     "ds_bn_apply_relu_z16": (C.c_int, [_P, _i64, _i32, _P, _P, _SG, _P]),
     "ds_bn_bwd_apply_z16": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _i32, _P, _P]),
     "ds_bn_infer_prepare": (C.c_int, [_P, _P, _P, _f32, _i32, _P, _P, _P]),
+    "ds_bn_infer_prepare_multi": (C.c_int, [_P, _i32, _f32, _P]),
     "ds_bn_bwd_partials": (C.c_int, [_i64, _i32]),
     "ds_bn_bwd_reduce": (C.c_int, [_P, _i32, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P]),
     "ds_bn_bwd_finalize_segs": (C.c_int, [_SS, _i64, _i32, _P, _P, _P, _P]),

@@ -681,6 +681,46 @@ extern "C" int ds_bn_infer_prepare(const float *beta, const float *moving_mean, 
     return ds::check_launch("ds_bn_infer_prepare");
 }
 
+// ds_bn_infer_prepare_multi: every layer of a net in one grid -- blockIdx.x = job, blockIdx.y = its 256-channel chunk; per
+// channel the expressions of bn_infer_prepare_kernel
+constexpr int kInferJobsMax = 64;
+struct InferJobsDev {
+    const float *beta[kInferJobsMax], *mm[kInferJobsMax], *mv[kInferJobsMax];
+    float *rstd[kInferJobsMax], *shift[kInferJobsMax];
+    int C[kInferJobsMax];
+};
+
+__global__ __launch_bounds__(256) void bn_infer_prepare_multi_kernel(const InferJobsDev jb, float eps) {
+    const int j = blockIdx.x;
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c < jb.C[j]) {
+        const float *mv = jb.mv[j], *mm = jb.mm[j], *beta = jb.beta[j];
+        const float r = 1.0f / sqrtf(mv[c] + eps);
+        jb.rstd[j][c] = r;
+        jb.shift[j][c] = beta[c] - mm[c] * r;
+    }
+}
+
+extern "C" int ds_bn_infer_prepare_multi(const ds_bn_infer_job *jobs, int32_t njobs, float eps, void *stream) {
+    DS_REQUIRE(jobs && njobs >= 1, "ds_bn_infer_prepare_multi: at least one job required");
+    for (int i = 0; i < njobs; ++i)
+        DS_REQUIRE(jobs[i].beta && jobs[i].moving_mean && jobs[i].moving_var && jobs[i].rstd && jobs[i].shift && jobs[i].C > 0,
+                   "ds_bn_infer_prepare_multi: job %d is malformed", i);
+    for (int i0 = 0; i0 < njobs; i0 += kInferJobsMax) {      // (one launch for up to 64 layers: the tower has 57)
+        InferJobsDev jb = {};
+        const int n = njobs - i0 < kInferJobsMax ? njobs - i0 : kInferJobsMax;
+        int cmax = 0;
+        for (int i = 0; i < n; ++i) {
+            const ds_bn_infer_job &j = jobs[i0 + i];
+            jb.beta[i] = j.beta; jb.mm[i] = j.moving_mean; jb.mv[i] = j.moving_var;
+            jb.rstd[i] = j.rstd; jb.shift[i] = j.shift; jb.C[i] = j.C;
+            if (j.C > cmax) cmax = j.C;
+        }
+        hipLaunchKernelGGL(bn_infer_prepare_multi_kernel, dim3(n, (cmax + 255) / 256), dim3(256), 0, (hipStream_t)stream, jb, eps);
+    }
+    return ds::check_launch("ds_bn_infer_prepare_multi");
+}
+
 extern "C" int ds_bn_apply_relu(const float *z, int64_t M, int32_t C, const float *rstd, const float *shift,
                                 const ds_segments *dst, void *stream) {
     DS_REQUIRE(z && rstd && shift && M > 0 && C > 0 && C % 4 == 0, "ds_bn_apply_relu: bad argument (C %% 4 != 0?)");

@@ -57,6 +57,7 @@ struct ConvParams {
     int pool_rpb, pool_bpi;      // gemm_wide_kernel<.., POOL = true>: image rows per 32-pixel block, blocks per image
     ds_bn_finalize_in_launch fin;      // gemm_wide_kernel: copy of *d.fin (fin.ticket == nullptr: the caller finalizes)
     double fin_inv_count;
+    const float *scale, *shift;  // DS_EPI_BN_RELU (the <.., BNR = true> instantiations): Cout floats each
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void *p, unsigned bytes) {
@@ -109,7 +110,9 @@ __device__ __forceinline__ f32x4 load4(__amdgpu_buffer_rsrc_t r, unsigned off, b
 
 // second launch-bound = waves per SIMD the register allocator must leave room for: the small tiles
 // are the workhorses and measured fastest at 3-4 resident workgroups per CU
-template <int MT, int NT, bool BNMAJOR, bool FOLD, bool VEC>
+// BNR: the inference epilogue DS_EPI_BN_RELU, y = max(fma(acc, scale[col], shift[col]), 0) stored in place of z -- its own
+// instantiation (forward, vector loads, MT = 1), so the training kernels' code is untouched
+template <int MT, int NT, bool BNMAJOR, bool FOLD, bool VEC, bool BNR = false>
 __global__ __launch_bounds__(256, (MT == 1 && NT == 1) ? 4 : (MT == 1 && NT == 2) ? 3 : 1) void conv_igemm_kernel(
     const ConvParams p) {
     constexpr int WM = 4;
@@ -334,6 +337,18 @@ __global__ __launch_bounds__(256, (MT == 1 && NT == 1) ? 4 : (MT == 1 && NT == 2
             const float bv = ((flags & DS_EPI_BIAS) && colok) ? p.bias[col] : 0.f;
             const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;      // statistics are taken about the pivot
             float s = 0.f, q = 0.f;
+            if constexpr (BNR) {          // scale / shift once per column, then nothing but stores
+                const float sc = colok ? p.scale[col] : 0.f, sh = colok ? p.shift[col] : 0.f;
+#pragma unroll
+                for (int a = 0; a < MT; ++a) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = m0 + wm * MT * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                        if (row < p.M && colok) zout[(int64_t)row * d.ldz + col] = fmaxf(fmaf(acc[a][b][r], sc, sh), 0.f);
+                    }
+                }
+                continue;
+            }
 #pragma unroll
             for (int a = 0; a < MT; ++a) {
 #pragma unroll
@@ -617,7 +632,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvParams p) {
 constexpr int GK = 32;            // K-tile (floats)
 constexpr int GCH = GK / 4;       // 16-byte chunks per row
 
-template <int NT, bool BNMAJOR>
+template <int NT, bool BNMAJOR, bool BNR = false>      // BNR: DS_EPI_BN_RELU (see conv_igemm_kernel)
 __global__ __launch_bounds__(256, NT == 1 ? 4 : (NT == 2 ? 3 : 2)) void conv_glds_kernel(const ConvParams p) {
     constexpr int BM = 128, BN = NT * 32;
     constexpr int ASZ = BM * GK, BSZ = BN * GK;       // floats per buffer
@@ -813,6 +828,15 @@ __global__ __launch_bounds__(256, NT == 1 ? 4 : (NT == 2 ? 3 : 2)) void conv_gld
             const float bv = ((flags & DS_EPI_BIAS) && colok) ? p.bias[col] : 0.f;
             const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;      // statistics are taken about the pivot
             float s = 0.f, q = 0.f;
+            if constexpr (BNR) {
+                const float sc = colok ? p.scale[col] : 0.f, sh = colok ? p.shift[col] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                    if (row < p.M && colok) zout[(int64_t)row * d.ldz + col] = fmaxf(fmaf(acc[b][r], sc, sh), 0.f);
+                }
+                continue;
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
@@ -1143,7 +1167,7 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void conv_bf16_kernel(const C
 template <int N>
 __device__ __forceinline__ void barrier_keep_vm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory"); }
 
-template <int NB, bool BNMAJOR, bool BNB = false, bool POOL = false, int AST = 0>
+template <int NB, bool BNMAJOR, bool BNB = false, bool POOL = false, int AST = 0, bool BNR = false>      // BNR: DS_EPI_BN_RELU (see conv_igemm_kernel)
 __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const ConvParams p) {
     constexpr int BN = NB * 32, WK = 16;                       // K step: 16 channels = two float4 per lane
     constexpr int DJ = (WK * BN / 4 + 255) / 256;              // 16-byte DMA slots per thread per K step: ceil(NB / 2)
@@ -1506,10 +1530,17 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         __builtin_amdgcn_raw_buffer_store_b32(bits, srd_z, v + (unsigned)(((r & 3) + 8 * (r >> 2)) * rz), 0, 2 /* nt */);
     };
     float pss[NB], pqq[NB];                          // (threads 0..31) this workgroup's partials of column block b
+    float bsc[BNR ? NB : 1], bsh[BNR ? NB : 1];      // BNR: scale / shift of this lane's column of block b (read phase)
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const int col = n0 + 32 * b + li;
         const bool colok = item && col < d.Cout;
+        if constexpr (BNR) {
+            bsc[b] = colok ? p.scale[col] : 0.f;
+            bsh[b] = colok ? p.shift[col] : 0.f;
+            pss[b] = pqq[b] = 0.f;
+            continue;
+        }
         const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;
         const unsigned vz = colok ? (unsigned)(rbase * d.ldz + col) * 4u : kOOB;
         const unsigned vm = colok ? (unsigned)(rbase * d.ldmask + col) * 4u : kOOB;
@@ -1578,8 +1609,10 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         const bool colok = item && col < d.Cout;
         const unsigned vz = colok ? (unsigned)(rbase * d.ldz + col) * 4u : kOOB;
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-            st_row(acc[b][r], vz, r);
+        for (int r = 0; r < 16; ++r) {
+            if constexpr (BNR) st_row(fmaxf(fmaf(acc[b][r], bsc[b], bsh[b]), 0.f), vz, r);
+            else st_row(acc[b][r], vz, r);
+        }
         if ((flags & (DS_EPI_STATS | DS_EPI_BNSUMS)) && tid < 32 && item && n0 + 32 * b + tid < d.Cout) {
             float *const sp = p.stats + (int64_t)(n0 + 32 * b + tid) * t0.stride + t0.row;
             float *const qp = p.stats + ((int64_t)d.Cout + n0 + 32 * b + tid) * t0.stride + t0.row;
@@ -2037,6 +2070,25 @@ KernelFn direct_kernel_m(int nt, Variant v) {
     }
 }
 
+// DS_EPI_BN_RELU instantiations: forward (n-contiguous weights), 16-byte loads, 128-row tiles
+KernelFn bnr_kernel(TileCfg c) {
+    if (c.glds) {
+        switch (c.nt) {
+            case 1: return conv_glds_kernel<1, true, true>;
+            case 2: return conv_glds_kernel<2, true, true>;
+            default: return conv_glds_kernel<3, true, true>;
+        }
+    }
+    switch (c.nt) {
+        case 1: return conv_igemm_kernel<1, 1, true, false, true, true>;
+        case 2: return conv_igemm_kernel<1, 2, true, false, true, true>;
+        case 3: return conv_igemm_kernel<1, 3, true, false, true, true>;
+        case 4: return conv_igemm_kernel<1, 4, true, false, true, true>;
+        case 5: return conv_igemm_kernel<1, 5, true, false, true, true>;
+        default: return conv_igemm_kernel<1, 6, true, false, true, true>;
+    }
+}
+
 KernelFn glds_kernel(int nt, Variant v) {
     switch (nt) {
         case 1: return v.bnmajor ? conv_glds_kernel<1, true> : conv_glds_kernel<1, false>;
@@ -2063,6 +2115,20 @@ KernelFn bf16_kernel(int nt, Variant v) {
 }
 
 void launch_wide(int nb, bool bnmajor, bool bnb, dim3 grid, hipStream_t st, const ConvParams &p) {
+    if (p.d.flags & DS_EPI_BN_RELU) {          // (bnr_supported: forward, no bnb)
+#define DS_WIDE_BNR(NBV, POOLV) \
+    case NBV: hipLaunchKernelGGL((gemm_wide_kernel<NBV, true, false, POOLV, 0, true>), grid, dim3(256), 0, st, p); break;
+        if (p.d.pool_argmax) {
+            switch (nb) { DS_WIDE_BNR(1, true) DS_WIDE_BNR(2, true) DS_WIDE_BNR(3, true) default: DS_WIDE_BNR(4, true) }
+        } else {
+            switch (nb) {
+                DS_WIDE_BNR(1, false) DS_WIDE_BNR(2, false) DS_WIDE_BNR(3, false) DS_WIDE_BNR(4, false)
+                DS_WIDE_BNR(5, false) DS_WIDE_BNR(6, false) DS_WIDE_BNR(7, false) default: DS_WIDE_BNR(8, false)
+            }
+        }
+#undef DS_WIDE_BNR
+        return;
+    }
     if (p.d.pool_argmax) {          // (pool3_nb: forward, one column tile of at most four blocks)
         switch (nb) {
             case 1: hipLaunchKernelGGL((gemm_wide_kernel<1, true, false, true>), grid, dim3(256), 0, st, p); break;
@@ -2127,7 +2193,7 @@ int force_wide = -1;
 int pool3_nb(const ds_conv_desc *d, bool vec) {
     if (!vec || d->dtype != DS_DTYPE_F32) return 0;
     if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->fold_cin || d->splits > 1 || d->bnb) return 0;
-    if (d->flags & ~DS_EPI_STATS) return 0;
+    if (d->flags & ~(DS_EPI_STATS | DS_EPI_BN_RELU)) return 0;
     if (!(d->w_n_stride == 1 && d->w_k_stride != 1)) return 0;
     if (d->W > 32 || d->Cin % 16 != 0 || d->Cin < 32 || d->Cin > 1024 || d->Cout > 128) return 0;
     const int64_t M = conv_M(d);
@@ -2149,7 +2215,7 @@ int wide_nb(const ds_conv_desc *d, bool vec, bool bnb_cap = false) {
     }
     if (!force_wide || !vec || d->dtype != DS_DTYPE_F32) return 0;
     if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->fold_cin || d->splits > 1) return 0;
-    if (d->flags & ~(DS_EPI_STATS | DS_EPI_ACCUM | DS_EPI_BNSUMS)) return 0;
+    if (d->flags & ~(DS_EPI_STATS | DS_EPI_ACCUM | DS_EPI_BNSUMS | DS_EPI_BN_RELU)) return 0;
     if (d->Cin % 8 != 0 || d->Cin < 32) return 0;
     const int64_t M = conv_M(d);
     // the epilogue addresses z (and the BatchNorm-sums activation) through 32-bit buffer offsets
@@ -2330,6 +2396,14 @@ void grid_for(const ds_conv_desc *d, TileCfg c, Variant v, int *gx, int *gy, int
     if (one_per_tile) *one_per_tile = one;
 }
 
+// Would the launch picked for `d` carry DS_EPI_BN_RELU?  The forward fp32 instantiations: n-contiguous weights, 16-byte loads
+// (pointer alignment is checked at launch), 128-row tiles of the LDS / LDS-DMA kernels or the wide 1x1 kernel.
+bool bnr_supported(const ds_conv_desc *d, TileCfg c, Variant v) {
+    if (d->dtype != DS_DTYPE_F32 || !v.bnmajor || !v.vec || v.fold || d->splits > 1 || d->bnb || d->fin) return false;
+    if (c.bf16 || c.direct || c.mt != 1) return false;
+    return true;
+}
+
 }  // namespace
 
 #ifdef DS_TUNING
@@ -2406,14 +2480,48 @@ extern "C" int ds_conv_igemm_finalize_tickets(const ds_conv_desc *d) {
     return rt <= 256 ? gy : 0;
 }
 
+// ds_conv_plan_enable_bn_relu's question for this family: would the launch picked for `d` carry DS_EPI_BN_RELU?  (forward
+// fp32: n-contiguous weights, strides and channel counts divisible by 4, LDS-tile / LDS-DMA / wide 1x1 kernel, with or
+// without pool_argmax; the kernel and tile are the ones the same descriptor gets without the flag)
+namespace ds {
+int conv_igemm_bn_relu_supported(const ds_conv_desc *d) {
+    if (!d || (d->flags & ~DS_EPI_BN_RELU)) return 0;
+    ds_conv_desc t = *d;
+    t.flags = DS_EPI_BN_RELU;
+    const Variant v = {t.w_n_stride == 1 && t.w_k_stride != 1, t.fold_cin > 0, dims_vec(&t)};
+    return bnr_supported(&t, pick_cfg(&t, v.vec), v) ? 1 : 0;
+}
+}  // namespace ds
+
 extern "C" int ds_conv_igemm_bnb_supported(const ds_conv_desc *d) {
     // BatchNorm backward on load lives in the wide 1x1 kernel's loader, k-contiguous-weights (dgrad) instantiation
     if (!d || d->Cin > 1024 || (d->w_n_stride == 1 && d->w_k_stride != 1) || d->norm_rstd) return 0;
     return wide_nb(d, dims_vec(d), true) > 0 ? 1 : 0;      // with the launch's own cap of two column blocks per wave
 }
 
+namespace {
+int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *bias, const float *mask,
+                 float *stats, const float *pivot, const float *scale, const float *shift, void *stream);
+}
+
 extern "C" int ds_conv_igemm(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *bias,
                              const float *mask, float *stats, const float *pivot, void *stream) {
+    DS_REQUIRE(!d || !(d->flags & DS_EPI_BN_RELU), "ds_conv_igemm: DS_EPI_BN_RELU takes its scale / shift through ds_conv_run (ds_conv_io)");
+    return igemm_launch(d, x, w, z, bias, mask, stats, pivot, nullptr, nullptr, stream);
+}
+
+// ds_conv_run's entry for DS_EPI_BN_RELU plans of this family
+namespace ds {
+int conv_igemm_bn_relu(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *scale, const float *shift,
+                       void *stream) {
+    DS_REQUIRE(d && (d->flags & DS_EPI_BN_RELU) && scale && shift, "ds_conv_run: DS_EPI_BN_RELU without scale / shift");
+    return igemm_launch(d, x, w, z, nullptr, nullptr, nullptr, nullptr, scale, shift, stream);
+}
+}  // namespace ds
+
+namespace {
+int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *bias, const float *mask,
+                 float *stats, const float *pivot, const float *scale, const float *shift, void *stream) {
     DS_REQUIRE(d && x && w && z, "ds_conv_igemm: null argument");
     DS_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->N > 0 && d->OH > 0 && d->OW > 0, "ds_conv_igemm: bad dims");
     DS_REQUIRE(d->w_n_stride == 1 || d->w_k_stride == 1, "ds_conv_igemm: one weight stride must be 1");
@@ -2458,6 +2566,11 @@ extern "C" int ds_conv_igemm(const ds_conv_desc *d, const float *x, const float 
                "ds_conv_igemm: split-K needs flags == 0 and non-overlapping output slabs");
     if (splits == 1) p.d.z_split_stride = 0;
     const TileCfg c = pick_cfg(d, v.vec);
+    const bool bnr = (d->flags & DS_EPI_BN_RELU) != 0;
+    DS_REQUIRE(!bnr || (d->flags == DS_EPI_BN_RELU && scale && shift && bnr_supported(d, c, v)),
+               "ds_conv_igemm: DS_EPI_BN_RELU excludes every other epilogue flag, needs scale / shift and a forward fp32 launch "
+               "with 16-byte aligned operands (ds_conv_plan_enable_bn_relu)");
+    p.scale = scale; p.shift = shift;
     int gx, gy, rt;
     bool one;
     grid_for(d, c, v, &gx, &gy, &rt, &one);
@@ -2517,9 +2630,10 @@ extern "C" int ds_conv_igemm(const ds_conv_desc *d, const float *x, const float 
         pool3_blocks(d, &p.pool_rpb, &p.pool_bpi);
     }
     if (c.wide) launch_wide(c.wide, v.bnmajor, d->bnb != nullptr, grid, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(kernel_for(c, v), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(bnr ? bnr_kernel(c) : kernel_for(c, v), grid, dim3(256), 0, (hipStream_t)stream, p);
     return ds::check_launch("ds_conv_igemm");
 }
+}  // namespace
 
 // ---- bf16 register-direct path -------------------------------------------------------------------------------------
 namespace {

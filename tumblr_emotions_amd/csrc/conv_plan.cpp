@@ -14,6 +14,15 @@
 
 namespace ds {
 void set_error(const char *fmt, ...);
+// the families' DS_EPI_BN_RELU launches (conv_igemm.hip, conv_wino.hip, conv_wino4.hip)
+int conv_igemm_bn_relu_supported(const ds_conv_desc *d);
+int conv_igemm_bn_relu(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *scale, const float *shift,
+                       void *stream);
+int conv_wino_bn_relu(const float *x, const float *u, float *z, const float *scale, const float *shift, int32_t N, int32_t H,
+                      int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz, void *stream);
+int conv_wino4_bn_relu(const float *x, const float *u, float *z, const float *scale, const float *shift, int32_t N, int32_t H,
+                       int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz, int32_t splits, void *ws, size_t ws_bytes,
+                       void *stream);
 }
 
 #define PLAN_REQUIRE(cond, ...)         \
@@ -205,6 +214,7 @@ extern "C" int ds_conv_plan(ds_conv_layer_plan *out, int32_t role, int32_t arith
     case DS_FAM_F32X3: out->w_bytes = (int64_t)ds_weights_f32x3_bytes(w_cin, w_cout, taps, dgrad); break;
     default: out->w_bytes = 0;          // reads the HWIO filter in place
     }
+    PLAN_REQUIRE(!(flags & DS_EPI_BN_RELU), "ds_conv_plan: DS_EPI_BN_RELU is added by ds_conv_plan_enable_bn_relu");
     if (is_wino(out)) PLAN_REQUIRE(!(flags & ~(DS_EPI_STATS | DS_EPI_BNSUMS)), "ds_conv_plan: Winograd epilogues are STATS / BNSUMS");
     out->partials = plan_partials(out);
     if (fam == DS_FAM_IGEMM) d.partials = out->partials;
@@ -271,6 +281,25 @@ extern "C" int ds_conv_plan_enable_pool3(ds_conv_layer_plan *p, uint8_t *argmax)
     return 1;
 }
 
+extern "C" int ds_conv_plan_enable_bn_relu(ds_conv_layer_plan *p) {
+    // forward fp32 plans without another epilogue; the family (and, inside the implicit GEMM, the kernel and tile) stays the
+    // one the plan already has, so the accumulators are those of the plain launch
+    if (p == nullptr || p->role != DS_CONV_FWD || p->d.dtype != DS_DTYPE_F32 || p->d.flags != 0) return 0;
+    if (p->family == DS_FAM_IGEMM) {
+        ds_conv_desc t = p->d;
+        t.partials = 0;
+        if (!ds::conv_igemm_bn_relu_supported(&t)) return 0;
+    } else if (p->family == DS_FAM_WINO4) {
+        if (p->d.ldz % 4 != 0 || p->d.ldz < p->d.Cout) return 0;
+    } else if (p->family != DS_FAM_WINO2) {
+        return 0;      // the stem keeps its pool-stage BatchNorm; F32X3 and the 16-bit families are out of scope
+    }
+    p->d.flags = DS_EPI_BN_RELU;
+    p->d.partials = 0;
+    p->partials = 0;
+    return 1;
+}
+
 extern "C" int ds_conv_plan_finalize_tickets(const ds_conv_layer_plan *p) {
     if (p == nullptr || p->role != DS_CONV_FWD || p->family != DS_FAM_IGEMM) return 0;
     ds_conv_desc t = p->d;
@@ -304,6 +333,23 @@ extern "C" int ds_conv_run(const ds_conv_layer_plan *p, const void *x, const voi
     static const ds_conv_io none = {};
     if (io == nullptr) io = &none;
     const ds_conv_desc &d = p->d;
+    if (d.flags & DS_EPI_BN_RELU) {
+        PLAN_REQUIRE(io->scale && io->shift, "ds_conv_run: DS_EPI_BN_RELU needs io.scale and io.shift");
+        PLAN_REQUIRE(d.flags == DS_EPI_BN_RELU, "ds_conv_run: DS_EPI_BN_RELU excludes every other epilogue flag");
+        switch (p->family) {
+        case DS_FAM_IGEMM: return ds::conv_igemm_bn_relu(&d, (const float *)x, (const float *)w, z, io->scale, io->shift, stream);
+        case DS_FAM_WINO2:
+            return ds::conv_wino_bn_relu((const float *)x, (const float *)w, z, io->scale, io->shift, d.N, d.H, d.W, d.Cin, d.ldx,
+                                         d.Cout, d.ldz, stream);
+        case DS_FAM_WINO4:
+            PLAN_REQUIRE(p->splitk <= 1 || (io->ws && io->ws_bytes >= (size_t)p->ws_bytes), "ds_conv_run: this plan needs io.ws of %lld bytes",
+                         (long long)p->ws_bytes);
+            return ds::conv_wino4_bn_relu((const float *)x, (const float *)w, z, io->scale, io->shift, d.N, d.H, d.W, d.Cin, d.ldx,
+                                          d.Cout, d.ldz, p->splitk, io->ws, io->ws_bytes, stream);
+        default: break;
+        }
+        PLAN_REQUIRE(false, "ds_conv_run: family %d does not carry DS_EPI_BN_RELU (ds_conv_plan_enable_bn_relu)", p->family);
+    }
     switch (p->family) {
     case DS_FAM_IGEMM:
         if (io->fin && (d.flags & DS_EPI_STATS)) {      // ds_bn_finalize inside the launch

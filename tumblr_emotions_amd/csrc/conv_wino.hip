@@ -51,6 +51,7 @@ struct WinoParams {
     int groups, ncol;       // 128-tile groups, 32-channel blocks
     unsigned x_bytes, u_bytes, z_bytes;
     int flags;
+    const float *scale, *shift;      // DS_EPI_BN_RELU (conv_wino_kernel<false, true>): Cout floats each
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t wsrd(const void *p, unsigned bytes) {
@@ -72,7 +73,9 @@ __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
     return f32x4{lo[0], lo[1], hi[0], hi[1]};
 }
 
-template <bool BNS>      // BNS: DS_EPI_BNSUMS epilogue (its own instantiation: the plain kernel's code is untouched)
+// BNS: DS_EPI_BNSUMS epilogue (its own instantiation: the plain kernel's code is untouched); BNR: the inference epilogue
+// DS_EPI_BN_RELU, y = max(fma(y, scale[col], shift[col]), 0) stored in place of z, no statistics (its own instantiation too)
+template <bool BNS, bool BNR = false>
 __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoParams p) {
     // B tile of one K step: [16 positions][32 channels][8 ci] floats = 16 KB, two buffers
     __shared__ __attribute__((aligned(128))) float smem[2 * 16 * 32 * 8];
@@ -216,6 +219,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoParams p) {
     const unsigned right = (unsigned)p.ldz * 4u, below = (unsigned)(p.W * p.ldz) * 4u;
     const unsigned cbyte = colok ? (unsigned)col * 4u : kOOB;
     float s = 0.f, q = 0.f;
+    float bsc = 0.f, bsh = 0.f;          // BNR: this lane's column (read before the first store)
+    if constexpr (BNR) {
+        if (colok) { bsc = p.scale[col]; bsh = p.shift[col]; }
+    }
     if constexpr (!BNS) {
     #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -242,6 +249,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoParams p) {
             const unsigned off[4] = {ob, ob + right, ob + below, ob + below + right};
     #pragma unroll
             for (int k = 0; k < 4; ++k) {
+                if constexpr (BNR) {
+                    const float yy = fmaxf(fmaf(y[k], bsc, bsh), 0.f);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, yy), srd_z, ok[k] ? off[k] + cbyte : kOOB, 0, 2 /* nt */);
+                    continue;
+                }
                 if (!(p.flags & 1024))
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[k]), srd_z, ok[k] ? off[k] + cbyte : kOOB, 0, 2 /* nt */);
                 const float u = ok[k] ? y[k] - pv : 0.f;
@@ -312,7 +324,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoParams p) {
         }
 
     }
-    if (BNS || (p.flags & DS_EPI_STATS)) {
+    if (!BNR && (BNS || (p.flags & DS_EPI_STATS))) {
         float *red = smem;        // [4 waves][32][2]; every wave passed the last K-loop barrier, no DMA in flight
         s += __shfl_xor(s, 32);
         q += __shfl_xor(q, 32);
@@ -394,10 +406,36 @@ extern "C" int ds_conv_wino_partials(int32_t N, int32_t H, int32_t W) {
     return (int)((mt + 127) / 128);
 }
 
+namespace {
+int wino_launch(const float *x, const float *u, float *z, float *stats, const float *pivot, const float *ymask, const float *scale,
+                const float *shift, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz,
+                int32_t flags, void *stream);
+}
+
 extern "C" int ds_conv_wino(const float *x, const float *u, float *z, float *stats, const float *pivot, const float *ymask,
                             int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz,
                             int32_t flags, void *stream) {
+    DS_REQUIRE(!(flags & DS_EPI_BN_RELU), "ds_conv_wino: DS_EPI_BN_RELU takes its scale / shift through ds_conv_run (ds_conv_io)");
+    return wino_launch(x, u, z, stats, pivot, ymask, nullptr, nullptr, N, H, W, Cin, ldx, Cout, ldz, flags, stream);
+}
+
+// ds_conv_run's entry for DS_EPI_BN_RELU plans of this family
+namespace ds {
+int conv_wino_bn_relu(const float *x, const float *u, float *z, const float *scale, const float *shift, int32_t N, int32_t H,
+                      int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz, void *stream) {
+    DS_REQUIRE(scale && shift, "ds_conv_run: DS_EPI_BN_RELU without scale / shift");
+    return wino_launch(x, u, z, nullptr, nullptr, nullptr, scale, shift, N, H, W, Cin, ldx, Cout, ldz, DS_EPI_BN_RELU, stream);
+}
+}  // namespace ds
+
+namespace {
+int wino_launch(const float *x, const float *u, float *z, float *stats, const float *pivot, const float *ymask, const float *scale,
+                const float *shift, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz,
+                int32_t flags, void *stream) {
     DS_REQUIRE(x && u && z && N > 0 && H > 0 && W > 0, "ds_conv_wino: bad argument");
+    const bool bnr = (flags & DS_EPI_BN_RELU) != 0;
+    DS_REQUIRE(!bnr || (flags == DS_EPI_BN_RELU && scale && shift), "ds_conv_wino: DS_EPI_BN_RELU excludes every other flag and needs scale / shift");
+    if (bnr) flags = 0;          // (the checks below and the kernel's flag word know the training epilogues only)
     DS_REQUIRE(Cin > 0 && Cin % 8 == 0 && ldx % 4 == 0 && ldx >= Cin && Cout > 0 && ldz >= Cout &&
                    ((((uintptr_t)x | (uintptr_t)u) & 15) == 0),
                "ds_conv_wino: needs Cin %% 8 == 0, ldx %% 4 == 0 and 16-byte aligned operands");
@@ -412,6 +450,7 @@ extern "C" int ds_conv_wino(const float *x, const float *u, float *z, float *sta
     WinoParams p;
     p.x = x; p.u = u; p.z = z; p.stats = stats; p.pivot = (flags & DS_EPI_STATS) ? pivot : nullptr;
     p.y = (flags & DS_EPI_BNSUMS) ? ymask : nullptr;
+    p.scale = scale; p.shift = shift;
     p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ldx; p.Cout = Cout; p.ldz = ldz;
     p.TH = (H + 1) / 2; p.TW = (W + 1) / 2;
     const int64_t mt = (int64_t)N * p.TH * p.TW;
@@ -427,7 +466,9 @@ extern "C" int ds_conv_wino(const float *x, const float *u, float *z, float *sta
     p.groups = (int)((mt + 127) / 128);
     p.ncol = (Cout + 31) / 32;
     const dim3 grid((unsigned)(((int64_t)p.groups * p.ncol + 7) / 8 * 8));
-    if (flags & DS_EPI_BNSUMS) hipLaunchKernelGGL(conv_wino_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    if (bnr) hipLaunchKernelGGL((conv_wino_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (flags & DS_EPI_BNSUMS) hipLaunchKernelGGL(conv_wino_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(conv_wino_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
     return ds::check_launch("ds_conv_wino");
 }
+}  // namespace

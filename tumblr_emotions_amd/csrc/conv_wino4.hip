@@ -63,6 +63,7 @@ struct Wino4Params {
     long long zslab;        // ... floats between the slices' partial outputs (z then points at slab 0, pixel stride ldz)
     unsigned x_bytes, u_bytes, z_bytes;
     int flags;
+    const float *scale, *shift;      // DS_EPI_BN_RELU (conv_wino4_kernel<.., BNR = true>): Cout floats each, 16-byte aligned
 #ifdef DS_W4_PROF
     unsigned long long *prof;      // [workgroup][16] s_memtime stamps (scripts/wino4_phase_prof.py builds this variant)
 #endif
@@ -200,7 +201,9 @@ __device__ __forceinline__ void out1d(float m1, f32x4 m0, f32x4 a1, f32x4 a2, f3
 // Everything else -- tiles, roles, software pipeline, epilogue -- is the fp32 kernel's.
 // X16 (AR = 1 only): x itself is stored as bf16 (the 16-bit configurations' dz, ds_bn_bwd_apply_bf16): a channel pair is one
 // 4-byte load and already the rounded operand -- the same bits as rounding the fp32 tensor on load, half the pixel bytes
-template <int NB, bool BNS, bool EDGE, int AR = 0, bool Y16 = false, bool X16 = false>      // EDGE: H or W is not a multiple of four (partial last tile row / column); Y16: the BatchNorm-sums activation is stored as bf16
+// BNR: the inference epilogue DS_EPI_BN_RELU -- y = max(fma(y, scale[col], shift[col]), 0) stored in place of z, no statistics;
+// a compile-time variant, so the training instantiations (at the register ceiling) keep their code
+template <int NB, bool BNS, bool EDGE, int AR = 0, bool Y16 = false, bool X16 = false, bool BNR = false>      // EDGE: H or W is not a multiple of four (partial last tile row / column); Y16: the BatchNorm-sums activation is stored as bf16
 __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const Wino4Params p) {
     static_assert(!X16 || AR == 1, "16-bit x storage goes with the bf16 matrix cores");
     constexpr unsigned EB = X16 ? 2u : 4u;          // bytes per element of x
@@ -597,7 +600,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const Wino4Params p)
         const int col = co0 + 32 * nb + 4 * eq;                 // first of this thread's four channels (Cout % 4 == 0)
         const bool colok = col < p.Cout;
         f32x4 pv = {0.f, 0.f, 0.f, 0.f};
-        if (!BNS && p.pivot && colok) pv = *reinterpret_cast<const f32x4 *>(p.pivot + col);
+        if (!BNS && !BNR && p.pivot && colok) pv = *reinterpret_cast<const f32x4 *>(p.pivot + col);
+        f32x4 bsc = {0.f, 0.f, 0.f, 0.f}, bsh = {0.f, 0.f, 0.f, 0.f};      // BNR: read with the block's other operands, before its stores
+        if constexpr (BNR) {
+            if (colok) {
+                bsc = *reinterpret_cast<const f32x4 *>(p.scale + col);
+                bsh = *reinterpret_cast<const f32x4 *>(p.shift + col);
+            }
+        }
         const unsigned vo = (tbase >= 0 && colok) ? (unsigned)(tbase * p.ldz + col) * 4u : kOOB;
         // DS_EPI_BNSUMS: the consumer's activations at the sixteen store offsets, ALL requested here -- in front of the
         // gathers and of every store of this pass.  Requested row by row inside the store loop, each row's reads sat behind
@@ -638,6 +648,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const Wino4Params p)
             out1d(neg1, P[rr][0], P[rr][1], P[rr][2], P[rr][3], P[rr][4], P[rr][5], y[0], y[1], y[2], y[3]);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
+                if constexpr (BNR) y[k] = __builtin_elementwise_max(__builtin_elementwise_fma(y[k], bsc, bsh), f32x4{0.f, 0.f, 0.f, 0.f});
                 // the pixel's offset goes into the VECTOR offset, the scalar offset stays the constant 0: with an SGPR there
                 // the compiler assumes that a 16-byte buffer store has no "VALU overwrites the store data" hazard (true on
                 // gfx900) and schedules the writes of y's registers right behind the store -- on gfx950 the store then
@@ -649,7 +660,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const Wino4Params p)
                     for (int c = 0; c < 4; ++c) g[c] = yv[k][c] > 0.f ? y[k][c] : 0.f;      // (an out-of-range offset reads y = 0)
                     s += g;
                     q = qfma(g, yv[k], q);
-                } else {
+                } else if constexpr (!BNR) {
                     // pixels outside the image (EDGE) and tiles / channels past the end do not count: on full maps the
                     // condition is the thread's own (vo), applied once behind the loop
                     f32x4 uu = qfma(q4(neg1), pv, y[k]);
@@ -661,7 +672,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const Wino4Params p)
         }
         if (!BNS && !EDGE && vo == kOOB) s = q = f32x4{0.f, 0.f, 0.f, 0.f};
         W4_STAMP(5 + 3 * nb);     // gathered, transformed, stores issued
-        if (BNS || (p.flags & DS_EPI_STATS)) {
+        if (!BNR && (BNS || (p.flags & DS_EPI_STATS))) {
             // the 32 tiles of a channel: every thread leaves its four channels' partial sums in LDS, then 64 threads (channel,
             // sum | sum of squares) add the 32 tiles in index order.  (Was: three rounds of eight ds_bpermute shuffles, a
             // four-wave combine and a barrier -- 1 us per channel block, measured by scripts/wino4_phase_prof.py.)
@@ -871,6 +882,28 @@ __global__ __launch_bounds__(256) void wino4_splitk_reduce_kernel(const float *s
     }
 }
 
+// DS_EPI_BN_RELU behind split K: the slices' sum (in slice order, as above) is the conv output, so this is where
+// y = max(fma(sum, scale, shift), 0) is formed and stored.  Its own kernel: the training reduce kernels above are untouched.
+__global__ __launch_bounds__(256) void wino4_splitk_bn_relu_kernel(const float *slab, int S, int64_t zslab, float *y, int ldz,
+                                                                   int64_t M, int C, int rpb, const float *scale,
+                                                                   const float *shift) {
+    const int C4 = C >> 2;
+    const int RG = 256 / C4 > 0 ? 256 / C4 : 1;
+    const int tid = threadIdx.x;
+    const int cg = tid % C4, rg = tid / C4;
+    if (tid >= RG * C4) return;
+    const int64_t r0 = (int64_t)blockIdx.x * rpb;
+    int64_t r1 = r0 + rpb;
+    if (r1 > M) r1 = M;
+    const int c = cg * 4;
+    const f32x4 bsc = *reinterpret_cast<const f32x4 *>(scale + c), bsh = *reinterpret_cast<const f32x4 *>(shift + c);
+    for (int64_t row = r0 + rg; row < r1; row += RG) {
+        f32x4 v = *reinterpret_cast<const f32x4 *>(slab + row * C + c);
+        for (int k = 1; k < S; ++k) v += *reinterpret_cast<const f32x4 *>(slab + k * zslab + row * C + c);
+        *reinterpret_cast<f32x4 *>(y + row * ldz + c) = __builtin_elementwise_max(__builtin_elementwise_fma(v, bsc, bsh), f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+}
+
 // rows per workgroup of the reduce launch: about 512 workgroups, at least 8 rows (a thread then walks 2-4 rows of S slabs: with
 // 64 rows per workgroup the 7x7 maps of 32 samples gave 25 workgroups and the reduce launch took longer than the conv it followed)
 inline int splitk_rpb(int64_t M) {
@@ -962,8 +995,12 @@ extern "C" int ds_conv_wino4_partials(int32_t N, int32_t H, int32_t W) {
 namespace {
 int w4_launch(int ar, bool y16, const float *x, const float *u, float *z, float *stats, const float *pivot, const float *ymask,
               int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz, int32_t flags, void *stream,
-              bool x16 = false, int ksplit = 1, float *slabs = nullptr) {
+              bool x16 = false, int ksplit = 1, float *slabs = nullptr, const float *scale = nullptr, const float *shift = nullptr) {
     DS_REQUIRE(x && u && z && N > 0, "ds_conv_wino4: bad argument");
+    const bool bnr = (flags & DS_EPI_BN_RELU) != 0;
+    DS_REQUIRE(!bnr || (flags == DS_EPI_BN_RELU && ar == 0 && scale && shift && ((((uintptr_t)scale) | ((uintptr_t)shift)) & 15) == 0),
+               "ds_conv_wino4: DS_EPI_BN_RELU is the fp32 kernel's, excludes every other flag and needs 16-byte aligned scale / shift");
+    if (bnr) flags = 0;          // (the checks below and the kernel's flag word know the training epilogues only)
     DS_REQUIRE(ksplit == 1 || (ar == 0 && slabs && ksplit >= 2 && ksplit <= Cin / 16), "ds_conv_wino4_splitk: 2 .. Cin / 16 slices, fp32, with a workspace");
     DS_REQUIRE(ds_conv_wino4_supported(H, W, Cin, Cout) && ldx >= Cin && ldx % 2 == 0 && ldz >= Cout && ldz % 4 == 0 && ((((uintptr_t)u) | ((uintptr_t)z)) & 15) == 0 &&
                    (((uintptr_t)x) & (x16 ? 3 : 7)) == 0 && (!x16 || ar == 1) && (!(flags & DS_EPI_BNSUMS) || (((uintptr_t)ymask) & 15) == 0) &&
@@ -988,6 +1025,7 @@ int w4_launch(int ar, bool y16, const float *x, const float *u, float *z, float 
     DS_REQUIRE(zb * 4 < (1ll << 31), "ds_conv_wino4: output larger than 2 GiB");
     p.z_bytes = (unsigned)(zb * 4);
     p.flags = flags;
+    p.scale = scale; p.shift = shift;
 #ifdef DS_W4_PROF
     p.prof = g_w4_prof;
 #endif
@@ -1018,7 +1056,12 @@ int w4_launch(int ar, bool y16, const float *x, const float *u, float *z, float 
         else if (ar) hipLaunchKernelGGL((conv_wino4_kernel<NBV, BNSV, EDGEV, 1>), grid, dim3(256), 0, st, p);   \
         else hipLaunchKernelGGL((conv_wino4_kernel<NBV, BNSV, EDGEV, 0>), grid, dim3(256), 0, st, p);           \
     } while (0)
-    if (nb == 2) {
+    if (bnr && ksplit == 1) {          // (split K: the conv launch is the plain one, the reduce launch carries the epilogue)
+#define DS_W4_BNR(NBV, EDGEV) hipLaunchKernelGGL((conv_wino4_kernel<NBV, false, EDGEV, 0, false, false, true>), grid, dim3(256), 0, st, p)
+        if (nb == 2) { if (edge) DS_W4_BNR(2, true); else DS_W4_BNR(2, false); }
+        else { if (edge) DS_W4_BNR(1, true); else DS_W4_BNR(1, false); }
+#undef DS_W4_BNR
+    } else if (nb == 2) {
         if (bns) { if (edge) DS_W4_LAUNCH(2, true, true); else DS_W4_LAUNCH(2, true, false); }
         else { if (edge) DS_W4_LAUNCH(2, false, true); else DS_W4_LAUNCH(2, false, false); }
     } else {
@@ -1030,7 +1073,9 @@ int w4_launch(int ar, bool y16, const float *x, const float *u, float *z, float 
         const int rpb = splitk_rpb(Mpix), P = (int)((Mpix + rpb - 1) / rpb);
         const int C4 = Cout / 4, RG = 256 / C4 > 0 ? 256 / C4 : 1;
         const size_t shm = (size_t)RG * C4 * 8 * sizeof(float);
-        if (flags & DS_EPI_BNSUMS) {
+        if (bnr) {
+            hipLaunchKernelGGL(wino4_splitk_bn_relu_kernel, dim3(P), dim3(256), 0, st, slabs, p.ksplit, (int64_t)p.zslab, z, ldz, Mpix, Cout, rpb, scale, shift);
+        } else if (flags & DS_EPI_BNSUMS) {
             if (y16) hipLaunchKernelGGL((wino4_splitk_reduce_kernel<2, true>), dim3(P), dim3(256), shm, st, slabs, p.ksplit, (int64_t)p.zslab, z, ldz, Mpix, Cout, nullptr, (const void *)ymask, stats, rpb);
             else hipLaunchKernelGGL((wino4_splitk_reduce_kernel<2, false>), dim3(P), dim3(256), shm, st, slabs, p.ksplit, (int64_t)p.zslab, z, ldz, Mpix, Cout, nullptr, (const void *)ymask, stats, rpb);
         } else if (flags & DS_EPI_STATS) {
@@ -1068,6 +1113,23 @@ extern "C" int ds_conv_wino4_splitk(const float *x, const float *u, float *z, fl
     return w4_launch(0, y_dtype == DS_DTYPE_BF16, x, u, z, stats, pivot, ymask, N, H, W, Cin, ldx, Cout, ldz, flags, stream, false,
                      splits, (float *)ws);
 }
+
+// ds_conv_run's entry for DS_EPI_BN_RELU plans of this family (splits > 1: the split-K form with its workspace)
+namespace ds {
+int conv_wino4_bn_relu(const float *x, const float *u, float *z, const float *scale, const float *shift, int32_t N, int32_t H,
+                       int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz, int32_t splits, void *ws, size_t ws_bytes,
+                       void *stream) {
+    DS_REQUIRE(scale && shift, "ds_conv_run: DS_EPI_BN_RELU without scale / shift");
+    if (splits > 1) {
+        DS_REQUIRE(ws && ws_bytes >= ds_conv_wino4_splitk_workspace(N, H, W, Cout, splits) && (((uintptr_t)ws) & 15) == 0 && Cout <= 1024,
+                   "ds_conv_wino4_splitk: needs a 16-byte aligned workspace of ds_conv_wino4_splitk_workspace bytes, Cout <= 1024");
+        return w4_launch(0, false, x, u, z, nullptr, nullptr, nullptr, N, H, W, Cin, ldx, Cout, ldz, DS_EPI_BN_RELU, stream, false, splits,
+                         (float *)ws, scale, shift);
+    }
+    return w4_launch(0, false, x, u, z, nullptr, nullptr, nullptr, N, H, W, Cin, ldx, Cout, ldz, DS_EPI_BN_RELU, stream, false, 1, nullptr,
+                     scale, shift);
+}
+}  // namespace ds
 
 extern "C" int ds_conv_wino4(const float *x, const float *u, float *z, float *stats, const float *pivot, const float *ymask,
                              int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t ldx, int32_t Cout, int32_t ldz,

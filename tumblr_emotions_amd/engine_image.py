@@ -115,6 +115,8 @@ class ConvBN:
             self.amax = torch.zeros(2, ops.AMAX_FLOATS, device=dev)      # fallback records for ds_absmax passes
             self.dz_amax = eng.new_amax()                # max|dz|, collected by ds_bn_bwd_apply
         self.u_version = -1
+        self._fused = None            # the forward plan's DS_EPI_BN_RELU variant (fused_plan(): made at the first fused forward)
+        eng._fused_key = None
         eng.need_stats(self.fwd.partials * 2 * cout)
         self.bwd_P = ops.bn_bwd_partials(self.M, cout)
         eng.need_bwd_partials(self.bwd_P * 2 * cout)
@@ -369,6 +371,38 @@ class ConvBN:
                 and self.dy_parts is not None:
             self.bnb = self.dgrad.enable_bn_backward_on_load(self.mean, self.rstd, self.shift, self.coef, self.dy_parts)
 
+    # ---- fused inference forward (InceptionV1Engine.forward(fused=True)) ----------------------------------------------
+    def fused_plan(self, ldz=None):
+        """The forward plan with BatchNorm + ReLU in the conv epilogue, storing with pixel stride `ldz` (shares the training
+        plan's prepared filter and workspace; the training plan itself is not touched), or None where the library cannot;
+        plus this layer's own scale / shift vectors, which no training pass reads or writes."""
+        if self._fused is None:
+            q = None if self.fold else self.fwd.bn_relu_variant(ldz)
+            self._fused = (q,)
+            if q is not None:
+                self.f_scale = torch.empty(self.cout, device=self.eng.device)
+                self.f_shift = torch.empty(self.cout, device=self.eng.device)
+        return self._fused[0]
+
+    def fused_target(self, segs):
+        """(address, pixel stride) of the ONE fp32 tensor that receives relu(bn(conv)), or the reason (str) why this layer
+        keeps conv -> apply inside a fused forward."""
+        if self.fold:
+            return "stem: the pool stage applies BatchNorm + ReLU to the pooled map"
+        if self.skip_apply:           # its slice of the block's concat buffer (the consumers then load activations: (1, 0))
+            tgt = (self.z.data_ptr(), self.ldz)
+        elif segs is None:
+            return "feeds only a max pool, which applies BatchNorm + ReLU to the pooled map"
+        elif segs.nseg != 1:
+            return "output scatters to %d destinations" % segs.nseg
+        elif segs.dtype[0] != ops.DS_DTYPE_F32:
+            return "16-bit destination"
+        else:
+            tgt = (segs.ptr[0], segs.ld[0])
+        if self.fused_plan(tgt[1]) is None or tgt[0] % 16:
+            return "kernel family %d does not carry the epilogue for this destination" % self.fwd.family
+        return tgt
+
     def _refresh_weights(self):
         """The prepared filter forms (G g G^T for the Winograd kernels, the bf16 / fp8 / three-piece K-loop orders):
         redone when the weights changed -- every step for a trainable layer (Adam moves them), once per load for a
@@ -432,6 +466,19 @@ class ConvBN:
                 else:
                     ops.bn_finalize(self.stats_buf, plan.partials, count, self.cout, self.beta, BN_EPS, BN_DECAY, self.mean,
                                     self.rstd, self.shift, mm, mv, pivot=self.mean)
+        elif eng.fused_infer:  # moving statistics, BatchNorm + ReLU in the conv epilogue where the layer allows
+            # (rstd, shift) of every layer were prepared once for this weight version (InceptionV1Engine._fused_prepare): the
+            # fused layers' in f_scale / f_shift, the others' where the per-call ds_bn_infer_prepare leaves them
+            tgt = eng._fused_targets.get(id(self))
+            if tgt is None:
+                tgt = eng._fused_targets[id(self)] = self.fused_target(segs)
+            if not isinstance(tgt, str):
+                q = self._fused[0]
+                q.d.ldx = ldx
+                q.run_bn_relu(x_ptr, self.w_ptr, _vp(tgt[0]), self.f_scale.data_ptr(), self.f_shift.data_ptr())
+                return
+            plan.d.flags = 0
+            plan.run(x_ptr, self.w_ptr, ops._p(self.z), x_amax=amax_p)
         else:                  # moving statistics (is_training=False: evaluate_* on the validation split)
             plan.d.flags = 0
             # (z16: z centred about the moving mean; with it the shift is beta itself: infer_prepare on a zero mean)
@@ -622,8 +669,15 @@ class ConvStage(Stage):
     def forward(self):
         # fused_into_pool: this conv feeds nothing but the next max pool, which then reads z and applies BN + ReLU
         # after pooling (a quarter of the elements); `out` is not produced
-        self.layer.forward(ops._p(self.prev.out), self.prev.C, None if self.fused_into_pool else self.segs,
+        self.layer.forward(ops._p(self.prev.out), self.prev.C, None if self.pool_applies_bn() else self.segs,
                            ops.act_dtype(self.prev.out), getattr(self.prev, "out_amax", None))
+
+    def pool_applies_bn(self):
+        """Does the max pool behind this conv apply BatchNorm + ReLU (to the pooled map, from z)?  Not in a fused inference
+        forward, where the conv's epilogue has applied them: the pool then takes the maximum of activations
+        (max relu(bn(z)) = relu(bn(max z)) bit for bit -- rstd > 0 and rounding are monotonic) -- except behind the stem, whose
+        kernel keeps its own arrangement."""
+        return self.fused_into_pool and not (self.eng.fused_infer and not self.layer.fold)
 
     def backward(self, need_dx):
         need_dx = need_dx and (not self.layer.fold or self.eng.input_grad)      # (the stem: the image gradient, input_backward)
@@ -702,7 +756,7 @@ class PoolStage(Stage):
                     self.apply_segs = make_segments([(0, self.C, self.out.data_ptr(), self.C, ops.act_dtype(self.out), ops._p(am))])
                 ops.bn_apply_relu(p.layer.z, self.B * self.H * self.W, self.C, self.rs[0], self.rs[1], self.apply_segs)
             return
-        if getattr(p, "fused_into_pool", False):
+        if getattr(p, "fused_into_pool", False) and p.pool_applies_bn():
             ops.maxpool_bn_relu_fwd(p.layer.z, p.layer.rstd, p.layer.shift, self.out, self.argmax, self.B, p.H, p.W, p.C,
                                     self.k, self.stride, amax=self._own_amax if getattr(self, "track_amax", True) else None)
         elif getattr(p, "zcat", False):      # the block's concat holds pre-BatchNorm values: normalise on load
@@ -1222,6 +1276,13 @@ class InceptionV1Engine:
         self.text_gate = int(e) if e else None
         self.text_gate_event = None
         self.weights_version = 0     # bumped by SentimentNet.after_load(): frozen layers redo their G g G^T
+        # forward(fused=True): the inference forward with BatchNorm + ReLU in the conv epilogues (fp32).  _fused_key: the weight
+        # version the prepared (rstd, shift) vectors belong to; None after a load, a training step, a plain forward or alloc
+        self.fused_infer = False
+        self.fused_request = False
+        self._fused_key = None
+        self._fused_targets = {}
+        self._fused_jobs = None
         # input gradients wanted (forward(input_grad=True) .. the next plain forward): the stem runs unpooled (ConvStage.alloc);
         # _pivots keeps the statistics pivots of the training state that was left, so the next training step is unchanged
         self.input_grad = False
@@ -1412,10 +1473,54 @@ class InceptionV1Engine:
             self._restore_pivots, self._pivots = self._pivots, None
             self.B = None
 
-    def forward(self, images, dropout_mask=None, seed=0, input_grad=False):
+    def invalidate_fused(self):
+        """The moving statistics or beta changed (load, training step) or a plain forward overwrote the per-layer rstd / shift."""
+        self._fused_key = None
+
+    def _fused_prepare(self):
+        """ds_bn_infer_prepare of all 57 layers as ONE launch, once per weight version: fused layers get their own scale / shift
+        (a layer that writes into a zcat concat slice also sets its slice of the block's on-load vectors to (1, 0): the consumers
+        then read activations), the others the vectors their apply pass / pool stage reads."""
+        if self._fused_key == (self.weights_version, self.alloc_gen):
+            return
+        if self._fused_jobs is None or self._fused_jobs[0] != self.alloc_gen:
+            self._fused_targets = {}
+            jobs = []
+            for st in self.stages:
+                if isinstance(st, ConvStage):
+                    pairs = [(st.layer, None if st.pool_applies_bn() else st.segs)]
+                elif isinstance(st, MixedStage):
+                    pairs = [(st.fused, st.seg_f), (st.c1, st.seg_1), (st.c2, st.seg_2), (st.c3, st.seg_3)]
+                else:
+                    pairs = []
+                for l, segs in pairs:
+                    tgt = self._fused_targets[id(l)] = l.fused_target(segs)
+                    on = not isinstance(tgt, str)
+                    jobs.append((l.beta, l.mm, l.mv, l.cout, l.f_scale if on else l.rstd, l.f_shift if on else l.shift))
+            self._fused_jobs = (self.alloc_gen, ops.BnInferJobs(jobs))
+        self._fused_jobs[1].run(BN_EPS)
+        for l in self.layers:
+            if l.skip_apply and not isinstance(self._fused_targets[id(l)], str):
+                ops.fill(l.rstd, l.cout, 1.0)
+                ops.fill(l.shift, l.cout, 0.0)
+        self._fused_key = (self.weights_version, self.alloc_gen)
+
+    def fused_report(self):
+        """[(layer key, reason)] of the layers that kept conv -> ds_bn_apply_relu (or a pool-stage BatchNorm) in the last fused
+        forward; every other conv layer ran with BatchNorm + ReLU in its epilogue."""
+        return [(l.key, self._fused_targets[id(l)]) for l in self.layers
+                if isinstance(self._fused_targets.get(id(l)), str)]
+
+    def forward(self, images, dropout_mask=None, seed=0, input_grad=False, fused=None):
         """images: [B,224,224,3] fp32 NHWC in [-1,1] (preprocess_for_eval range).  Returns the
-        internal logits buffer [B,num_classes].  input_grad: the pass input_backward() differentiates (unpooled stem)."""
+        internal logits buffer [B,num_classes].  input_grad: the pass input_backward() differentiates (unpooled stem).
+        fused: moving-statistics forward with BatchNorm + ReLU inside the conv launches (fp32, not training)."""
         B = images.shape[0]
+        if fused is None:             # (SentimentNet.predict(fused=True) reaches this pass through the autograd function)
+            fused = self.fused_request
+        if fused and (self.training or input_grad or self.dtype != "f32" or self.mul3):
+            raise ValueError("the fused forward is the fp32 moving-statistics pass (is_training=False)")
+        self.fused_infer = bool(fused)
         self._set_input_grad(input_grad)
         self.alloc(B)
         if self._restore_pivots is not None:
@@ -1443,6 +1548,10 @@ class InceptionV1Engine:
         if not stem.stem_direct or (stem.trainable and self.training):
             # the generic stem kernel and the stem's wgrad (train_all) read a zero-padded 4-channel copy
             ops.pad_channels(images, 3, self.input.out, 4, B * self.input.H * self.input.W)
+        if self.fused_infer:
+            self._fused_prepare()
+        else:
+            self._fused_key = None      # (this pass leaves its own rstd / shift in the vectors the fused pass prepared)
         gate = self.text_gate
         for i, s in enumerate(self.stages):
             s.forward()

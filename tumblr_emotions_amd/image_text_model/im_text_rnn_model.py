@@ -95,7 +95,7 @@ def _forward_batches(model, nb_batches, want_features=False):
     """Yield (logits, labels, days, post_ids[, concat_features]) as numpy arrays for `nb_batches` batches."""
     for i in range(nb_batches):
         batch = model.next_batch(10 ** 6 + i)
-        logits = model.net.predict(batch, is_training=False)
+        logits = model.net.predict(batch, is_training=False, fused=bool(model.config.get('fused_inference', False)))
         out = [logits.cpu().numpy(), batch["labels"].cpu().numpy(), model.days.cpu().numpy(),
                model.post_ids.cpu().numpy()]
         if want_features:
@@ -182,7 +182,7 @@ def word_most_relevant(top_words, num_classes, checkpoint_dir, *, config=None, o
                  "texts": torch.from_numpy(texts).to(dev),
                  "seq_lens": torch.ones(batch_size, dtype=torch.int64, device=dev),
                  "labels": torch.zeros(batch_size, dtype=torch.int64, device=dev)}
-        scores.append(model.net.predict(batch, is_training=False).cpu().numpy())
+        scores.append(model.net.predict(batch, is_training=False, fused=bool(cfg.get('fused_inference', False))).cpu().numpy())
     scores = np.vstack(scores) if scores else np.zeros((0, model.dataset.num_classes), np.float32)
     _save(out_dir, top_words_scores=scores, top_words=top_words)
     return scores, vocabulary, word_to_id

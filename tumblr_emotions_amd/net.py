@@ -219,12 +219,21 @@ class SentimentNet:
                                                   L["b_softmax"])
         return self.logits
 
-    def predict(self, batch, is_training=False, seed=None):
+    def predict(self, batch, is_training=False, seed=None, fused=False):
         """Forward only (evaluate_*): is_training=False -> BatchNorm moving statistics, no dropout;
         is_training=True reproduces the reference's evaluation on mode='train' (batch statistics and
-        dropout stay on, im_text_rnn_model.py:65) but never touches the moving averages."""
+        dropout stay on, im_text_rnn_model.py:65) but never touches the moving averages.
+        fused=True (fp32, is_training=False): the image tower applies BatchNorm + ReLU inside its conv launches and prepares
+        the moving statistics once per weight version -- the same logits bit for bit, fewer passes over the activations
+        (fused_report() lists the layers that kept the separate pass).  The text tower and the heads are
+        unchanged."""
+        if fused and is_training:
+            raise ValueError("predict(fused=True) is the moving-statistics forward: is_training must be False")
+        if fused and self.dtype != "f32":
+            raise NotImplementedError("predict(fused=True) is implemented for the fp32 configuration, not %r" % self.dtype)
         if self.image is not None:
             self.image.training, self.image.update_moving = is_training, False
+            self.image.fused_request = bool(fused)
         # evaluation on mode='train' keeps dropout on: every call draws a fresh mask (a fixed seed would apply
         # the identical mask to every evaluation batch)
         self._predict_calls = getattr(self, "_predict_calls", 0) + 1
@@ -235,6 +244,11 @@ class SentimentNet:
         finally:
             if self.image is not None:
                 self.image.training, self.image.update_moving = True, True
+                self.image.fused_request = False
+
+    def fused_report(self):
+        """[(layer key, reason)]: the conv layers that kept conv -> BatchNorm-apply in the last predict(fused=True)."""
+        return [] if self.image is None else self.image.fused_report()
 
     def input_gradient(self, batch, target, *, is_training=True, dropout_mask=None, seed=None):
         """(logits, dimages): the forward pass of predict(is_training=True) and the exact gradient of
@@ -312,6 +326,8 @@ class SentimentNet:
         st = self.store
         self.step += 1
         t = self.step
+        if self.image is not None:
+            self.image.invalidate_fused()      # beta and the moving statistics move: predict(fused=True) prepares them again
         lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
         # dropout stream: one seed per (step, rank) -- ranks must not share a mask pattern across their shards
         seed = self._rank_seed(self.step) if seed is None else seed

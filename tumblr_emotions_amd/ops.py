@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import (ConvDesc, Segments, SumSegments, DS_EPI_ACCUM, DS_EPI_BIAS, DS_EPI_BNSUMS, DS_EPI_MASK, DS_EPI_RELU,  # noqa: F401
-                   DS_EPI_STATS,
+                   DS_EPI_STATS, DS_EPI_BN_RELU,
                    DS_DTYPE_BF16, DS_DTYPE_F32, DS_FP8_E4M3, DS_FP8_E5M2, DS_CONV_FWD, DS_CONV_DGRAD, DS_ARITH_F32, DS_ARITH_BF16,
                    DS_ARITH_FP8, DS_ARITH_F32X3, DS_FAM_IGEMM, DS_FAM_WINO2, DS_FAM_WINO4, DS_FAM_STEM, DS_FAM_BF16D, DS_FAM_FP8D,
                    DS_FAM_F32X3, DS_FAM_WINO4H, DS_FAM_STEM_POOL, DS_FAM_STEM_DGRAD, DS_PLAN_STEM_POOL, DS_PLAN_NO_SPLITK, DS_PLAN_NO_WINO4H, DS_PLAN_NO_WINO, DS_PLAN_NO_WINO4, DS_PLAN_NO_STEM_DIRECT, DS_PLAN_NO_BF16_DIRECT, DS_PLAN_ACT16,
@@ -302,6 +302,45 @@ class LayerPlan:
             return False
         self.pool_argmax = argmax            # (kept alive: the descriptor holds its address)
         return True
+
+    def copy(self):
+        """A second plan for the same launch that SHARES this plan's prepared filter and workspace: its descriptor (ldx, ldz,
+        flags, on-load pointers) can be changed without touching this one."""
+        q = object.__new__(LayerPlan)
+        q.p = _lib.LayerPlanStruct()
+        C.memmove(C.byref(q.p), self._ref, C.sizeof(q.p))
+        q._ref = C.byref(q.p)
+        q.d, q.family, q.M, q.alg_flops = q.p.d, q.p.family, self.M, self.alg_flops
+        q.u, q.wscale, q._ws = self.u, self.wscale, self._ws
+        q.io = _lib.ConvIO()
+        q.io.ws, q.io.ws_bytes = self.io.ws, self.io.ws_bytes
+        q.ws_bytes, q.splitk = self.ws_bytes, self.splitk
+        q._run, q._io_ref = self._run, C.byref(q.io)
+        q.pool_argmax = getattr(self, "pool_argmax", None)
+        return q
+
+    def bn_relu_variant(self, ldz=None):
+        """copy() with the inference epilogue DS_EPI_BN_RELU (run_bn_relu: relu(acc * scale + shift) stored with pixel stride
+        `ldz`, nothing else written), or None where the chosen family does not carry it for that stride.  The kernel family
+        and tile are this plan's, so the accumulators are bit-identical."""
+        q = self.copy()
+        q.p.d.flags, q.p.d.partials, q.p.partials = 0, 0, 0
+        if ldz is not None:
+            q.p.d.ldz = ldz          # (the library decides on the stride the launch will use)
+        if not _lib.load().ds_conv_plan_enable_bn_relu(q._ref):
+            return None
+        return q
+
+    def run_bn_relu(self, x, w_hwio, y, scale, shift):
+        """A bn_relu_variant() plan: y (pixel stride d.ldz) = relu(conv * scale + shift); scale / shift device addresses."""
+        t = CONV_TIMER
+        if t is not None:
+            t.begin()
+        self.io.scale, self.io.shift = scale, shift
+        _lib.check(self._run(self._ref, x, w_hwio if self.u is None else self.u.data_ptr(), y, self._io_ref, _stream()),
+                   "ds_conv_run")
+        if t is not None:
+            t.end(self)
 
     def finalize_tickets(self):
         """> 0: ds_conv_run can run ds_bn_finalize INSIDE this launch (run(fin=...)); the number of ticket words it needs."""
@@ -594,6 +633,23 @@ def bn_apply_relu(z, M, C_, rstd, shift, segs):
 def bn_infer_prepare(beta, mm, mv, eps, C_, rstd, shift):
     _lib.check(_lib.load().ds_bn_infer_prepare(_p(beta), _p(mm), _p(mv), eps, C_, _p(rstd), _p(shift), _stream()),
                "ds_bn_infer_prepare")
+
+
+class BnInferJobs:
+    """ds_bn_infer_prepare_multi: (rstd, shift) of every listed BatchNorm layer from its moving statistics as ONE launch.
+    jobs: (beta, moving_mean, moving_var, C, rstd, shift) tensors / int."""
+
+    def __init__(self, jobs):
+        self.n = len(jobs)
+        self.arr = (_lib.BnInferJob * self.n)()
+        self._keep = jobs
+        for a, (beta, mm, mv, C_, rstd, shift) in zip(self.arr, jobs):
+            a.beta, a.moving_mean, a.moving_var, a.C = _p(beta), _p(mm), _p(mv), C_
+            a.rstd, a.shift = _p(rstd), _p(shift)
+
+    def run(self, eps):
+        _lib.check(_lib.load().ds_bn_infer_prepare_multi(C.cast(self.arr, C.c_void_p), self.n, eps, _stream()),
+                   "ds_bn_infer_prepare_multi")
 
 
 def bn_bwd_partials(M, C_):

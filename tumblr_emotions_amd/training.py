@@ -106,16 +106,19 @@ def run_evaluation(model, checkpoint_dir, log_dir, mode, num_evals, batch_fn=Non
     batches, accumulate accuracy = mean(argmax(logits) == labels).  The reference's loop then waits for
     the next checkpoint forever and writes TensorBoard summaries; here one pass is made, the result is
     returned, printed and appended to <log_dir>/<mode>/accuracy.jsonl.
-    As in the reference the graph is built with is_training = (mode == 'train') (:65)."""
+    As in the reference the graph is built with is_training = (mode == 'train') (:65).  config['fused_inference'] = True:
+    the moving-statistics evaluation runs SentimentNet.predict(fused=True) (same logits bit for bit; ignored for mode 'train',
+    which keeps batch statistics)."""
     path = latest_checkpoint(checkpoint_dir)
     if path is None:
         raise FileNotFoundError("no checkpoint in %s" % checkpoint_dir)
     step = load_checkpoint(model, path)
     is_training = mode == "train"
+    fused = bool(getattr(model, "config", {}).get("fused_inference", False)) and not is_training
     correct = total = 0
     for i in range(num_evals):
         batch = batch_fn(i) if batch_fn is not None else model.next_batch(10 ** 6 + i)
-        logits = model.net.predict(batch, is_training=is_training)
+        logits = model.net.predict(batch, is_training=is_training, fused=fused)
         model.logits, model.labels = logits, batch["labels"]
         correct += int((logits.argmax(dim=1) == batch["labels"]).sum().item())     # streaming_accuracy
         total += int(batch["labels"].shape[0])
