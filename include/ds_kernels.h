@@ -583,6 +583,12 @@ int ds_bn_bwd_finalize_apply(const ds_bn_sum_segments *sg, const float *beta, fl
 /* Inception concat buffer is differentiated in place there                                                          */
 int ds_bn_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *mean,
                     const float *rstd, const float *shift, const float *coef, float *dz, float *amax, void *stream);
+/* The moving-statistics twin (is_training=False: BatchNorm is a fixed per-channel affine map, its backward pointwise):
+ * dz = rstd * dy * [z*rstd + shift > 0], the predicate evaluated as ds_bn_apply_relu evaluates it.  No mean, no coef, no
+ * sums.  dy as for ds_bn_bwd_apply (up to four segments, ptr2 second addends honoured); ldz: row stride of z AND dz; dz may
+ * alias z.  fp32 only.                                                                                                      */
+int ds_bn_infer_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *rstd,
+                          const float *shift, float *dz, void *stream);
 /* The same with dz written to a SEPARATE bf16 tensor (pixel stride lddz) and z left as it is: the 16-bit configurations' 1x1  */
 /* input gradients (ds_conv_bf16 with x_dtype = DS_DTYPE_BF16) read 2 instead of 4 bytes per element and get exactly the values */
 /* they would have rounded on load (RNE), so Conv2DBackpropInput has the same bits                                            */
@@ -617,6 +623,11 @@ int ds_bn_pool_bwd_reduce(const float *z, const float *dpool, const uint8_t *arg
 int ds_bn_pool_bwd_apply(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H, int32_t W,
                          int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW, const float *mean,
                          const float *rstd, const float *shift, const float *coef, float *dz, void *stream);
+/* ... and the moving-statistics twin of the apply: dz = rstd * g * [z*rstd + shift > 0], g the pool's gradient rebuilt per
+ * patch from the pooled gradient and the arg-max record (dz may alias z)                                                    */
+int ds_bn_pool_infer_bwd_apply(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H, int32_t W,
+                               int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW, const float *rstd,
+                               const float *shift, float *dz, void *stream);
 int ds_maxpool_bwd(const float *dy, const uint8_t *argmax, float *dx, int32_t accumulate, int32_t N,
                    int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
                    int32_t OH, int32_t OW, void *stream);
@@ -650,6 +661,11 @@ int ds_avgpool_dropout_bwd(const float *dout, const float *mask, int32_t N, int3
  * time_major!=0 writes row t*B+b (the layout the LSTM consumes), else b*T+t.               */
 int ds_gather_rows(const float *table, const int64_t *ids, float *out, int32_t B, int32_t T, int32_t D,
                    int64_t table_rows, int32_t time_major, void *stream);
+
+/* Gradient x input per word: out[b*T + t] = sum_d dx[row, d] * x[row, d], row = t*B + b (the text tower's time-major
+ * [T*B, D] buffers), fp32, fixed summation order; exactly 0 where t >= seq_len[b].                                 */
+int ds_token_dot(const float *dx, const float *x, const int64_t *seq_len, float *out, int32_t B, int32_t T, int32_t D,
+                 void *stream);
 
 /* Gradient of tf.nn.embedding_lookup w.r.t. the table (a dense [table_rows, D] result of what TF returns as
  * IndexedSlices): dtable[v] = sum_{(b,t): ids[b,t]==v} dx[row(b,t)], rows summed in ascending b*T+t order

@@ -198,12 +198,14 @@ SIGNATURES = {
     "ds_bn_finalize_apply_relu": (C.c_int, [_P, _i32, _i64, _i32, _P, _P, _f32, _f32, _P, _P, _P, _P, _P, _P, _i64, _SG, _P, _P]),
     "ds_bn_bwd_finalize_apply": (C.c_int, [_SS, _P, _P, _P, _P, _P, _P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _i32, _i32, _P, _P, _P]),
     "ds_bn_bwd_apply": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _P, _P]),
+    "ds_bn_infer_bwd_apply": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P]),
     "ds_bn_bwd_apply_bf16": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _i32, _P, _P]),
     "ds_maxpool_fwd": (C.c_int, [_P, _P, _P] + [_i32] * 11 + [_P]),
     "ds_maxpool_bn_relu_fwd": (C.c_int, [_P, _P, _P, _P, _P] + [_i32] * 11 + [_P, _P]),
     "ds_bn_pool_bwd_partials": (C.c_int, [_i32, _i32, _i32, _i32]),
     "ds_bn_pool_bwd_reduce": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P, _P]),
     "ds_bn_pool_bwd_apply": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P, _P, _P]),
+    "ds_bn_pool_infer_bwd_apply": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P]),
     "ds_maxpool_bwd": (C.c_int, [_P, _P, _P] + [_i32] * 11 + [_P]),
     "ds_maxpool3_bwd_sums_partials": (C.c_int, [_i32, _i32, _i32]),
     "ds_maxpool3_bwd_sums": (C.c_int, [_P, _P, _P, _i32, _P, _i32, _i32, _i32, _i32, _i32, _P, _P]),
@@ -211,6 +213,7 @@ SIGNATURES = {
     "ds_avgpool_dropout_fwd": (C.c_int, [_P, _i32, _i32, _i32, _f32, _u64, _P, _P, _P, _P, _P]),
     "ds_avgpool_dropout_bwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _f32, _P, _P]),
     "ds_gather_rows": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i64, _i32, _P]),
+    "ds_token_dot": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i32, _P]),
     "ds_embedding_grad": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i64, _i32, _P]),
     "ds_lstm_cell_fwd": (C.c_int, [_P, _P, _i32, _i64, _P, _P, _P, _i32, _i32, _i32, _f32, _P, _P, _P]),
     "ds_lstm_cell_bwd": (C.c_int, [_P, _P, _P, _P, _P, _i32, _i64, _P, _P, _i32, _i32, _i32, _P, _P, _P, _P]),

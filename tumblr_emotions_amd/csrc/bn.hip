@@ -554,6 +554,60 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *z, int l
     bwd_apply_body<OUT16, false, ADD2, Z16>((int)blockIdx.x, z, ldz, dy, M, C, mean, rstd, shift, coef, dz, amax, drow, lddz);
 }
 
+// ---- moving-statistics (is_training=False) backward ------------------------------------------------------------------------
+// BatchNorm with fixed statistics is a per-channel affine map, so its backward with the ReLU behind it is pointwise:
+// dz = rstd * dy * [z*rstd + shift > 0].  No column sums, no mean, no coef: one streaming pass (12 B per element, in place)
+// in the launch shape of bn_bwd_apply_kernel.  The predicate is the fused multiply-add bn_apply_relu_kernel evaluates
+// (the compiler contracts its v*r + s), so the mask has the decision bits of the activation the forward pass wrote.
+template <bool ADD2>
+__global__ __launch_bounds__(256) void bn_infer_bwd_apply_kernel(const float *z, int ldz, SegDev dy, int64_t M, int C,
+                                                                 const float *rstd, const float *shift, float *dz, int drow) {
+    const int C4 = C >> 2;
+    const int t0 = (int)blockIdx.x * 256 + threadIdx.x;
+    const int row0 = t0 / C4, c = (t0 - row0 * C4) * 4;
+    const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c), s4 = *reinterpret_cast<const float4 *>(shift + c);
+    const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+    int sgi = 0;
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (i < dy.nseg && c >= dy.c_begin[i] && c < dy.c_end[i]) sgi = i;
+    const float *const dyp = dy.ptr[sgi] + (c - dy.c_begin[sgi]);
+    const int64_t dyld = dy.ld[sgi];
+    const float *const dyp2 = (ADD2 && dy.ptr2[sgi]) ? dy.ptr2[sgi] + (c - dy.c_begin[sgi]) : nullptr;
+    constexpr int NR = DS_BN_ROWS;          // rows per pass: every load of the pass before any of its stores
+    for (int64_t row = row0; row < M; row += NR * (int64_t)drow) {
+        int64_t rws[NR];
+        bool ok[NR];
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            ok[u] = row + u * (int64_t)drow < M;
+            rws[u] = ok[u] ? row + u * (int64_t)drow : row;
+        }
+        float4 zv[NR], dv[NR];
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            zv[u] = ds::ld_stream4(z + rws[u] * ldz + c);
+            dv[u] = ds::ld_stream4(dyp + rws[u] * dyld);
+        }
+        if (ADD2 && dyp2) {
+#pragma unroll
+            for (int u = 0; u < NR; ++u) {
+                const float4 e = ds::ld_stream4(dyp2 + rws[u] * dyld);
+                dv[u].x += e.x; dv[u].y += e.y; dv[u].z += e.z; dv[u].w += e.w;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            if (u > 0 && !ok[u]) break;
+            const float zz[4] = {zv[u].x, zv[u].y, zv[u].z, zv[u].w}, dd[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
+            f32x4_t o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = __builtin_fmaf(zz[j], rr[j], ss[j]) > 0.f ? rr[j] * dd[j] : 0.f;
+            __builtin_nontemporal_store(o, reinterpret_cast<f32x4_t *>(dz + rws[u] * ldz + c));
+        }
+    }
+}
+
 // ds_bn_bwd_finalize_apply: the backward finalize (segments, per-segment beta / dbeta) and the apply pass as one launch
 // (see bn_finalize_apply_relu_kernel)
 struct BwdFinApplyArgs {
@@ -920,4 +974,21 @@ extern "C" int ds_bn_bwd_apply_bf16(const float *z, int32_t ldz, const ds_segmen
         hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, mean,
                            rstd, shift, coef, reinterpret_cast<float *>(dz16), amax, drow, lddz);
     return ds::check_launch("ds_bn_bwd_apply_bf16");
+}
+
+extern "C" int ds_bn_infer_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *rstd,
+                                     const float *shift, float *dz, void *stream) {
+    DS_REQUIRE(z && rstd && shift && dz && M > 0 && C > 0 && C % 4 == 0 && ldz >= C && ldz % 4 == 0 &&
+                   ((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)rstd) | ((uintptr_t)shift)) & 15) == 0,
+               "ds_bn_infer_bwd_apply: bad argument (need C %% 4 == 0, ldz >= C, ldz %% 4 == 0, 16-byte aligned z / dz / rstd / shift)");
+    if (int e = check_segments(dy, C, "ds_bn_infer_bwd_apply")) return e;
+    int drow;
+    const int grid = column_grid(M, C / 4, &drow);
+    if (has_second_addend(dy))
+        hipLaunchKernelGGL(bn_infer_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, rstd,
+                           shift, dz, drow);
+    else
+        hipLaunchKernelGGL(bn_infer_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, rstd,
+                           shift, dz, drow);
+    return ds::check_launch("ds_bn_infer_bwd_apply");
 }

@@ -376,6 +376,36 @@ __global__ __launch_bounds__(256) void fill_kernel(float *dst, int64_t n, float 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dst[i] = value;
 }
 
+// ds_token_dot: out[b, t] = sum_d dx[t*B + b, d] * x[t*B + b, d] (gradient x input per word) over the text tower's time-major
+// buffers.  One wave per row: 16-byte loads where D and the addresses allow, fp32 products added per lane in index order,
+// then the wave's butterfly -- a fixed order, so repeated runs give the same bits.  Rows past the post's length write 0
+// without reading.
+template <int VEC>
+__global__ __launch_bounds__(256) void token_dot_kernel(const float *dx, const float *x, const int64_t *seq_len, float *out,
+                                                        int B, int T, int D) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // t * B + b
+    if (row >= (int64_t)T * B) return;                                      // (wave-uniform)
+    const int t = (int)(row / B), b = (int)(row - (int64_t)t * B);
+    float acc = 0.f;
+    if ((int64_t)t < seq_len[b]) {
+        const float *a = dx + row * D, *e = x + row * D;
+        if (VEC == 4) {
+            for (int d = lane * 4; d < D; d += 256) {
+                const float4 u = *reinterpret_cast<const float4 *>(a + d), v = *reinterpret_cast<const float4 *>(e + d);
+                acc = __builtin_fmaf(u.x, v.x, acc);
+                acc = __builtin_fmaf(u.y, v.y, acc);
+                acc = __builtin_fmaf(u.z, v.z, acc);
+                acc = __builtin_fmaf(u.w, v.w, acc);
+            }
+        } else {
+            for (int d = lane; d < D; d += 64) acc = __builtin_fmaf(a[d], e[d], acc);
+        }
+        acc = ds::wave_sum(acc);
+    }
+    if (lane == 0) out[(int64_t)b * T + t] = acc;
+}
+
 }  // namespace
 
 extern "C" int ds_gather_rows(const float *table, const int64_t *ids, float *out, int32_t B, int32_t T, int32_t D,
@@ -413,6 +443,18 @@ extern "C" int ds_gather_rows(const float *table, const int64_t *ids, float *out
         hipLaunchKernelGGL(gather_rows_kernel<1>, grid, dim3(256), 0, s, table, ids, out, B, T, D, table_rows, time_major, rpw);
     }
     return ds::check_launch("ds_gather_rows");
+}
+
+extern "C" int ds_token_dot(const float *dx, const float *x, const int64_t *seq_len, float *out, int32_t B, int32_t T,
+                            int32_t D, void *stream) {
+    DS_REQUIRE(dx && x && seq_len && out && B > 0 && T > 0 && D > 0, "ds_token_dot: bad argument");
+    const int64_t rows = (int64_t)B * T;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (D % 4 == 0 && ((((uintptr_t)dx) | ((uintptr_t)x)) & 15) == 0)
+        hipLaunchKernelGGL(token_dot_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, dx, x, seq_len, out, B, T, D);
+    else
+        hipLaunchKernelGGL(token_dot_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, dx, x, seq_len, out, B, T, D);
+    return ds::check_launch("ds_token_dot");
 }
 
 extern "C" int ds_embedding_grad(const float *dx, const int64_t *ids, float *dtable, int32_t B, int32_t T, int32_t D,

@@ -517,9 +517,25 @@ class ConvBN:
         if need_dx:
             self._run_dgrad(dx_ptr)
 
+    def backward_infer(self, dx_ptr, pool=None, apply=True):
+        """Moving-statistics backward (InceptionV1Engine.input_backward(eval_mode=True)): BatchNorm with fixed statistics is a
+        per-channel affine map, so dz = rstd * dy * [z*rstd + shift > 0] is ONE pointwise pass over z (ds_bn_infer_bwd_apply;
+        pool: from the pooled gradient, ds_bn_pool_infer_bwd_apply) -- no sums, no finalize -- and then the plain dgrad.
+        rstd / shift are the vectors the forward pass applied (a zcat layer's: its slices of the block's on-load vectors)."""
+        if apply:
+            if pool is not None:
+                ops.bn_pool_infer_bwd_apply(self.z, pool.dout, pool.argmax, self.B, self.OH, self.OW, self.cout, self.rstd,
+                                            self.shift, self.z)
+            else:
+                ops.bn_infer_bwd_apply(self.z, self.dy_segs, self.M, self.cout, self.rstd, self.shift, self.z, ldz=self.ldz)
+        self._dz_amax_live = False
+        self._run_dgrad(dx_ptr)
+
     def _run_dgrad(self, dx_ptr, use16=False):
         sums = ops._p(self.dx_sums) if self.dx_sums is not None else None
         y = ops._p(self.dx_y) if self.dx_sums is not None else None
+        if self.eng.infer_bwd:       # (the sum-emitting epilogue and the on-load BatchNorm backward are switched off for the pass)
+            sums = y = None
         am = None
         if self.dgrad.family == ops.DS_FAM_FP8D:
             am = self.dz_amax if self._dz_amax_live else self.amax[1]
@@ -682,6 +698,9 @@ class ConvStage(Stage):
     def backward(self, need_dx):
         need_dx = need_dx and (not self.layer.fold or self.eng.input_grad)      # (the stem: the image gradient, input_backward)
         dx = ops._p(self.prev.dout) if need_dx else None
+        if self.eng.infer_bwd:
+            self.layer.backward_infer(dx, self.pool if (self.fused_into_pool and self.pool.stride == 2) else None)
+            return
         if self.fused_into_pool and self.pool.stride == 2:
             self.layer.backward_pooled(self.pool, ops._p(self.prev.out), self.prev.C, dx, need_dx)
         else:
@@ -862,6 +881,7 @@ class MixedStage(Stage):
         # +0.06 ms at B = 256 -- the joint finalize waits for the LAST of the three chains, one more dependent launch on the
         # critical path per block -- so it is on up to 128 samples only (bit 0 forward, bit 1 backward)
         self.batch_bn = 0
+        self._infer_close = None
         if self.zcat:
             self.rs_cat = torch.empty(2, Ct, device=dev)
             self.rs_cat[0].fill_(1.0)
@@ -1112,12 +1132,21 @@ class MixedStage(Stage):
         keep = self.fused.dgrad.d.flags & ops.DS_EPI_BNSUMS
         self.fused.dgrad.d.flags = (ops.DS_EPI_ACCUM if pool_first else 0) | keep
 
-        batched = self._batch_backward(need_dx)
+        infer = eng.infer_bwd        # moving-statistics backward: pointwise BatchNorm passes, plain pool gradients, no sums
+        batched = self._batch_backward(need_dx) and not infer
         if batched:                  # BatchNorm backward of the three block-closing layers: two launches in front of the fork
             self._bn_backward_closing()
+        if infer and self.zcat:      # the block-closing layers' z are the columns [b0, Ct) of the concat: ONE pointwise pass
+            M, Ct = self.B * self.H * self.W, self.C
+            if self._infer_close is None:
+                self._infer_close = (make_segments([(0, Ct - b0, self.dout.data_ptr() + 4 * b0, Ct)]), self.out.view(M, Ct)[:, b0:])
+            dy, z = self._infer_close
+            ops.bn_infer_bwd_apply(z, dy, M, Ct - b0, self.rs_cat[0, b0:], self.rs_cat[1, b0:], z, ldz=Ct)
 
         def closing(layer, x_ptr, ldx, dx_ptr, ndx):
-            if batched:
+            if infer:
+                layer.backward_infer(dx_ptr, apply=not self.zcat)
+            elif batched:
                 layer._run_dgrad(dx_ptr)
             else:
                 layer.backward(x_ptr, ldx, dx_ptr, ndx)
@@ -1126,6 +1155,8 @@ class MixedStage(Stage):
             closing(self.c3, None if self.fuse_b3 else ops._p(self.pooled), p.C, ops._p(self.dpooled), need_dx)      # (x: weight gradient only)
             if pool_first:
                 ops.maxpool_bwd(self.dpooled, self.argmax, p.dout, False, self.B, p.H, p.W, p.C, 3, 1, "SAME")
+            elif need_dx and self.split_dout and infer:
+                ops.maxpool_bwd(self.dpooled, self.argmax, p.dout2, False, self.B, p.H, p.W, p.C, 3, 1, "SAME")
             elif need_dx and self.split_dout:       # the pool gradient into its OWN tensor, with its own sums: inside this chain
                 ops.maxpool3_bwd_sums(self.dpooled, self.argmax, p.dout2, False, p.out, self.B, p.H, p.W, p.C, self.pool_sums)
 
@@ -1159,6 +1190,11 @@ class MixedStage(Stage):
             main.wait_event(e_2)
             if not eng.one_side_stream:
                 main.wait_event(e_3)
+        if infer:
+            self.fused.backward_infer(ops._p(p.dout))
+            if not pool_first and not self.split_dout:
+                ops.maxpool_bwd(self.dpooled, self.argmax, p.dout, True, self.B, p.H, p.W, p.C, 3, 1, "SAME")
+            return
         self.fused.backward(x, p.C, ops._p(p.dout) if need_dx else None, need_dx)
         if need_dx and self.split_dout:             # the sums of the dgrad's addend (the pool gradient's came with it: branch3)
             ops.bn_bwd_reduce(p.out, self._dgrad_sum_segs, self.B * p.H * p.W, p.C, eng.zeros, eng.ones, eng.zeros, self.dgrad_sums,
@@ -1286,6 +1322,8 @@ class InceptionV1Engine:
         # input gradients wanted (forward(input_grad=True) .. the next plain forward): the stem runs unpooled (ConvStage.alloc);
         # _pivots keeps the statistics pivots of the training state that was left, so the next training step is unchanged
         self.input_grad = False
+        self.infer_bwd = False       # inside input_backward(eval_mode=True): the stages run their moving-statistics backward
+        self._input_grad_training = True     # was the last forward(input_grad=True) a batch-statistics pass?
         self._pivots = None
         self._restore_pivots = None
         self._stats_n = self._bwdp_n = self._ws_bytes = 0
@@ -1529,7 +1567,9 @@ class InceptionV1Engine:
             if pB == B:
                 for l, m in zip(self.layers, pivots):
                     l.mean.copy_(m)
-        if input_grad:      # every input-gradient pass from the same pivots: a function of the state and its arguments only
+        if input_grad:
+            self._input_grad_training = bool(self.training)
+        if input_grad and self.training:      # every input-gradient pass from the same pivots: a function of the state and its arguments only
             saved = self._pivots if self._pivots is not None and self._pivots[0] == B else None
             for i, l in enumerate(self.layers):
                 l.mean.copy_(saved[1][i] if saved is not None else l.mm)
@@ -1595,32 +1635,50 @@ class InceptionV1Engine:
         if self.reducer is not None and self.train_all:
             self.reducer.stage_done(TRAINABLE_ENDPOINTS[0])      # whole tower trainable: bucket 1 closes with the stem
 
-    def input_backward(self, dlogits, dimages):
+    def input_backward(self, dlogits, dimages, eval_mode=False):
         """d(sum dlogits * logits) / d(images) of the last forward(input_grad=True) into dimages [B, H, W, 3] (fp32, packed):
         the backward pass down to the stem's Conv2DBackpropInput, BatchNorm with its batch-statistics terms.  No weight or
         beta gradient is formed (every layer runs as a frozen one without a beta gradient for the pass), nothing is handed to
-        the gradient reducer: this rank's own gradient."""
+        the gradient reducer: this rank's own gradient.
+        eval_mode: the forward was the moving-statistics pass (training False).  The same stage walk, but every BatchNorm
+        backward is the pointwise ds_bn_infer_bwd_apply / ds_bn_pool_infer_bwd_apply: no reduce pass, no finalize, no dgrad
+        epilogue that emits sums, plain pool gradients; dropout is the identity; pivots and moving statistics are not written."""
         if not self.input_grad:
             raise RuntimeError("input_backward needs a forward pass with input_grad=True")
+        if bool(eval_mode) == self._input_grad_training:
+            raise RuntimeError("input_backward(eval_mode=%s) after a forward pass with training=%s" % (bool(eval_mode), self._input_grad_training))
+        if eval_mode and self.dtype != "f32":
+            raise NotImplementedError("the moving-statistics backward is implemented for the fp32 configuration only")
         B, F = self.B, self.feat
         if tuple(dimages.shape) != (B, self.input.H, self.input.W, 3) or dimages.dtype != torch.float32 or not dimages.is_contiguous():
             raise ValueError("dimages must be a contiguous float32 [%d, %d, %d, 3] tensor" % (B, self.input.H, self.input.W))
         last = self.last
         self.fc_dgrad.run(ops._p(dlogits), self.w_fc, ops._p(self.dpooled))
-        ops.avgpool_dropout_bwd(self.dpooled, self.mask, B, last.H * last.W, F, self.keep, last.dout)
+        ops.avgpool_dropout_bwd(self.dpooled, self.mask, B, last.H * last.W, F, 1.0 if eval_mode else self.keep, last.dout)
         stem = self.stages[0].layer
         if stem.dgrad is None:
             stem.make_dgrad(3)
         saved = [(l.trainable, l.gbeta) for l in self.layers]
+        # eval_mode: the dgrads run plain -- their DS_EPI_BNSUMS epilogues and on-load BatchNorm backward (bnb) are taken off
+        # the descriptors for the pass and put back behind it
+        plans = [l.dgrad for l in self.layers if l.dgrad is not None] if eval_mode else []
+        saved_plans = [(pl.d.flags, pl.d.bnb, pl.d.mask_rstd, pl.d.mask_shift) for pl in plans]
         self.input.dout = dimages
         try:
             for l in self.layers:
                 l.trainable, l.gbeta = False, None
+            for pl in plans:
+                pl.d.flags &= ~ops.DS_EPI_BNSUMS
+                pl.d.bnb = pl.d.mask_rstd = pl.d.mask_shift = None
+            self.infer_bwd = bool(eval_mode)
             self.wgrad_stream, self.wgrad_pending = None, False
             for s in reversed(self.stages):
                 s.backward(need_dx=True)
         finally:
+            self.infer_bwd = False
             for l, (tr, gb) in zip(self.layers, saved):
                 l.trainable, l.gbeta = tr, gb
+            for pl, (fl, bnb, mr, ms) in zip(plans, saved_plans):
+                pl.d.flags, pl.d.bnb, pl.d.mask_rstd, pl.d.mask_shift = fl, bnb, mr, ms
             self.input.dout = None
         return dimages

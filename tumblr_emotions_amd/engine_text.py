@@ -106,14 +106,23 @@ class TextTowerEngine:
         self.ws_bytes = max(self.wgrad_x.ws_bytes, self.wgrad_h.ws_bytes)
         self.ws = torch.empty(max(self.ws_bytes // 4, 4), device=dev)
         self.colsum_scratch = torch.empty(64 * 4 * H, device=dev)
+        self.dx = None            # d / d(embedded words): _ensure_dx(), for trainable_embedding and input_backward
         if self.trainable_embedding:
-            self.dx = torch.empty(T * B, D, device=dev)
-            self.x_dgrad = gemm_plan(T * B, 4 * H, D, 4 * H, D, 4 * H, transposed_w=True)
+            self._ensure_dx()
             self.gtable = st.grad_view(self.EMB)
 
-    def forward(self, texts, seq_lens):
+    def _ensure_dx(self):
+        """The word-gradient buffer and its GEMM dX = dgates * Wx^T, allocated once per batch size, on demand."""
+        if self.dx is None:
+            B, T, D, H = self.B, self.T, self.D, self.H
+            self.dx = torch.empty(T * B, D, device=self.device)
+            self.x_dgrad = gemm_plan(T * B, 4 * H, D, 4 * H, D, 4 * H, transposed_w=True)
+            self.tok = torch.empty(B, T, device=self.device)
+
+    def forward(self, texts, seq_lens, scale=None):
         """texts int64 [B,T] (pad id = vocab size), seq_lens int64 [B] (>= 1).  Returns h_last [B,H]
-        (a view of the internal state buffer)."""
+        (a view of the internal state buffer).  scale (optional, fp32 [B]): the embedded words of sample b are
+        scale[b] * table[id] (the interpolation path of integrated gradients; layout plumbing, one multiply over x)."""
         B, T, H = texts.shape[0], self.T, self.H
         assert texts.shape[1] == T and texts.dtype == torch.int64 and seq_lens.dtype == torch.int64
         self.alloc(B)
@@ -125,6 +134,12 @@ class TextTowerEngine:
             seq_lens, texts = self.len_sorted, self.texts_sorted
         self.seq_lens, self.texts = seq_lens, texts
         ops.gather_rows(self.table, texts, self.x, B, T, self.D, time_major=True)
+        if scale is not None:
+            if tuple(scale.shape) != (B,) or scale.dtype != torch.float32:
+                raise ValueError("scale must be a float32 [%d] tensor" % B)
+            if self.sorted:
+                scale = scale[self.perm.long()]
+            self.x.view(T, B, self.D).mul_(scale.view(1, B, 1))
         self.xproj.run(ops._p(self.x), self.wx, ops._p(self.gates), bias=self.bias)
         if self.use_seq:
             rows = self.seq_rows | (_lib.DS_LSTM_SKIP_MASKED if self.sorted else 0)
@@ -150,6 +165,29 @@ class TextTowerEngine:
             ops.lstm_seq_status(self.seq_ws, self.B)
 
     def backward(self, dh_last):
+        self._bptt(dh_last)
+        self._weight_grads()
+
+    def input_backward(self, dh_last):
+        """(dwords [B, T, D], token_scores [B, T]) of the last forward: the gradient of sum(dh_last * h_last) with respect to the
+        embedded words x (BPTT, then dX = dgates * Wx^T -- the GEMM `trainable_embedding` runs in front of its scatter) and
+        gradient x input per word (ds_token_dot), both in the caller's sample order and exactly 0 past each post's length.
+        No weight gradient and no embedding-table gradient is formed; nothing is handed to the gradient reducer."""
+        B, T, D, H = self.B, self.T, self.D, self.H
+        self._bptt(dh_last)
+        self._ensure_dx()
+        self.x_dgrad.run(ops._p(self.dgates), self.wx, ops._p(self.dx))
+        ops.token_dot(self.dx, self.x, self.seq_lens, self.tok, B, T, D)
+        live = torch.arange(T, device=self.device).view(1, T) < self.seq_lens.view(B, 1)
+        dwords = torch.where(live.unsqueeze(-1), self.dx.view(T, B, D).permute(1, 0, 2), self.dx.new_zeros(()))
+        scores = self.tok
+        if self.sorted:          # back to the caller's order: row perm[j] of the result is sorted row j
+            order = torch.empty_like(self.perm, dtype=torch.int64)
+            order[self.perm.long()] = torch.arange(B, device=self.device)
+            dwords, scores = dwords[order], scores[order]
+        return dwords.contiguous(), scores.clone()
+
+    def _bptt(self, dh_last):
         B, T, H = self.B, self.T, self.H
         if self.use_seq:
             rows = self.seq_rows
@@ -158,7 +196,7 @@ class TextTowerEngine:
                 dh_last, rows = self.dh_sorted, rows | _lib.DS_LSTM_SKIP_MASKED
             ops.lstm_seq_bwd(self.gates, self.wh, 4 * H, self.c, dh_last, dh_last.stride(0), self.seq_lens, T, B, H,
                              self.dgates, self.seq_ws, rows=rows)
-            return self._weight_grads()
+            return
         dh, dh2 = self.dh
         ops.copy2d(dh_last, dh_last.stride(0), dh, H, B, H)
         ops.fill(self.dc, B * H, 0.0)
@@ -171,7 +209,6 @@ class TextTowerEngine:
                 self.rec_dgrad.run(ops._p(self.dgates[t]), self.wh, ops._p(self.dh_slabs))
                 ns = self.sb
             dh, dh2 = dh2, dh
-        self._weight_grads()
 
     def _weight_grads(self):
         B, T, H = self.B, self.T, self.H
@@ -265,10 +302,14 @@ class JointHeadEngine:
             self.reducer.stage_done("head")
         return self.d_im, self.d_tx
 
-    def input_backward(self, dlogits):
-        """d_im alone (SentimentNet.input_gradient): the text features are constants, no weight gradient is formed."""
+    def input_backward(self, dlogits, with_text=False):
+        """d_im alone (SentimentNet.input_gradient: the text features are constants), or -- with_text -- (d_im, d_tx)
+        (SentimentNet.eval_gradients).  No weight gradient is formed."""
         self.sm_dgrad.run(ops._p(dlogits), self.w_sm, ops._p(self.ddense), mask=ops._p(self.dense))      # ReluGrad fused
         self.im_dgrad.run(ops._p(self.ddense), self.w_im, ops._p(self.d_im))
+        if with_text:
+            self.tx_dgrad.run(ops._p(self.ddense), self.w_tx, ops._p(self.d_tx))
+            return self.d_im, self.d_tx
         return self.d_im
 
 
@@ -315,4 +356,9 @@ class TextHeadEngine:
         self.sm_dgrad.run(dl, self.w_sm, ops._p(self.d_tx))
         if self.reducer is not None:
             self.reducer.stage_done("head")
+        return self.d_tx
+
+    def input_backward(self, dlogits):
+        """d_tx alone (SentimentNet.eval_gradients): no weight gradient is formed."""
+        self.sm_dgrad.run(ops._p(dlogits), self.w_sm, ops._p(self.d_tx))
         return self.d_tx

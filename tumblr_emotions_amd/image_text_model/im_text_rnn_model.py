@@ -258,3 +258,43 @@ def class_visualisation(label, learning_rate, checkpoint_dir, *, config=None, nu
     os.makedirs(out_dir, exist_ok=True)
     np.save(os.path.join(out_dir, "class_visualisation_%d.npy" % int(label)), np_image[0])
     return np_image[0]
+
+
+# ---- why did the trained model give this post this emotion? --------------------------------------------------------------
+
+def explain_posts(checkpoint_dir, nb_batches, *, config=None, out_dir='data', method='gradient', steps=32):
+    """Explain the PREDICTED class of `nb_batches` validation batches through the newest checkpoint of `checkpoint_dir`, with
+    the model as it predicts (BatchNorm on moving statistics, no dropout: SentimentNet.eval_gradients, HIP).
+    method 'gradient': gradient x input -- per pixel dlogit/dimage * image, per word sum_d dlogit/dx * x;
+    method 'integrated': integrated gradients over `steps` midpoints from a mid-grey image and the zero <ukn> words
+    (SentimentNet.integrated_gradients).  Writes under `out_dir` and returns
+      saliency_maps.npy      [N, 224, 224]  max over the colour channels of |attribution|
+      token_scores.npy       [N, T]         attribution per word, exactly 0 past each post's length
+      explained_logits.npy   [N, classes]   the logits that were explained
+      explained_post_ids.npy [N]
+    Cost of 'integrated': the engines allocate per batch size and layout, so every validation batch re-allocates them twice (the
+    forward of predict at `batch_size`, then the interpolation batches at `steps`); choose steps for accuracy, not to match.
+    No counterpart in the reference, whose analyses score words in isolation (word_most_relevant) or ascend a class logit from
+    noise (class_visualisation)."""
+    if method not in ('gradient', 'integrated'):
+        raise ValueError("method must be 'gradient' or 'integrated', not %r" % (method,))
+    model = _restored_validation_model(checkpoint_dir, config)
+    net = model.net
+    maps, scores, all_logits, ids = [], [], [], []
+    for i in range(nb_batches):
+        batch = model.next_batch(10 ** 6 + i)
+        batch = {k: batch[k] for k in ("images", "texts", "seq_lens")}
+        logits = net.predict(batch, is_training=False).clone()      # (predict hands out the head's own buffer: the calls below rewrite it)
+        label = logits.argmax(dim=1)
+        if method == 'gradient':
+            _, dimg, _, tok = net.eval_gradients(batch, label)
+            attr = dimg * batch["images"]
+        else:
+            attr, tok, _ = net.integrated_gradients(batch, label, steps=steps)
+        maps.append(attr.abs().amax(dim=3).cpu().numpy())
+        scores.append(tok.cpu().numpy())
+        all_logits.append(logits.cpu().numpy())
+        ids.append(model.post_ids.cpu().numpy())
+    maps, scores, all_logits, ids = np.concatenate(maps), np.concatenate(scores), np.vstack(all_logits), np.hstack(ids)
+    _save(out_dir, saliency_maps=maps, token_scores=scores, explained_logits=all_logits, explained_post_ids=ids)
+    return maps, scores, all_logits, ids

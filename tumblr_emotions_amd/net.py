@@ -264,18 +264,8 @@ class SentimentNet:
         if not is_training:
             raise NotImplementedError("input_gradient differentiates batch-statistics BatchNorm (is_training=True) only")
         images = batch["images"]
-        B, nc = images.shape[0], self.nb_emotions
-        if isinstance(target, (int, np.integer)):
-            target = torch.full((B,), int(target), dtype=torch.int64, device=self.device)
-        target = torch.as_tensor(target, device=self.device)
-        if target.dtype in (torch.int32, torch.int64) and target.dim() == 1 and target.shape[0] == B:
-            if bool(((target < 0) | (target >= nc)).any()):
-                raise ValueError("target labels must lie in [0, %d)" % nc)
-            target = torch.nn.functional.one_hot(target.long(), nc).float()
-        elif target.is_floating_point() and tuple(target.shape) == (B, nc):
-            target = target.float().contiguous()
-        else:
-            raise ValueError("target must be an int, a [B] label tensor or a [B, %d] float tensor" % nc)
+        B = images.shape[0]
+        target = self._target_matrix(target, B)
         self._input_grad_calls = getattr(self, "_input_grad_calls", 0) + 1
         seed = (1 << 41) + self._input_grad_calls if seed is None else seed
         eng = self.image
@@ -295,6 +285,130 @@ class SentimentNet:
         finally:
             eng.training, eng.update_moving, eng.sync_bn = True, True, sync
         return logits, dimg
+
+    def _target_matrix(self, target, B):
+        """The three target forms of input_gradient / eval_gradients as a float32 [B, nb_emotions] matrix on the device."""
+        nc = self.nb_emotions
+        if isinstance(target, (int, np.integer)):
+            target = torch.full((B,), int(target), dtype=torch.int64, device=self.device)
+        target = torch.as_tensor(target, device=self.device)
+        if target.dtype in (torch.int32, torch.int64) and target.dim() == 1 and target.shape[0] == B:
+            if bool(((target < 0) | (target >= nc)).any()):
+                raise ValueError("target labels must lie in [0, %d)" % nc)
+            target = torch.nn.functional.one_hot(target.long(), nc).float()
+        elif target.is_floating_point() and tuple(target.shape) == (B, nc):
+            target = target.float().contiguous()
+        else:
+            raise ValueError("target must be an int, a [B] label tensor or a [B, %d] float tensor" % nc)
+        return target
+
+    def eval_gradients(self, batch, target, *, text_scale=None):
+        """(logits, dimages, dwords, token_scores) of the TRAINED model's prediction: the forward pass of
+        predict(is_training=False) -- BatchNorm with its moving statistics, no dropout; the logits are that call's, bit for
+        bit -- and the exact gradient of J = sum_b sum_k target[b, k] logits[b, k] with respect to
+          * batch['images']: dimages [B, H, W, 3] (None in mode 'text'),
+          * the embedded words x[b, t, :] = table[texts[b, t]]: dwords [B, T, D], zero at t >= seq_lens[b] (None in mode 'image'),
+        plus token_scores [B, T] = sum_d dwords * x (gradient x input; exactly 0 past each post's length).  target: as for
+        input_gradient.  text_scale (optional float32 [B]): the embedded words of sample b are text_scale[b] * table[id] (the
+        straight path from the zero <ukn> row that integrated_gradients walks); dwords / token_scores are then with respect to
+        those scaled words.  fp32 only.
+        With fixed statistics every sample is independent and BatchNorm's backward is pointwise: no reduction, no finalize
+        (DESIGN.md 7.5).  Variables, Adam slots, `step`, moving statistics and statistics pivots are not touched, no weight
+        gradient is formed, nothing is all-reduced; the next train_step is that of a net that never called this."""
+        if self.dtype != "f32":
+            raise NotImplementedError("eval_gradients is implemented for the fp32 configuration, not %r" % self.dtype)
+        B = (batch["images"] if self.image is not None else batch["texts"]).shape[0]
+        target = self._target_matrix(target, B)
+        if text_scale is not None:
+            if self.text is None:
+                raise ValueError("text_scale needs the text tower (mode 'text' or 'joint')")
+            text_scale = torch.as_tensor(text_scale, dtype=torch.float32, device=self.device).contiguous()
+            if tuple(text_scale.shape) != (B,):
+                raise ValueError("text_scale must be a [B] float tensor")
+        eng = self.image
+        dimg = dwords = scores = None
+        if eng is not None:
+            eng.training, eng.update_moving, eng.fused_request = False, False, False
+        try:
+            with torch.no_grad():
+                im = tx = None
+                if eng is not None:
+                    images = batch["images"]
+                    im = eng.forward(images, None, 0, input_grad=True)
+                if self.text is not None:
+                    tx = self.text.forward(batch["texts"], batch["seq_lens"], scale=text_scale)
+                if self.mode == "image":
+                    logits = im.clone()
+                    dimg = eng.input_backward(target, torch.empty(images.shape, device=self.device), eval_mode=True)
+                elif self.mode == "text":
+                    logits = self.head.forward(tx).clone()
+                    dwords, scores = self.text.input_backward(self.head.input_backward(target))
+                else:
+                    logits = self.head.forward(im, tx).clone()
+                    d_im, d_tx = self.head.input_backward(target, with_text=True)
+                    dimg = eng.input_backward(d_im, torch.empty(images.shape, device=self.device), eval_mode=True)
+                    dwords, scores = self.text.input_backward(d_tx)
+        finally:
+            if eng is not None:
+                eng.training, eng.update_moving = True, True
+                eng.invalidate_fused()      # (this pass left its own rstd / shift where the fused pass keeps its prepared ones)
+        return logits, dimg, dwords, scores
+
+    def integrated_gradients(self, batch, target, *, steps=32, image_baseline=None):
+        """Integrated gradients of the trained model's logit J (target as for eval_gradients), one post at a time: the `steps`
+        midpoints alpha_k = (k + 0.5) / steps of the straight path from the baseline go through eval_gradients as ONE batch of
+        `steps` samples (exact: with moving statistics the samples are independent).  Image path x0 + alpha (x - x0), x0 =
+        image_baseline ([H, W, 3] or [B, H, W, 3]; default zeros, the preprocessed mid-grey); word path alpha * x, from the zero
+        <ukn> row.  Returns (image_attr [B, H, W, 3] or None, token_attr [B, T] or None, f_x - f_x0 [B]): attribution =
+        (x - x0) * mean gradient, summed over D for the words; f_x - f_x0 is what the attributions sum to as steps grows.
+        Every call inside runs at batch size `steps`, so the engines are allocated once for the whole method."""
+        if self.dtype != "f32":
+            raise NotImplementedError("integrated_gradients is implemented for the fp32 configuration, not %r" % self.dtype)
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        has_im, has_tx = self.image is not None, self.text is not None
+        B = (batch["images"] if has_im else batch["texts"]).shape[0]
+        target = self._target_matrix(target, B)
+        alpha = (torch.arange(steps, device=self.device, dtype=torch.float32) + 0.5) / steps
+        im_attr = torch.empty(batch["images"].shape, device=self.device) if has_im else None
+        tok_attr = torch.empty(batch["texts"].shape, device=self.device) if has_tx else None
+        if has_im:
+            x_all = batch["images"]
+            x0_all = torch.zeros_like(x_all) if image_baseline is None else \
+                torch.as_tensor(image_baseline, dtype=torch.float32, device=self.device).expand_as(x_all).contiguous()
+        for b in range(B):
+            sub = {}
+            if has_im:
+                x, x0 = x_all[b:b + 1], x0_all[b:b + 1]
+                sub["images"] = (x0 + alpha.view(steps, 1, 1, 1) * (x - x0)).contiguous()
+            if has_tx:
+                sub["texts"] = batch["texts"][b:b + 1].expand(steps, -1).contiguous()
+                sub["seq_lens"] = batch["seq_lens"][b:b + 1].expand(steps).contiguous()
+            _, dimg, dwords, _ = self.eval_gradients(sub, target[b:b + 1].expand(steps, -1).contiguous(),
+                                                    text_scale=alpha if has_tx else None)
+            if has_im:
+                im_attr[b] = (x_all[b] - x0_all[b]) * dimg.mean(0)
+            if has_tx:
+                words = self.text.table[batch["texts"][b]]          # [T, D]: the embedded words of the post itself
+                tok_attr[b] = (words * dwords.mean(0)).sum(-1)
+        # f(x) - f(x0): the 2 B end points, in batches of `steps` samples (the batch size the engines are allocated for: another
+        # one would re-allocate every tower); a short last batch is filled up with its own last sample
+        idx = torch.arange(2 * B, device=self.device)
+        f = torch.empty(2 * B, device=self.device)
+        for i in range(0, 2 * B, steps):
+            take = idx[i:i + steps]
+            pad = torch.cat([take, take[-1:].expand(steps - take.shape[0])])
+            post, at_x = pad % B, pad >= B                  # samples [0, B): the baselines, [B, 2 B): the posts themselves
+            ends = {}
+            if has_im:
+                ends["images"] = torch.where(at_x.view(-1, 1, 1, 1), x_all[post], x0_all[post]).contiguous()
+            if has_tx:
+                ends["texts"], ends["seq_lens"] = batch["texts"][post].contiguous(), batch["seq_lens"][post].contiguous()
+            lg, _, _, _ = self.eval_gradients(ends, target[post].contiguous(), text_scale=at_x.float() if has_tx else None)
+            f[take] = (lg * target[post]).sum(1)[:take.shape[0]]
+        delta = f[B:] - f[:B]
+        return im_attr, tok_attr, delta
 
     def cross_entropy(self, logits, labels):
         if self.dlogits is None or self.dlogits.shape != logits.shape:

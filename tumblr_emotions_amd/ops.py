@@ -744,6 +744,14 @@ def bn_bwd_apply(z, segs, M, C_, mean, rstd, shift, coef, dz, amax=None, ldz=0):
                                            _p(dz), _p(amax), _stream()), "ds_bn_bwd_apply")
 
 
+def bn_infer_bwd_apply(z, segs, M, C_, rstd, shift, dz, ldz=0):
+    """Moving-statistics BatchNorm + ReLU backward, pointwise: dz = rstd * dy * [z*rstd + shift > 0] (dz over z, or any fp32
+    tensor with z's row stride).  z .. dz: tensors or raw device addresses."""
+    ptr = lambda t: t if isinstance(t, C.c_void_p) else _p(t)
+    _lib.check(_lib.load().ds_bn_infer_bwd_apply(ptr(z), ldz or C_, C.byref(segs), M, C_, ptr(rstd), ptr(shift), ptr(dz),
+                                                 _stream()), "ds_bn_infer_bwd_apply")
+
+
 def maxpool_fwd(x, y, argmax, N, H, W, C_, k, stride, mode="SAME"):
     if mode == "SAME":
         OH, pt = same_pad(H, k, stride)
@@ -785,6 +793,14 @@ def bn_pool_bwd_apply(z, dpool, argmax, N, H, W, C_, mean, rstd, shift, coef, dz
     OW, pl = same_pad(W, 3, 2)
     _lib.check(_lib.load().ds_bn_pool_bwd_apply(_p(z), _p(dpool), _p(argmax), N, H, W, C_, pt, pl, OH, OW, _p(mean),
                                                 _p(rstd), _p(shift), _p(coef), _p(dz), _stream()), "ds_bn_pool_bwd_apply")
+
+
+def bn_pool_infer_bwd_apply(z, dpool, argmax, N, H, W, C_, rstd, shift, dz):
+    """ds_bn_pool_bwd_apply's moving-statistics twin (conv -> BN -> ReLU -> 3x3/2 SAME pool, from the pooled gradient)."""
+    OH, pt = same_pad(H, 3, 2)
+    OW, pl = same_pad(W, 3, 2)
+    _lib.check(_lib.load().ds_bn_pool_infer_bwd_apply(_p(z), _p(dpool), _p(argmax), N, H, W, C_, pt, pl, OH, OW, _p(rstd),
+                                                      _p(shift), _p(dz), _stream()), "ds_bn_pool_infer_bwd_apply")
 
 
 def maxpool_bwd(dy, argmax, dx, accumulate, N, H, W, C_, k, stride, mode="SAME"):
@@ -834,6 +850,11 @@ def gather_rows(table, ids, out, B, T, D, time_major=True):
 def embedding_grad(dx, ids, dtable, B, T, D, time_major=True):
     _lib.check(_lib.load().ds_embedding_grad(_p(dx), _p(ids), _p(dtable), B, T, D, dtable.shape[0], int(time_major),
                                              _stream()), "ds_embedding_grad")
+
+
+def token_dot(dx, x, seq_len, out, B, T, D):
+    """out [B, T] = sum_d dx * x over time-major [T*B, D] buffers; exactly 0 at t >= seq_len[b]."""
+    _lib.check(_lib.load().ds_token_dot(_p(dx), _p(x), _p(seq_len), _p(out), B, T, D, _stream()), "ds_token_dot")
 
 
 def lstm_cell_fwd(gates, c_prev, h_prev, seq_len, t, B, H, forget_bias, c_out, h_out, rec_slabs=None, nslabs=0,
