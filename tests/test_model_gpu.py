@@ -1005,6 +1005,28 @@ def test_captured_step_is_dropped_when_buffers_or_weights_change():
     assert torch.equal(net.logits, ref.logits) and torch.equal(net.store.theta, ref.store.theta)
 
 
+def test_release_graph_leaves_the_arrangement_alloc_chose():
+    """The side-stream arrangement is derived, not saved: a capture narrows it to one side stream, an eager step at another
+    batch size re-allocates (and re-derives it), and release_graph() then leaves what alloc chooses for the CURRENT batch
+    size -- 129 fp32 samples: 1 -- not the value that was current when the step was captured (2 samples: 2)."""
+    from tumblr_emotions_amd.net import SentimentNet
+    from tumblr_emotions_amd.synthetic import synthetic_batch_numpy, to_device
+    small = to_device(synthetic_batch_numpy(2, 10, 50, seed=1))
+    big = to_device(synthetic_batch_numpy(129, 10, 50, seed=2))
+    net = SentimentNet(mode="joint", nb_emotions=15, rnn_size=32, vocab_size=50, embedding_dim=20, post_size=10)
+    net.initialize(seed=3)
+    eng = net.image
+    assert eng.side_mode is None
+    assert net.capture_step(small) and net._graph is not None
+    assert eng.one_side_stream == eng.side_arrangement(None, 2, eng.dtype, capturing=True) == 1
+    net.train_step(big, 1e-3)
+    net.release_graph()
+    torch.cuda.synchronize()
+    assert net._graph is None and eng.B == 129
+    assert eng.one_side_stream == eng.side_arrangement(None, eng.B, eng.dtype, capturing=False) == 1
+    assert eng.side_arrangement(None, 2, eng.dtype, capturing=False) == 2       # (what a saved value would have put back)
+
+
 @pytest.mark.parametrize("B", [16, 96])
 def test_branch_streams_and_pool_order_do_not_change_a_bit(B):
     """The Mixed-block branches on three streams (fork/join by events, one scratch set per stream) and the
@@ -1032,6 +1054,30 @@ def test_branch_streams_and_pool_order_do_not_change_a_bit(B):
         for o in outs[1:]:
             for a, b in zip(outs[0], o):
                 assert torch.equal(a, b), sums
+
+
+def test_input_gradients_do_not_depend_on_the_stream_arrangement():
+    """MixedStage.backward has branches of its own for the input-gradient passes (the moving-statistics backward, the
+    block-closing layers' joint pass) inside the three chains: the image gradient and the logits of input_gradient (batch
+    statistics) and of eval_gradients (moving statistics) are the same bits on one stream and in each side-stream
+    arrangement.  B = 2: the smallest batch at which all nine Mixed blocks still fork and join."""
+    from tumblr_emotions_amd.net import SentimentNet
+    from tumblr_emotions_amd.synthetic import synthetic_batch_numpy, to_device
+    batch = to_device(synthetic_batch_numpy(2, 10, 50, seed=2))
+    outs = []
+    for streams, side in ((False, 1), (True, 0), (True, 1), (True, 2)):
+        net = SentimentNet(mode="joint", nb_emotions=15, rnn_size=32, vocab_size=50, embedding_dim=20, post_size=10)
+        net.initialize(seed=3)
+        net.image.branch_streams, net.image.side_mode = streams, side
+        logits_t, dimg_t = net.input_gradient(batch, 3, seed=5)
+        assert net.image.one_side_stream == side
+        logits_e, dimg_e = net.eval_gradients(batch, 3)[:2]
+        torch.cuda.synchronize()
+        outs.append([t.clone() for t in (logits_t, dimg_t, logits_e, dimg_e)])
+    assert all(float(t.abs().max()) > 0 for t in outs[0])
+    for o in outs[1:]:
+        for a, b in zip(outs[0], o):
+            assert torch.equal(a, b)
 
 
 def test_training_runs_are_bit_reproducible():

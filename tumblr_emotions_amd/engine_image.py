@@ -15,6 +15,7 @@ slim/nets/inception_utils.py:32-71); how is MI355X-first:
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import torch
 
@@ -53,6 +54,25 @@ def _vp(addr):
     return C.c_void_p(addr)
 
 
+# Where a part of a layer's BatchNorm-backward sums comes from when the dgrad that WRITES the part's gradient emitted them
+# (DS_EPI_BNSUMS): the partials tensor [2][ctot][P] of that producer (ctot: its column count) and the part's first column in it
+class SumSource(namedtuple("SumSource", "buf P off ctot")):
+    def ptrs(self):
+        """Addresses of the part's partials of sum g and of sum g*xhat."""
+        return self.buf.data_ptr() + 4 * self.off * self.P, self.buf.data_ptr() + 4 * (self.ctot + self.off) * self.P
+
+    def views(self, n):
+        """... and the two regions themselves, for a part of n columns (sync_bn all-reduces them)."""
+        buf, P, off, ctot = self
+        return [buf[off * P:(off + n) * P], buf[(ctot + off) * P:(ctot + off + n) * P]]
+
+
+# ... and the ds_bn_bwd_reduce launch of a part nobody emitted them for (ConvBN._sum_plan, _run_reduce_jobs): over the
+# part's columns [c0, c0 + n) of the layer's z, or over a max pool's output (y, row stride ldy) and gradient (segs)
+FullReduce = namedtuple("FullReduce", "part c0 n dst")
+PoolReduce = namedtuple("PoolReduce", "segs M n y ldy mean rstd shift dst y_dtype")
+
+
 class ConvBN:
     """slim.conv2d under inception_arg_scope: conv (no bias) -> BatchNorm(train, beta only) -> ReLU.
     `scopes` lists (tf_scope, c0, c1): more than one entry = horizontally fused 1x1 convs."""
@@ -63,6 +83,7 @@ class ConvBN:
         self.trainable, self.fold = trainable, fold
         self.pool_inside = False   # Conv2d_1a_7x7 only: MaxPool_2a inside the conv kernel (z = the window maxima)
         self.slot = 0          # which of the engine's scratch sets (one per branch stream) this layer uses
+        self.z16 = False       # (alloc)
         self.OH, _ = same_pad(H, k, stride)
         self.OW, _ = same_pad(W, k, stride)
         st = eng.store
@@ -191,9 +212,8 @@ class ConvBN:
 
     def set_dy_parts(self, parts):
         """parts: [(c0, c1, address, ld)] -- the channel ranges of this layer's output gradient and where each lives
-        (slices of the block's concat gradient, the reduce buffers' gradients).  part_sums[i] is filled in by the
-        stage whose dgrad WRITES that part when it can also emit the part's BatchNorm sums (DS_EPI_BNSUMS):
-        (partials tensor, P, first column of the part in the producer's output, producer's column count)."""
+        (slices of the block's concat gradient, the reduce buffers' gradients).  part_sums[i] is filled in (sums_from) by
+        the stage whose dgrad WRITES that part when it can also emit the part's BatchNorm sums (a SumSource)."""
         self.dy_parts = parts
         self.dy_segs = make_segments(parts)
         self.part_segs = [make_segments([(0, c1 - c0, ptr, ld)]) for (c0, c1, ptr, ld) in parts]
@@ -203,10 +223,20 @@ class ConvBN:
         self.part_pool = [None] * len(parts)     # (pool stage, first column): the part feeds nothing but that max pool
         self._sum_segs = None
 
+    def sums_from(self, part, src, src2=None):
+        """Part `part` takes its sums from the dgrad epilogue that writes its gradient (src2: its second addend's, dy2)."""
+        self.part_sums[part], self.part_sums2[part] = src, src2
+        self._sum_segs = None
+
+    def sums_from_pool(self, part, pool, off):
+        """Part `part` feeds nothing but the max pool `pool`, from column `off` of its input (_pool_reduce)."""
+        self.part_pool[part] = (pool, off)
+        self._sum_segs = None
+
     def emit_dx_sums(self, y):
         """This layer's dgrad writes the gradient of `y` (an activation relu(bn(.)) with the dgrad output's pixel
         stride): have its epilogue emit the column sums that layer's BatchNorm backward needs.  Returns
-        (partials tensor, P) or None when the dgrad kernel of this shape cannot (implicit-GEMM fallbacks, bf16)."""
+        the SumSource of y's column 0 or None when the dgrad kernel of this shape cannot (implicit-GEMM fallbacks, bf16)."""
         eng = self.eng
         if not eng.bwd_sums or self.dgrad is None:
             return None
@@ -216,13 +246,11 @@ class ConvBN:
         self.dgrad.d.mask_dtype = ops.act_dtype(y)          # (bf16 under 16-bit activation storage)
         self.dx_sums = torch.empty(2 * self.cin * P, device=eng.device)
         self.dx_y = y
-        return self.dx_sums, P
+        return SumSource(self.dx_sums, P, 0, self.cin)
 
     def _sum_plan(self):
         """Where sum g and sum g*xhat of this layer come from: parts whose producer emitted them are taken as they are, the
         others are reduced over their column range (_run_reduce_jobs).  Built once per allocation."""
-        eng = self.eng
-        M, Cc = self.M, self.cout
         if self._sum_segs is None:
             sg = ops.SumSegments()
             sg.nseg = len(self.dy_parts)
@@ -233,96 +261,80 @@ class ConvBN:
                 sg.c_begin[i], sg.c_end[i] = c0, c1
                 src = self.part_sums[i]
                 if src is not None:
-                    buf, P, off, ctot = src
-                    sg.P[i], sg.kind[i] = P, 1
-                    sg.s[i] = buf.data_ptr() + 4 * off * P
-                    sg.q[i] = buf.data_ptr() + 4 * (ctot + off) * P
-                    n = c1 - c0
-                    self._sync_views += [buf[off * P:(off + n) * P], buf[(ctot + off) * P:(ctot + off + n) * P]]
-                    if self.part_sums2[i] is not None:          # the other addend's sums, added by the finalize
-                        buf2, P2, off2, ctot2 = self.part_sums2[i]
-                        sg.P2[i] = P2
-                        sg.s2[i] = buf2.data_ptr() + 4 * off2 * P2
-                        sg.q2[i] = buf2.data_ptr() + 4 * (ctot2 + off2) * P2
-                        self._sync_views += [buf2[off2 * P2:(off2 + n) * P2], buf2[(ctot2 + off2) * P2:(ctot2 + off2 + n) * P2]]
-                elif self.part_pool[i] is not None:
-                    # The part feeds only a max pool.  Every window hands its gradient to ONE input pixel p*, whose
-                    # activation is the pooled value, so   sum_pixels g = sum_windows dpool (ypool > 0)   and
-                    # sum_pixels g*xhat = sum_windows dpool (ypool - beta) (ypool > 0)   -- both sums from the POOLED
-                    # tensors (a quarter of the elements; z is not read at all).  That is ds_bn_bwd_reduce run on
-                    # (z := ypool, mean := beta, rstd := 1, shift := 0).
-                    pool, off = self.part_pool[i]
-                    n = c1 - c0
-                    Mp = pool.B * pool.H * pool.W
-                    Pp = ops.bn_bwd_partials(Mp, n)
-                    sg.P[i], sg.kind[i] = Pp, 0
-                    sg.s[i], sg.q[i] = scratch, scratch + 4 * n * Pp
-                    o0 = (scratch - self.bwdp_buf.data_ptr()) // 4
-                    self._sync_views.append(self.bwdp_buf[o0:o0 + 2 * n * Pp])
-                    seg = make_segments([(0, n, pool.dout.data_ptr() + 4 * off, pool.C)])
-                    if getattr(pool, "raw", False):
-                        # the pool's output holds the window maxima of z itself (pool_inside): the plain reduce on
-                        # (zmax, mean, rstd, shift) -- the same predicate rstd * zmax + shift > 0, the same sum of g
-                        stat = (_vp(self.mean.data_ptr() + 4 * c0), _vp(self.rstd.data_ptr() + 4 * c0), _vp(self.shift.data_ptr() + 4 * c0))
-                    else:
-                        stat = (_vp(self.beta.data_ptr() + 4 * c0), ops._p(eng.ones), ops._p(eng.zeros))
-                    self._reduce_jobs.append(("pool", seg, Mp, n, _vp(pool.out.data_ptr() + pool.out.element_size() * off),
-                                              pool.C, stat, _vp(scratch), ops.act_dtype(pool.out)))
-                    scratch += 4 * 2 * n * Pp
+                    sg.P[i], sg.kind[i] = src.P, 1
+                    sg.s[i], sg.q[i] = src.ptrs()
+                    self._sync_views += src.views(c1 - c0)
+                    src2 = self.part_sums2[i]
+                    if src2 is not None:          # the other addend's sums, added by the finalize
+                        sg.P2[i] = src2.P
+                        sg.s2[i], sg.q2[i] = src2.ptrs()
+                        self._sync_views += src2.views(c1 - c0)
+                    continue
+                n, dst = c1 - c0, _vp(scratch)          # nobody emitted them: one ds_bn_bwd_reduce into this layer's scratch
+                if self.part_pool[i] is None:
+                    job, P = FullReduce(i, c0, n, dst), P0
                 else:
-                    n = c1 - c0
-                    sg.P[i], sg.kind[i] = P0, 0
-                    sg.s[i], sg.q[i] = scratch, scratch + 4 * n * P0
-                    o0 = (scratch - self.bwdp_buf.data_ptr()) // 4
-                    self._sync_views.append(self.bwdp_buf[o0:o0 + 2 * n * P0])
-                    self._reduce_jobs.append(("full", i, c0, n, _vp(scratch)))
-                    scratch += 4 * 2 * n * P0
+                    job = self._pool_reduce(*self.part_pool[i], c0, n, dst)
+                    P = ops.bn_bwd_partials(job.M, n)
+                sg.P[i], sg.kind[i] = P, 0
+                sg.s[i], sg.q[i] = scratch, scratch + 4 * n * P
+                o0 = (scratch - self.bwdp_buf.data_ptr()) // 4
+                self._sync_views.append(self.bwdp_buf[o0:o0 + 2 * n * P])
+                self._reduce_jobs.append(job)
+                scratch += 4 * 2 * n * P
             self._sum_segs = sg
         return self._sum_segs
 
-    def _run_reduce_jobs(self):
+    def _pool_reduce(self, pool, off, c0, n, dst):
+        """The part [c0, c0 + n) feeds only a max pool (its columns from `off`).  Every window hands its gradient to ONE input
+        pixel p*, whose activation is the pooled value, so   sum_pixels g = sum_windows dpool (ypool > 0)   and
+        sum_pixels g*xhat = sum_windows dpool (ypool - beta) (ypool > 0)   -- both sums from the POOLED tensors (a quarter of
+        the elements; z is not read at all).  That is ds_bn_bwd_reduce run on (z := ypool, mean := beta, rstd := 1, shift := 0)."""
         eng = self.eng
-        M = self.M
+        if pool.raw:
+            # the pool's output holds the window maxima of z itself (pool_inside): the plain reduce on
+            # (zmax, mean, rstd, shift) -- the same predicate rstd * zmax + shift > 0, the same sum of g
+            stat = (_vp(self.mean.data_ptr() + 4 * c0), _vp(self.rstd.data_ptr() + 4 * c0), _vp(self.shift.data_ptr() + 4 * c0))
+        else:
+            stat = (_vp(self.beta.data_ptr() + 4 * c0), ops._p(eng.ones), ops._p(eng.zeros))
+        return PoolReduce(make_segments([(0, n, pool.dout.data_ptr() + 4 * off, pool.C)]), pool.B * pool.H * pool.W, n,
+                          _vp(pool.out.data_ptr() + pool.out.element_size() * off), pool.C, *stat, dst, ops.act_dtype(pool.out))
+
+    def _run_reduce_jobs(self):
         for job in self._reduce_jobs:
-            if job[0] == "pool":
-                _, seg, Mp, n, yp, ldy, stat, dst, ydt = job
-                ops.bn_bwd_reduce(yp, seg, Mp, n, stat[0], stat[1], stat[2], dst, ldz=ldy, z_dtype=ydt)
+            if isinstance(job, PoolReduce):
+                ops.bn_bwd_reduce(job.y, job.segs, job.M, job.n, job.mean, job.rstd, job.shift, job.dst, ldz=job.ldy,
+                                  z_dtype=job.y_dtype)
                 continue
-            _, i, c0, n, dst = job
-            off = 4 * c0
-            ops.bn_bwd_reduce(_vp(self.z.data_ptr() + self.z.element_size() * c0), self.part_segs[i], M, n, _vp(self.zmean.data_ptr() + off),
-                              _vp(self.rstd.data_ptr() + off), _vp(self.zshift.data_ptr() + off), dst, ldz=self.ldz,
-                              z_dtype=ops.act_dtype(self.z))
+            off = 4 * job.c0
+            ops.bn_bwd_reduce(_vp(self.z.data_ptr() + self.z.element_size() * job.c0), self.part_segs[job.part], self.M, job.n,
+                              _vp(self.zmean.data_ptr() + off), _vp(self.rstd.data_ptr() + off), _vp(self.zshift.data_ptr() + off),
+                              job.dst, ldz=self.ldz, z_dtype=ops.act_dtype(self.z))
 
     def _bn_bwd_sums(self):
         """Sum g and sum g*xhat of this layer (_sum_plan, _run_reduce_jobs) and one finalize launch."""
-        eng = self.eng
-        M, Cc = self.M, self.cout
-        self._sum_plan()
+        sg = self._sum_plan()
         self._run_reduce_jobs()
-        if eng.sync_bn:
-            # beta's gradient stays this rank's own sum (the gradient all-reduce adds the ranks); the two column MEANS of the
-            # backward formula are over the global batch: finalize once locally for dbeta, all-reduce, finalize again
-            if self.gbeta is not None:
-                ops.bn_bwd_finalize_segs(self._sum_segs, M, Cc, self.beta, self.gbeta, self.coef)
-            for v in self._sync_views:
-                eng.all_reduce(v)
-            ops.bn_bwd_finalize_segs(self._sum_segs, M * eng.sync_world, Cc, self.beta, None, self.coef)
-            return
-        ops.bn_bwd_finalize_segs(self._sum_segs, M, Cc, self.beta, self.gbeta, self.coef)
+        self._finalize(lambda count, gbeta: ops.bn_bwd_finalize_segs(sg, count, self.cout, self.beta, gbeta, self.coef),
+                       self._sync_views)
 
     def _finalize_plain(self, P):
-        """ds_bn_bwd_finalize of bwdp_buf [2][C][P] (sync_bn: as in _bn_bwd_sums)."""
+        """ds_bn_bwd_finalize of bwdp_buf [2][C][P]."""
+        eng, Cc = self.eng, self.cout
+        self._finalize(lambda count, gbeta: ops.bn_bwd_finalize(self.bwdp_buf, P, count, Cc, eng.dummy if gbeta is None else gbeta, self.coef),
+                       (self.bwdp_buf[:2 * Cc * P],) if eng.sync_bn else ())
+
+    def _finalize(self, finalize, views):
+        """The BatchNorm-backward finalize `finalize(count, dbeta)`: one launch -- sync_bn: beta's gradient stays this rank's
+        own sum (the gradient all-reduce adds the ranks) while the two column MEANS of the backward formula are over the
+        global batch, so finalize once locally for dbeta, all-reduce the partial sums (`views`), finalize again."""
         eng = self.eng
-        M, Cc = self.M, self.cout
-        gb = self.gbeta if self.gbeta is not None else eng.dummy
-        if not eng.sync_bn:
-            ops.bn_bwd_finalize(self.bwdp_buf, P, M, Cc, gb, self.coef)
-            return
-        if self.gbeta is not None:
-            ops.bn_bwd_finalize(self.bwdp_buf, P, M, Cc, gb, self.coef)
-        eng.all_reduce(self.bwdp_buf[:2 * Cc * P])
-        ops.bn_bwd_finalize(self.bwdp_buf, P, M * eng.sync_world, Cc, eng.dummy, self.coef)
+        if self.gbeta is not None or not eng.sync_bn:
+            finalize(self.M, self.gbeta)
+        if eng.sync_bn:
+            for v in views:
+                eng.all_reduce(v)
+            finalize(self.M * eng.sync_world, None)
 
     def make_dgrad(self, lddx, allow_z16=False):
         """Conv2DBackpropInput as a forward conv over dz with flipped taps (stride-1 SAME convs only); the library picks
@@ -454,7 +466,7 @@ class ConvBN:
                 count = self.M * eng.sync_world
             if fin is None and not defer_finalize:
                 mm, mv = (self.mm, self.mv) if eng.update_moving else (None, None)
-                if eng.fuse_fin_apply and not eng.sync_bn and segs is not None and not self.skip_apply and not getattr(self, "z16", False):
+                if eng.fuse_fin_apply and not eng.sync_bn and segs is not None and not self.skip_apply and not self.z16:
                     # ds_bn_finalize and the apply pass that reads its result as ONE launch (no dependent-launch boundary)
                     ops.bn_finalize_apply_relu(self.stats_buf, plan.partials, count, self.cout, self.beta, BN_EPS, BN_DECAY,
                                                self.mean, self.rstd, self.shift, mm, mv, self.mean, self.z, self.M, segs,
@@ -609,6 +621,14 @@ class Stage:
     name = ""
     out = None
     dout = None
+    # what the neighbouring stages and the engine ask of ANY stage; the classes that have more to say set them
+    next = None                # the stage that consumes `out` (InceptionV1Engine.__init__)
+    zcat = False               # MixedStage: `out` holds pre-BatchNorm values, the consumers apply rs_cat as they load
+    rs_cat = None
+    raw = False                # PoolStage: `out` holds raw window maxima of the stem's z
+    out_amax = None            # fp8: the device record of max|out|
+    fused_into_pool = False    # ConvStage: feeds nothing but the next max pool, which applies BatchNorm + ReLU
+    track_amax = True          # PoolStage (fp8): some fp8 conv reads `out` (InceptionV1Engine._prune_amax)
 
 
 class InputStage(Stage):
@@ -630,13 +650,10 @@ class ConvStage(Stage):
                             beta_bucket, fold=fold)
         self.H, self.W, self.C = self.layer.OH, self.layer.OW, cout
         self.layers = [self.layer]
-        self.fused_into_pool = False
         self.pool = None
 
     def alloc(self, B):
-        dev = self.eng.device
-        eng = self.eng
-        nxt = getattr(self, "next", None)
+        eng, dev = self.eng, self.eng.device
         # Conv2d_1a_7x7 -> MaxPool_2a_3x3 in one kernel (ds_conv_stem_pool / _bf16): a frozen stem whose BatchNorm + ReLU run
         # behind the pool anyway (fuse_bn_pool); its backward sums come from the pooled tensors (PoolStage.alloc)
         self.layer.pool_inside = self.pool_inside_wanted()
@@ -650,7 +667,7 @@ class ConvStage(Stage):
         self.layer.set_dy_parts([(0, self.C, self.dout.data_ptr(), self.C)])
         # the layer behind a pool that holds raw window maxima (the pooled stem) applies BatchNorm + ReLU as it loads
         self.norm_in = None
-        if getattr(self.prev, "raw", False):
+        if self.prev.raw:
             assert self.layer.fwd.norm_supported()           # (PoolStage.alloc checked it with the same plan arguments)
             self.norm_in = self.prev.rs
             self.layer.fwd.d.norm_rstd, self.layer.fwd.d.norm_shift = self.norm_in[0].data_ptr(), self.norm_in[1].data_ptr()
@@ -660,7 +677,7 @@ class ConvStage(Stage):
             if isinstance(self.prev, ConvStage) and not self.prev.layer.fold:
                 src = self.layer.emit_dx_sums(self.prev.out)
                 if src is not None:
-                    self.prev.layer.part_sums[0] = (src[0], src[1], 0, self.prev.C)
+                    self.prev.layer.sums_from(0, src)
             # ... and Conv2d_2b's dgrad writes the gradient of MaxPool_2a's output.  Behind the pooled stem that IS the stem's
             # whole backward input (sum over windows of dpool (ypool > 0), ConvBN._bn_bwd_sums): its epilogue emits the sums
             # (y rebuilt from the raw window maxima where the pool's output holds those) and the reduce pass over the pooled
@@ -671,13 +688,12 @@ class ConvStage(Stage):
                 if src is not None:
                     if self.prev.raw:
                         self.layer.dgrad.d.mask_rstd, self.layer.dgrad.d.mask_shift = stem.rstd.data_ptr(), stem.shift.data_ptr()
-                    stem.part_sums[0] = (src[0], src[1], 0, self.prev.C)
-                    stem._sum_segs = None
+                    stem.sums_from(0, src)
 
     def pool_inside_wanted(self):
         """The stem with MaxPool_2a inside its kernel -- not while input gradients are wanted: BatchNorm's backward then needs
         the full-resolution z (its mean terms make dz dense), which only the unpooled stem writes."""
-        eng, nxt = self.eng, getattr(self, "next", None)
+        eng, nxt = self.eng, self.next
         return bool(self.layer.fold and eng.stem_pool and eng.stem_direct and eng.fuse_bn_pool and not eng.input_grad
                     and not eng.mul3 and not self.layer.trainable
                     and isinstance(nxt, PoolStage) and nxt.k == 3 and nxt.stride == 2)
@@ -686,7 +702,7 @@ class ConvStage(Stage):
         # fused_into_pool: this conv feeds nothing but the next max pool, which then reads z and applies BN + ReLU
         # after pooling (a quarter of the elements); `out` is not produced
         self.layer.forward(ops._p(self.prev.out), self.prev.C, None if self.pool_applies_bn() else self.segs,
-                           ops.act_dtype(self.prev.out), getattr(self.prev, "out_amax", None))
+                           ops.act_dtype(self.prev.out), self.prev.out_amax)
 
     def pool_applies_bn(self):
         """Does the max pool behind this conv apply BatchNorm + ReLU (to the pooled map, from z)?  Not in a fused inference
@@ -728,7 +744,7 @@ class PoolStage(Stage):
         self.raw, self.rs, self.zmax = False, None, None
         if inside:
             self.zmax = p.layer.z.view(B, self.H, self.W, self.C)
-            nxt = getattr(self, "next", None)
+            nxt = self.next
             if isinstance(nxt, ConvStage) and nxt.layer.k == 1 and not nxt.layer.trainable and not o16:
                 probe = ops.LayerPlan(ops.DS_CONV_FWD, self.eng.arith, self.eng.plan_options(), B, self.H, self.W, self.C,
                                       nxt.layer.cout, 1, 1, self.C, nxt.layer.cout, DS_EPI_STATS)
@@ -744,41 +760,36 @@ class PoolStage(Stage):
         self._own_amax = self.eng.new_amax()
         # the layers whose activation feeds nothing but this pool take their BatchNorm backward sums from the pooled
         # tensors (ConvBN._bn_bwd_sums)
-        if self.eng.bwd_sums or inside:          # (the pooled stem has nothing else to take them from, whatever the switch says)
-            if isinstance(p, ConvStage) and self.k == 3 and self.stride == 2:
-                targets = [(p.layer, 0)]
-            elif not self.eng.bwd_sums:
-                targets = []
-            elif isinstance(p, MixedStage):
-                pb0, _, pb1b, _, pb2b, _ = p.b
-                targets = [(p.fused, 0), (p.c1, pb0), (p.c2, pb0 + pb1b), (p.c3, pb0 + pb1b + pb2b)]
-            else:
-                targets = []
-            for layer, off in targets:
-                layer.part_pool[0] = (self, off)
-                layer._sum_segs = None
+        targets = ()
+        if isinstance(p, ConvStage) and self.k == 3 and self.stride == 2:
+            if self.eng.bwd_sums or inside:      # (the pooled stem has nothing else to take them from, whatever the switch says)
+                targets = ((p.layer, 0),)
+        elif self.eng.bwd_sums and isinstance(p, MixedStage):
+            targets = p.concat_layers()
+        for layer, off in targets:
+            layer.sums_from_pool(0, self, off)
 
     @property
     def out_amax(self):
         # behind a conv fused into the pool the pool kernel produces the activation and tracks its maximum; a plain
         # pool copies values, so its input's maximum bounds its output's
-        if getattr(self.prev, "fused_into_pool", False):
+        if self.prev.fused_into_pool:
             return self._own_amax
-        return getattr(self.prev, "out_amax", None)
+        return self.prev.out_amax
 
     def forward(self):
         p = self.prev
         if self.zmax is not None:        # the stem kernel pooled already
             if not self.raw:
                 if self.apply_segs is None:
-                    am = self._own_amax if getattr(self, "track_amax", True) else None
+                    am = self._own_amax if self.track_amax else None
                     self.apply_segs = make_segments([(0, self.C, self.out.data_ptr(), self.C, ops.act_dtype(self.out), ops._p(am))])
                 ops.bn_apply_relu(p.layer.z, self.B * self.H * self.W, self.C, self.rs[0], self.rs[1], self.apply_segs)
             return
-        if getattr(p, "fused_into_pool", False) and p.pool_applies_bn():
+        if p.fused_into_pool and p.pool_applies_bn():
             ops.maxpool_bn_relu_fwd(p.layer.z, p.layer.rstd, p.layer.shift, self.out, self.argmax, self.B, p.H, p.W, p.C,
-                                    self.k, self.stride, amax=self._own_amax if getattr(self, "track_amax", True) else None)
-        elif getattr(p, "zcat", False):      # the block's concat holds pre-BatchNorm values: normalise on load
+                                    self.k, self.stride, amax=self._own_amax if self.track_amax else None)
+        elif p.zcat:      # the block's concat holds pre-BatchNorm values: normalise on load
             ops.maxpool_bn_relu_fwd(p.out, p.rs_cat[0], p.rs_cat[1], self.out, self.argmax, self.B, p.H, p.W, p.C,
                                     self.k, self.stride)
         else:
@@ -788,7 +799,7 @@ class PoolStage(Stage):
 
     def backward(self, need_dx):
         p = self.prev
-        if getattr(p, "fused_into_pool", False) and self.stride == 2:
+        if p.fused_into_pool and self.stride == 2:
             return          # the conv in front consumes self.dout / self.argmax directly (ConvBN.backward_pooled)
         if need_dx:
             ops.maxpool_bwd(self.dout, self.argmax, p.dout, False, self.B, p.H, p.W, p.C, self.k, self.stride, "SAME")
@@ -819,6 +830,11 @@ class MixedStage(Stage):
         self.layers = [self.fused, self.c1, self.c2, self.c3]
         self.c2.slot, self.c3.slot = 1, 2
         self.ev = None
+
+    def concat_layers(self):
+        """(layer, first column of its output in the block's concat) of the four layers that write the concat."""
+        b0, _, b1b, _, b2b, _ = self.b
+        return ((self.fused, 0), (self.c1, b0), (self.c2, b0 + b1b), (self.c3, b0 + b1b + b2b))
 
     def alloc(self, B):
         eng, dev = self.eng, self.eng.device
@@ -851,21 +867,18 @@ class MixedStage(Stage):
             eng.need_stats(self.c3.fwd.partials * 2 * b3)          # (the fused launch groups its partial sums by image rows)
         self.pooled = None if self.fuse_b3 else torch.empty(M, cin, device=dev, dtype=self.prev.out.dtype)       # a pool copies values
         o, do = self.out.data_ptr(), self.dout.data_ptr()
-        off1, off2, off3 = b0, b0 + b1b, b0 + b1b + b2b
         nf = b0 + b1a + b2a
         es, dt_o, dt_r = self.out.element_size(), ops.act_dtype(self.out), ops.act_dtype(self.r1)
         self.out_amax, self.r1_amax, self.r2_amax = eng.new_amax(), eng.new_amax(), eng.new_amax()
         am_o, am_1, am_2 = ops._p(self.out_amax), ops._p(self.r1_amax), ops._p(self.r2_amax)
         self.seg_f = make_segments([(0, b0, o, Ct, dt_o, am_o), (b0, b0 + b1a, self.r1.data_ptr(), b1a, dt_r, am_1),
                                     (b0 + b1a, nf, self.r2.data_ptr(), b2a, dt_r, am_2)])
-        self.seg_1 = make_segments([(0, b1b, o + es * off1, Ct, dt_o, am_o)])
-        self.seg_2 = make_segments([(0, b2b, o + es * off2, Ct, dt_o, am_o)])
-        self.seg_3 = make_segments([(0, b3, o + es * off3, Ct, dt_o, am_o)])
+        self.seg_1, self.seg_2, self.seg_3 = (make_segments([(0, layer.cout, o + es * off, Ct, dt_o, am_o)])
+                                              for layer, off in self.concat_layers()[1:])
         self.fused.set_dy_parts([(0, b0, do, Ct), (b0, b0 + b1a, self.dr1.data_ptr(), b1a),
                                  (b0 + b1a, nf, self.dr2.data_ptr(), b2a)])
-        self.c1.set_dy_parts([(0, b1b, do + 4 * off1, Ct)])
-        self.c2.set_dy_parts([(0, b2b, do + 4 * off2, Ct)])
-        self.c3.set_dy_parts([(0, b3, do + 4 * off3, Ct)])
+        for layer, off in self.concat_layers()[1:]:
+            layer.set_dy_parts([(0, layer.cout, do + 4 * off, Ct)])
         # zcat: the Branch_1 / Branch_2 3x3 and the Branch_3 1x1 convs write z straight into their slices of the concat
         # buffer and NO BatchNorm-apply pass follows; whoever reads the concat -- the next block's fused 1x1 conv, its
         # Branch_3 pool, the stage pool, the BatchNorm-sums epilogue of the next block's fused dgrad -- applies
@@ -889,7 +902,7 @@ class MixedStage(Stage):
             self.mean_cat = torch.zeros(Ct, device=dev)
             self.coef_cat = torch.empty(2, Ct - b0, device=dev)
             zc = self.out.view(M, Ct)
-            for layer, off in ((self.c1, off1), (self.c2, off2), (self.c3, off3)):
+            for layer, off in self.concat_layers()[1:]:
                 n = layer.cout
                 layer.use_concat_slice(zc[:, off:off + n], Ct, self.rs_cat[0, off:off + n], self.rs_cat[1, off:off + n],
                                        self.mean_cat[off:off + n])
@@ -897,7 +910,7 @@ class MixedStage(Stage):
             self._fin_jobs = {}
             self._close_plan = None
             self.fa_ticket = torch.zeros(2, dtype=torch.int32, device=dev)
-        if getattr(self.prev, "zcat", False):    # this block reads a zcat concat
+        if self.prev.zcat:    # this block reads a zcat concat
             self.fused.fwd.d.norm_rstd = self.prev.rs_cat[0].data_ptr()
             self.fused.fwd.d.norm_shift = self.prev.rs_cat[1].data_ptr()
             if self.fuse_b3:                     # ... and so does the pooling loader of its Branch_3 conv
@@ -919,7 +932,7 @@ class MixedStage(Stage):
         for part, (layer, r) in enumerate(((self.c1, self.r1), (self.c2, self.r2)), start=1):
             src = layer.emit_dx_sums(r)
             if src is not None:
-                self.fused.part_sums[part] = (src[0], src[1], 0, layer.cin)
+                self.fused.sums_from(part, src)
         #  * the fused 1x1 dgrad writes (last, accumulating onto the pool path: pool_first) the gradient of the block
         #    input = the previous block's concat output, i.e. one part of each of ITS four layers.
         p = self.prev
@@ -931,14 +944,12 @@ class MixedStage(Stage):
         self.pool_first = bool(eng.pool_first and self.fused.dgrad.family in fams)
         if isinstance(p, MixedStage) and self.pool_first:
             src = self.fused.emit_dx_sums(p.out)
-            if src is not None and getattr(p, "zcat", False):      # the epilogue rebuilds y from the concat's z
+            if src is not None and p.zcat:      # the epilogue rebuilds y from the concat's z
                 self.fused.dgrad.d.mask_rstd = p.rs_cat[0].data_ptr()
                 self.fused.dgrad.d.mask_shift = p.rs_cat[1].data_ptr()
             if src is not None:
-                pb0, _, pb1b, _, pb2b, pb3 = p.b
-                for layer, off in ((p.fused, 0), (p.c1, pb0), (p.c2, pb0 + pb1b), (p.c3, pb0 + pb1b + pb2b)):
-                    layer.part_sums[0] = (src[0], src[1], off, cin)
-                    layer._sum_segs = None
+                for layer, off in p.concat_layers():
+                    layer.sums_from(0, src._replace(off=off))
         #  * where the fused dgrad cannot accumulate (the 16-bit configurations' register-direct kernels) the order is the
         #    reverse: the dgrad writes, Branch_3's pool gradient is added LAST -- and that launch, which then holds the complete
         #    gradient of the previous block's output, emits the sums instead (ds_maxpool3_bwd_sums)
@@ -950,7 +961,7 @@ class MixedStage(Stage):
         self.pool_sums = None
         self.split_dout = False
         if isinstance(p, MixedStage) and not self.pool_first and eng.bwd_sums and eng.pool_sums and cin <= 1024 \
-                and not getattr(p, "zcat", False):          # (a zcat concat holds z, not y: the dgrad epilogue's business)
+                and not p.zcat:          # (a zcat concat holds z, not y: the dgrad epilogue's business)
             P = ops.maxpool3_bwd_sums_partials(B, p.W, cin)
             self.pool_sums = torch.empty(2 * cin * P, device=dev)
             # (the dgrad addend's sums: NOT from the register-direct kernels' DS_EPI_BNSUMS epilogue -- measured, it costs the
@@ -962,36 +973,73 @@ class MixedStage(Stage):
                 P1 = ops.bn_bwd_partials(M, cin)
                 self.dgrad_sums = torch.empty(2 * cin * P1, device=dev)
                 self._dgrad_sum_segs = make_segments([(0, cin, p.dout.data_ptr(), cin)])
-                src = (self.dgrad_sums, P1)
+                src = SumSource(self.dgrad_sums, P1, 0, cin)
                 self.split_dout = True
                 p.dout2 = torch.empty_like(p.dout)
                 delta = p.dout2.data_ptr() - p.dout.data_ptr()
-            pb0, _, pb1b, _, pb2b, pb3 = p.b
-            for layer, off in ((p.fused, 0), (p.c1, pb0), (p.c2, pb0 + pb1b), (p.c3, pb0 + pb1b + pb2b)):
+            for layer, off in p.concat_layers():
+                pool_src = SumSource(self.pool_sums, P, off, cin)
                 if self.split_dout:
-                    layer.part_sums[0] = (src[0], src[1], off, cin)
-                    layer.part_sums2[0] = (self.pool_sums, P, off, cin)
+                    layer.sums_from(0, src._replace(off=off), pool_src)
                     layer.dy_segs.ptr2[0] = layer.dy_segs.ptr[0] + delta          # (part 0 of each layer lives in p.dout)
                     layer.dy2 = True
                 else:
-                    layer.part_sums[0] = (self.pool_sums, P, off, cin)
-                layer._sum_segs = None
+                    layer.sums_from(0, pool_src)
 
     # The three chains behind the block input -- [fused 1x1 -> Branch_1 3x3], [... -> Branch_2 3x3] and
     # [3x3/1 pool -> Branch_3 1x1] -- are independent: Branch_3 and then Branch_2 are issued on a side stream (fork /
     # join by events, each chain with its own scratch set), so one chain's single-workgroup finalize kernels and the
     # partly filled last round of its conv launches run under another chain's kernels.
-    def _events(self):
+    def _fork_join(self, head, tail, branch2, branch3):
+        """Issue the three chains in the arrangement the engine selects and join them on the current stream.  The main
+        chain is head (None: nothing) then tail; the Branch_2 chain starts behind `head` where there is one (forward: it
+        reads r2, which the fused 1x1 conv writes), else at the fork like Branch_3 (backward).  eng.one_side_stream 0:
+        Branch_2 and Branch_3 on a side stream each; 1: Branch_3, then Branch_2, on ONE side stream; 2: only Branch_3 beside
+        the main chain."""
+        eng = self.eng
+        if not (eng.branch_streams and eng.side):
+            for chain in ((branch3, tail, branch2) if head is None else (head, tail, branch2, branch3)):
+                chain()
+            return
+        main = torch.cuda.current_stream()
+        one = eng.one_side_stream
+        s3 = eng.side[1]
         if self.ev is None:
             self.ev = [torch.cuda.Event() for _ in range(4)]
-        return self.ev
+        e_in, e_f, e_2, e_3 = self.ev
+        e_in.record(main)
+        with torch.cuda.stream(s3):
+            s3.wait_event(e_in)
+            branch3()
+            if not one:
+                e_3.record(s3)
+        if head is not None:
+            head()
+        if one == 2:
+            e_2.record(s3)                # (the join below: the end of the Branch_3 chain)
+            branch2()
+        else:
+            s2 = s3 if one else eng.side[0]
+            if head is not None:
+                e_f.record(main)
+            with torch.cuda.stream(s2):
+                if head is not None:
+                    s2.wait_event(e_f)
+                elif not one:             # (one side stream: it has waited for the fork in front of Branch_3)
+                    s2.wait_event(e_in)
+                branch2()
+                e_2.record(s2)
+        tail()
+        main.wait_event(e_2)
+        if not one:
+            main.wait_event(e_3)
 
     def _zcat_ok(self, B):
         """Can this block leave z in its concat buffer (see alloc)?  fp32 storage, nothing trainable in this block or in
         its consumer (a weight gradient reads activations), and a consumer whose loader can normalise: a MixedStage whose
         fused 1x1 conv runs on the wide kernel (ds_conv_igemm_norm_supported), or a max pool."""
         eng = self.eng
-        nxt = getattr(self, "next", None)
+        nxt = self.next
         if not (eng.zcat and eng.dtype == "f32" and not eng.act16 and not eng.train_all):
             return False
         if any(l.trainable for l in self.layers):
@@ -1010,7 +1058,7 @@ class MixedStage(Stage):
         p = self.prev
         if self.fuse_b3:                 # formed on load by the Branch_3 conv (alloc)
             return
-        if getattr(p, "zcat", False):
+        if p.zcat:
             ops.maxpool_bn_relu_fwd(p.out, p.rs_cat[0], p.rs_cat[1], self.pooled, self.argmax, self.B, p.H, p.W, p.C, 3, 1)
         else:
             ops.maxpool_fwd(p.out, self.pooled, self.argmax, self.B, p.H, p.W, p.C, 3, 1, "SAME")
@@ -1073,50 +1121,17 @@ class MixedStage(Stage):
         p = self.prev
         b0, b1a, b1b, b2a, b2b, b3 = self.b
         x = ops._p(p.out)
-        eng = self.eng
         dx_, dr_ = ops.act_dtype(p.out), ops.act_dtype(self.r1)
-        ax_, a1_, a2_ = getattr(p, "out_amax", None), self.r1_amax, self.r2_amax      # fp8: max|.| words of the inputs
+        ax_, a1_, a2_ = p.out_amax, self.r1_amax, self.r2_amax      # fp8: max|.| words of the inputs
         defer = self._batch_forward()
-        if not (eng.branch_streams and eng.side):
-            self.fused.forward(x, p.C, self.seg_f, dx_, ax_)
-            self.c1.forward(ops._p(self.r1), b1a, self.seg_1, dr_, a1_, defer)
-            self.c2.forward(ops._p(self.r2), b2a, self.seg_2, dr_, a2_, defer)
+
+        def branch3():
             self._pool_fwd()
             self.c3.forward(x if self.fuse_b3 else ops._p(self.pooled), p.C, self.seg_3, dx_, ax_, defer)
-            if defer:
-                self._finalize_closing()
-            return
-        main = torch.cuda.current_stream()
-        s1, s2 = eng.side
-        e_in, e_f, e_2, e_3 = self._events()
-        e_in.record(main)
-        if eng.one_side_stream:
-            s1 = s2
-        with torch.cuda.stream(s2):
-            s2.wait_event(e_in)
-            self._pool_fwd()
-            self.c3.forward(x if self.fuse_b3 else ops._p(self.pooled), p.C, self.seg_3, dx_, ax_, defer)
-            if not eng.one_side_stream:
-                e_3.record(s2)
-        self.fused.forward(x, p.C, self.seg_f, dx_, ax_)
-        if eng.one_side_stream == 2:        # only the Branch_3 chain on the side stream
-            with torch.cuda.stream(s2):
-                e_2.record(s2)
-            self.c2.forward(ops._p(self.r2), b2a, self.seg_2, dr_, a2_, defer)
-            self.c1.forward(ops._p(self.r1), b1a, self.seg_1, dr_, a1_, defer)
-            main.wait_event(e_2)
-            if defer:
-                self._finalize_closing()
-            return
-        e_f.record(main)
-        with torch.cuda.stream(s1):
-            s1.wait_event(e_f)
-            self.c2.forward(ops._p(self.r2), b2a, self.seg_2, dr_, a2_, defer)
-            e_2.record(s1)
-        self.c1.forward(ops._p(self.r1), b1a, self.seg_1, dr_, a1_, defer)
-        main.wait_event(e_2)
-        if not eng.one_side_stream:
-            main.wait_event(e_3)
+
+        self._fork_join(lambda: self.fused.forward(x, p.C, self.seg_f, dx_, ax_),
+                        lambda: self.c1.forward(ops._p(self.r1), b1a, self.seg_1, dr_, a1_, defer),
+                        lambda: self.c2.forward(ops._p(self.r2), b2a, self.seg_2, dr_, a2_, defer), branch3)
         if defer:
             self._finalize_closing()
 
@@ -1160,36 +1175,9 @@ class MixedStage(Stage):
             elif need_dx and self.split_dout:       # the pool gradient into its OWN tensor, with its own sums: inside this chain
                 ops.maxpool3_bwd_sums(self.dpooled, self.argmax, p.dout2, False, p.out, self.B, p.H, p.W, p.C, self.pool_sums)
 
-        if not (eng.branch_streams and eng.side):
-            branch3()
-            closing(self.c1, ops._p(self.r1), b1a, ops._p(self.dr1), True)
-            closing(self.c2, ops._p(self.r2), b2a, ops._p(self.dr2), True)
-        else:
-            main = torch.cuda.current_stream()
-            s1, s2 = eng.side
-            e_in, e_f, e_2, e_3 = self._events()
-            e_in.record(main)
-            if eng.one_side_stream:
-                s1 = s2
-            with torch.cuda.stream(s2):
-                s2.wait_event(e_in)
-                branch3()
-                if not eng.one_side_stream:
-                    e_3.record(s2)
-            if eng.one_side_stream == 2:
-                with torch.cuda.stream(s2):
-                    e_2.record(s2)
-                closing(self.c2, ops._p(self.r2), b2a, ops._p(self.dr2), True)
-            else:
-                with torch.cuda.stream(s1):
-                    if not eng.one_side_stream:
-                        s1.wait_event(e_in)
-                    closing(self.c2, ops._p(self.r2), b2a, ops._p(self.dr2), True)
-                    e_2.record(s1)
-            closing(self.c1, ops._p(self.r1), b1a, ops._p(self.dr1), True)
-            main.wait_event(e_2)
-            if not eng.one_side_stream:
-                main.wait_event(e_3)
+        # (the fused layer runs last, behind the join: nothing in the three chains waits for more than the block's gradient)
+        self._fork_join(None, lambda: closing(self.c1, ops._p(self.r1), b1a, ops._p(self.dr1), True),
+                        lambda: closing(self.c2, ops._p(self.r2), b2a, ops._p(self.dr2), True), branch3)
         if infer:
             self.fused.backward_infer(ops._p(p.dout))
             if not pool_first and not self.split_dout:
@@ -1328,6 +1316,7 @@ class InceptionV1Engine:
         self._restore_pivots = None
         self._stats_n = self._bwdp_n = self._ws_bytes = 0
         self.B = None
+        self.alloc_gen = 0           # bumped by every alloc(): SentimentNet keys a captured step on it
         self.input = InputStage(self, image_size)
         self.stages = []
         prev = self.input
@@ -1401,7 +1390,7 @@ class InceptionV1Engine:
             return layer.fwd.family == ops.DS_FAM_FP8D
 
         def consumers(st):
-            nxt = getattr(st, "next", None)
+            nxt = st.next
             if isinstance(nxt, ConvStage):
                 return [nxt.layer]
             if isinstance(nxt, MixedStage):
@@ -1445,13 +1434,21 @@ class InceptionV1Engine:
     def need_ws(self, nbytes):
         self._ws_bytes = max(self._ws_bytes, nbytes)
 
+    @staticmethod
+    def side_arrangement(side_mode, B, dtype, capturing=False):
+        """one_side_stream (MixedStage._fork_join): side_mode where one is set, else by batch size (the sweeps quoted in
+        __init__); a step captured into a hipGraph keeps ONE side stream whatever side_mode says (SentimentNet.capture_step)."""
+        if capturing:
+            return 1
+        return (2 if (B <= 128 and dtype == "f32") else 1) if side_mode is None else int(side_mode)
+
     def alloc(self, B):
         if self.B == B:
             return
         dev = self.device
         self.B = B
-        self.alloc_gen = getattr(self, "alloc_gen", 0) + 1      # SentimentNet: a captured step is stale after this
-        self.one_side_stream = (2 if (B <= 128 and self.dtype == "f32") else 1) if self.side_mode is None else int(self.side_mode)
+        self.alloc_gen += 1      # SentimentNet: a captured step is stale after this
+        self.one_side_stream = self.side_arrangement(self.side_mode, B, self.dtype)
         # fp8: device words that collect max|.| of the tensors the fp8 convs read (atomic max in the producing kernels,
         # zeroed at the start of every forward pass): the per-tensor scales without separate ds_absmax passes
         self.amax_pool = torch.zeros(AMAX_RECORDS * ops.AMAX_FLOATS, device=dev) if self.dtype == "fp8" else None

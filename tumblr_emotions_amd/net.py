@@ -95,7 +95,6 @@ class SentimentNet:
         self.logits = None
         self._graph = None           # captured training step (capture_step)
         self._graph_key = None
-        self._eager_side_streams = None      # the image engine's one_side_stream before a capture narrowed it (release_graph)
 
     # ---- variables --------------------------------------------------------------------------------
     def initialize(self, seed=1):
@@ -544,11 +543,10 @@ class SentimentNet:
             # the small-batch default (a side stream per branch chain, side_mode 0) is for eager launches: hipStreamEndCapture
             # of this ROCm (7.2) segfaults on the joint step captured with three chains joined per block (B = 32, real dims),
             # and a replayed graph gains nothing from it (4.07 ms with one side stream) -- whatever side_mode says, a captured
-            # step keeps ONE side stream; release_graph() restores the eager setting
-            if self._eager_side_streams is None:
-                self._eager_side_streams = self.image.one_side_stream
-            if self.image.one_side_stream != 1:      # (0: three joined side streams break hipStreamEndCapture; 2: slower as a graph, 3.95 vs 3.78 ms)
-                self.image.one_side_stream = 1
+            # step keeps ONE side stream (0: three joined side streams break hipStreamEndCapture; 2: slower as a graph, 3.95 vs
+            # 3.78 ms); release_graph() puts the eager arrangement back
+            im = self.image
+            im.one_side_stream = im.side_arrangement(im.side_mode, im.B, im.dtype, capturing=True)
         # ... and of the BatchNorm pivots (each layer's previous batch mean), so that the first replayed step rounds
         # exactly like the eager step it replaces
         pivots = [] if self.image is None else [l.mean for l in self.image.layers]
@@ -575,6 +573,6 @@ class SentimentNet:
         self._graph = self._graph_key = None
         if self.image is not None:
             self.image.seed_dev = None       # eager steps and predict() take the host seed again
-            if self._eager_side_streams is not None:      # (capture_step may have narrowed it to one side stream)
-                self.image.one_side_stream = self._eager_side_streams
-                self._eager_side_streams = None
+            im = self.image
+            if im.B is not None:      # capture_step narrowed it to one side stream: back to what alloc chooses for this batch size
+                im.one_side_stream = im.side_arrangement(im.side_mode, im.B, im.dtype)
