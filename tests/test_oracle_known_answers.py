@@ -217,3 +217,86 @@ def test_third_lstm_restatement_torch_nn_lstm_agrees():
     ht.backward(torch.tensor(dh))
     np.testing.assert_allclose(ht.detach().numpy(), h_last_nn.detach().numpy(), atol=1e-13)
     np.testing.assert_allclose(ref.p["Text/rnn/basic_lstm_cell/kernel"].grad.numpy(), dk_nn, atol=1e-12)
+
+
+# ------------------------------------------------------------------------------------------------------
+# MaxPool / MaxPoolGrad tie rule ("MaxPool"): the winner of a window is its FIRST maximum in row-major
+# order of the padded window, named by the tap index kh*k + kw; MaxPoolGrad sends the whole gradient of the window
+# there.  TensorFlow's MaxPoolGrad does this ([TF-sem]: its CPU kernel takes Eigen's argmax of the window, its GPU
+# kernel the first index reaching the maximum).  With 16-bit activation storage exact ties among POSITIVE values
+# are routine, so the rule decides where gradients go; every kernel-level pool test leans on it.  The answers
+# below are worked out by hand on an input whose windows hold several equal positive maxima.
+# ------------------------------------------------------------------------------------------------------
+POOL_TIE_INPUT = [[1, 3, 3, 0],
+                  [2, 3, 1, 4],
+                  [4, 0, 4, 4],
+                  [1, 2, 2, 2]]
+
+
+def _pool_tie_case(k, stride, mode, dy):
+    x = np.array(POOL_TIE_INPUT, dtype=np.float64).reshape(1, 4, 4, 1)
+    dy = np.array(dy, dtype=np.float64)
+    dy = dy.reshape(1, dy.shape[0], dy.shape[1], 1)
+    return (S.max_pool(x, k, stride, mode)[0, :, :, 0], S.max_pool_argmax(x, k, stride, mode)[0, :, :, 0],
+            S.max_pool_bwd(x, dy, k, stride, mode)[0, :, :, 0])
+
+
+def test_max_pool_tie_rule_known_answers():
+    # 3x3 / 1 SAME (one padded cell all round); dy = 2**(4*oh + ow) so that a sum names its windows
+    y, arg, dx = _pool_tie_case(3, 1, "SAME", [[2.0 ** (4 * i + j) for j in range(4)] for i in range(4)])
+    np.testing.assert_array_equal(y, [[3, 3, 4, 4], [4, 4, 4, 4], [4, 4, 4, 4], [4, 4, 4, 4]])
+    np.testing.assert_array_equal(arg, [[5, 4, 8, 7], [7, 6, 5, 4], [4, 3, 2, 1], [1, 0, 1, 0]])
+    # the 3 at (0,1) beats the equal 3s at (0,2) and (1,1); of the 4s only (1,3), (2,0) and (2,2) ever come first:
+    # (2,3) never wins although it is a maximum of six windows
+    np.testing.assert_array_equal(dx, [[0, 1 + 2, 0, 0],
+                                       [0, 0, 0, 4 + 8 + 64 + 128 + 1024 + 2048],
+                                       [16 + 32 + 256 + 512 + 4096 + 8192, 0, 16384 + 32768, 0],
+                                       [0, 0, 0, 0]])
+    # 3x3 / 2 SAME on an even size: no padding above / left, one cell below / right
+    y, arg, dx = _pool_tie_case(3, 2, "SAME", [[1, 2], [4, 8]])
+    np.testing.assert_array_equal(y, [[4, 4], [4, 4]])
+    np.testing.assert_array_equal(arg, [[6, 4], [0, 0]])
+    np.testing.assert_array_equal(dx, [[0, 0, 0, 0], [0, 0, 0, 2], [1 + 4, 0, 8, 0], [0, 0, 0, 0]])
+    # 2x2 / 2 (SAME and VALID coincide): the 3s of the first window and the 4s of the last one tie
+    for mode in ("SAME", "VALID"):
+        y, arg, dx = _pool_tie_case(2, 2, mode, [[1, 2], [4, 8]])
+        np.testing.assert_array_equal(y, [[3, 4], [4, 4]])
+        np.testing.assert_array_equal(arg, [[1, 3], [0, 0]])
+        np.testing.assert_array_equal(dx, [[0, 1, 0, 0], [0, 0, 0, 2], [4, 0, 8, 0], [0, 0, 0, 0]])
+
+
+@pytest.mark.parametrize("geometry", [(3, 1, "SAME"), (3, 2, "SAME"), (3, 2, "VALID"), (2, 2, "SAME"), (2, 2, "VALID"),
+                                      (2, 1, "SAME"), (5, 3, "SAME")])
+def test_max_pool_bwd_is_the_scatter_of_dy_by_max_pool_argmax(geometry):
+    """max_pool_argmax and max_pool_bwd state the same rule: adding every window's dy onto the input cell its winner
+    names (an explicit loop, no window views) gives max_pool_bwd, on inputs where most windows tie."""
+    k, s, mode = geometry
+    rng = np.random.RandomState(k * 10 + s)
+    tied = windows = 0
+    for shape in [(2, 7, 5, 3), (1, 4, 9, 2), (2, 6, 6, 1)]:
+        n, h, w, c = shape
+        x = np.maximum(np.round(rng.normal(scale=0.3, size=shape) * 4) / 4, 0)
+        arg = S.max_pool_argmax(x, k, s, mode)
+        y = S.max_pool(x, k, s, mode)
+        dy = rng.normal(size=arg.shape)
+        oh, ow = arg.shape[1:3]
+        pt = S.same_pad(h, k, s)[1] if mode == "SAME" else 0
+        pl = S.same_pad(w, k, s)[1] if mode == "SAME" else 0
+        dx = np.zeros(shape)
+        windows += arg.size
+        for i in np.ndindex(n, oh, ow, c):
+            kh, kw = divmod(int(arg[i]), k)
+            ih, iw = i[1] * s - pt + kh, i[2] * s - pl + kw
+            assert 0 <= ih < h and 0 <= iw < w              # a padded cell never wins
+            assert x[i[0], ih, iw, i[3]] == y[i]
+            # first in row-major order: no earlier tap of the window holds the maximum
+            for t in range(int(arg[i])):
+                jh, jw = i[1] * s - pt + t // k, i[2] * s - pl + t % k
+                if 0 <= jh < h and 0 <= jw < w:
+                    assert x[i[0], jh, jw, i[3]] < y[i]
+            tied += sum(1 for t in range(int(arg[i]) + 1, k * k)
+                        if 0 <= i[1] * s - pt + t // k < h and 0 <= i[2] * s - pl + t % k < w
+                        and x[i[0], i[1] * s - pt + t // k, i[2] * s - pl + t % k, i[3]] == y[i]) > 0
+            dx[i[0], ih, iw, i[3]] += dy[i]
+        np.testing.assert_allclose(S.max_pool_bwd(x, dy, k, s, mode), dx, rtol=0, atol=1e-12)
+    assert 4 * tied >= windows                                  # the inputs do tie
