@@ -824,6 +824,98 @@ typedef struct ds_preprocess_train_desc {
 int ds_preprocess_train(const uint8_t *bytes, int64_t nbytes, const ds_preprocess_train_desc *desc, int32_t batch,
                         const float *lut, float *out, int32_t out_h, int32_t out_w, void *stream);
 
+/* Baseline JPEG decode, split in two (the decode of load_batch_with_text, image_model/im_model.py:78-116, which the
+ * reference leaves to tf.image.decode_jpeg): the sequential half -- marker parse and Huffman decode -- is host code
+ * (csrc/jpeg_host.cpp: no HIP call, HOST pointers, callable from any thread, no global state); the parallel half --
+ * dequantisation, 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB and the crop -- is ds_jpeg_reconstruct on the device,
+ * which writes the ragged uint8 buffer ds_preprocess_eval / ds_preprocess_train read.  The arithmetic is libjpeg's default
+ * decode path (jpeg_idct_islow, fancy upsampling, the fixed-point ycc_rgb tables): integers throughout, so the pixels
+ * equal Pillow's byte for byte.
+ *
+ * Supported streams: SOF0 / SOF1 Huffman, 8-bit samples, 8-bit quantisation tables, ONE interleaved scan, one component
+ * (grey) or three (YCbCr) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, any restart interval.  Everything else --
+ * progressive / arithmetic / lossless coding, 12-bit samples, four components, an Adobe marker that does not say YCbCr,
+ * component ids 'R','G','B', other sampling factors, 16-bit tables, a stream that ends early, any marker irregularity,
+ * a Huffman code that does not decode, a coefficient whose product with its quantiser exceeds 32767 in magnitude, a block
+ * with a column of dequantised coefficients large enough to make a pass-1 output of the inverse DCT leave +-16383
+ * (libjpeg-turbo's SIMD path forms sums in 16 bits beyond that; pixel data stays far below), an image of more than
+ * 89478485 pixels or with more blocks than its scan can hold -- is DS_JPEG_UNSUPPORTED: not an error, the caller decodes
+ * that image some other way.
+ * The host functions read untrusted bytes: every length and index is checked against `n`, nothing is read past the
+ * buffer or written past `capacity`.  They do not set ds_last_error(); they return DS_OK, DS_JPEG_UNSUPPORTED,
+ * DS_JPEG_MORE or DS_ERR_ARG (a null pointer, a negative size).
+ *
+ * Coefficient storage of one image: quantised coefficients, de-zigzagged to natural order (row * 8 + column), 64 int16
+ * per block, the blocks of a component in raster order over its PADDED grid (whole MCUs: blocks_w = ceil(width / (8 h))
+ * * h for luma, ceil(width / (8 h)) for chroma and grey, likewise blocks_h), component after component. */
+#define DS_JPEG_UNSUPPORTED 1      /* not an error: outside the supported set                                          */
+#define DS_JPEG_MORE 2             /* `capacity` is too small: ds_jpeg_info.coef_count int16 are needed                */
+#define DS_JPEG_444 0              /* sampling classes: the numbers Pillow's `subsampling` uses                        */
+#define DS_JPEG_422 1
+#define DS_JPEG_420 2
+#define DS_JPEG_GREY 3
+typedef struct ds_jpeg_info {
+    int32_t width, height;         /* pixels                                                                           */
+    int32_t components;            /* 1 or 3                                                                           */
+    int32_t sampling;              /* DS_JPEG_444 / _422 / _420 / _GREY                                                */
+    int32_t restart_interval;      /* MCUs between restart markers, 0 = none                                           */
+    int32_t supported;             /* 1 when the stream is in the supported set (the fields above are then valid)      */
+    int64_t coef_count;            /* int16 coefficients of the padded block grids, all components                     */
+    int64_t coef_bytes;            /* 2 * coef_count                                                                   */
+    uint8_t quant[3][64];          /* per component, natural order (grey: [0] only)                                    */
+} ds_jpeg_info;
+/* Markers only (and a walk over the entropy-coded bytes that checks stuffing, the restart sequence and the EOI). */
+int ds_jpeg_probe(const uint8_t *bytes, int64_t n, ds_jpeg_info *info);
+/* Huffman decode into coef[0 .. info->coef_count); `info` is what ds_jpeg_probe returned for the same bytes. */
+int ds_jpeg_entropy_decode(const uint8_t *bytes, int64_t n, const ds_jpeg_info *info, int16_t *coef, int64_t capacity);
+
+/* One ds_jpeg_desc per image of a ragged launch. */
+typedef struct ds_jpeg_desc {
+    int64_t coef_offset;           /* first int16 of the image in `coef`; a multiple of 8 (16-byte loads)              */
+    int64_t out_offset;            /* first byte of the crop in `out_bytes`; a multiple of 4 (pack_ragged's layout)    */
+    int32_t width, height;         /* image size in pixels                                                             */
+    int32_t sampling;              /* DS_JPEG_*                                                                        */
+    int32_t y0, x0, crop_h, crop_w;/* crop box, inside the image, at least 1 x 1                                       */
+    int32_t reserved;              /* 0                                                                                */
+    uint8_t quant[3][64];          /* ds_jpeg_info.quant                                                               */
+} ds_jpeg_desc;
+/* The reconstruction on the HOST, plain C++: out_bytes[out_offset + (y * crop_w + x) * 3 + c] for every image of the
+ * table, the same arithmetic as ds_jpeg_reconstruct (one definition, csrc/jpeg_common.h).  Checks every descriptor
+ * against ncoef and nbytes (DS_ERR_ARG).  Bytes outside the crops are not touched. */
+int ds_jpeg_reconstruct_host(const int16_t *coef, int64_t ncoef, const ds_jpeg_desc *desc, int32_t batch,
+                             uint8_t *out_bytes, int64_t nbytes);
+/* The reconstruction on the device, two launches on `stream`: (1) dequantise + inverse DCT of the blocks that intersect
+ * the crop plus a one-sample chroma halo, into uint8 component planes in `scratch` (scratch_bytes >= ncoef; the plane of a
+ * block grid lies at the byte offset its coefficients have as int16 index); (2) upsample + convert + crop, four pixels
+ * (12 bytes, three aligned dwords) per lane into out_bytes.  Exactly one lane writes each byte of a crop and no other
+ * byte is written: the alignment gaps of the ragged layout, and images that are not in the table, keep their contents.
+ * coef, desc, out_bytes, scratch: DEVICE pointers, coef 16-byte and out_bytes / scratch 4-byte aligned; the caller
+ * guarantees that every descriptor lies inside ncoef / nbytes (ops.check_jpeg_descs; the launch cannot report one that
+ * does not) and batch <= 65535. */
+int ds_jpeg_reconstruct(const int16_t *coef, int64_t ncoef, const ds_jpeg_desc *desc, int32_t batch, uint8_t *out_bytes,
+                        int64_t nbytes, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* Compiled reader of ONE tf.train.Example payload with the dataset's schema (datasets/convert_to_dataset.py:148-161):
+ * what input_pipeline.decode_record takes from datasets.tfrecord.decode_example.  image_offset / image_length: the first
+ * value of 'image/encoded' inside `rec`; text[0 .. text_len): every value of 'text'; seq_len / label
+ * ('image/class/label') / post_id / day: the first value, 0 when the key is absent.  A payload this reader does not
+ * take in full -- a malformed or truncated message, a missing or empty 'image/encoded', an empty list under an integer
+ * key, more than text_capacity ids, a value of the wrong kind -- is DS_JPEG_UNSUPPORTED: the caller runs the Python
+ * parser on it and gets that parser's result or exception. */
+typedef struct ds_example_fields {
+    int64_t image_offset, image_length;
+    int64_t seq_len, label, post_id, day;
+    int32_t text_len;
+    int32_t reserved;
+} ds_example_fields;
+int ds_example_parse(const uint8_t *rec, int64_t n, int64_t *text, int32_t text_capacity, ds_example_fields *fields);
+/* One call per record, for a worker thread: ds_example_parse, then ds_jpeg_probe of the image and, when it is supported
+ * and coef_count <= capacity, ds_jpeg_entropy_decode.  Returns DS_JPEG_UNSUPPORTED when the PAYLOAD cannot be taken
+ * (nothing else is then valid); otherwise DS_OK with *jpeg_status = DS_OK (coefficients decoded), DS_JPEG_UNSUPPORTED
+ * (decode the image bytes some other way) or DS_JPEG_MORE (call again with info->coef_count int16 of room). */
+int ds_jpeg_record_decode(const uint8_t *rec, int64_t n, int64_t *text, int32_t text_capacity, ds_example_fields *fields,
+                          ds_jpeg_info *info, int16_t *coef, int64_t capacity, int32_t *jpeg_status);
+
 #ifdef __cplusplus
 }
 #endif

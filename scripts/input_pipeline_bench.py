@@ -15,6 +15,13 @@ Writes a seeded dataset of 500 x 375 JPEGs (quality 90, smooth content) under DI
            under `rocprofv3 --kernel-trace --stats`
   augment  device pipeline at 8 workers, alternating windows without and with is_training=True; the cost of
            record_rng + sample_train_params per image on one thread (ordinary and 100-attempt sizes)
+  jpeg     the third arm: device pipeline + jpeg_decode='device' beside the device pipeline decoding with PIL (the yardstick: the
+           parent's path, same worker count, same session) and the host pipeline, alternating windows at 1, 2, 4, 8, 16
+           workers; ds_jpeg_reconstruct at B = 256 by device events, the coefficient bytes per batch against the pixel bytes
+           they replace, the fallback count, and the kernel's share of the training step (--step-ms, default the 13.06 ms
+           of bench.py's resident-batch step at 19.6k samples/s) against the 2 % budget of DESIGN.md 7.2.  All three loaders
+           of a worker count stay alive through its windows: at every switch the idle arms refill their prefetch queues
+           on their own worker pools, which overlaps the first batches of the measured arm -- read the rates with that in mind
 One JSON line per measurement on stdout; everything is merged into FILE (default DIR/input_pipeline.json)."""
 import argparse
 import concurrent.futures
@@ -221,6 +228,64 @@ def part_augment(ds, args, results):
          eval_spread=round(float(max(e) - min(e)), 1), ratio=round(float(np.mean(a) / np.mean(e)), 3))
 
 
+def part_jpeg(ds, args, results):
+    import torch
+    from tumblr_emotions_amd import input_pipeline as P
+    from tumblr_emotions_amd import ops
+    from tumblr_emotions_amd.datasets.tfrecord import read_records
+    from tumblr_emotions_amd.image_model.im_model import load_batch_with_text
+    kw = dict(batch_size=B, height=OUT, width=OUT, max_token_id=V, num_classes=15)
+    epoch = ds.num_samples // B
+    host = load_batch_with_text(ds, pipeline='host', **kw)
+    for _ in range(2):
+        next(host)
+    for workers in (1, 2, 4, 8, 16):
+        pil = load_batch_with_text(ds, pipeline='device', workers=workers, **kw)
+        jpg = load_batch_with_text(ds, pipeline='device', workers=workers, jpeg_decode='device', **kw)
+        for it in (pil, jpg):
+            for _ in range(epoch):
+                next(it)
+        rates = {"host": [], "pil": [], "jpeg": []}
+        for _ in range(args.windows):
+            rates["host"].append(_window(host, args.seconds))
+            rates["pil"].append(_window(pil, args.seconds))
+            rates["jpeg"].append(_window(jpg, args.seconds))
+        fallbacks = jpg.jpeg_fallbacks
+        pil.close()
+        jpg.close()
+        m = {k: float(np.mean(v)) for k, v in rates.items()}
+        emit(results, what="loader_jpeg", workers=workers, windows=args.windows, seconds=args.seconds,
+             host_images_per_s=round(m["host"], 1), device_pil_images_per_s=round(m["pil"], 1),
+             device_jpeg_images_per_s=round(m["jpeg"], 1), device_pil_windows=[round(x, 1) for x in rates["pil"]],
+             device_jpeg_windows=[round(x, 1) for x in rates["jpeg"]], ratio_jpeg_over_pil=round(m["jpeg"] / m["pil"], 3),
+             jpeg_fallbacks=fallbacks)
+    # the kernel alone: one batch of the dataset's own records
+    recs = []
+    for rec in read_records(ds.data_sources[0]):
+        recs.append(bytes(rec))
+        if len(recs) == B:
+            break
+    items = [P.decode_record_jpeg(r)[0] for r in recs]
+    st = P._Staging(B, 50, torch.device("cuda"), True, False, True)
+    used, ncoef, nj, copies = P.pack_ragged_jpeg(items, OUT, OUT, st)
+    coef = st.coef[:ncoef].cuda()
+    ddesc = st.jdesc.cuda()
+    out = torch.empty(used, dtype=torch.uint8, device="cuda")
+    scratch = torch.empty(ncoef, dtype=torch.uint8, device="cuda")
+    for _ in range(5):
+        ops.jpeg_reconstruct(coef, st.jdesc_np[:nj], out, scratch=scratch, desc_dev=ddesc)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(50):
+        ops.jpeg_reconstruct(coef, st.jdesc_np[:nj], out, scratch=scratch, desc_dev=ddesc)
+    e1.record()
+    torch.cuda.synchronize()
+    us = e0.elapsed_time(e1) / 50 * 1e3
+    emit(results, what="ds_jpeg_reconstruct", B=B, device_decoded=nj, coef_bytes=2 * ncoef, pixel_bytes=used,
+         coef_over_pixel_bytes=round(2 * ncoef / used, 3), us_events=round(us, 1), step_ms=args.step_ms,
+         share_of_step=round(us / 1e3 / args.step_ms, 4), budget_share=0.02)
+
+
 def kernel_stats(path, results):
     """Average duration of the preprocessing kernels from a rocprofv3 --kernel-trace --stats csv (Name, Calls, ..., AverageNs)."""
     with open(path) as f:
@@ -238,6 +303,7 @@ if __name__ == "__main__":
     ap.add_argument("--seconds", type=float, default=5.0)
     ap.add_argument("--windows", type=int, default=4)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--step-ms", type=float, default=13.06)
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("parts", nargs="*", default=["loader", "train", "kernel"])
     args = ap.parse_args()
@@ -250,6 +316,6 @@ if __name__ == "__main__":
         ds = make_dataset(os.path.join(args.out, "dataset"), args.images)
         for p in args.parts:
             {"loader": part_loader, "train": part_train, "kernel": part_kernel, "kernel_train": part_kernel_train,
-             "augment": part_augment}[p](ds, args, results)
+             "augment": part_augment, "jpeg": part_jpeg}[p](ds, args, results)
     with open(path, "w") as f:
         json.dump(results, f, indent=1)

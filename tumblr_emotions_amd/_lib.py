@@ -29,6 +29,8 @@ DS_PLAN_NO_WINO, DS_PLAN_NO_WINO4, DS_PLAN_NO_STEM_DIRECT, DS_PLAN_NO_BF16_DIREC
 DS_PLAN_FP8_EVERYWHERE, DS_PLAN_FP8_WIDE_RULE, DS_PLAN_NO_WINO4H, DS_PLAN_STEM_POOL = 64, 128, 256, 512
 DS_PLAN_NO_SPLITK = 1024
 DS_PREPROCESS_FLIP, DS_PREPROCESS_SATURATION_FIRST = 1, 2
+DS_JPEG_UNSUPPORTED, DS_JPEG_MORE = 1, 2
+DS_JPEG_444, DS_JPEG_422, DS_JPEG_420, DS_JPEG_GREY = 0, 1, 2, 3
 
 
 class ConvDesc(C.Structure):
@@ -108,6 +110,26 @@ class PreprocessTrainDesc(C.Structure):
     """ds_preprocess_train_desc"""
     _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32), ("scale_y", C.c_float), ("scale_x", C.c_float),
                 ("delta", C.c_float), ("factor", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class JpegInfo(C.Structure):
+    """ds_jpeg_info"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
+                ("restart_interval", C.c_int32), ("supported", C.c_int32), ("coef_count", C.c_int64), ("coef_bytes", C.c_int64),
+                ("quant", C.c_uint8 * 192)]
+
+
+class JpegDesc(C.Structure):
+    """ds_jpeg_desc"""
+    _fields_ = [("coef_offset", C.c_int64), ("out_offset", C.c_int64), ("width", C.c_int32), ("height", C.c_int32),
+                ("sampling", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32),
+                ("reserved", C.c_int32), ("quant", C.c_uint8 * 192)]
+
+
+class ExampleFields(C.Structure):
+    """ds_example_fields"""
+    _fields_ = [("image_offset", C.c_int64), ("image_length", C.c_int64), ("seq_len", C.c_int64), ("label", C.c_int64),
+                ("post_id", C.c_int64), ("day", C.c_int64), ("text_len", C.c_int32), ("reserved", C.c_int32)]
 
 
 _P = C.c_void_p
@@ -234,6 +256,13 @@ SIGNATURES = {
     "ds_fill": (C.c_int, [_P, _i64, _f32, _P]),
     "ds_preprocess_eval": (C.c_int, [_P, _i64, _P, _i32, _P, _P, _i32, _i32, _P]),
     "ds_preprocess_train": (C.c_int, [_P, _i64, _P, _i32, _P, _P, _i32, _i32, _P]),
+    "ds_jpeg_probe": (C.c_int, [_P, _i64, C.POINTER(JpegInfo)]),
+    "ds_jpeg_entropy_decode": (C.c_int, [_P, _i64, C.POINTER(JpegInfo), _P, _i64]),
+    "ds_jpeg_reconstruct_host": (C.c_int, [_P, _i64, _P, _i32, _P, _i64]),
+    "ds_jpeg_reconstruct": (C.c_int, [_P, _i64, _P, _i32, _P, _i64, _P, _i64, _P]),
+    "ds_example_parse": (C.c_int, [_P, _i64, _P, _i32, C.POINTER(ExampleFields)]),
+    "ds_jpeg_record_decode": (C.c_int, [_P, _i64, _P, _i32, C.POINTER(ExampleFields), C.POINTER(JpegInfo), _P, _i64,
+                                        C.POINTER(_i32)]),
 }
 
 _lib = None

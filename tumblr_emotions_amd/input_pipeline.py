@@ -17,6 +17,15 @@ Source shuffling, the in-batch permutation and the ragged tail draw from one Ran
 sequence.  Staging sets are filled by the feeder (not by the workers: an image's offset in the ragged buffer is known
 only once every earlier image of the batch has been decoded) and are reused only after the event of their last upload
 has completed.
+
+jpeg_decode='device' (opt-in) moves the decode itself off PIL: a worker makes ONE call into compiled host code per record
+(ds_jpeg_record_decode: the tf.Example parse, the JPEG marker parse and the Huffman decode, the GIL released throughout)
+and returns quantised DCT coefficients instead of pixels; the image size comes from the header, so the central crop -- or,
+with is_training=True, the draws of sample_train_params -- are made before any pixel exists.  The feeder packs coefficients
+and ds_jpeg_desc records into the staging set, and ds_jpeg_reconstruct (inverse DCT, upsampling, colour conversion, crop)
+writes the ragged byte buffer on the copy stream in front of the unchanged preprocessing kernel.  A stream outside the
+decoder's supported set (progressive, CMYK, ...) takes the PIL path for that image alone -- its pixels are uploaded into
+their slot of the same buffer, a corrupt file raises what it raises today -- and is counted in DeviceLoader.jpeg_fallbacks.
 """
 import io
 import queue
@@ -50,13 +59,22 @@ def clamp_workers(workers):
     return max(1, min(int(workers), MAX_WORKERS))
 
 
+def _desc_record(off, h, w, out_h, out_w, p=None):
+    """One ds_preprocess_desc record (p None) or ds_preprocess_train_desc record of a crop of h x w pixels at byte `off`."""
+    geom = (off, h, w, resize_scale(h, out_h), resize_scale(w, out_w))
+    if p is None:
+        return geom
+    from ._lib import DS_PREPROCESS_FLIP, DS_PREPROCESS_SATURATION_FIRST
+    flags = (DS_PREPROCESS_FLIP if p.flip else 0) | (DS_PREPROCESS_SATURATION_FIRST if p.saturation_first else 0)
+    return geom + (p.delta, p.factor, flags, 0)
+
+
 def pack_ragged(images, out_h, out_w, out=None, desc=None, align=4, params=None):
     """Lay cropped uint8 HWC images back to back (each start rounded up to `align` bytes) and describe them.
     images: list of [h, w, 3] uint8 arrays; out: uint8 buffer to fill (a new one when None; ValueError when too small);
     desc: descriptor array to fill (first len(images) records); params: one TrainParams per image (the images are their
     sampled crops) -- the descriptors are then ds_preprocess_train_desc records.  Returns (buffer, descriptors, bytes used)."""
     from .ops import preprocess_desc_dtype, preprocess_train_desc_dtype
-    from ._lib import DS_PREPROCESS_FLIP, DS_PREPROCESS_SATURATION_FIRST
     n = len(images)
     if params is not None and len(params) != n:
         raise ValueError("pack_ragged: one parameter set per image")
@@ -74,15 +92,10 @@ def pack_ragged(images, out_h, out_w, out=None, desc=None, align=4, params=None)
         raise ValueError("pack_ragged: %d bytes do not fit a buffer of %d" % (pos, out.size))
     for i, (im, off) in enumerate(zip(images, offsets)):
         out[off:off + im.size].reshape(im.shape)[...] = im
-        geom = (off, im.shape[0], im.shape[1], resize_scale(im.shape[0], out_h), resize_scale(im.shape[1], out_w))
-        if params is None:
-            desc[i] = geom
-        else:
-            p = params[i]
-            if (p.crop_h, p.crop_w) != im.shape[:2]:
-                raise ValueError("pack_ragged: image %d is not the crop its parameters describe" % i)
-            flags = (DS_PREPROCESS_FLIP if p.flip else 0) | (DS_PREPROCESS_SATURATION_FIRST if p.saturation_first else 0)
-            desc[i] = geom + (p.delta, p.factor, flags, 0)
+        p = None if params is None else params[i]
+        if p is not None and (p.crop_h, p.crop_w) != im.shape[:2]:
+            raise ValueError("pack_ragged: image %d is not the crop its parameters describe" % i)
+        desc[i] = _desc_record(off, im.shape[0], im.shape[1], out_h, out_w, p)
     return out, desc[:n], pos
 
 
@@ -153,15 +166,7 @@ def decode_record(rec, decode_image=True, train_key=None):
     ex = decode_example(rec)
     img = None
     if decode_image:
-        from PIL import Image
-        img = np.asarray(Image.open(io.BytesIO(ex['image/encoded'][0])).convert('RGB'))
-        if train_key is None:
-            y0, x0, ch, cw = crop_box(img.shape[0], img.shape[1])
-            img = np.ascontiguousarray(img[y0:y0 + ch, x0:x0 + cw])
-        else:
-            from .preprocessing.inception_preprocessing import record_rng, sample_train_params
-            p = sample_train_params(img.shape[0], img.shape[1], record_rng(*train_key))
-            img = (np.ascontiguousarray(img[p.y0:p.y0 + p.crop_h, p.x0:p.x0 + p.crop_w]), p)
+        img = decode_pixels(ex['image/encoded'][0], train_key)
     text = np.zeros(_POST_SIZE, np.int64)
     t = ex.get('text', [])
     text[:len(t)] = t
@@ -169,12 +174,123 @@ def decode_record(rec, decode_image=True, train_key=None):
             int(ex.get('post_id', [0])[0]), int(ex.get('day', [0])[0]))
 
 
+def decode_pixels(data, train_key=None):
+    """The PIL decode of one encoded image and its crop: the central one, or (crop, TrainParams) for train_key."""
+    from PIL import Image
+    img = np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))
+    if train_key is None:
+        y0, x0, ch, cw = crop_box(img.shape[0], img.shape[1])
+        return np.ascontiguousarray(img[y0:y0 + ch, x0:x0 + cw])
+    from .preprocessing.inception_preprocessing import record_rng, sample_train_params
+    p = sample_train_params(img.shape[0], img.shape[1], record_rng(*train_key))
+    return np.ascontiguousarray(img[p.y0:p.y0 + p.crop_h, p.x0:p.x0 + p.crop_w]), p
+
+
+# ---- jpeg_decode='device': coefficients instead of pixels ----------------------------------------------------------------------
+class JpegCoefs:
+    """What a worker hands the feeder for an image the device reconstructs: quantised coefficients (int16, the layout of
+    ds_jpeg_entropy_decode), the header's geometry and tables, the crop box and, at train time, the TrainParams."""
+    __slots__ = ("coef", "height", "width", "sampling", "quant", "box", "params")
+
+    def __init__(self, coef, height, width, sampling, quant, box, params=None):
+        self.coef, self.height, self.width, self.sampling, self.quant = coef, height, width, sampling, quant
+        self.box, self.params = box, params
+
+
+_worker = threading.local()
+
+
+def decode_jpeg_bytes(data, train_key=None):
+    """One encoded image -> JpegCoefs when the compiled decoder supports the stream, else what decode_pixels returns (the
+    PIL path; it raises what PIL raises)."""
+    from . import ops
+    info = ops.jpeg_probe(data)
+    coef = ops.jpeg_entropy_decode(data, info) if info is not None else None
+    if coef is None:
+        return decode_pixels(data, train_key)
+    return _coefs(coef, info, train_key)
+
+
+def _coefs(coef, info, train_key):
+    from . import ops
+    h, w = int(info.height), int(info.width)
+    if train_key is None:
+        box, p = crop_box(h, w), None
+    else:
+        from .preprocessing.inception_preprocessing import record_rng, sample_train_params
+        p = sample_train_params(h, w, record_rng(*train_key))
+        box = (p.y0, p.x0, p.crop_h, p.crop_w)
+    return JpegCoefs(coef, h, w, int(info.sampling), ops.jpeg_quant(info), box, p)
+
+
+def decode_record_jpeg(rec, train_key=None):
+    """decode_record with the compiled path: one ds_jpeg_record_decode call (payload parse + probe + Huffman decode, no GIL);
+    the first item is a JpegCoefs, or -- for a stream outside the supported set -- exactly decode_record's.  A payload the
+    compiled reader does not take goes through decode_record whole."""
+    from . import _lib, ops
+    rec = bytes(rec)
+    size = max(getattr(_worker, "size", 0), 1 << 16)
+    buf = np.empty(size, np.int16)          # handed over to the feeder with the result: a fresh one per record
+    r = ops.jpeg_record_decode(rec, buf)
+    if r is not None and r[0] == _lib.DS_JPEG_MORE:
+        _worker.size = size = int(r[1].coef_count)
+        buf = np.empty(size, np.int16)
+        r = ops.jpeg_record_decode(rec, buf)
+    if r is None:
+        return decode_record(rec, True, train_key)
+    status, info, (off, length, text, seq_len, label, post_id, day) = r
+    if status == 0:
+        img = _coefs(buf[:int(info.coef_count)], info, train_key)
+    else:
+        img = decode_pixels(rec[off:off + length], train_key)
+    return img, text, int(seq_len), int(label), int(post_id), int(day)
+
+
+def pack_ragged_jpeg(items, out_h, out_w, st, train=False):
+    """pack_ragged for a batch whose items are JpegCoefs or decoded crops (train: (crop, TrainParams)): the preprocessing
+    descriptors of ALL images and the pixels of the decoded ones go where pack_ragged puts them (st.desc_np, st.bytes);
+    coefficients go to st.coef back to back (starts rounded up to 8 int16) with one st.jdesc_np record each.  Returns
+    (bytes used, int16 used, JpegCoefs count, [(offset, size) of every decoded crop])."""
+    shapes, pos, cpos = [], 0, 0
+    for it in items:
+        if isinstance(it, JpegCoefs):
+            ch, cw = it.box[2], it.box[3]
+            cpos = -(-cpos // 8) * 8 + it.coef.size
+        else:
+            im = it[0] if train else it
+            if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
+                raise ValueError("pack_ragged_jpeg: images must be non-empty uint8 [h, w, 3] arrays")
+            ch, cw = im.shape[:2]
+        shapes.append((pos, ch, cw))
+        pos = -(-(pos + ch * cw * 3) // 4) * 4
+    st.reserve(pos)
+    st.reserve_coef(cpos)
+    out, coef = st.bytes.numpy(), st.coef.numpy()
+    cpos, nj, copies = 0, 0, []
+    for i, (it, (off, ch, cw)) in enumerate(zip(items, shapes)):
+        if isinstance(it, JpegCoefs):
+            p = it.params
+            cpos = -(-cpos // 8) * 8
+            coef[cpos:cpos + it.coef.size] = it.coef
+            st.jdesc_np[nj] = (cpos, off, it.width, it.height, it.sampling, it.box[0], it.box[1], ch, cw, 0, it.quant)
+            cpos += it.coef.size
+            nj += 1
+        else:
+            im, p = it if train else (it, None)
+            out[off:off + im.size].reshape(im.shape)[...] = im
+            copies.append((off, im.size))
+        if train and (p.crop_h, p.crop_w) != (ch, cw):
+            raise ValueError("pack_ragged_jpeg: image %d is not the crop its parameters describe" % i)
+        st.desc_np[i] = _desc_record(off, ch, cw, out_h, out_w, p if train else None)
+    return pos, cpos, nj, copies
+
+
 # ---- staging ----------------------------------------------------------------------------------------------------------------
 class _Staging:
     """One pinned staging set: ragged image bytes + descriptor table + the int64 fields, with the device byte buffer and
     descriptor table they are uploaded into and the event of the last upload."""
 
-    def __init__(self, batch_size, post_size, device, cuda, train=False):
+    def __init__(self, batch_size, post_size, device, cuda, train=False, jpeg=False):
         import torch
         from . import ops
         preprocess_desc_dtype = ops.preprocess_train_desc_dtype if train else ops.preprocess_desc_dtype
@@ -186,6 +302,12 @@ class _Staging:
         self.desc_dev = torch.empty(self.desc.numel(), dtype=torch.uint8, device=device) if cuda else None
         self.bytes = self.bytes_dev = None
         self.reserve(1 << 20)
+        self.coef = self.coef_dev = self.scratch_dev = None
+        if jpeg:                  # jpeg_decode='device': coefficients, their descriptors, the planes of ds_jpeg_reconstruct
+            self.jdesc = self._host(batch_size * ops.jpeg_desc_dtype().itemsize, torch.uint8)
+            self.jdesc_np = self.jdesc.numpy().view(ops.jpeg_desc_dtype())
+            self.jdesc_dev = torch.empty(self.jdesc.numel(), dtype=torch.uint8, device=device) if cuda else None
+            self.reserve_coef(1 << 20)
 
     def _host(self, n, dtype):
         return self.torch.empty(n, dtype=dtype, pin_memory=self.cuda)
@@ -195,6 +317,14 @@ class _Staging:
             cap = -(-int(nbytes * 1.25) // 4096) * 4096
             self.bytes = self._host(cap, self.torch.uint8)
             self.bytes_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device) if self.cuda else None
+
+    def reserve_coef(self, n):
+        if self.coef is None or self.coef.numel() < n:
+            cap = -(-int(n * 1.25) // 4096) * 4096
+            self.coef = self._host(cap, self.torch.int16)
+            if self.cuda:
+                self.coef_dev = self.torch.empty(cap, dtype=self.torch.int16, device=self.device)
+                self.scratch_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device)
 
     def wait_free(self):
         if self.event is not None:
@@ -251,7 +381,7 @@ def _record_stream(dataset, shuffle, rng, rank, world, loop):
 
 
 def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, world, seed, loop, max_token_id,
-            num_classes, decode_images, prefetch, inflight, train=False):
+            num_classes, decode_images, prefetch, inflight, train=False, jpeg=False):
     import collections
     try:
         import torch
@@ -287,8 +417,11 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                     boundary = True
                 else:
                     pass_no, idx, payload = rec
-                    pending.append(state.pool.submit(decode_record, payload, decode_images,
-                                                     (seed, pass_no, idx) if train and decode_images else None))
+                    key = (seed, pass_no, idx) if train and decode_images else None
+                    if jpeg and decode_images:
+                        pending.append(state.pool.submit(decode_record_jpeg, payload, key))
+                    else:
+                        pending.append(state.pool.submit(decode_record, payload, decode_images, key))
             if not pending:
                 break
             img, text, seq_len, label, post_id, day = pending.popleft().result()
@@ -303,7 +436,8 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             order = rng.permutation(batch_size) if shuffle else np.arange(batch_size)
             if post_size is None:
                 post_size = len(buf[0][1])
-                stagings = [_Staging(batch_size, post_size, dev, cuda, train and decode_images) for _ in range(max(2, prefetch + 1))]
+                stagings = [_Staging(batch_size, post_size, dev, cuda, train and decode_images, jpeg and decode_images)
+                            for _ in range(max(2, prefetch + 1))]
             st = stagings[turn]
             turn = (turn + 1) % len(stagings)
             st.wait_free()
@@ -312,8 +446,14 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             ints[:nt].reshape(batch_size, post_size)[...] = np.stack([b[1] for b in buf])[order]
             for k in range(len(_FIELDS)):
                 ints[nt + k * batch_size:nt + (k + 1) * batch_size] = np.asarray([b[2 + k] for b in buf], np.int64)[order]
-            used = 0
-            if decode_images:
+            used = ncoef = njpeg = 0
+            copies = []
+            if decode_images and jpeg:
+                used, ncoef, njpeg, copies = pack_ragged_jpeg([buf[j][0] for j in order], height, width, st, train)
+                (ops.check_preprocess_train_descs if train else ops.check_preprocess_descs)(st.desc_np[:batch_size], used)
+                if njpeg:
+                    ops.check_jpeg_descs(st.jdesc_np[:njpeg], ncoef, used)
+            elif decode_images:
                 images = [buf[j][0] for j in order]          # descriptor j = output slot j: the permutation costs nothing
                 params = None
                 if train:
@@ -325,8 +465,17 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             out = {}
             if cuda:
                 with torch.cuda.stream(stream):
-                    if decode_images:
+                    if decode_images and jpeg:
+                        for off, size in copies:                 # the images PIL decoded: their slots only
+                            st.bytes_dev[off:off + size].copy_(st.bytes[off:off + size], non_blocking=True)
+                        if njpeg:
+                            st.coef_dev[:ncoef].copy_(st.coef[:ncoef], non_blocking=True)
+                            st.jdesc_dev.copy_(st.jdesc, non_blocking=True)
+                            ops.jpeg_reconstruct(st.coef_dev[:ncoef], st.jdesc_np[:njpeg], st.bytes_dev[:used],
+                                                 scratch=st.scratch_dev, desc_dev=st.jdesc_dev)
+                    elif decode_images:
                         st.bytes_dev[:used].copy_(st.bytes[:used], non_blocking=True)
+                    if decode_images:
                         st.desc_dev.copy_(st.desc, non_blocking=True)
                         run = ops.preprocess_train if train else ops.preprocess_eval
                         out["images"] = run(st.bytes_dev[:used], st.desc_np[:batch_size], height, width, desc_dev=st.desc_dev)
@@ -339,7 +488,7 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             out["texts"] = ints_dev[:nt].view(batch_size, post_size)
             for k, (name, _) in enumerate(_FIELDS):
                 out[name] = ints_dev[nt + k * batch_size:nt + (k + 1) * batch_size]
-            if not _put(state, ("batch", out, event, stream)):
+            if not _put(state, ("batch", out, event, stream, len(copies) if jpeg else 0)):
                 return
         _put(state, ("end",))
     except BaseException as e:
@@ -366,11 +515,17 @@ class DeviceLoader:
     wait for the batch's upload + preprocessing (an event; the host is not blocked by the device) and returns the dict.
     close() -- also run by the context manager, by garbage collection of the loader and at interpreter exit -- stops the
     feeder and joins every worker; a closed or exhausted loader raises StopIteration.  is_training=True: the train-time
-    augmentation (ds_preprocess_train) instead of the eval chain; ignored with decode_images=False."""
+    augmentation (ds_preprocess_train) instead of the eval chain; ignored with decode_images=False.  jpeg_decode='device':
+    compiled Huffman decode in the workers and ds_jpeg_reconstruct on the copy stream instead of PIL (ignored with
+    decode_images=False); jpeg_fallbacks counts the images of the batches handed out so far that took the PIL path."""
 
     def __init__(self, dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False, device="cuda",
                  rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None, workers=8, prefetch=2,
-                 decode_images=True):
+                 decode_images=True, jpeg_decode='host'):
+        if jpeg_decode not in ('host', 'device'):
+            raise ValueError("jpeg_decode must be 'host' or 'device', not %r" % (jpeg_decode,))
+        self.jpeg_decode = jpeg_decode
+        self.jpeg_fallbacks = 0
         if batch_size < 1 or height < 1 or width < 1 or world < 1 or not 0 <= rank < world:
             raise ValueError("DeviceLoader: bad batch_size / height / width / rank / world")
         self.workers = clamp_workers(workers)
@@ -388,7 +543,7 @@ class DeviceLoader:
         st.thread = threading.Thread(target=_feeder, name="ds-input-feeder", daemon=True,
                                      args=(st, dataset, int(batch_size), bool(shuffle), int(height), int(width), device, rank,
                                            world, seed, bool(loop), max_token_id, num_classes, self.decode_images,
-                                           self.prefetch, inflight, bool(is_training)))
+                                           self.prefetch, inflight, bool(is_training), jpeg_decode == 'device'))
         self._finalizer = weakref.finalize(self, _shutdown, st)
         st.thread.start()
 
@@ -400,7 +555,8 @@ class DeviceLoader:
             raise StopIteration
         item = self._state.out.get()
         if item[0] == "batch":
-            _, out, event, stream = item
+            _, out, event, stream, fallbacks = item
+            self.jpeg_fallbacks += fallbacks
             if event is not None:
                 import torch
                 cur = torch.cuda.current_stream(stream.device)

@@ -1051,3 +1051,153 @@ def preprocess_train(image_bytes, desc, out_h, out_w, desc_dev=None, out=None):
     brightness delta and saturation factor."""
     return _preprocess("preprocess_train", check_preprocess_train_descs, preprocess_train_desc_dtype().itemsize,
                        image_bytes, desc, out_h, out_w, desc_dev, out)
+
+
+# ---- baseline JPEG decode: host entropy decoder + ds_jpeg_reconstruct ----------------------------------------------------------
+JPEG_TEXT_CAPACITY = 50             # datasets.convert_to_dataset._POST_SIZE: the ids one record may carry
+
+
+def jpeg_desc_dtype():
+    """NumPy view of ds_jpeg_desc (240 bytes): one record per image of a ragged ds_jpeg_reconstruct launch."""
+    import numpy as np
+    return np.dtype([("coef_offset", np.int64), ("out_offset", np.int64), ("width", np.int32), ("height", np.int32),
+                     ("sampling", np.int32), ("y0", np.int32), ("x0", np.int32), ("crop_h", np.int32), ("crop_w", np.int32),
+                     ("reserved", np.int32), ("quant", np.uint8, (3, 64))], align=True)
+
+
+def jpeg_blocks(height, width, sampling):
+    """8 x 8 blocks of the padded (whole-MCU) grids of an image, all components: its coefficient storage is 64 int16 each."""
+    if sampling == _lib.DS_JPEG_GREY:
+        return -(-width // 8) * -(-height // 8)
+    h, v = (2 if sampling in (_lib.DS_JPEG_422, _lib.DS_JPEG_420) else 1), (2 if sampling == _lib.DS_JPEG_420 else 1)
+    return -(-width // (8 * h)) * -(-height // (8 * v)) * (h * v + 2)
+
+
+def check_jpeg_descs(desc, ncoef, nbytes):
+    """Every image of the table has a known sampling class, a crop inside the image, its coefficients inside a buffer of
+    `ncoef` int16 (offset a multiple of 8) and its crop inside a byte buffer of `nbytes` bytes (offset a multiple of 4), and
+    no two crops overlap: raises ValueError before anything is launched (the kernels cannot report a bad descriptor)."""
+    import numpy as np
+    desc = np.asarray(desc)
+    if desc.dtype != jpeg_desc_dtype() or desc.ndim != 1 or desc.size == 0:
+        raise ValueError("jpeg_reconstruct: descriptors must be a non-empty 1-D array of ops.jpeg_desc_dtype()")
+    i64 = lambda k: desc[k].astype(np.int64)
+    w, h, s = i64("width"), i64("height"), i64("sampling")
+    if ((s < 0) | (s > 3) | (w < 1) | (h < 1) | (w > 65535) | (h > 65535)).any() or desc["reserved"].any():
+        raise ValueError("jpeg_reconstruct: bad image size or sampling class")
+    y0, x0, ch, cw = i64("y0"), i64("x0"), i64("crop_h"), i64("crop_w")
+    if ((y0 < 0) | (x0 < 0) | (ch < 1) | (cw < 1) | (y0 + ch > h) | (x0 + cw > w)).any():
+        raise ValueError("jpeg_reconstruct: a crop box leaves its image")
+    hs, vs = np.where((s == 1) | (s == 2), 2, 1), np.where(s == 2, 2, 1)         # jpeg_blocks, for the whole table at once
+    need = -(-w // (8 * hs)) * -(-h // (8 * vs)) * np.where(s == 3, 1, hs * vs + 2) * 64
+    co, oo = desc["coef_offset"], desc["out_offset"]
+    if ((co < 0) | (co % 8 != 0) | (co + need > int(ncoef))).any():
+        raise ValueError("jpeg_reconstruct: coefficients outside the buffer of %d int16 (or an offset that is no multiple of 8)" % int(ncoef))
+    end = oo + ch * cw * 3
+    if ((oo < 0) | (oo % 4 != 0) | (end > int(nbytes))).any():
+        raise ValueError("jpeg_reconstruct: a crop outside the byte buffer of %d bytes (or an offset that is no multiple of 4)" % int(nbytes))
+    order = np.argsort(oo, kind="stable")
+    if (end[order][:-1] > oo[order][1:]).any():
+        raise ValueError("jpeg_reconstruct: two crops overlap in the byte buffer")
+    order = np.argsort(co, kind="stable")
+    if ((co + need)[order][:-1] > co[order][1:]).any():
+        raise ValueError("jpeg_reconstruct: two images share coefficient storage (their planes share the scratch)")
+    return desc
+
+
+def _host_ptr(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def jpeg_probe(data):
+    """ds_jpeg_probe of a bytes object: the _lib.JpegInfo of a supported stream, None otherwise."""
+    info = _lib.JpegInfo()
+    rc = _lib.load().ds_jpeg_probe(C.cast(C.c_char_p(data), C.c_void_p), len(data), C.byref(info))
+    if rc < 0:
+        raise ValueError("ds_jpeg_probe: bad argument")
+    return info if rc == 0 and info.supported else None
+
+
+def jpeg_entropy_decode(data, info):
+    """ds_jpeg_entropy_decode: int16 coefficients (natural order, block raster over the padded grids, component after
+    component) of a stream ds_jpeg_probe supports; None when the entropy-coded data turn out to be outside the set."""
+    import numpy as np
+    coef = np.empty(int(info.coef_count), np.int16)
+    rc = _lib.load().ds_jpeg_entropy_decode(C.cast(C.c_char_p(data), C.c_void_p), len(data), C.byref(info), _host_ptr(coef), coef.size)
+    if rc < 0 or rc == _lib.DS_JPEG_MORE:
+        raise ValueError("ds_jpeg_entropy_decode: bad argument (%d)" % rc)
+    return coef if rc == 0 else None
+
+
+def jpeg_quant(info):
+    """The [3, 64] uint8 quantisation tables of a JpegInfo (natural order), as a descriptor's `quant` field takes them."""
+    import numpy as np
+    return np.frombuffer(bytes(info.quant), np.uint8).reshape(3, 64)
+
+
+def example_parse(rec):
+    """ds_example_parse of one TFRecord payload: (image offset, image length, text int64[50], seq_len, label, post_id,
+    day), or None when the compiled reader does not take the payload (the Python parser decides then)."""
+    import numpy as np
+    text = np.zeros(JPEG_TEXT_CAPACITY, np.int64)
+    f = _lib.ExampleFields()
+    rc = _lib.load().ds_example_parse(C.cast(C.c_char_p(rec), C.c_void_p), len(rec), _host_ptr(text), text.size, C.byref(f))
+    if rc < 0:
+        raise ValueError("ds_example_parse: bad argument")
+    if rc != 0:
+        return None
+    return f.image_offset, f.image_length, text, f.seq_len, f.label, f.post_id, f.day
+
+
+def jpeg_record_decode(rec, coef):
+    """One call per record (the GIL is released for its duration): parse the payload, probe the JPEG and Huffman-decode it
+    into `coef` (a C-contiguous int16 array) when it fits.  Returns None when the payload is not taken, otherwise
+    (status, info, fields tuple as example_parse) with status DS_OK (coef[:info.coef_count] holds the image),
+    _lib.DS_JPEG_UNSUPPORTED or _lib.DS_JPEG_MORE (info.coef_count int16 are needed)."""
+    import numpy as np
+    text = np.zeros(JPEG_TEXT_CAPACITY, np.int64)
+    f, info, status = _lib.ExampleFields(), _lib.JpegInfo(), C.c_int32(0)
+    rc = _lib.load().ds_jpeg_record_decode(C.cast(C.c_char_p(rec), C.c_void_p), len(rec), _host_ptr(text), text.size, C.byref(f),
+                                           C.byref(info), _host_ptr(coef) if coef.size else None, coef.size, C.byref(status))
+    if rc < 0:
+        raise ValueError("ds_jpeg_record_decode: bad argument")
+    if rc != 0:
+        return None
+    return status.value, info, (f.image_offset, f.image_length, text, f.seq_len, f.label, f.post_id, f.day)
+
+
+def jpeg_reconstruct_host(coef, desc, out_bytes):
+    """ds_jpeg_reconstruct_host on NumPy arrays: fills the crops of `desc` in out_bytes (uint8) from coef (int16)."""
+    import numpy as np
+    desc = check_jpeg_descs(desc, coef.size, out_bytes.size)
+    if coef.dtype != np.int16 or out_bytes.dtype != np.uint8 or not coef.flags.c_contiguous or not out_bytes.flags.c_contiguous:
+        raise ValueError("jpeg_reconstruct_host: coef int16 and out_bytes uint8, both contiguous")
+    desc = np.ascontiguousarray(desc)
+    rc = _lib.load().ds_jpeg_reconstruct_host(_host_ptr(coef), coef.size, _host_ptr(desc), desc.size, _host_ptr(out_bytes), out_bytes.size)
+    if rc != 0:
+        raise ValueError("ds_jpeg_reconstruct_host: bad descriptor (%d)" % rc)
+    return out_bytes
+
+
+def jpeg_reconstruct(coef, desc, out_bytes, scratch=None, desc_dev=None):
+    """ds_jpeg_reconstruct: coef (device int16), desc (HOST array of ops.jpeg_desc_dtype(), checked here), out_bytes (device
+    uint8, written in place: only the crops' bytes), scratch (device uint8, >= coef.numel() bytes; allocated when None),
+    desc_dev (the table already on the device; uploaded here when None).  Returns out_bytes."""
+    import numpy as np
+    if not (coef.is_cuda and out_bytes.is_cuda):
+        raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
+    if coef.dtype != torch.int16 or out_bytes.dtype != torch.uint8 or not coef.is_contiguous() or not out_bytes.is_contiguous():
+        raise ValueError("jpeg_reconstruct: coef must be a contiguous int16 tensor and out_bytes a contiguous uint8 tensor")
+    desc = check_jpeg_descs(desc, coef.numel(), out_bytes.numel())
+    B = int(desc.size)
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8)).to(coef.device)
+    if desc_dev.numel() * desc_dev.element_size() < B * jpeg_desc_dtype().itemsize or not desc_dev.is_contiguous():
+        raise ValueError("jpeg_reconstruct: desc_dev is smaller than the descriptor table")
+    if scratch is None:
+        scratch = torch.empty(coef.numel(), dtype=torch.uint8, device=coef.device)
+    if scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < coef.numel():
+        raise ValueError("jpeg_reconstruct: scratch must be a contiguous uint8 tensor of at least coef.numel() bytes")
+    _lib.check(_lib.load().ds_jpeg_reconstruct(_p(coef), coef.numel(), _p(desc_dev), B, _p(out_bytes), out_bytes.numel(),
+                                               _p(scratch), scratch.numel(), _stream()), "ds_jpeg_reconstruct")
+    return out_bytes

@@ -141,7 +141,10 @@ class SyntheticInput:
     config['augment'] (default False): the train-time augmentation of preprocess_for_train (load_batch_with_text's
     is_training=True) on a real dataset -- honoured only once a trainer has called use_augmentation() (train_image_model,
     train_deep_sentiment); evaluate_*, the analyses and class_visualisation always read eval-chain batches, as in the
-    reference (im_text_rnn_model.py:291,602).  With config['synthetic'] the key is a ValueError: there is no JPEG to augment."""
+    reference (im_text_rnn_model.py:291,602).  With config['synthetic'] the key is a ValueError: there is no JPEG to augment.
+    config['jpeg_decode']: 'host' (default) or 'device' (compiled Huffman decode + ds_jpeg_reconstruct instead of PIL; the
+    same batches bit for bit) -- honoured only with config['input_pipeline'] = 'device'; with the host pipeline the key is
+    a ValueError: that pipeline decodes with PIL."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
@@ -151,6 +154,11 @@ class SyntheticInput:
         self._augment = False
         if config.get("augment", False) and config.get("synthetic", False):
             raise ValueError("config['augment'] needs a real dataset: synthetic batches have no JPEG to augment")
+        if config.get("jpeg_decode", "host") not in ("host", "device"):
+            raise ValueError("config['jpeg_decode'] must be 'host' or 'device', not %r" % (config["jpeg_decode"],))
+        if config.get("jpeg_decode", "host") == "device" and config.get("input_pipeline", "host") != "device":
+            raise ValueError("config['jpeg_decode'] = 'device' needs config['input_pipeline'] = 'device': the host pipeline "
+                             "decodes with PIL")
         ddir = config.get("dataset_dir")
         split = os.path.join(ddir or "", "photos", "train_valid_split.txt")
         if config.get("synthetic", False):
@@ -179,6 +187,7 @@ class SyntheticInput:
                                                      num_classes=getattr(self.dataset, "num_classes", nb),
                                                      pipeline=self.config.get("input_pipeline", "host"),
                                                      workers=self.config.get("input_workers", 8),
+                                                     jpeg_decode=self.config.get("jpeg_decode", "host"),
                                                      decode_images=with_images)     # text-only: no JPEG is decoded
             b = next(self._records)
         else:
