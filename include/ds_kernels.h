@@ -826,7 +826,8 @@ int ds_preprocess_train(const uint8_t *bytes, int64_t nbytes, const ds_preproces
 
 /* Baseline JPEG decode, split in two (the decode of load_batch_with_text, image_model/im_model.py:78-116, which the
  * reference leaves to tf.image.decode_jpeg): the sequential half -- marker parse and Huffman decode -- is host code
- * (csrc/jpeg_host.cpp: no HIP call, HOST pointers, callable from any thread, no global state); the parallel half --
+ * (csrc/jpeg_host.cpp: no HIP call, HOST pointers, callable from any thread, no global state; for streams with restart
+ * markers the Huffman decode can run on the device instead, ds_jpeg_entropy_decode_device below); the parallel half --
  * dequantisation, 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB and the crop -- is ds_jpeg_reconstruct on the device,
  * which writes the ragged uint8 buffer ds_preprocess_eval / ds_preprocess_train read.  The arithmetic is libjpeg's default
  * decode path (jpeg_idct_islow, fancy upsampling, the fixed-point ycc_rgb tables): integers throughout, so the pixels
@@ -915,6 +916,82 @@ int ds_example_parse(const uint8_t *rec, int64_t n, int64_t *text, int32_t text_
  * (decode the image bytes some other way) or DS_JPEG_MORE (call again with info->coef_count int16 of room). */
 int ds_jpeg_record_decode(const uint8_t *rec, int64_t n, int64_t *text, int32_t text_capacity, ds_example_fields *fields,
                           ds_jpeg_info *info, int16_t *coef, int64_t capacity, int32_t *jpeg_status);
+
+/* Restart-segmented streams: the Huffman decode on the device.  Huffman decode is sequential only between restart markers:
+ * at every RSTn the bit stream is byte-aligned and the DC predictors are zero, so each restart segment decodes on its own.
+ * ds_jpeg_scan describes the scan of a supported stream WITHOUT decoding it (markers and the walk of ds_jpeg_probe only),
+ * ds_jpeg_restart_transcode gives a stream a restart interval losslessly, and ds_jpeg_entropy_decode_device decodes all
+ * segments of a batch in one launch, straight into the coefficient buffer ds_jpeg_reconstruct reads.  One definition of the
+ * segment decoder (csrc/jpeg_common.h) serves ds_jpeg_entropy_decode, the host statement of the launch and the kernel. */
+typedef struct ds_jpeg_huff {      /* a Huffman table in its DHT form                                                  */
+    uint8_t counts[16];            /* codes of length 1 .. 16                                                          */
+    uint8_t values[256];           /* the symbols in code order; the entries past sum(counts) are 0                    */
+} ds_jpeg_huff;
+typedef struct ds_jpeg_scan_info {
+    int64_t scan_begin;            /* first entropy-coded byte                                                         */
+    int64_t cut_count;             /* restart segments of the scan = cut positions (>= 1)                              */
+    ds_jpeg_huff dc[3], ac[3];     /* the DC and the AC table of each component (grey: [0] only, the rest zero)        */
+} ds_jpeg_scan_info;
+/* ds_jpeg_probe plus the scan's tables and cuts: cuts[i] is the position of the marker that ends segment i (RSTn, the
+ * last one EOI), so segment i is bytes[i ? cuts[i - 1] + 2 : scan_begin, cuts[i]).  DS_JPEG_UNSUPPORTED exactly where
+ * ds_jpeg_probe returns it; DS_JPEG_MORE when capacity < scan->cut_count (info and scan are valid, cuts is not). */
+int ds_jpeg_scan(const uint8_t *bytes, int64_t n, ds_jpeg_info *info, ds_jpeg_scan_info *scan, int64_t *cuts, int64_t capacity);
+/* One call per record, for a worker thread: ds_example_parse, then ds_jpeg_scan of the image (positions relative to the
+ * image's first byte).  Returns as ds_jpeg_record_decode does, *jpeg_status = what ds_jpeg_scan returned. */
+int ds_jpeg_record_scan(const uint8_t *rec, int64_t n, int64_t *text, int32_t text_capacity, ds_example_fields *fields,
+                        ds_jpeg_info *info, ds_jpeg_scan_info *scan, int64_t *cuts, int64_t capacity, int32_t *jpeg_status);
+/* Lossless re-encode of a supported stream with a restart interval of interval_mcus MCUs (0 = one MCU row; at most 65535):
+ * the coefficients of ds_jpeg_entropy_decode (every check of it applies) are Huffman-coded again with RSTn markers in
+ * sequence, one-bits padding in front of each marker and byte stuffing.  Every segment other than DRI, DHT and the scan
+ * data is copied through unchanged; a DRI already present is replaced; the scan's tables are written as one DHT segment
+ * in front of SOS.  The stream keeps its own Huffman tables, except a table that has no code for a symbol the new stream
+ * needs (the DC difference at a segment start is taken from zero, and an optimised table may lack that category): that
+ * table is replaced by the typical table of its class from Annex K of the JPEG standard.  *out_n = the size of the new
+ * stream; DS_JPEG_MORE when capacity < *out_n (nothing is written), DS_JPEG_UNSUPPORTED when the input is outside the
+ * supported set or needs a symbol the Annex K tables lack either (the caller keeps the original bytes). */
+int ds_jpeg_restart_transcode(const uint8_t *bytes, int64_t n, int32_t interval_mcus, uint8_t *out, int64_t capacity,
+                              int64_t *out_n);
+
+/* One launch decodes the segments of `nimages` images.  scan: the entropy-coded bytes of the batch, concatenated. */
+typedef struct ds_jpeg_scan_desc { /* one per image                                                                    */
+    int64_t coef_offset;           /* first int16 of the image in `coef`; a multiple of 8                              */
+    int32_t width, height;         /* pixels                                                                           */
+    int32_t sampling;              /* DS_JPEG_*                                                                        */
+    int32_t first_segment;         /* the image's segments are segs[first_segment .. first_segment + segments)         */
+    int32_t segments;              /* >= 1                                                                             */
+    int32_t reserved;              /* 0                                                                                */
+    uint8_t quant[3][64];          /* ds_jpeg_info.quant: for the range checks of ds_jpeg_entropy_decode               */
+    ds_jpeg_huff dc[3], ac[3];     /* ds_jpeg_scan_info's                                                              */
+} ds_jpeg_scan_desc;
+typedef struct ds_jpeg_segment {   /* one per restart segment                                                          */
+    int64_t begin, end;            /* its bytes in `scan`: [begin, end)                                                */
+    int32_t first_mcu, mcus;       /* the MCUs it holds; the segments of an image continue each other from 0 to the end */
+} ds_jpeg_segment;
+/* status bits of an image (0 = decoded; the coefficients equal ds_jpeg_entropy_decode's) */
+#define DS_JPEG_E_CODE 1           /* no Huffman code matches                                                          */
+#define DS_JPEG_E_RUN 2            /* a zero run past coefficient 63                                                   */
+#define DS_JPEG_E_RANGE 4          /* a coefficient, or its product with the quantiser, beyond +-32767                 */
+#define DS_JPEG_E_COLUMN 8         /* the column bound of the inverse DCT (see above)                                  */
+#define DS_JPEG_E_SEGMENT 16       /* a segment not used up exactly, or bits taken from past its end                   */
+#define DS_JPEG_E_TABLE 32         /* a bad record: Huffman table, geometry, storage, segment bytes or MCU counts      */
+/* Equivalence contract, for any stream ds_jpeg_probe accepts and tables made from ds_jpeg_scan of it: status[i] == 0
+ * exactly when ds_jpeg_entropy_decode returns DS_OK, and then all coef_count coefficients are equal; otherwise status[i]
+ * != 0 and the image's coefficients are unspecified.  Nothing outside [coef_offset, coef_offset + coef_count) of an
+ * image is ever written.  The host statement, plain C++ on HOST pointers: returns DS_ERR_ARG for a null pointer or a
+ * negative size; a record that does not fit the buffers only flags its image (DS_JPEG_E_TABLE). */
+int ds_jpeg_entropy_decode_segments_host(const uint8_t *scan, int64_t nscan, const ds_jpeg_scan_desc *images, int32_t nimages,
+                                         const ds_jpeg_segment *segs, int64_t nsegs, int16_t *coef, int64_t ncoef,
+                                         int32_t *status);
+/* The launch, on `stream`, DEVICE pointers (coef 16-byte aligned): one workgroup of 256 lanes per image zeroes the image's
+ * coefficient range and builds its decoding tables in LDS behind one barrier; then lane k decodes segments k, k + 256, ...
+ * serially and stores the non-zero coefficients.  Every loop is bounded, every byte read is checked against its segment's
+ * end, every store lies inside the image's range, and a failure sets the image's status and ends that lane's segment.
+ * The caller validates both tables against the buffer sizes on the host first (ops.check_jpeg_scan_descs: two images
+ * must not share storage); the kernel re-checks what it needs to stay inside the buffers and flags the image otherwise.
+ * nimages <= 65535. */
+int ds_jpeg_entropy_decode_device(const uint8_t *scan, int64_t nscan, const ds_jpeg_scan_desc *images, int32_t nimages,
+                                  const ds_jpeg_segment *segs, int64_t nsegs, int16_t *coef, int64_t ncoef, int32_t *status,
+                                  void *stream);
 
 #ifdef __cplusplus
 }

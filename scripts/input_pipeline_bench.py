@@ -21,7 +21,11 @@ Writes a seeded dataset of 500 x 375 JPEGs (quality 90, smooth content) under DI
            they replace, the fallback count, and the kernel's share of the training step (--step-ms, default the 13.06 ms
            of bench.py's resident-batch step at 19.6k samples/s) against the 2 % budget of DESIGN.md 7.2.  All three loaders
            of a worker count stay alive through its windows: at every switch the idle arms refill their prefetch queues
-           on their own worker pools, which overlaps the first batches of the measured arm -- read the rates with that in mind
+           on their own worker pools, which overlaps the first batches of the measured arm -- read the rates with that in mind.
+           The fourth arm: the same images rewritten by add_restart_markers (one restart interval per MCU row) read with
+           jpeg_entropy='device', beside ITS yardstick -- jpeg_decode='device' alone on the same restart-marked files --
+           in the same alternation; the growth of the files, and ds_jpeg_entropy_decode_device at B = 256 by device events
+           with the bytes it reads against the coefficient bytes whose upload it replaces (--workers picks the worker counts)
 One JSON line per measurement on stdout; everything is merged into FILE (default DIR/input_pipeline.json)."""
 import argparse
 import concurrent.futures
@@ -70,6 +74,20 @@ def make_dataset(root, n, shards=8, seed=0):
     for s in range(shards):
         T.write_records(cd.dataset_filename(root, "tfrecords", "train", s, shards), recs[s::shards])
     return cd.get_split_with_text("train", root)
+
+
+def restart_dataset(ds, root):
+    """The dataset's images with one restart interval per MCU row (add_restart_markers, written once beside the original
+    shards) and what the transcode cost in file size."""
+    from tumblr_emotions_amd.datasets import convert_to_dataset as cd
+    if not os.path.isdir(os.path.join(root, "tfrecords_rst")):
+        done = cd.add_restart_markers(root)
+        assert done == (ds.num_samples, 0), done
+    size = lambda sub: sum(os.path.getsize(os.path.join(root, sub, f)) for f in os.listdir(os.path.join(root, sub)))
+    a, b = size("tfrecords"), size("tfrecords_rst")
+    growth = dict(images=ds.num_samples, bytes_before=a, bytes_after=b, bytes_per_image=round((b - a) / ds.num_samples, 1),
+                  relative=round((b - a) / a, 5))
+    return cd.get_split_with_text("train", root, tfrecords_subdir="tfrecords_rst"), growth
 
 
 def emit(results, **kw):
@@ -239,20 +257,34 @@ def part_jpeg(ds, args, results):
     host = load_batch_with_text(ds, pipeline='host', **kw)
     for _ in range(2):
         next(host)
-    for workers in (1, 2, 4, 8, 16):
+    ds_rst, growth = restart_dataset(ds, os.path.join(args.out, "dataset"))
+    emit(results, what="restart_transcode_growth", **growth)
+    for workers in [int(w) for w in args.workers.split(",")]:
         pil = load_batch_with_text(ds, pipeline='device', workers=workers, **kw)
         jpg = load_batch_with_text(ds, pipeline='device', workers=workers, jpeg_decode='device', **kw)
-        for it in (pil, jpg):
+        rst = load_batch_with_text(ds_rst, pipeline='device', workers=workers, jpeg_decode='device', **kw)
+        ent = load_batch_with_text(ds_rst, pipeline='device', workers=workers, jpeg_decode='device', jpeg_entropy='device', **kw)
+        for it in (pil, jpg, rst, ent):
             for _ in range(epoch):
                 next(it)
-        rates = {"host": [], "pil": [], "jpeg": []}
+        rates = {"host": [], "pil": [], "jpeg": [], "jpeg_rst": [], "entropy": []}
         for _ in range(args.windows):
             rates["host"].append(_window(host, args.seconds))
             rates["pil"].append(_window(pil, args.seconds))
             rates["jpeg"].append(_window(jpg, args.seconds))
+            rates["jpeg_rst"].append(_window(rst, args.seconds))
+            rates["entropy"].append(_window(ent, args.seconds))
         fallbacks = jpg.jpeg_fallbacks
-        pil.close()
-        jpg.close()
+        r, e = rates["jpeg_rst"], rates["entropy"]
+        emit(results, what="loader_jpeg_entropy", workers=workers, windows=args.windows, seconds=args.seconds,
+             yardstick_jpeg_on_restart_files_windows=[round(x, 1) for x in r], device_entropy_windows=[round(x, 1) for x in e],
+             yardstick_images_per_s=round(float(np.mean(r)), 1), device_entropy_images_per_s=round(float(np.mean(e)), 1),
+             yardstick_spread=round(float(max(r) - min(r)), 1), gain=round(float(np.mean(e) - np.mean(r)), 1),
+             ratio_entropy_over_yardstick=round(float(np.mean(e) / np.mean(r)), 3),
+             beats_yardstick_by_more_than_its_spread=bool(np.mean(e) - np.mean(r) > max(r) - min(r)),
+             device_entropy_images=ent.jpeg_device_entropy, fallbacks=ent.jpeg_fallbacks, yardstick_fallbacks=rst.jpeg_fallbacks)
+        for it in (pil, jpg, rst, ent):
+            it.close()
         m = {k: float(np.mean(v)) for k, v in rates.items()}
         emit(results, what="loader_jpeg", workers=workers, windows=args.windows, seconds=args.seconds,
              host_images_per_s=round(m["host"], 1), device_pil_images_per_s=round(m["pil"], 1),
@@ -284,6 +316,32 @@ def part_jpeg(ds, args, results):
     emit(results, what="ds_jpeg_reconstruct", B=B, device_decoded=nj, coef_bytes=2 * ncoef, pixel_bytes=used,
          coef_over_pixel_bytes=round(2 * ncoef / used, 3), us_events=round(us, 1), step_ms=args.step_ms,
          share_of_step=round(us / 1e3 / args.step_ms, 4), budget_share=0.02)
+    # the entropy kernel alone: one batch of the restart-marked records
+    recs = []
+    for rec in read_records(ds_rst.data_sources[0]):
+        recs.append(bytes(rec))
+        if len(recs) == B:
+            break
+    items = [P.decode_record_jpeg_scan(r)[0] for r in recs]
+    assert all(isinstance(it, P.JpegScan) for it in items)
+    scan, images, segs, ncoef = ops.make_jpeg_scan_tables([(it.data, it.info, it.scan, it.cuts) for it in items])
+    dscan, dimg, dseg = torch.from_numpy(scan).cuda(), torch.from_numpy(images.view(np.uint8)).cuda(), torch.from_numpy(segs.view(np.uint8)).cuda()
+    coef = torch.empty(ncoef, dtype=torch.int16, device="cuda")
+    status = torch.empty(B, dtype=torch.int32, device="cuda")
+    run = lambda: ops.jpeg_entropy_decode_device(dscan, images, segs, coef, images_dev=dimg, segs_dev=dseg, status=status)
+    for _ in range(3):
+        run()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    us = e0.elapsed_time(e1) / 20 * 1e3
+    emit(results, what="ds_jpeg_entropy_decode_device", B=B, segments=int(segs.size), flagged=int((status != 0).sum()),
+         scan_bytes=int(scan.size), table_bytes=int(images.nbytes + segs.nbytes), coef_bytes=2 * ncoef,
+         upload_ratio=round(2 * ncoef / (scan.size + images.nbytes + segs.nbytes), 2), us_events=round(us, 1),
+         images_per_s_kernel_alone=round(B / us * 1e6, 1), step_ms=args.step_ms, share_of_step=round(us / 1e3 / args.step_ms, 4))
 
 
 def kernel_stats(path, results):
@@ -305,6 +363,7 @@ if __name__ == "__main__":
     ap.add_argument("--json", default=None)
     ap.add_argument("--step-ms", type=float, default=13.06)
     ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("--workers", default="1,2,4,8,16", help="worker counts of the jpeg part")
     ap.add_argument("parts", nargs="*", default=["loader", "train", "kernel"])
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)

@@ -31,6 +31,7 @@ DS_PLAN_NO_SPLITK = 1024
 DS_PREPROCESS_FLIP, DS_PREPROCESS_SATURATION_FIRST = 1, 2
 DS_JPEG_UNSUPPORTED, DS_JPEG_MORE = 1, 2
 DS_JPEG_444, DS_JPEG_422, DS_JPEG_420, DS_JPEG_GREY = 0, 1, 2, 3
+DS_JPEG_E_CODE, DS_JPEG_E_RUN, DS_JPEG_E_RANGE, DS_JPEG_E_COLUMN, DS_JPEG_E_SEGMENT, DS_JPEG_E_TABLE = 1, 2, 4, 8, 16, 32
 
 
 class ConvDesc(C.Structure):
@@ -124,6 +125,16 @@ class JpegDesc(C.Structure):
     _fields_ = [("coef_offset", C.c_int64), ("out_offset", C.c_int64), ("width", C.c_int32), ("height", C.c_int32),
                 ("sampling", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32),
                 ("reserved", C.c_int32), ("quant", C.c_uint8 * 192)]
+
+
+class JpegHuff(C.Structure):
+    """ds_jpeg_huff"""
+    _fields_ = [("counts", C.c_uint8 * 16), ("values", C.c_uint8 * 256)]
+
+
+class JpegScanInfo(C.Structure):
+    """ds_jpeg_scan_info"""
+    _fields_ = [("scan_begin", C.c_int64), ("cut_count", C.c_int64), ("dc", JpegHuff * 3), ("ac", JpegHuff * 3)]
 
 
 class ExampleFields(C.Structure):
@@ -263,6 +274,12 @@ SIGNATURES = {
     "ds_example_parse": (C.c_int, [_P, _i64, _P, _i32, C.POINTER(ExampleFields)]),
     "ds_jpeg_record_decode": (C.c_int, [_P, _i64, _P, _i32, C.POINTER(ExampleFields), C.POINTER(JpegInfo), _P, _i64,
                                         C.POINTER(_i32)]),
+    "ds_jpeg_scan": (C.c_int, [_P, _i64, C.POINTER(JpegInfo), C.POINTER(JpegScanInfo), _P, _i64]),
+    "ds_jpeg_record_scan": (C.c_int, [_P, _i64, _P, _i32, C.POINTER(ExampleFields), C.POINTER(JpegInfo), C.POINTER(JpegScanInfo),
+                                      _P, _i64, C.POINTER(_i32)]),
+    "ds_jpeg_restart_transcode": (C.c_int, [_P, _i64, _i32, _P, _i64, C.POINTER(_i64)]),
+    "ds_jpeg_entropy_decode_segments_host": (C.c_int, [_P, _i64, _P, _i32, _P, _i64, _P, _i64, _P]),
+    "ds_jpeg_entropy_decode_device": (C.c_int, [_P, _i64, _P, _i32, _P, _i64, _P, _i64, _P, _P]),
 }
 
 _lib = None

@@ -1,4 +1,5 @@
-// The parallel half of the baseline JPEG decode (ds_jpeg_reconstruct): quantised coefficients -> the ragged uint8 RGB crops
+// The device side of the baseline JPEG decode.  ds_jpeg_entropy_decode_device (opt-in, restart-segmented streams only) is at
+// the end of the file.  The parallel half of the decode (ds_jpeg_reconstruct): quantised coefficients -> the ragged uint8 RGB crops
 // that ds_preprocess_eval / ds_preprocess_train read.  The arithmetic is jpeg_common.h's (shared with the host statement in
 // jpeg_host.cpp): integers only, so the bytes equal libjpeg's.  Two launches, blockIdx.y = image:
 //
@@ -174,6 +175,78 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const uint8_t *__restr
     }
 }
 
+// ---- ds_jpeg_entropy_decode_device: the Huffman decode of restart-segmented streams ------------------------------------------------
+//   jpeg_entropy_kernel   blockIdx.x = image, 256 lanes.  All lanes zero the image's coefficient range with 16-byte stores
+//                         while lanes 0..5 build the decoding tables of the (up to) three DC and three AC tables from their
+//                         DHT form into LDS (8.3 KB); one barrier; then lane k decodes segments k, k + 256, ... with the
+//                         segment decoder of jpeg_common.h, byte by byte from global memory, and stores the non-zero
+//                         coefficients through the zig-zag table in LDS.  The eight column sums of the block being decoded
+//                         sit in LDS (s_col[c][lane]: consecutive lanes on consecutive banks), the three DC predictors in
+//                         named registers.  Lanes diverge freely there: the last barrier is in front of the segment loop.
+static_assert(sizeof(ds_jpeg_huff) == 272 && sizeof(ds_jpeg_scan_desc) == 1856 && offsetof(ds_jpeg_scan_desc, quant) == 32 &&
+                  offsetof(ds_jpeg_scan_desc, dc) == 224 && offsetof(ds_jpeg_scan_desc, ac) == 1040 && sizeof(ds_jpeg_segment) == 24 &&
+                  offsetof(ds_jpeg_segment, first_mcu) == 16,
+              "ds_jpeg_scan_desc / ds_jpeg_segment are ABI: ops.jpeg_scan_desc_dtype() / jpeg_segment_dtype() mirror them");
+
+__constant__ uint8_t c_zigzag[64] = DS_JPEG_ZIGZAG_INIT;
+
+constexpr int kEntropyLanes = 256;
+
+__global__ __launch_bounds__(kEntropyLanes) void jpeg_entropy_kernel(const uint8_t *__restrict__ scan, int64_t nscan,
+                                                                     const ds_jpeg_scan_desc *__restrict__ images,
+                                                                     const ds_jpeg_segment *__restrict__ segs, int64_t nsegs,
+                                                                     int16_t *__restrict__ coef, int64_t ncoef,
+                                                                     int32_t *__restrict__ status) {
+    __shared__ dsjpeg::HuffTable s_tab[6];                 // DC of components 0..2, AC of components 0..2
+    __shared__ int32_t s_col[8][kEntropyLanes];
+    __shared__ uint8_t s_q[3][64];
+    __shared__ uint8_t s_zigzag[64];
+    __shared__ int32_t s_err;
+
+    const ds_jpeg_scan_desc &d = images[blockIdx.x];
+    const int t = threadIdx.x;
+    dsjpeg::Geometry g;
+    const bool usable = dsjpeg::scan_desc_ok(d, ncoef, nsegs, g);      // uniform over the workgroup
+    if (t == 0) {
+        s_err = usable ? 0 : DS_JPEG_E_TABLE;
+        status[blockIdx.x] = 0;                            // failing lanes OR their bits in behind the second barrier
+    }
+    if (t < 64) s_zigzag[t] = c_zigzag[t];
+    if (t < 192) s_q[t >> 6][t & 63] = d.quant[t >> 6][t & 63];
+    __syncthreads();
+    if (usable) {
+        uint4 *dst = reinterpret_cast<uint4 *>(coef + d.coef_offset);       // 16-byte aligned: base and offset are
+        const int64_t n16 = g.blocks * 8;                                   // 64 int16 = 8 x 16 bytes per block
+        for (int64_t i = t; i < n16; i += kEntropyLanes) dst[i] = make_uint4(0, 0, 0, 0);
+        if (t < 6 && t % 3 < g.ncomp) {
+            const ds_jpeg_huff &h = t < 3 ? d.dc[t] : d.ac[t - 3];
+            if (!dsjpeg::huff_build(h.counts, h.values, t < 3, s_tab[t])) atomicOr(&s_err, DS_JPEG_E_TABLE);
+        }
+    }
+    __threadfence();                                       // the zeros are in place before any lane stores a coefficient
+    __syncthreads();
+    int err = s_err;
+    if (usable && !err) {
+        dsjpeg::SegmentTables tab;
+        tab.dc[0] = &s_tab[0], tab.dc[1] = &s_tab[1], tab.dc[2] = &s_tab[2];
+        tab.ac[0] = &s_tab[3], tab.ac[1] = &s_tab[4], tab.ac[2] = &s_tab[5];
+        tab.q[0] = s_q[0], tab.q[1] = s_q[1], tab.q[2] = s_q[2];
+        tab.zigzag = s_zigzag;
+        const int64_t mcus = dsjpeg::mcu_count(g);
+        const ds_jpeg_segment *sg = segs + d.first_segment;
+        for (int i = t; i < d.segments; i += kEntropyLanes) {
+            const ds_jpeg_segment s = sg[i], prev = sg[i ? i - 1 : 0];
+            if (!dsjpeg::segment_ok(s, prev, i, d.segments, nscan, mcus)) {
+                err |= DS_JPEG_E_TABLE;
+                continue;
+            }
+            err |= dsjpeg::decode_segment(scan + s.begin, scan + s.end, s.first_mcu, s.mcus, g, tab, coef + d.coef_offset,
+                                          &s_col[0][t], kEntropyLanes);
+        }
+    }
+    if (err) atomicOr(&status[blockIdx.x], err);
+}
+
 }  // namespace
 
 extern "C" int ds_jpeg_reconstruct(const int16_t *coef, int64_t ncoef, const ds_jpeg_desc *desc, int32_t batch,
@@ -193,4 +266,17 @@ extern "C" int ds_jpeg_reconstruct(const int16_t *coef, int64_t ncoef, const ds_
     hipLaunchKernelGGL(jpeg_colour_kernel, dim3(gx, batch), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)scratch,
                        scratch_bytes, desc, ncoef, out_bytes, nbytes);
     return ds::check_launch("ds_jpeg_reconstruct");
+}
+
+extern "C" int ds_jpeg_entropy_decode_device(const uint8_t *scan, int64_t nscan, const ds_jpeg_scan_desc *images, int32_t nimages,
+                                             const ds_jpeg_segment *segs, int64_t nsegs, int16_t *coef, int64_t ncoef,
+                                             int32_t *status, void *stream) {
+    DS_REQUIRE(scan && images && segs && coef && status && nscan > 0 && nsegs > 0 && ncoef > 0 && nimages > 0,
+               "ds_jpeg_entropy_decode_device: bad argument");
+    DS_REQUIRE(nimages <= 65535, "ds_jpeg_entropy_decode_device: at most 65535 images per launch");
+    DS_REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)images & 7) == 0 && ((uintptr_t)segs & 7) == 0 && ((uintptr_t)status & 3) == 0,
+               "ds_jpeg_entropy_decode_device: coef must be 16-byte aligned, the tables 8-byte, status 4-byte");
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(nimages), dim3(kEntropyLanes), 0, (hipStream_t)stream, scan, nscan, images, segs,
+                       nsegs, coef, ncoef, status);
+    return ds::check_launch("ds_jpeg_entropy_decode_device");
 }

@@ -1,7 +1,9 @@
 // The sequential half of the JPEG decode, on the host: marker parse, Huffman decode into quantised coefficients, a
-// compiled reader of one tf.train.Example payload, and the reconstruction in plain C++ (the CPU statement of what
-// jpeg.hip computes; both use jpeg_common.h).  No HIP call, no global state, no allocation beyond a vector of restart
-// segments and the planes of ds_jpeg_reconstruct_host; callable from any thread.  Contract: include/ds_kernels.h.
+// compiled reader of one tf.train.Example payload, the reconstruction in plain C++ (the CPU statement of what jpeg.hip
+// computes; both use jpeg_common.h), the scan description and host statement of the device Huffman decode, and the lossless
+// restart transcoder.  No HIP call, no global state, no allocation beyond vectors of restart segments, the planes of
+// ds_jpeg_reconstruct_host and the transcoder's coefficients and output; callable from any thread.  Contract:
+// include/ds_kernels.h.
 //
 // The bytes are untrusted.  Every read goes through a position checked against the end of the buffer; every coefficient
 // store is inside the image's block grid, whose size the caller's capacity was checked against.  Anything outside the
@@ -15,60 +17,17 @@
 
 namespace {
 
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+const uint8_t kZigzag[64] = DS_JPEG_ZIGZAG_INIT;
 
-constexpr int kLookBits = 9;
 constexpr int64_t kMaxPixels = 89478485;       // Pillow's MAX_IMAGE_PIXELS: beyond it PIL warns or raises, so PIL decides
-
-// What keeps the reconstruction equal to libjpeg-turbo's SIMD jpeg_idct_islow, which forms in0 + in4, in0 - in4, in7 + in3 and
-// in5 + in1 in 16 bits in BOTH passes and packs the pass-1 workspace with saturation: a block is taken only when no pass-1
-// output can leave +-16383, so that nothing wraps or saturates there and the 32-bit statement in jpeg_common.h is the same
-// function.  A pass-1 output is 4 * sum_k w_k in_k over a column of dequantised coefficients with |w_0| = |w_4| = 1,
-// |w_2|, |w_6| <= 1.30657 and |w_odd| <= 1.38704 (sqrt 2 cos); the test is sum_k ceil(4096 |w_k|) |in_k| <= 4090 * 4096 per
-// column (4095.75 less the rounding of the 13-bit constants and of the descale).  Pixel data cannot come near it: by
-// Parseval a column of an 8-bit block has sum_k |w_k| |F_k| <= 3.62 * 1024.
-const int32_t kRowWeight[8] = {4096, 5682, 5352, 5682, 4096, 5682, 5352, 5682};
-constexpr int32_t kColumnBound = 4090 * 4096;
 
 struct Huffman {
     bool defined = false;
-    uint8_t counts[17];            // codes of each length 1..16
+    uint8_t counts[16];            // codes of each length 1..16: the DHT form, with vals
     uint8_t vals[256];
     int nvals = 0;
-    int32_t maxcode[18];           // largest code of length l, -1 when none
-    int32_t valoff[17];            // vals index of the first code of length l, minus that code
-    uint16_t look[1 << kLookBits]; // (length << 8) | symbol for codes of <= kLookBits bits, 0 otherwise
+    dsjpeg::HuffTable t;           // the decoding tables (jpeg_common.h)
 };
-
-// derive the decoding tables; false when the counts do not describe a prefix code
-bool build(Huffman &h, bool dc) {
-    int32_t code = 0;
-    int k = 0;
-    memset(h.look, 0, sizeof(h.look));
-    for (int l = 1; l <= 16; ++l) {
-        h.valoff[l] = k - code;
-        if (h.counts[l]) {
-            if (code + h.counts[l] > (1 << l)) return false;
-            for (int i = 0; i < h.counts[l]; ++i, ++k, ++code) {
-                if (l <= kLookBits) {
-                    const int first = code << (kLookBits - l);
-                    for (int j = 0; j < (1 << (kLookBits - l)); ++j) h.look[first + j] = (uint16_t)((l << 8) | h.vals[k]);
-                }
-            }
-            h.maxcode[l] = code - 1;
-        } else {
-            h.maxcode[l] = -1;
-        }
-        code <<= 1;
-    }
-    h.maxcode[17] = 0x7fffffff;
-    if (dc)
-        for (int i = 0; i < h.nvals; ++i)
-            if (h.vals[i] > 15) return false;
-    return true;
-}
 
 struct Component {
     int id, h, v, tq, td, ta;
@@ -118,12 +77,12 @@ bool parse_header(const uint8_t *b, int64_t n, Header &hd) {
                 if (tc > 1 || th > 3) return false;
                 Huffman &h = tc ? hd.ac[th] : hd.dc[th];
                 int total = 0;
-                h.counts[0] = 0;
-                for (int l = 1; l <= 16; ++l) total += (h.counts[l] = p[o + l]);
+                for (int l = 1; l <= 16; ++l) total += (h.counts[l - 1] = p[o + l]);
                 if (total > 256 || o + 17 + total > body) return false;
+                memset(h.vals, 0, sizeof(h.vals));
                 memcpy(h.vals, p + o + 17, (size_t)total);
                 h.nvals = total;
-                if (!build(h, tc == 0)) return false;
+                if (!dsjpeg::huff_build(h.counts, h.vals, tc == 0, h.t)) return false;
                 h.defined = true;
                 o += 17 + total;
             }
@@ -229,129 +188,274 @@ void fill_info(const Header &hd, ds_jpeg_info *info) {
     for (int c = 0; c < hd.ncomp; ++c) memcpy(info->quant[c], hd.q[hd.comp[c].tq], 64);
 }
 
-// bits of one restart segment [p, end): inside it every 0xFF is followed by a stuffed 0x00 (walk_scan); past its end the
-// reader supplies zeros and counts them
-struct Bits {
-    const uint8_t *p, *end;
-    uint64_t acc = 0;
-    int n = 0;                     // bits in acc (from the top)
-    int fake = 0;                  // of which supplied past the end
-
-    inline void refill() {
-        while (n <= 56) {
-            if (p < end) {
-                const uint8_t v = *p++;
-                if (v == 0xFF && p < end) ++p;
-                acc |= (uint64_t)v << (56 - n);
-            } else {
-                fake += 8;
-            }
-            n += 8;
-        }
+// the tables a segment decode reads, from the header
+dsjpeg::SegmentTables segment_tables(const Header &hd) {
+    dsjpeg::SegmentTables t = {};
+    for (int c = 0; c < hd.ncomp; ++c) {
+        t.dc[c] = &hd.dc[hd.comp[c].td].t;
+        t.ac[c] = &hd.ac[hd.comp[c].ta].t;
+        t.q[c] = hd.q[hd.comp[c].tq];
     }
-    inline uint32_t peek(int k) const { return (uint32_t)(acc >> (64 - k)); }
-    inline void skip(int k) {
-        acc <<= k;
-        n -= k;
-    }
-    bool overrun() const { return n < fake; }
-};
-
-// one Huffman symbol, -1 when no code matches; at least 16 bits are in the buffer
-inline int decode(Bits &br, const Huffman &h) {
-    const uint16_t e = h.look[br.peek(kLookBits)];
-    if (e) {
-        br.skip(e >> 8);
-        return e & 255;
-    }
-    for (int l = kLookBits + 1; l <= 16; ++l) {
-        const int32_t code = (int32_t)br.peek(l);
-        if (code <= h.maxcode[l]) {
-            br.skip(l);
-            return h.vals[(h.valoff[l] + code) & 255];
-        }
-    }
-    return -1;
-}
-
-inline int receive_extend(Bits &br, int s) {
-    const int v = (int)br.peek(s);
-    br.skip(s);
-    return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-}
-
-// one block; false = unsupported
-inline bool decode_block(Bits &br, const Huffman &dc, const Huffman &ac, const uint8_t *q, int &pred, int16_t *blk) {
-    br.refill();
-    int s = decode(br, dc);
-    if (s < 0) return false;
-    if (s) {
-        br.refill();
-        pred += receive_extend(br, s);
-    }
-    if (pred * (int)q[0] > 32767 || pred * (int)q[0] < -32767 || pred > 32767 || pred < -32767) return false;
-    blk[0] = (int16_t)pred;
-    int32_t column[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // weighted |dequantised coefficient| per column: at most 8 * 32767 * 5682
-    column[0] = kRowWeight[0] * (pred < 0 ? -pred : pred) * (int)q[0];
-    for (int k = 1; k < 64;) {
-        br.refill();
-        const int rs = decode(br, ac);
-        if (rs < 0) return false;
-        const int r = rs >> 4;
-        s = rs & 15;
-        if (!s) {
-            if (r != 15) break;                    // end of block
-            k += 16;
-            if (k > 64) return false;
-            continue;
-        }
-        k += r;
-        if (k > 63) return false;
-        const int v = receive_extend(br, s);
-        const int nat = kZigzag[k];
-        const int prod = v * (int)q[nat];
-        if (prod > 32767 || prod < -32767) return false;
-        column[nat & 7] += kRowWeight[nat >> 3] * (prod < 0 ? -prod : prod);
-        blk[nat] = (int16_t)v;
-        ++k;
-    }
-    for (int c = 0; c < 8; ++c)
-        if (column[c] > kColumnBound) return false;
-    return !br.overrun();
+    t.zigzag = kZigzag;
+    return t;
 }
 
 int entropy_decode(const uint8_t *b, int64_t n, Header &hd, int16_t *coef) {
     std::vector<int64_t> cuts;
     if (!walk_scan(b, n, hd, &cuts)) return DS_JPEG_UNSUPPORTED;
-    const dsjpeg::Geometry &g = hd.g;
-    memset(coef, 0, (size_t)g.blocks * 128);
-    const int mw = g.bw[hd.ncomp == 1 ? 0 : 1];
-    const int bh[3] = {hd.ncomp == 1 ? 1 : g.hs, 1, 1}, bv[3] = {hd.ncomp == 1 ? 1 : g.vs, 1, 1};
+    memset(coef, 0, (size_t)hd.g.blocks * 128);
+    const dsjpeg::SegmentTables t = segment_tables(hd);
     int64_t mcu = 0, begin = hd.scan_begin;
     for (size_t seg = 0; seg < cuts.size(); ++seg) {
-        Bits br;
-        br.p = b + begin;
-        br.end = b + cuts[seg];
-        int pred[3] = {0, 0, 0};
         const int64_t stop = hd.restart && mcu + hd.restart < hd.mcus ? mcu + hd.restart : hd.mcus;
         if (seg + 1 == cuts.size() && stop != hd.mcus) return DS_JPEG_UNSUPPORTED;
-        for (; mcu < stop; ++mcu) {
-            const int my = (int)(mcu / mw), mx = (int)(mcu % mw);
-            for (int c = 0; c < hd.ncomp; ++c) {
-                const Component &k = hd.comp[c];
-                for (int v = 0; v < bv[c]; ++v)
-                    for (int h = 0; h < bh[c]; ++h) {
-                        const int64_t blk = g.base[c] + (int64_t)(my * bv[c] + v) * g.bw[c] + (mx * bh[c] + h);
-                        if (!decode_block(br, hd.dc[k.td], hd.ac[k.ta], hd.q[k.tq], pred[c], coef + blk * 64))
-                            return DS_JPEG_UNSUPPORTED;
-                    }
-            }
-        }
-        // the segment is used up: every byte fetched, less than a byte of padding left, no bit taken from past its end
-        if (br.p != br.end || br.overrun() || br.n - br.fake >= 8) return DS_JPEG_UNSUPPORTED;
+        int32_t column[8];
+        if (dsjpeg::decode_segment(b + begin, b + cuts[seg], mcu, stop - mcu, hd.g, t, coef, column, 1)) return DS_JPEG_UNSUPPORTED;
+        mcu = stop;
         begin = cuts[seg] + 2;
     }
     return mcu == hd.mcus ? DS_OK : DS_JPEG_UNSUPPORTED;
+}
+
+void fill_scan(const Header &hd, const std::vector<int64_t> &cuts, ds_jpeg_scan_info *scan) {
+    memset(scan, 0, sizeof(*scan));
+    scan->scan_begin = hd.scan_begin;
+    scan->cut_count = (int64_t)cuts.size();
+    for (int c = 0; c < hd.ncomp; ++c) {
+        const Huffman &dc = hd.dc[hd.comp[c].td], &ac = hd.ac[hd.comp[c].ta];
+        memcpy(scan->dc[c].counts, dc.counts, 16);
+        memcpy(scan->dc[c].values, dc.vals, 256);
+        memcpy(scan->ac[c].counts, ac.counts, 16);
+        memcpy(scan->ac[c].values, ac.vals, 256);
+    }
+}
+
+// info, scan and (when they fit) the cuts of a stream
+int scan_stream(const uint8_t *bytes, int64_t n, ds_jpeg_info *info, ds_jpeg_scan_info *scan, int64_t *cuts, int64_t capacity) {
+    memset(info, 0, sizeof(*info));
+    info->sampling = -1;
+    memset(scan, 0, sizeof(*scan));
+    Header hd;
+    std::vector<int64_t> found;
+    if (!parse_header(bytes, n, hd) || !walk_scan(bytes, n, hd, &found)) return DS_JPEG_UNSUPPORTED;
+    fill_info(hd, info);
+    fill_scan(hd, found, scan);
+    if ((int64_t)found.size() > capacity) return DS_JPEG_MORE;
+    memcpy(cuts, found.data(), found.size() * sizeof(int64_t));
+    return DS_OK;
+}
+
+// ---- restart transcoder --------------------------------------------------------------------------------------------------------
+// The typical Huffman tables of Annex K of the JPEG standard (K.3 - K.6), in DHT form: what a table that lacks a needed
+// symbol is replaced by.  Every DC category 0..11 and every AC symbol run 0..15 x size 1..10, EOB and ZRL has a code.
+struct StdTable {
+    uint8_t counts[16];
+    int nvals;
+    const uint8_t *vals;
+};
+const uint8_t kStdDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kStdAcLumaVals[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+const uint8_t kStdAcChromaVals[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+const StdTable kStdTables[2][2] = {          // [class: DC, AC][luma, chroma]
+    {{{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, kStdDcVals}, {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, kStdDcVals}},
+    {{{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, 162, kStdAcLumaVals},
+     {{0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}, 162, kStdAcChromaVals}}};
+
+// the encoder's view of a table: code and length per symbol (length 0 = the table has no code for it)
+struct Encoder {
+    uint16_t code[256];
+    uint8_t size[256];
+};
+
+void make_encoder(const Huffman &h, Encoder &e) {
+    memset(&e, 0, sizeof(e));
+    uint32_t code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < h.counts[l - 1]; ++i, ++k, ++code)
+            if (!e.size[h.vals[k]]) {          // (a repeated value keeps its first code)
+                e.code[h.vals[k]] = (uint16_t)code;
+                e.size[h.vals[k]] = (uint8_t)l;
+            }
+        code <<= 1;
+    }
+}
+
+inline int bit_length(int v) {                 // of |v| <= 65534
+    v = v < 0 ? -v : v;
+    int s = 0;
+    while (v) {
+        ++s;
+        v >>= 1;
+    }
+    return s;
+}
+
+// The blocks of the image in scan order with the DC predictors reset every `interval` MCUs: `use` sees every symbol,
+// use(table class, component, symbol, extra bits, their count); restart(index) runs between two intervals.
+template <class Use, class Restart>
+void for_each_symbol(const Header &hd, const int16_t *coef, int64_t interval, Use use, Restart restart) {
+    const dsjpeg::Geometry &g = hd.g;
+    const int mw = g.bw[hd.ncomp == 1 ? 0 : 1];
+    int pred[3] = {0, 0, 0};
+    for (int64_t mcu = 0; mcu < hd.mcus; ++mcu) {
+        if (mcu && mcu % interval == 0) {
+            restart(mcu / interval - 1);
+            pred[0] = pred[1] = pred[2] = 0;
+        }
+        const int my = (int)(mcu / mw), mx = (int)(mcu % mw);
+        for (int c = 0; c < hd.ncomp; ++c) {
+            const int bh = c == 0 ? g.hs : 1, bv = c == 0 ? g.vs : 1;
+            for (int v = 0; v < bv; ++v)
+                for (int h = 0; h < bh; ++h) {
+                    const int16_t *blk = coef + (g.base[c] + (int64_t)(my * bv + v) * g.bw[c] + (mx * bh + h)) * 64;
+                    const int diff = blk[0] - pred[c];
+                    pred[c] = blk[0];
+                    int s = bit_length(diff);
+                    use(0, c, s, (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
+                    int run = 0;
+                    for (int k = 1; k < 64; ++k) {
+                        const int x = blk[kZigzag[k]];
+                        if (!x) {
+                            ++run;
+                            continue;
+                        }
+                        for (; run > 15; run -= 16) use(1, c, 0xF0, 0, 0);
+                        s = bit_length(x);
+                        use(1, c, (run << 4) | s, (uint32_t)(x < 0 ? x - 1 : x) & ((1u << s) - 1), s);
+                        run = 0;
+                    }
+                    if (run) use(1, c, 0x00, 0, 0);
+                }
+        }
+    }
+}
+
+// entropy-coded bytes: bits from the top, a stuffed 0x00 behind every 0xFF
+struct BitWriter {
+    std::vector<uint8_t> &out;
+    uint32_t acc = 0;
+    int n = 0;
+    explicit BitWriter(std::vector<uint8_t> &o) : out(o) {}
+    void put(uint32_t bits, int count) {       // count <= 16
+        acc = (acc << count) | bits;
+        n += count;
+        while (n >= 8) {
+            const uint8_t v = (uint8_t)(acc >> (n - 8));
+            out.push_back(v);
+            if (v == 0xFF) out.push_back(0x00);
+            n -= 8;
+        }
+        acc &= (1u << n) - 1;
+    }
+    void pad() {                               // one-bits up to the byte boundary
+        if (n) put((1u << (8 - n)) - 1, 8 - n);
+    }
+};
+
+int restart_transcode(const uint8_t *b, int64_t n, int32_t interval_mcus, std::vector<uint8_t> &out) {
+    Header hd;
+    if (!parse_header(b, n, hd)) return DS_JPEG_UNSUPPORTED;
+    std::vector<int16_t> coef((size_t)hd.g.blocks * 64);
+    if (entropy_decode(b, n, hd, coef.data()) != DS_OK) return DS_JPEG_UNSUPPORTED;
+    const int64_t interval = interval_mcus ? interval_mcus : hd.g.bw[hd.ncomp == 1 ? 0 : 1];       // a row: <= 8192 MCUs
+    // the symbols the new stream needs, per table; a table that lacks one is replaced by its class's Annex K table
+    bool need[2][4][256] = {};
+    bool wide = false;
+    for_each_symbol(hd, coef.data(), interval,
+                    [&](int cls, int c, int sym, uint32_t, int s) {
+                        need[cls][cls ? hd.comp[c].ta : hd.comp[c].td][sym] = true;
+                        wide |= s > 15;
+                    },
+                    [](int64_t) {});
+    if (wide) return DS_JPEG_UNSUPPORTED;      // (a DC difference of 17 bits: between predictors of opposite extremes)
+    Encoder enc[2][4];
+    for (int cls = 0; cls < 2; ++cls)
+        for (int id = 0; id < 4; ++id) {
+            Huffman &h = cls ? hd.ac[id] : hd.dc[id];
+            if (!h.defined) continue;
+            make_encoder(h, enc[cls][id]);
+            bool missing = false;
+            for (int sym = 0; sym < 256; ++sym) missing |= need[cls][id][sym] && !enc[cls][id].size[sym];
+            if (!missing) continue;
+            bool luma = false;
+            for (int c = 0; c < hd.ncomp; ++c) luma |= c == 0 && (cls ? hd.comp[c].ta : hd.comp[c].td) == id;
+            const StdTable &st = kStdTables[cls][luma ? 0 : 1];
+            memcpy(h.counts, st.counts, 16);
+            memset(h.vals, 0, sizeof(h.vals));
+            memcpy(h.vals, st.vals, (size_t)st.nvals);
+            h.nvals = st.nvals;
+            make_encoder(h, enc[cls][id]);
+            for (int sym = 0; sym < 256; ++sym)
+                if (need[cls][id][sym] && !enc[cls][id].size[sym]) return DS_JPEG_UNSUPPORTED;
+        }
+    // the segments in front of the scan: everything but DRI and DHT as it is; then the tables, the interval and SOS
+    out.clear();
+    out.reserve((size_t)n + (size_t)n / 8 + 1024);
+    out.push_back(0xFF);
+    out.push_back(0xD8);
+    int64_t pos = 2, sos = 0;
+    for (;;) {                                 // parse_header accepted these bytes: every length is inside the buffer
+        const int m = b[pos + 1];
+        const int64_t len = be16(b + pos + 2);
+        if (m == 0xDA) {
+            sos = pos;
+            break;
+        }
+        if (m != 0xDD && m != 0xC4) out.insert(out.end(), b + pos, b + pos + 2 + len);
+        pos += 2 + len;
+    }
+    size_t dht = 2;
+    for (int cls = 0; cls < 2; ++cls)
+        for (int id = 0; id < 4; ++id)
+            if ((cls ? hd.ac[id] : hd.dc[id]).defined) dht += 17 + (size_t)(cls ? hd.ac[id] : hd.dc[id]).nvals;
+    if (dht > 65535) return DS_JPEG_UNSUPPORTED;
+    out.push_back(0xFF);
+    out.push_back(0xC4);
+    out.push_back((uint8_t)(dht >> 8));
+    out.push_back((uint8_t)dht);
+    for (int cls = 0; cls < 2; ++cls)
+        for (int id = 0; id < 4; ++id) {
+            const Huffman &h = cls ? hd.ac[id] : hd.dc[id];
+            if (!h.defined) continue;
+            out.push_back((uint8_t)((cls << 4) | id));
+            out.insert(out.end(), h.counts, h.counts + 16);
+            out.insert(out.end(), h.vals, h.vals + h.nvals);
+        }
+    const uint8_t dri[6] = {0xFF, 0xDD, 0x00, 0x04, (uint8_t)(interval >> 8), (uint8_t)interval};
+    out.insert(out.end(), dri, dri + 6);
+    out.insert(out.end(), b + sos, b + hd.scan_begin);
+    BitWriter w(out);
+    for_each_symbol(hd, coef.data(), interval,
+                    [&](int cls, int c, int sym, uint32_t extra, int s) {
+                        const Encoder &e = enc[cls][cls ? hd.comp[c].ta : hd.comp[c].td];
+                        w.put(e.code[sym], e.size[sym]);
+                        if (s) w.put(extra, s);
+                    },
+                    [&](int64_t index) {
+                        w.pad();
+                        out.push_back(0xFF);
+                        out.push_back((uint8_t)(0xD0 + (index & 7)));
+                    });
+    w.pad();
+    out.insert(out.end(), b + hd.scan_end, b + n);           // EOI and whatever follows it
+    return DS_OK;
 }
 
 // ---- tf.train.Example ------------------------------------------------------------------------------------------------------
@@ -613,6 +717,74 @@ extern "C" int ds_jpeg_reconstruct_host(const int16_t *coef, int64_t ncoef, cons
         uint8_t *dst = out_bytes + d.out_offset;
         for (int y = 0; y < d.crop_h; ++y)
             for (int x = 0; x < d.crop_w; ++x, dst += 3) dsjpeg::pixel(pl, g, d.y0 + y, d.x0 + x, dst);
+    }
+    return DS_OK;
+}
+
+extern "C" int ds_jpeg_scan(const uint8_t *bytes, int64_t n, ds_jpeg_info *info, ds_jpeg_scan_info *scan, int64_t *cuts,
+                            int64_t capacity) {
+    if (!bytes || n < 0 || !info || !scan || capacity < 0 || (capacity > 0 && !cuts)) return DS_ERR_ARG;
+    return scan_stream(bytes, n, info, scan, cuts, capacity);
+}
+
+extern "C" int ds_jpeg_record_scan(const uint8_t *rec, int64_t n, int64_t *text, int32_t text_capacity, ds_example_fields *fields,
+                                   ds_jpeg_info *info, ds_jpeg_scan_info *scan, int64_t *cuts, int64_t capacity,
+                                   int32_t *jpeg_status) {
+    if (!info || !scan || !jpeg_status || capacity < 0 || (capacity > 0 && !cuts)) return DS_ERR_ARG;
+    const int rc = ds_example_parse(rec, n, text, text_capacity, fields);
+    if (rc != DS_OK) return rc;
+    *jpeg_status = scan_stream(rec + fields->image_offset, fields->image_length, info, scan, cuts, capacity);
+    return DS_OK;
+}
+
+extern "C" int ds_jpeg_restart_transcode(const uint8_t *bytes, int64_t n, int32_t interval_mcus, uint8_t *out, int64_t capacity,
+                                         int64_t *out_n) {
+    if (!bytes || n < 0 || interval_mcus < 0 || interval_mcus > 65535 || capacity < 0 || (capacity > 0 && !out) || !out_n)
+        return DS_ERR_ARG;
+    *out_n = 0;
+    std::vector<uint8_t> stream;
+    const int rc = restart_transcode(bytes, n, interval_mcus, stream);
+    if (rc != DS_OK) return rc;
+    *out_n = (int64_t)stream.size();
+    if (capacity < *out_n) return DS_JPEG_MORE;
+    memcpy(out, stream.data(), stream.size());
+    return DS_OK;
+}
+
+extern "C" int ds_jpeg_entropy_decode_segments_host(const uint8_t *scan, int64_t nscan, const ds_jpeg_scan_desc *images,
+                                                    int32_t nimages, const ds_jpeg_segment *segs, int64_t nsegs, int16_t *coef,
+                                                    int64_t ncoef, int32_t *status) {
+    if (!scan || nscan < 0 || !images || nimages < 1 || !segs || nsegs < 0 || !coef || ncoef < 0 || !status) return DS_ERR_ARG;
+    std::vector<dsjpeg::HuffTable> tables(6);
+    for (int32_t b = 0; b < nimages; ++b) {
+        const ds_jpeg_scan_desc &d = images[b];
+        status[b] = DS_JPEG_E_TABLE;
+        dsjpeg::Geometry g;
+        if (!dsjpeg::scan_desc_ok(d, ncoef, nsegs, g)) continue;
+        dsjpeg::SegmentTables t = {};
+        bool ok = true;
+        for (int c = 0; c < g.ncomp; ++c) {
+            ok = ok && dsjpeg::huff_build(d.dc[c].counts, d.dc[c].values, true, tables[c]);
+            ok = ok && dsjpeg::huff_build(d.ac[c].counts, d.ac[c].values, false, tables[3 + c]);
+            t.dc[c] = &tables[c];
+            t.ac[c] = &tables[3 + c];
+            t.q[c] = d.quant[c];
+        }
+        t.zigzag = kZigzag;
+        if (!ok) continue;
+        int16_t *image = coef + d.coef_offset;
+        memset(image, 0, (size_t)g.blocks * 128);
+        int err = 0;
+        const ds_jpeg_segment *sg = segs + d.first_segment;
+        for (int i = 0; i < d.segments; ++i) {
+            if (!dsjpeg::segment_ok(sg[i], sg[i ? i - 1 : 0], i, d.segments, nscan, dsjpeg::mcu_count(g))) {
+                err |= DS_JPEG_E_TABLE;
+                continue;
+            }
+            int32_t column[8];
+            err |= dsjpeg::decode_segment(scan + sg[i].begin, scan + sg[i].end, sg[i].first_mcu, sg[i].mcus, g, t, image, column, 1);
+        }
+        status[b] = err;
     }
     return DS_OK;
 }

@@ -61,3 +61,35 @@ def get_split_with_text(split_name, dataset_dir, photos_subdir='photos', tfrecor
         i = line.index(':')
         sizes[line[:i]] = int(line[i + 1:])
     return Dataset(sorted(glob.glob(pattern)), sizes[split_name], len(labels_to_names), labels_to_names)
+
+
+def add_restart_markers(dataset_dir, tfrecords_subdir='tfrecords', out_subdir='tfrecords_rst', interval_mcus=0):
+    """Rewrite every shard of dataset_dir/tfrecords_subdir under the same file name into dataset_dir/out_subdir with
+    'image/encoded' re-encoded LOSSLESSLY with a restart interval of interval_mcus MCUs (0 = one MCU row): the Huffman data
+    of such a stream can be decoded segment by segment, which load_batch_with_text(jpeg_entropy='device') does on the GPU.
+    The coefficients, and so the pixels, do not change (ds_jpeg_restart_transcode).  A stream outside the compiled
+    decoder's supported set (progressive, CMYK, ...) keeps its bytes; every other feature and the record order are
+    unchanged.  get_split_with_text(..., tfrecords_subdir=out_subdir) reads the result.  Returns (transcoded, kept)."""
+    from .. import ops
+    from .tfrecord import encode_example, write_records
+    src, dst = os.path.join(dataset_dir, tfrecords_subdir), os.path.join(dataset_dir, out_subdir)
+    if os.path.abspath(src) == os.path.abspath(dst):
+        raise ValueError("add_restart_markers: out_subdir must differ from tfrecords_subdir")
+    os.makedirs(dst, exist_ok=True)
+    transcoded = kept = 0
+    for path in sorted(glob.glob(os.path.join(src, '*.tfrecord'))):
+        records = []
+        for rec in read_records(path):
+            rec = bytes(rec)
+            ex = decode_example(rec)
+            images = ex.get('image/encoded', [])
+            new = ops.jpeg_restart_transcode(images[0], interval_mcus) if images else None
+            if new is None:
+                kept += 1
+                records.append(rec)
+                continue
+            transcoded += 1
+            ex['image/encoded'] = [new] + images[1:]
+            records.append(encode_example(ex))
+        write_records(os.path.join(dst, os.path.basename(path)), records)
+    return transcoded, kept

@@ -85,7 +85,8 @@ def evaluate_image_model(checkpoint_dir, log_dir, mode, num_evals, *, config=Non
 
 def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False,
                          device="cuda", rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None,
-                         pipeline='host', workers=8, prefetch=2, decode_images=True, jpeg_decode='host'):
+                         pipeline='host', workers=8, prefetch=2, decode_images=True, jpeg_decode='host',
+                         jpeg_entropy='host'):
     """Generator of training batches from a `datasets.convert_to_dataset.Dataset` -- the role of
     load_batch_with_text + tf.train.batch in the reference (im_model.py:78-116): decode the JPEG, apply the
     EVAL preprocessing (is_training=False is what every reference call site uses, :78,102), batch.  is_training=True:
@@ -104,7 +105,14 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
     (text-only models): the JPEGs are neither decoded nor preprocessed and the batches carry no 'images'.
     jpeg_decode: 'host' (PIL in the workers) or 'device' (pipeline='device' only, a ValueError otherwise: compiled Huffman
     decode in the workers, inverse DCT / upsampling / colour conversion in ds_jpeg_reconstruct; the same batches bit for
-    bit, streams outside the baseline set fall back to PIL one by one, DeviceLoader.jpeg_fallbacks counts them)."""
+    bit, streams outside the baseline set fall back to PIL one by one, DeviceLoader.jpeg_fallbacks counts them).
+    jpeg_entropy: 'host' (the Huffman decode in the workers) or 'device' (jpeg_decode='device' only, a ValueError otherwise:
+    streams with restart markers -- datasets.convert_to_dataset.add_restart_markers writes them -- are Huffman-decoded by
+    ds_jpeg_entropy_decode_device, all others as with 'host'; the same batches bit for bit)."""
+    if jpeg_entropy not in ('host', 'device'):
+        raise ValueError("jpeg_entropy must be 'host' or 'device', not %r" % (jpeg_entropy,))
+    if jpeg_entropy == 'device' and jpeg_decode != 'device':
+        raise ValueError("jpeg_entropy='device' needs jpeg_decode='device': the coefficients go to ds_jpeg_reconstruct")
     if jpeg_decode not in ('host', 'device'):
         raise ValueError("jpeg_decode must be 'host' or 'device', not %r" % (jpeg_decode,))
     if jpeg_decode == 'device' and pipeline != 'device':
@@ -112,7 +120,8 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
     if pipeline == 'device':
         from ..input_pipeline import DeviceLoader
         return DeviceLoader(dataset, batch_size, shuffle, height, width, is_training, device, rank, world, seed, loop,
-                            max_token_id, num_classes, workers=workers, prefetch=prefetch, decode_images=decode_images, jpeg_decode=jpeg_decode)
+                            max_token_id, num_classes, workers=workers, prefetch=prefetch, decode_images=decode_images, jpeg_decode=jpeg_decode,
+                            jpeg_entropy=jpeg_entropy)
     if pipeline != 'host':
         raise ValueError("pipeline must be 'host' or 'device', not %r" % (pipeline,))
     return _host_batches(dataset, batch_size, shuffle, height, width, is_training, device, rank, world, seed, loop,

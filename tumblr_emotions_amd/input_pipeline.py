@@ -26,6 +26,16 @@ and ds_jpeg_desc records into the staging set, and ds_jpeg_reconstruct (inverse 
 writes the ragged byte buffer on the copy stream in front of the unchanged preprocessing kernel.  A stream outside the
 decoder's supported set (progressive, CMYK, ...) takes the PIL path for that image alone -- its pixels are uploaded into
 their slot of the same buffer, a corrupt file raises what it raises today -- and is counted in DeviceLoader.jpeg_fallbacks.
+
+jpeg_entropy='device' (opt-in, with jpeg_decode='device' only) moves the Huffman decode of restart-segmented streams to the
+GPU as well: for a supported stream whose restart interval is short enough (device_entropy_eligible) the worker only parses
+markers (ds_jpeg_record_scan) and hands over a JpegScan -- the encoded bytes, the header's tables and the positions of the
+restart markers; the feeder packs the entropy-coded bytes and two small tables into pinned staging and
+ds_jpeg_entropy_decode_device writes the coefficients where ds_jpeg_reconstruct reads them, so neither a coefficient buffer
+nor its upload exists on the host.  The feeder reads the per-image status words back (it blocks on that event; the consumer
+does not, the feeder runs `prefetch` batches ahead) and decodes a flagged image with PIL from the bytes it still holds: a
+fallback like any other.  Every other image of the batch goes the way it goes with jpeg_entropy='host'.
+datasets.convert_to_dataset.add_restart_markers gives a converted dataset one restart interval per MCU row, losslessly.
 """
 import io
 import queue
@@ -199,6 +209,29 @@ class JpegCoefs:
 
 _worker = threading.local()
 
+# A stream takes the device entropy path when 0 < restart interval <= max(MCUs per row, this): a lane decodes a segment
+# serially, so long segments leave most of a workgroup idle.  The value is a guess that nobody has measured.
+DEVICE_ENTROPY_MAX_INTERVAL = 64
+
+
+def device_entropy_eligible(info):
+    """The stream of this _lib.JpegInfo is decoded by ds_jpeg_entropy_decode_device under jpeg_entropy='device'."""
+    from . import ops
+    mw, _ = ops.jpeg_mcus(int(info.height), int(info.width), int(info.sampling))
+    return 0 < info.restart_interval <= max(mw, DEVICE_ENTROPY_MAX_INTERVAL)
+
+
+class JpegScan:
+    """What a worker hands the feeder for an image whose Huffman decode runs on the device: the encoded bytes, the header
+    (ds_jpeg_info), the scan's tables and cut positions (ds_jpeg_scan), the crop box and, at train time, the TrainParams
+    and the key they were drawn from (a flagged image is decoded by decode_pixels(data, train_key))."""
+    __slots__ = ("data", "info", "scan", "cuts", "height", "width", "sampling", "quant", "box", "params", "train_key", "coef_count")
+
+    def __init__(self, data, info, scan, cuts, like, train_key):
+        self.data, self.info, self.scan, self.cuts, self.train_key = data, info, scan, cuts, train_key
+        self.height, self.width, self.sampling, self.quant = like.height, like.width, like.sampling, like.quant
+        self.box, self.params, self.coef_count = like.box, like.params, int(info.coef_count)
+
 
 def decode_jpeg_bytes(data, train_key=None):
     """One encoded image -> JpegCoefs when the compiled decoder supports the stream, else what decode_pixels returns (the
@@ -246,16 +279,39 @@ def decode_record_jpeg(rec, train_key=None):
     return img, text, int(seq_len), int(label), int(post_id), int(day)
 
 
+def decode_record_jpeg_scan(rec, train_key=None):
+    """decode_record_jpeg under jpeg_entropy='device': one ds_jpeg_record_scan call (payload parse + marker parse, nothing
+    decoded, no GIL); the first item is a JpegScan for an eligible stream, and exactly decode_record_jpeg's otherwise."""
+    from . import _lib, ops
+    rec = bytes(rec)
+    cuts = np.empty(max(getattr(_worker, "cuts", 0), 256), np.int64)      # handed over with the result: a fresh one per record
+    r = ops.jpeg_record_scan(rec, cuts)
+    if r is not None and r[0] == _lib.DS_JPEG_MORE and device_entropy_eligible(r[1]):
+        _worker.cuts = int(r[2].cut_count)
+        cuts = np.empty(_worker.cuts, np.int64)
+        r = ops.jpeg_record_scan(rec, cuts)
+    if r is None or r[0] != 0 or not device_entropy_eligible(r[1]):
+        return decode_record_jpeg(rec, train_key)
+    _, info, scan, (off, length, text, seq_len, label, post_id, day) = r
+    img = JpegScan(rec[off:off + length], info, scan, cuts[:int(scan.cut_count)], _coefs(None, info, train_key), train_key)
+    return img, text, int(seq_len), int(label), int(post_id), int(day)
+
+
 def pack_ragged_jpeg(items, out_h, out_w, st, train=False):
     """pack_ragged for a batch whose items are JpegCoefs or decoded crops (train: (crop, TrainParams)): the preprocessing
     descriptors of ALL images and the pixels of the decoded ones go where pack_ragged puts them (st.desc_np, st.bytes);
     coefficients go to st.coef back to back (starts rounded up to 8 int16) with one st.jdesc_np record each.  Returns
     (bytes used, int16 used, JpegCoefs count, [(offset, size) of every decoded crop])."""
-    shapes, pos, cpos = [], 0, 0
+    shapes, pos, cpos, spos, nseg = [], 0, 0, 0, 0
     for it in items:
         if isinstance(it, JpegCoefs):
             ch, cw = it.box[2], it.box[3]
             cpos = -(-cpos // 8) * 8 + it.coef.size
+        elif isinstance(it, JpegScan):
+            ch, cw = it.box[2], it.box[3]
+            cpos = -(-cpos // 8) * 8 + it.coef_count
+            spos += int(it.cuts[-1]) - int(it.scan.scan_begin)
+            nseg += it.cuts.size
         else:
             im = it[0] if train else it
             if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
@@ -265,15 +321,24 @@ def pack_ragged_jpeg(items, out_h, out_w, st, train=False):
         pos = -(-(pos + ch * cw * 3) // 4) * 4
     st.reserve(pos)
     st.reserve_coef(cpos)
+    if nseg:
+        st.reserve_scan(spos, nseg)
     out, coef = st.bytes.numpy(), st.coef.numpy()
     cpos, nj, copies = 0, 0, []
+    st.scans, st.coef_copies = [], []
     for i, (it, (off, ch, cw)) in enumerate(zip(items, shapes)):
-        if isinstance(it, JpegCoefs):
+        if isinstance(it, (JpegCoefs, JpegScan)):
             p = it.params
             cpos = -(-cpos // 8) * 8
-            coef[cpos:cpos + it.coef.size] = it.coef
+            if isinstance(it, JpegCoefs):
+                size = it.coef.size
+                coef[cpos:cpos + size] = it.coef
+                st.coef_copies.append((cpos, size))
+            else:                                  # the device writes these coefficients: (descriptor row, item, byte offset)
+                size = it.coef_count
+                st.scans.append((nj, it, off, cpos))
             st.jdesc_np[nj] = (cpos, off, it.width, it.height, it.sampling, it.box[0], it.box[1], ch, cw, 0, it.quant)
-            cpos += it.coef.size
+            cpos += size
             nj += 1
         else:
             im, p = it if train else (it, None)
@@ -282,6 +347,11 @@ def pack_ragged_jpeg(items, out_h, out_w, st, train=False):
         if train and (p.crop_h, p.crop_w) != (ch, cw):
             raise ValueError("pack_ragged_jpeg: image %d is not the crop its parameters describe" % i)
         st.desc_np[i] = _desc_record(off, ch, cw, out_h, out_w, p if train else None)
+    if st.scans:
+        from . import ops
+        ops.fill_jpeg_scan_tables([(it.data, it.info, it.scan, it.cuts) for _, it, _, _ in st.scans],
+                                  [c for _, _, _, c in st.scans], st.scan.numpy(), st.sdesc_np, st.segs_np)
+        st.scan_used, st.segs_used = spos, nseg
     return pos, cpos, nj, copies
 
 
@@ -290,7 +360,7 @@ class _Staging:
     """One pinned staging set: ragged image bytes + descriptor table + the int64 fields, with the device byte buffer and
     descriptor table they are uploaded into and the event of the last upload."""
 
-    def __init__(self, batch_size, post_size, device, cuda, train=False, jpeg=False):
+    def __init__(self, batch_size, post_size, device, cuda, train=False, jpeg=False, entropy=False):
         import torch
         from . import ops
         preprocess_desc_dtype = ops.preprocess_train_desc_dtype if train else ops.preprocess_desc_dtype
@@ -308,6 +378,16 @@ class _Staging:
             self.jdesc_np = self.jdesc.numpy().view(ops.jpeg_desc_dtype())
             self.jdesc_dev = torch.empty(self.jdesc.numel(), dtype=torch.uint8, device=device) if cuda else None
             self.reserve_coef(1 << 20)
+        self.scans, self.coef_copies = [], []     # pack_ragged_jpeg: the JpegScan images, the ranges of host-decoded coefficients
+        self.scan = self.scan_dev = self.segs = self.segs_np = self.segs_dev = None
+        if jpeg and entropy:      # jpeg_entropy='device': entropy-coded bytes, the two tables, the status words
+            self.sdesc = self._host(batch_size * ops.jpeg_scan_desc_dtype().itemsize, torch.uint8)
+            self.sdesc_np = self.sdesc.numpy().view(ops.jpeg_scan_desc_dtype())
+            self.status = self._host(batch_size, torch.int32)
+            if cuda:
+                self.sdesc_dev = torch.empty(self.sdesc.numel(), dtype=torch.uint8, device=device)
+                self.status_dev = torch.empty(batch_size, dtype=torch.int32, device=device)
+            self.reserve_scan(1 << 20, 1 << 12)
 
     def _host(self, n, dtype):
         return self.torch.empty(n, dtype=dtype, pin_memory=self.cuda)
@@ -325,6 +405,19 @@ class _Staging:
             if self.cuda:
                 self.coef_dev = self.torch.empty(cap, dtype=self.torch.int16, device=self.device)
                 self.scratch_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device)
+
+    def reserve_scan(self, nbytes, nseg):
+        from . import ops
+        if self.scan is None or self.scan.numel() < nbytes:
+            cap = -(-int(nbytes * 1.25) // 4096) * 4096
+            self.scan = self._host(cap, self.torch.uint8)
+            self.scan_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device) if self.cuda else None
+        item = ops.jpeg_segment_dtype().itemsize
+        if self.segs is None or self.segs.numel() < nseg * item:
+            cap = -(-int(nseg * 1.25) // 256) * 256 * item
+            self.segs = self._host(cap, self.torch.uint8)
+            self.segs_np = self.segs.numpy().view(ops.jpeg_segment_dtype())
+            self.segs_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device) if self.cuda else None
 
     def wait_free(self):
         if self.event is not None:
@@ -381,7 +474,7 @@ def _record_stream(dataset, shuffle, rng, rank, world, loop):
 
 
 def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, world, seed, loop, max_token_id,
-            num_classes, decode_images, prefetch, inflight, train=False, jpeg=False):
+            num_classes, decode_images, prefetch, inflight, train=False, jpeg=False, entropy=False):
     import collections
     try:
         import torch
@@ -419,7 +512,7 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                     pass_no, idx, payload = rec
                     key = (seed, pass_no, idx) if train and decode_images else None
                     if jpeg and decode_images:
-                        pending.append(state.pool.submit(decode_record_jpeg, payload, key))
+                        pending.append(state.pool.submit(decode_record_jpeg_scan if entropy else decode_record_jpeg, payload, key))
                     else:
                         pending.append(state.pool.submit(decode_record, payload, decode_images, key))
             if not pending:
@@ -436,7 +529,7 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             order = rng.permutation(batch_size) if shuffle else np.arange(batch_size)
             if post_size is None:
                 post_size = len(buf[0][1])
-                stagings = [_Staging(batch_size, post_size, dev, cuda, train and decode_images, jpeg and decode_images)
+                stagings = [_Staging(batch_size, post_size, dev, cuda, train and decode_images, jpeg and decode_images, entropy)
                             for _ in range(max(2, prefetch + 1))]
             st = stagings[turn]
             turn = (turn + 1) % len(stagings)
@@ -463,13 +556,18 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                 (ops.check_preprocess_train_descs if train else ops.check_preprocess_descs)(st.desc_np[:batch_size], used)
             buf = []
             out = {}
+            flagged = on_device = 0
             if cuda:
                 with torch.cuda.stream(stream):
                     if decode_images and jpeg:
                         for off, size in copies:                 # the images PIL decoded: their slots only
                             st.bytes_dev[off:off + size].copy_(st.bytes[off:off + size], non_blocking=True)
-                        if njpeg:
+                        if st.scans:
+                            njpeg, flagged = _device_entropy(st, stream, ncoef, njpeg, train)
+                            on_device = len(st.scans) - flagged
+                        elif njpeg:
                             st.coef_dev[:ncoef].copy_(st.coef[:ncoef], non_blocking=True)
+                        if njpeg:
                             st.jdesc_dev.copy_(st.jdesc, non_blocking=True)
                             ops.jpeg_reconstruct(st.coef_dev[:ncoef], st.jdesc_np[:njpeg], st.bytes_dev[:used],
                                                  scratch=st.scratch_dev, desc_dev=st.jdesc_dev)
@@ -488,11 +586,50 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             out["texts"] = ints_dev[:nt].view(batch_size, post_size)
             for k, (name, _) in enumerate(_FIELDS):
                 out[name] = ints_dev[nt + k * batch_size:nt + (k + 1) * batch_size]
-            if not _put(state, ("batch", out, event, stream, len(copies) if jpeg else 0)):
+            if not _put(state, ("batch", out, event, stream, len(copies) + flagged if jpeg else 0, on_device)):
                 return
         _put(state, ("end",))
     except BaseException as e:
         _put(state, ("error", e))
+
+
+def _device_entropy(st, stream, ncoef, njpeg, train):
+    """The Huffman decode of the batch's JpegScan images on the copy stream (the current one), into their ranges of
+    st.coef_dev; host-decoded images' coefficients are uploaded into theirs.  The status words come back to pinned memory
+    and the FEEDER waits for them; a flagged image is decoded with PIL from the bytes it holds, its crop uploaded into its
+    slot of the ragged buffer and its row dropped from the reconstruct table.  Returns (rows left in st.jdesc_np, flagged)."""
+    import torch
+    from . import ops
+    for off, size in st.coef_copies:
+        st.coef_dev[off:off + size].copy_(st.coef[off:off + size], non_blocking=True)
+    ns, nscan, nseg = len(st.scans), st.scan_used, st.segs_used
+    st.scan_dev[:nscan].copy_(st.scan[:nscan], non_blocking=True)
+    st.sdesc_dev.copy_(st.sdesc, non_blocking=True)
+    nb = nseg * ops.jpeg_segment_dtype().itemsize
+    st.segs_dev[:nb].copy_(st.segs[:nb], non_blocking=True)
+    ops.jpeg_entropy_decode_device(st.scan_dev[:nscan], st.sdesc_np[:ns], st.segs_np[:nseg], st.coef_dev[:ncoef],
+                                   images_dev=st.sdesc_dev, segs_dev=st.segs_dev, status=st.status_dev)
+    st.status[:ns].copy_(st.status_dev[:ns], non_blocking=True)
+    done = torch.cuda.Event()
+    done.record(stream)
+    done.synchronize()
+    bad = np.nonzero(st.status.numpy()[:ns])[0]
+    if not bad.size:
+        return njpeg, 0
+    keep = np.ones(njpeg, bool)
+    out = st.bytes.numpy()
+    for k in bad:
+        row, it, off, _ = st.scans[k]
+        im = decode_pixels(it.data, it.train_key)
+        im = im[0] if train else im
+        if im.shape[:2] != (it.box[2], it.box[3]):
+            raise ValueError("a JPEG decodes to another size than its header states")
+        out[off:off + im.size].reshape(im.shape)[...] = im
+        st.bytes_dev[off:off + im.size].copy_(st.bytes[off:off + im.size], non_blocking=True)
+        keep[row] = False
+    left = int(keep.sum())
+    st.jdesc_np[:left] = st.jdesc_np[:njpeg][keep]
+    return left, int(bad.size)
 
 
 
@@ -517,15 +654,23 @@ class DeviceLoader:
     feeder and joins every worker; a closed or exhausted loader raises StopIteration.  is_training=True: the train-time
     augmentation (ds_preprocess_train) instead of the eval chain; ignored with decode_images=False.  jpeg_decode='device':
     compiled Huffman decode in the workers and ds_jpeg_reconstruct on the copy stream instead of PIL (ignored with
-    decode_images=False); jpeg_fallbacks counts the images of the batches handed out so far that took the PIL path."""
+    decode_images=False); jpeg_fallbacks counts the images of the batches handed out so far that took the PIL path.
+    jpeg_entropy='device' (with jpeg_decode='device' only, a ValueError otherwise): the Huffman decode of restart-segmented
+    streams in ds_jpeg_entropy_decode_device as well; jpeg_device_entropy counts the images whose coefficients the device
+    produced, and an image the kernel flags is a fallback."""
 
     def __init__(self, dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False, device="cuda",
                  rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None, workers=8, prefetch=2,
-                 decode_images=True, jpeg_decode='host'):
+                 decode_images=True, jpeg_decode='host', jpeg_entropy='host'):
         if jpeg_decode not in ('host', 'device'):
             raise ValueError("jpeg_decode must be 'host' or 'device', not %r" % (jpeg_decode,))
-        self.jpeg_decode = jpeg_decode
+        if jpeg_entropy not in ('host', 'device'):
+            raise ValueError("jpeg_entropy must be 'host' or 'device', not %r" % (jpeg_entropy,))
+        if jpeg_entropy == 'device' and jpeg_decode != 'device':
+            raise ValueError("jpeg_entropy='device' needs jpeg_decode='device': the coefficients go to ds_jpeg_reconstruct")
+        self.jpeg_decode, self.jpeg_entropy = jpeg_decode, jpeg_entropy
         self.jpeg_fallbacks = 0
+        self.jpeg_device_entropy = 0
         if batch_size < 1 or height < 1 or width < 1 or world < 1 or not 0 <= rank < world:
             raise ValueError("DeviceLoader: bad batch_size / height / width / rank / world")
         self.workers = clamp_workers(workers)
@@ -543,7 +688,8 @@ class DeviceLoader:
         st.thread = threading.Thread(target=_feeder, name="ds-input-feeder", daemon=True,
                                      args=(st, dataset, int(batch_size), bool(shuffle), int(height), int(width), device, rank,
                                            world, seed, bool(loop), max_token_id, num_classes, self.decode_images,
-                                           self.prefetch, inflight, bool(is_training), jpeg_decode == 'device'))
+                                           self.prefetch, inflight, bool(is_training), jpeg_decode == 'device',
+                                           jpeg_entropy == 'device'))
         self._finalizer = weakref.finalize(self, _shutdown, st)
         st.thread.start()
 
@@ -555,8 +701,9 @@ class DeviceLoader:
             raise StopIteration
         item = self._state.out.get()
         if item[0] == "batch":
-            _, out, event, stream, fallbacks = item
+            _, out, event, stream, fallbacks, on_device = item
             self.jpeg_fallbacks += fallbacks
+            self.jpeg_device_entropy += on_device
             if event is not None:
                 import torch
                 cur = torch.cuda.current_stream(stream.device)

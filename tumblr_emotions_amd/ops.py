@@ -1201,3 +1201,214 @@ def jpeg_reconstruct(coef, desc, out_bytes, scratch=None, desc_dev=None):
     _lib.check(_lib.load().ds_jpeg_reconstruct(_p(coef), coef.numel(), _p(desc_dev), B, _p(out_bytes), out_bytes.numel(),
                                                _p(scratch), scratch.numel(), _stream()), "ds_jpeg_reconstruct")
     return out_bytes
+
+
+# ---- restart-segmented JPEGs: scan description, lossless restart transcoder, the Huffman decode on the device ------------------
+def jpeg_huff_dtype():
+    """NumPy view of ds_jpeg_huff (272 bytes): a Huffman table in its DHT form."""
+    import numpy as np
+    return np.dtype([("counts", np.uint8, (16,)), ("values", np.uint8, (256,))])
+
+
+def jpeg_scan_desc_dtype():
+    """NumPy view of ds_jpeg_scan_desc (1856 bytes): one record per image of a ds_jpeg_entropy_decode_device launch."""
+    import numpy as np
+    return np.dtype([("coef_offset", np.int64), ("width", np.int32), ("height", np.int32), ("sampling", np.int32),
+                     ("first_segment", np.int32), ("segments", np.int32), ("reserved", np.int32), ("quant", np.uint8, (3, 64)),
+                     ("dc", jpeg_huff_dtype(), (3,)), ("ac", jpeg_huff_dtype(), (3,))], align=True)
+
+
+def jpeg_segment_dtype():
+    """NumPy view of ds_jpeg_segment (24 bytes): one record per restart segment."""
+    import numpy as np
+    return np.dtype([("begin", np.int64), ("end", np.int64), ("first_mcu", np.int32), ("mcus", np.int32)], align=True)
+
+
+def jpeg_mcus(height, width, sampling):
+    """(MCUs per row, MCU rows) of an image."""
+    h, v = (2 if sampling in (_lib.DS_JPEG_422, _lib.DS_JPEG_420) else 1), (2 if sampling == _lib.DS_JPEG_420 else 1)
+    return -(-width // (8 * h)), -(-height // (8 * v))
+
+
+def jpeg_scan(data):
+    """ds_jpeg_scan of a bytes object: (_lib.JpegInfo, _lib.JpegScanInfo, int64 cut positions) of a supported stream --
+    markers and the walk over the entropy-coded bytes only, nothing is decoded -- or None where ds_jpeg_probe says
+    unsupported."""
+    import numpy as np
+    info, scan = _lib.JpegInfo(), _lib.JpegScanInfo()
+    cuts = np.empty(64, np.int64)
+    for _ in range(2):
+        rc = _lib.load().ds_jpeg_scan(C.cast(C.c_char_p(data), C.c_void_p), len(data), C.byref(info), C.byref(scan), _host_ptr(cuts), cuts.size)
+        if rc != _lib.DS_JPEG_MORE:
+            break
+        cuts = np.empty(int(scan.cut_count), np.int64)
+    if rc < 0:
+        raise ValueError("ds_jpeg_scan: bad argument")
+    return (info, scan, cuts[:int(scan.cut_count)]) if rc == 0 else None
+
+
+def jpeg_record_scan(rec, cuts):
+    """One call per record (the GIL is released for its duration): parse the payload and describe the JPEG's scan; `cuts`
+    is a C-contiguous int64 array for the cut positions.  Returns None when the payload is not taken, otherwise (status,
+    info, scan, fields tuple as example_parse) with status DS_OK (cuts[:scan.cut_count] are valid), _lib.DS_JPEG_UNSUPPORTED
+    or _lib.DS_JPEG_MORE (scan.cut_count entries are needed).  Positions count from the image's first byte."""
+    import numpy as np
+    text = np.zeros(JPEG_TEXT_CAPACITY, np.int64)
+    f, info, scan, status = _lib.ExampleFields(), _lib.JpegInfo(), _lib.JpegScanInfo(), C.c_int32(0)
+    rc = _lib.load().ds_jpeg_record_scan(C.cast(C.c_char_p(rec), C.c_void_p), len(rec), _host_ptr(text), text.size, C.byref(f),
+                                         C.byref(info), C.byref(scan), _host_ptr(cuts) if cuts.size else None, cuts.size,
+                                         C.byref(status))
+    if rc < 0:
+        raise ValueError("ds_jpeg_record_scan: bad argument")
+    if rc != 0:
+        return None
+    return status.value, info, scan, (f.image_offset, f.image_length, text, f.seq_len, f.label, f.post_id, f.day)
+
+
+def jpeg_restart_transcode(data, interval_mcus=0):
+    """ds_jpeg_restart_transcode: the stream re-encoded losslessly with a restart interval of `interval_mcus` MCUs (0 = one
+    MCU row) as bytes, or None when the stream is outside the supported set (the caller keeps the original)."""
+    import numpy as np
+    out = np.empty(len(data) + len(data) // 4 + 4096, np.uint8)
+    n = C.c_int64(0)
+    for _ in range(2):
+        rc = _lib.load().ds_jpeg_restart_transcode(C.cast(C.c_char_p(data), C.c_void_p), len(data), int(interval_mcus), _host_ptr(out),
+                                                   out.size, C.byref(n))
+        if rc != _lib.DS_JPEG_MORE:
+            break
+        out = np.empty(n.value, np.uint8)
+    if rc < 0:
+        raise ValueError("ds_jpeg_restart_transcode: bad argument (interval_mcus must be 0 .. 65535)")
+    return out[:n.value].tobytes() if rc == 0 else None
+
+
+def fill_jpeg_scan_tables(streams, coef_offsets, scan, images, segs):
+    """Lay the entropy-coded bytes of `streams` -- [(encoded bytes, info, scan info, cuts)] as jpeg_scan returns them --
+    back to back into `scan` (uint8) and describe them: images[i] (ops.jpeg_scan_desc_dtype(), coefficient storage at
+    coef_offsets[i]) and one segs record (ops.jpeg_segment_dtype()) per restart segment.  The arrays must be large enough.
+    Returns (scan bytes used, segments used)."""
+    import numpy as np
+    raw = images.view(np.uint8).reshape(images.size, -1)
+    pos = nseg = 0
+    for i, (data, info, si, cuts) in enumerate(streams):
+        begin, end, n = int(si.scan_begin), int(cuts[-1]), int(cuts.size)
+        scan[pos:pos + end - begin] = np.frombuffer(data, np.uint8, end - begin, begin)
+        images[i] = (coef_offsets[i], info.width, info.height, info.sampling, nseg, n, 0, 0, 0, 0)
+        raw[i, 32:224] = np.frombuffer(info.quant, np.uint8)
+        raw[i, 224:] = np.frombuffer(si, np.uint8, 6 * 272, 16)            # dc[3], ac[3]: the same layout in both structs
+        mw, mh = jpeg_mcus(info.height, info.width, info.sampling)
+        interval = info.restart_interval or mw * mh
+        s = segs[nseg:nseg + n]
+        s["end"] = cuts + (pos - begin)
+        s["begin"][0] = pos
+        s["begin"][1:] = s["end"][:-1] + 2
+        first = np.arange(n, dtype=np.int64) * interval
+        s["first_mcu"] = first
+        s["mcus"] = np.minimum(interval, mw * mh - first)
+        pos += end - begin
+        nseg += n
+    return pos, nseg
+
+
+def make_jpeg_scan_tables(streams, coef_offsets=None):
+    """fill_jpeg_scan_tables into new arrays: (scan uint8, images, segs, coefficient count); coefficient storage back to
+    back (starts rounded up to 8 int16) when coef_offsets is None."""
+    import numpy as np
+    if coef_offsets is None:
+        coef_offsets, cpos = [], 0
+        for _, info, _, _ in streams:
+            coef_offsets.append(cpos)
+            cpos = -(-(cpos + int(info.coef_count)) // 8) * 8
+    ncoef = max(o + int(st[1].coef_count) for o, st in zip(coef_offsets, streams))
+    scan = np.zeros(max(1, sum(int(c[-1]) - int(si.scan_begin) for _, _, si, c in streams)), np.uint8)
+    images = np.zeros(len(streams), jpeg_scan_desc_dtype())
+    segs = np.zeros(sum(c.size for _, _, _, c in streams), jpeg_segment_dtype())
+    fill_jpeg_scan_tables(streams, coef_offsets, scan, images, segs)
+    return scan, images, segs, ncoef
+
+
+def check_jpeg_scan_descs(images, segs, nscan, ncoef):
+    """Every image of the table has a known sampling class, its coefficients inside a buffer of `ncoef` int16 (offset a
+    multiple of 8, no two images on the same storage) and its segments inside `segs`; every segment has its bytes inside a
+    scan buffer of `nscan` bytes, and the segments of an image continue each other from MCU 0 to the image's last: raises
+    ValueError before anything is launched.  (What the bytes and the Huffman tables hold is the kernel's to judge: it
+    reports that per image.)"""
+    import numpy as np
+    images, segs = np.asarray(images), np.asarray(segs)
+    if images.dtype != jpeg_scan_desc_dtype() or images.ndim != 1 or images.size == 0:
+        raise ValueError("jpeg_entropy_decode: images must be a non-empty 1-D array of ops.jpeg_scan_desc_dtype()")
+    if segs.dtype != jpeg_segment_dtype() or segs.ndim != 1 or segs.size == 0:
+        raise ValueError("jpeg_entropy_decode: segs must be a non-empty 1-D array of ops.jpeg_segment_dtype()")
+    i64 = lambda a, k: a[k].astype(np.int64)
+    w, h, s = i64(images, "width"), i64(images, "height"), i64(images, "sampling")
+    if ((s < 0) | (s > 3) | (w < 1) | (h < 1) | (w > 65535) | (h > 65535)).any() or images["reserved"].any():
+        raise ValueError("jpeg_entropy_decode: bad image size or sampling class")
+    hs, vs = np.where((s == 1) | (s == 2), 2, 1), np.where(s == 2, 2, 1)
+    mcus = -(-w // (8 * hs)) * -(-h // (8 * vs))
+    need = mcus * np.where(s == 3, 1, hs * vs + 2) * 64
+    co = images["coef_offset"]
+    if ((co < 0) | (co % 8 != 0) | (co + need > int(ncoef))).any():
+        raise ValueError("jpeg_entropy_decode: coefficients outside the buffer of %d int16 (or an offset that is no multiple of 8)" % int(ncoef))
+    order = np.argsort(co, kind="stable")
+    if ((co + need)[order][:-1] > co[order][1:]).any():
+        raise ValueError("jpeg_entropy_decode: two images share coefficient storage")
+    first, count = i64(images, "first_segment"), i64(images, "segments")
+    if ((first < 0) | (count < 1) | (first + count > segs.size)).any():
+        raise ValueError("jpeg_entropy_decode: an image's segments lie outside the table of %d" % segs.size)
+    b, e, fm, m = segs["begin"], segs["end"], i64(segs, "first_mcu"), i64(segs, "mcus")
+    if ((b < 0) | (b > e) | (e > int(nscan)) | (fm < 0) | (m < 1)).any():
+        raise ValueError("jpeg_entropy_decode: a segment outside the scan buffer of %d bytes (or without MCUs)" % int(nscan))
+    total = int(count.sum())
+    starts = np.cumsum(count) - count
+    idx = np.repeat(first - starts, count) + np.arange(total)             # the segments of image 0, of image 1, ...
+    head = np.zeros(total, bool)
+    head[starts] = True
+    expect = np.where(head, 0, np.roll(fm[idx] + m[idx], 1))
+    last = starts + count - 1
+    if (fm[idx] != expect).any() or ((fm[idx] + m[idx])[last] != mcus).any():
+        raise ValueError("jpeg_entropy_decode: the segments of an image do not cover its MCUs in sequence")
+    return images, segs
+
+
+def jpeg_entropy_decode_segments_host(scan, images, segs, coef):
+    """ds_jpeg_entropy_decode_segments_host on NumPy arrays: decodes into coef (int16, in place) and returns the int32
+    status word of every image (0 = decoded)."""
+    import numpy as np
+    if scan.dtype != np.uint8 or coef.dtype != np.int16 or not scan.flags.c_contiguous or not coef.flags.c_contiguous:
+        raise ValueError("jpeg_entropy_decode_segments_host: scan uint8 and coef int16, both contiguous")
+    images, segs = check_jpeg_scan_descs(images, segs, scan.size, coef.size)
+    images, segs = np.ascontiguousarray(images), np.ascontiguousarray(segs)
+    status = np.full(images.size, -1, np.int32)
+    rc = _lib.load().ds_jpeg_entropy_decode_segments_host(_host_ptr(scan), scan.size, _host_ptr(images), images.size, _host_ptr(segs),
+                                                          segs.size, _host_ptr(coef), coef.size, _host_ptr(status))
+    if rc != 0:
+        raise ValueError("ds_jpeg_entropy_decode_segments_host: bad argument (%d)" % rc)
+    return status
+
+
+def jpeg_entropy_decode_device(scan, images, segs, coef, images_dev=None, segs_dev=None, status=None):
+    """ds_jpeg_entropy_decode_device: scan (device uint8: the entropy-coded bytes of the batch), images / segs (HOST arrays
+    of ops.jpeg_scan_desc_dtype() / jpeg_segment_dtype(), checked here against the buffer sizes; images_dev / segs_dev: the
+    same tables already on the device, uploaded here when None), coef (device int16, written in place: each image's own
+    range only).  Returns status (device int32, one word per image, 0 = decoded; allocated when None)."""
+    import numpy as np
+    if not (scan.is_cuda and coef.is_cuda):
+        raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
+    if scan.dtype != torch.uint8 or coef.dtype != torch.int16 or not scan.is_contiguous() or not coef.is_contiguous():
+        raise ValueError("jpeg_entropy_decode_device: scan must be a contiguous uint8 tensor and coef a contiguous int16 tensor")
+    images, segs = check_jpeg_scan_descs(images, segs, scan.numel(), coef.numel())
+    B, S = int(images.size), int(segs.size)
+    if images_dev is None:
+        images_dev = torch.from_numpy(np.ascontiguousarray(images).view(np.uint8)).to(coef.device)
+    if segs_dev is None:
+        segs_dev = torch.from_numpy(np.ascontiguousarray(segs).view(np.uint8)).to(coef.device)
+    for name, t, need in (("images_dev", images_dev, B * jpeg_scan_desc_dtype().itemsize), ("segs_dev", segs_dev, S * jpeg_segment_dtype().itemsize)):
+        if not t.is_cuda or not t.is_contiguous() or t.numel() * t.element_size() < need:
+            raise ValueError("jpeg_entropy_decode_device: %s is smaller than its table" % name)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=coef.device)
+    if status.dtype != torch.int32 or not status.is_cuda or not status.is_contiguous() or status.numel() < B:
+        raise ValueError("jpeg_entropy_decode_device: status must be a contiguous int32 device tensor, one word per image")
+    _lib.check(_lib.load().ds_jpeg_entropy_decode_device(_p(scan), scan.numel(), _p(images_dev), B, _p(segs_dev), S, _p(coef),
+                                                         coef.numel(), _p(status), _stream()), "ds_jpeg_entropy_decode_device")
+    return status[:B]

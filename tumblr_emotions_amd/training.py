@@ -144,7 +144,9 @@ class SyntheticInput:
     reference (im_text_rnn_model.py:291,602).  With config['synthetic'] the key is a ValueError: there is no JPEG to augment.
     config['jpeg_decode']: 'host' (default) or 'device' (compiled Huffman decode + ds_jpeg_reconstruct instead of PIL; the
     same batches bit for bit) -- honoured only with config['input_pipeline'] = 'device'; with the host pipeline the key is
-    a ValueError: that pipeline decodes with PIL."""
+    a ValueError: that pipeline decodes with PIL.
+    config['jpeg_entropy']: 'host' (default) or 'device' (the Huffman decode of restart-segmented JPEGs on the GPU too) --
+    honoured only with config['jpeg_decode'] = 'device'; with anything else the key is a ValueError."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
@@ -159,6 +161,11 @@ class SyntheticInput:
         if config.get("jpeg_decode", "host") == "device" and config.get("input_pipeline", "host") != "device":
             raise ValueError("config['jpeg_decode'] = 'device' needs config['input_pipeline'] = 'device': the host pipeline "
                              "decodes with PIL")
+        if config.get("jpeg_entropy", "host") not in ("host", "device"):
+            raise ValueError("config['jpeg_entropy'] must be 'host' or 'device', not %r" % (config["jpeg_entropy"],))
+        if config.get("jpeg_entropy", "host") == "device" and config.get("jpeg_decode", "host") != "device":
+            raise ValueError("config['jpeg_entropy'] = 'device' needs config['jpeg_decode'] = 'device': the coefficients go "
+                             "to ds_jpeg_reconstruct")
         ddir = config.get("dataset_dir")
         split = os.path.join(ddir or "", "photos", "train_valid_split.txt")
         if config.get("synthetic", False):
@@ -188,6 +195,7 @@ class SyntheticInput:
                                                      pipeline=self.config.get("input_pipeline", "host"),
                                                      workers=self.config.get("input_workers", 8),
                                                      jpeg_decode=self.config.get("jpeg_decode", "host"),
+                                                     jpeg_entropy=self.config.get("jpeg_entropy", "host"),
                                                      decode_images=with_images)     # text-only: no JPEG is decoded
             b = next(self._records)
         else:
