@@ -993,6 +993,35 @@ int ds_jpeg_entropy_decode_device(const uint8_t *scan, int64_t nscan, const ds_j
                                   const ds_jpeg_segment *segs, int64_t nsegs, int16_t *coef, int64_t ncoef, int32_t *status,
                                   void *stream);
 
+/* The decoded-image cache of the input pipeline: one launch assembles the ragged uint8 batch buffer that
+ * ds_preprocess_eval / ds_preprocess_train read (pack_ragged's layout: windows back to back, each start a multiple of
+ * 4 bytes, rows contiguous) from packed-RGB uint8 images that are resident on the device -- in the loader's arena, or in
+ * the batch's spill buffer for an image the arena had no room for. */
+typedef struct ds_gather_desc {
+    int64_t src_offset;        /* first byte of pixel (0,0) of the resident image in its source buffer                  */
+    int64_t out_offset;        /* first byte of the window in `out`; a multiple of 4                                    */
+    int32_t src;               /* 0 = arena, 1 = spill                                                                  */
+    int32_t pitch;             /* bytes per source row (= 3 * source width)                                             */
+    int32_t y0, x0;            /* window origin in pixels                                                               */
+    int32_t height, width;     /* window size in pixels (>= 1); height * width * 3 < 2^31                               */
+} ds_gather_desc;
+/* out[out_offset + (y * width + x) * 3 + c] = source[src_offset + (y0 + y) * pitch + (x0 + x) * 3 + c] for every image of
+ * the table.  Every destination byte of every window is stored exactly once and no other byte of `out` is written (the
+ * up-to-3 alignment bytes between windows keep their contents).  A record that does not fit -- an unknown src, src = 1
+ * with spill == NULL, a window that leaves its row (3 * (x0 + width) > pitch) or its source buffer, a destination range
+ * outside nout, a misaligned out_offset, a window of 2^31 bytes or more -- is re-checked in 64-bit arithmetic and its image
+ * is left without a single store; the other images are copied.  The caller validates the table on the host first
+ * (ops.check_gather_descs: it also refuses two windows that share output bytes, which the launch cannot see).
+ * spill may be NULL (nspill = 0) when no record names it.  One definition of the address arithmetic (csrc/gather_common.h)
+ * serves both functions.
+ * ds_ragged_gather: DEVICE pointers, arena / spill / out 16-byte aligned, batch <= 65535, one launch on `stream`.
+ * ds_ragged_gather_host: the CPU statement, plain C++ on HOST pointers of any alignment.  Both return DS_ERR_ARG for a
+ * null arena / desc / out, a negative size or batch < 1, before anything is written. */
+int ds_ragged_gather(const uint8_t *arena, int64_t narena, const uint8_t *spill, int64_t nspill, const ds_gather_desc *desc,
+                     int32_t batch, uint8_t *out, int64_t nout, void *stream);
+int ds_ragged_gather_host(const uint8_t *arena, int64_t narena, const uint8_t *spill, int64_t nspill,
+                          const ds_gather_desc *desc, int32_t batch, uint8_t *out, int64_t nout);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,13 @@ Writes a seeded dataset of 500 x 375 JPEGs (quality 90, smooth content) under DI
            jpeg_entropy='device', beside ITS yardstick -- jpeg_decode='device' alone on the same restart-marked files --
            in the same alternation; the growth of the files, and ds_jpeg_entropy_decode_device at B = 256 by device events
            with the bytes it reads against the coefficient bytes whose upload it replaces (--workers picks the worker counts)
+  cache    the decoded-image cache (cache='device', --cache-gb of arena) on the restart-marked files with jpeg_entropy='device',
+           eval chain and is_training=True, at the worker counts of --workers: pass 0 (a fresh loader's first epoch, arena
+           writes included) beside the first epoch of a fresh loader of its yardstick arm, then alternating windows of the
+           steady state (passes >= 1: every record a hit) and of the parent's three arms (device + PIL, jpeg_decode='device',
+           + jpeg_entropy='device' on the restart files); the feeder's host time per cached batch; ds_ragged_gather at
+           B = 256 by device events, launch by launch, on the eval windows and on sampled train windows, against the 2 %
+           budget of DESIGN.md 7.2.  Writes profiles/input_pipeline_cache.json as well.
 One JSON line per measurement on stdout; everything is merged into FILE (default DIR/input_pipeline.json)."""
 import argparse
 import concurrent.futures
@@ -344,6 +351,119 @@ def part_jpeg(ds, args, results):
          images_per_s_kernel_alone=round(B / us * 1e6, 1), step_ms=args.step_ms, share_of_step=round(us / 1e3 / args.step_ms, 4))
 
 
+def _first_epoch(make, epoch):
+    """images/s of a fresh loader's first `epoch` batches, from its construction to the end of the last batch's kernels."""
+    import torch
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    it = make()
+    for _ in range(epoch):
+        next(it)
+    torch.cuda.synchronize()
+    return it, B * epoch / (time.perf_counter() - t0)
+
+
+def part_cache(ds, args, results):
+    import torch
+    from tumblr_emotions_amd import input_pipeline as P
+    from tumblr_emotions_amd import ops
+    from tumblr_emotions_amd.image_model.im_model import load_batch_with_text
+    from tumblr_emotions_amd.preprocessing.inception_preprocessing import record_rng, sample_train_params
+    first = len(results)
+    epoch = ds.num_samples // B
+    ds_rst, _ = restart_dataset(ds, os.path.join(args.out, "dataset"))
+    nbytes = int(args.cache_gb * 1e9)
+    ent = dict(pipeline='device', jpeg_decode='device', jpeg_entropy='device')
+    for train in (False, True):
+        kw = dict(batch_size=B, height=OUT, width=OUT, max_token_id=V, num_classes=15, is_training=train)
+        for workers in [int(w) for w in args.workers.split(",")]:
+            pass0, yard0 = [], []
+            for _ in range(args.windows):              # pass 0: fresh loaders, the cache arm and its yardstick in turn
+                it, r = _first_epoch(lambda: load_batch_with_text(ds_rst, workers=workers, cache='device', cache_bytes=nbytes, **ent, **kw), epoch)
+                pass0.append(r)
+                it.close()
+                it, r = _first_epoch(lambda: load_batch_with_text(ds_rst, workers=workers, **ent, **kw), epoch)
+                yard0.append(r)
+                it.close()
+            arms = {"pil": load_batch_with_text(ds, pipeline='device', workers=workers, **kw),
+                    "jpeg": load_batch_with_text(ds, pipeline='device', workers=workers, jpeg_decode='device', **kw),
+                    "entropy": load_batch_with_text(ds_rst, workers=workers, **ent, **kw),
+                    "cache": load_batch_with_text(ds_rst, workers=workers, cache='device', cache_bytes=nbytes, **ent, **kw)}
+            for it in arms.values():
+                for _ in range(epoch + 2):
+                    next(it)
+            rates = {k: [] for k in arms}
+            for _ in range(args.windows):
+                for k, it in arms.items():
+                    rates[k].append(_window(it, args.seconds))
+            stats = arms["cache"].cache_stats()
+            for it in arms.values():
+                it.close()
+            best = max(("pil", "jpeg", "entropy"), key=lambda k: np.mean(rates[k]))
+            y, c = rates[best], rates["cache"]
+            emit(results, what="loader_cache", is_training=train, workers=workers, windows=args.windows, seconds=args.seconds,
+                 cache_gb=args.cache_gb, pass0_windows=[round(x, 1) for x in pass0], pass0_yardstick_windows=[round(x, 1) for x in yard0],
+                 pass0_images_per_s=round(float(np.mean(pass0)), 1), pass0_yardstick_images_per_s=round(float(np.mean(yard0)), 1),
+                 steady_windows=[round(x, 1) for x in c], steady_images_per_s=round(float(np.mean(c)), 1),
+                 **{"%s_windows" % k: [round(x, 1) for x in rates[k]] for k in ("pil", "jpeg", "entropy")},
+                 best_yardstick=best, best_yardstick_images_per_s=round(float(np.mean(y)), 1),
+                 best_yardstick_spread=round(float(max(y) - min(y)), 1), gain=round(float(np.mean(c) - np.mean(y)), 1),
+                 beats_best_yardstick_by_more_than_its_spread=bool(np.mean(c) - np.mean(y) > max(y) - min(y)),
+                 resident_step_samples_per_s=19400, passes_resident_step=bool(np.mean(c) > 19400), **stats)
+    # where a cached batch's host time goes: the feeder's work for 256 hits, no device in the loop
+    rng = np.random.RandomState(0)
+    ch, cw = P.crop_box(H, W)[2:]
+    for train in (False, True):
+        st = P._Staging(B, 50, torch.device("cuda"), True, train, False, False, True)
+        t0 = time.perf_counter()
+        for rep in range(20):
+            items = []
+            for i in range(B):
+                h, w = (H, W) if train else (ch, cw)
+                p, box = None, (0, 0, h, w)
+                if train:
+                    p = sample_train_params(h, w, record_rng(0, rep, i))
+                    box = (p.y0, p.x0, p.crop_h, p.crop_w)
+                items.append(P._CacheItem(i * (-(-h * w * 3 // 16) * 16), h, w, None, p, box))
+            P._pack_cached(items, OUT, OUT, st)
+        emit(results, what="cache_feeder_host_time", is_training=train, B=B,
+             ms_per_batch=round((time.perf_counter() - t0) / 20 * 1e3, 3))
+    # the kernel alone
+    for train in (False, True):
+        h, w = (H, W) if train else (ch, cw)
+        size = -(-h * w * 3 // 16) * 16
+        arena = torch.from_numpy(rng.randint(0, 256, B * size).astype(np.uint8)).cuda()
+        desc = np.zeros(B, ops.gather_desc_dtype())
+        pos = 0
+        for i in range(B):
+            box = (0, 0, h, w)
+            if train:
+                p = sample_train_params(h, w, record_rng(0, 0, i))
+                box = (p.y0, p.x0, p.crop_h, p.crop_w)
+            desc[i] = (i * size, pos, 0, 3 * w, box[0], box[1], box[2], box[3])
+            pos = -(-(pos + box[2] * box[3] * 3) // 4) * 4
+        out = torch.empty(pos, dtype=torch.uint8, device="cuda")
+        ddesc = torch.from_numpy(desc.view(np.uint8)).cuda()
+        for _ in range(5):
+            ops.ragged_gather(arena, None, desc, out, desc_dev=ddesc)
+        times = []
+        for _ in range(40):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ops.ragged_gather(arena, None, desc, out, desc_dev=ddesc)
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) * 1e3)
+        med = float(np.median(times))
+        emit(results, what="ds_ragged_gather", windows="train" if train else "eval", B=B, bytes_in_and_out=2 * pos,
+             us_median=round(med, 1), us_min=round(min(times), 1), us_max=round(max(times), 1),
+             gb_per_s=round(2 * pos / med / 1e3, 1), step_ms=args.step_ms, share_of_step=round(med / 1e3 / args.step_ms, 4),
+             budget_us=round(0.02 * args.step_ms * 1e3, 1), within_budget=bool(med <= 0.02 * args.step_ms * 1e3))
+    prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "input_pipeline_cache.json")
+    with open(prof, "w") as f:
+        json.dump(results[first:], f, indent=1)
+
+
 def kernel_stats(path, results):
     """Average duration of the preprocessing kernels from a rocprofv3 --kernel-trace --stats csv (Name, Calls, ..., AverageNs)."""
     with open(path) as f:
@@ -363,7 +483,8 @@ if __name__ == "__main__":
     ap.add_argument("--json", default=None)
     ap.add_argument("--step-ms", type=float, default=13.06)
     ap.add_argument("--kernel-stats", default=None)
-    ap.add_argument("--workers", default="1,2,4,8,16", help="worker counts of the jpeg part")
+    ap.add_argument("--workers", default="1,2,4,8,16", help="worker counts of the jpeg and cache parts")
+    ap.add_argument("--cache-gb", type=float, default=3.0, help="arena of the cache part (4096 images of 500 x 375: 2.3 GB)")
     ap.add_argument("parts", nargs="*", default=["loader", "train", "kernel"])
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
@@ -375,6 +496,6 @@ if __name__ == "__main__":
         ds = make_dataset(os.path.join(args.out, "dataset"), args.images)
         for p in args.parts:
             {"loader": part_loader, "train": part_train, "kernel": part_kernel, "kernel_train": part_kernel_train,
-             "augment": part_augment, "jpeg": part_jpeg}[p](ds, args, results)
+             "augment": part_augment, "jpeg": part_jpeg, "cache": part_cache}[p](ds, args, results)
     with open(path, "w") as f:
         json.dump(results, f, indent=1)

@@ -137,6 +137,12 @@ class JpegScanInfo(C.Structure):
     _fields_ = [("scan_begin", C.c_int64), ("cut_count", C.c_int64), ("dc", JpegHuff * 3), ("ac", JpegHuff * 3)]
 
 
+class GatherDesc(C.Structure):
+    """ds_gather_desc"""
+    _fields_ = [("src_offset", C.c_int64), ("out_offset", C.c_int64), ("src", C.c_int32), ("pitch", C.c_int32),
+                ("y0", C.c_int32), ("x0", C.c_int32), ("height", C.c_int32), ("width", C.c_int32)]
+
+
 class ExampleFields(C.Structure):
     """ds_example_fields"""
     _fields_ = [("image_offset", C.c_int64), ("image_length", C.c_int64), ("seq_len", C.c_int64), ("label", C.c_int64),
@@ -280,6 +286,8 @@ SIGNATURES = {
     "ds_jpeg_restart_transcode": (C.c_int, [_P, _i64, _i32, _P, _i64, C.POINTER(_i64)]),
     "ds_jpeg_entropy_decode_segments_host": (C.c_int, [_P, _i64, _P, _i32, _P, _i64, _P, _i64, _P]),
     "ds_jpeg_entropy_decode_device": (C.c_int, [_P, _i64, _P, _i32, _P, _i64, _P, _i64, _P, _P]),
+    "ds_ragged_gather": (C.c_int, [_P, _i64, _P, _i64, _P, _i32, _P, _i64, _P]),
+    "ds_ragged_gather_host": (C.c_int, [_P, _i64, _P, _i64, _P, _i32, _P, _i64]),
 }
 
 _lib = None

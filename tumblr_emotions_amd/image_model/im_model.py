@@ -86,7 +86,7 @@ def evaluate_image_model(checkpoint_dir, log_dir, mode, num_evals, *, config=Non
 def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False,
                          device="cuda", rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None,
                          pipeline='host', workers=8, prefetch=2, decode_images=True, jpeg_decode='host',
-                         jpeg_entropy='host'):
+                         jpeg_entropy='host', cache='none', cache_bytes=None):
     """Generator of training batches from a `datasets.convert_to_dataset.Dataset` -- the role of
     load_batch_with_text + tf.train.batch in the reference (im_model.py:78-116): decode the JPEG, apply the
     EVAL preprocessing (is_training=False is what every reference call site uses, :78,102), batch.  is_training=True:
@@ -108,7 +108,15 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
     bit, streams outside the baseline set fall back to PIL one by one, DeviceLoader.jpeg_fallbacks counts them).
     jpeg_entropy: 'host' (the Huffman decode in the workers) or 'device' (jpeg_decode='device' only, a ValueError otherwise:
     streams with restart markers -- datasets.convert_to_dataset.add_restart_markers writes them -- are Huffman-decoded by
-    ds_jpeg_entropy_decode_device, all others as with 'host'; the same batches bit for bit)."""
+    ds_jpeg_entropy_decode_device, all others as with 'host'; the same batches bit for bit).
+    cache: 'none' or 'device' (pipeline='device' only, a ValueError otherwise; needs an explicit positive cache_bytes):
+    every record is decoded once, its uint8 pixels stay in an arena of cache_bytes bytes of device memory, and from the
+    second pass on the batches are assembled from there by ds_ragged_gather -- the same batches bit for bit, no file read
+    for a resident record; what does not fit is decoded again on every pass.  DeviceLoader.cache_stats() reports."""
+    if cache not in ('none', 'device'):
+        raise ValueError("cache must be 'none' or 'device', not %r" % (cache,))
+    if cache == 'device' and pipeline != 'device':
+        raise ValueError("cache='device' needs pipeline='device': the arena feeds the device preprocessing")
     if jpeg_entropy not in ('host', 'device'):
         raise ValueError("jpeg_entropy must be 'host' or 'device', not %r" % (jpeg_entropy,))
     if jpeg_entropy == 'device' and jpeg_decode != 'device':
@@ -121,7 +129,7 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
         from ..input_pipeline import DeviceLoader
         return DeviceLoader(dataset, batch_size, shuffle, height, width, is_training, device, rank, world, seed, loop,
                             max_token_id, num_classes, workers=workers, prefetch=prefetch, decode_images=decode_images, jpeg_decode=jpeg_decode,
-                            jpeg_entropy=jpeg_entropy)
+                            jpeg_entropy=jpeg_entropy, cache=cache, cache_bytes=cache_bytes)
     if pipeline != 'host':
         raise ValueError("pipeline must be 'host' or 'device', not %r" % (pipeline,))
     return _host_batches(dataset, batch_size, shuffle, height, width, is_training, device, rank, world, seed, loop,

@@ -36,6 +36,18 @@ nor its upload exists on the host.  The feeder reads the per-image status words 
 does not, the feeder runs `prefetch` batches ahead) and decodes a flagged image with PIL from the bytes it still holds: a
 fallback like any other.  Every other image of the batch goes the way it goes with jpeg_entropy='host'.
 datasets.convert_to_dataset.add_restart_markers gives a converted dataset one restart interval per MCU row, losslessly.
+
+cache='device' (opt-in, with an explicit cache_bytes) keeps the decoded uint8 pixels of every record in one arena of device
+memory: a record -- (index of its file in dataset.data_sources, index in the file) -- is decoded once, the way the loader is
+configured, and its pixels are written INTO THE ARENA (an H2D copy for the PIL path; ds_jpeg_reconstruct writes there
+itself): the central crop, or with is_training=True the whole image, whose crop changes from pass to pass while the pixels
+do not.  Every image of a batch, hit or miss, is then moved into the ragged buffer by ONE ds_ragged_gather launch on the copy
+stream, and the preprocessing kernel runs as ever.  A record is resident from the moment the feeder takes it off the decode
+queue (its arena offset is reserved there; the write is enqueued with its batch, ahead of every gather that reads it).  The
+record stream opens a file only when it does not know its size yet or a record of this rank in it is not resident, so a fully
+cached pass opens nothing and submits nothing to the pool; a pass starts only when the one before it has been consumed, so what
+is resident is known.  Nothing is evicted: once an image finds no room, nothing more is inserted, and such records are decoded
+on every pass into the staging set's spill buffer, which the same gather reads.
 """
 import io
 import queue
@@ -166,17 +178,17 @@ class OrderedPool:
         self._threads = []
 
 
-def decode_record(rec, decode_image=True, train_key=None):
+def decode_record(rec, decode_image=True, train_key=None, whole=False):
     """One TFRecord payload -> (cropped uint8 image or None, text int64[50], seq_len, label, post_id, day): the work of
     Dataset.examples for one record plus central_crop (only the cropped region is ever uploaded).  train_key = (seed, pass,
     global record index): the crop is the one sample_train_params draws from record_rng(*train_key), and the first item
-    is (crop, TrainParams)."""
+    is (crop, TrainParams).  whole (cache='device' at train time): the uncropped image, nothing drawn."""
     from .datasets.convert_to_dataset import _POST_SIZE
     from .datasets.tfrecord import decode_example
     ex = decode_example(rec)
     img = None
     if decode_image:
-        img = decode_pixels(ex['image/encoded'][0], train_key)
+        img = decode_pixels(ex['image/encoded'][0], train_key, whole)
     text = np.zeros(_POST_SIZE, np.int64)
     t = ex.get('text', [])
     text[:len(t)] = t
@@ -184,10 +196,13 @@ def decode_record(rec, decode_image=True, train_key=None):
             int(ex.get('post_id', [0])[0]), int(ex.get('day', [0])[0]))
 
 
-def decode_pixels(data, train_key=None):
-    """The PIL decode of one encoded image and its crop: the central one, or (crop, TrainParams) for train_key."""
+def decode_pixels(data, train_key=None, whole=False):
+    """The PIL decode of one encoded image and its crop: the central one, or (crop, TrainParams) for train_key, or -- whole
+    -- no crop at all."""
     from PIL import Image
     img = np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))
+    if whole:
+        return np.ascontiguousarray(img)
     if train_key is None:
         y0, x0, ch, cw = crop_box(img.shape[0], img.shape[1])
         return np.ascontiguousarray(img[y0:y0 + ch, x0:x0 + cw])
@@ -244,10 +259,12 @@ def decode_jpeg_bytes(data, train_key=None):
     return _coefs(coef, info, train_key)
 
 
-def _coefs(coef, info, train_key):
+def _coefs(coef, info, train_key, whole=False):
     from . import ops
     h, w = int(info.height), int(info.width)
-    if train_key is None:
+    if whole:
+        box, p = (0, 0, h, w), None
+    elif train_key is None:
         box, p = crop_box(h, w), None
     else:
         from .preprocessing.inception_preprocessing import record_rng, sample_train_params
@@ -256,7 +273,7 @@ def _coefs(coef, info, train_key):
     return JpegCoefs(coef, h, w, int(info.sampling), ops.jpeg_quant(info), box, p)
 
 
-def decode_record_jpeg(rec, train_key=None):
+def decode_record_jpeg(rec, train_key=None, whole=False):
     """decode_record with the compiled path: one ds_jpeg_record_decode call (payload parse + probe + Huffman decode, no GIL);
     the first item is a JpegCoefs, or -- for a stream outside the supported set -- exactly decode_record's.  A payload the
     compiled reader does not take goes through decode_record whole."""
@@ -270,16 +287,16 @@ def decode_record_jpeg(rec, train_key=None):
         buf = np.empty(size, np.int16)
         r = ops.jpeg_record_decode(rec, buf)
     if r is None:
-        return decode_record(rec, True, train_key)
+        return decode_record(rec, True, train_key, whole)
     status, info, (off, length, text, seq_len, label, post_id, day) = r
     if status == 0:
-        img = _coefs(buf[:int(info.coef_count)], info, train_key)
+        img = _coefs(buf[:int(info.coef_count)], info, train_key, whole)
     else:
-        img = decode_pixels(rec[off:off + length], train_key)
+        img = decode_pixels(rec[off:off + length], train_key, whole)
     return img, text, int(seq_len), int(label), int(post_id), int(day)
 
 
-def decode_record_jpeg_scan(rec, train_key=None):
+def decode_record_jpeg_scan(rec, train_key=None, whole=False):
     """decode_record_jpeg under jpeg_entropy='device': one ds_jpeg_record_scan call (payload parse + marker parse, nothing
     decoded, no GIL); the first item is a JpegScan for an eligible stream, and exactly decode_record_jpeg's otherwise."""
     from . import _lib, ops
@@ -291,9 +308,9 @@ def decode_record_jpeg_scan(rec, train_key=None):
         cuts = np.empty(_worker.cuts, np.int64)
         r = ops.jpeg_record_scan(rec, cuts)
     if r is None or r[0] != 0 or not device_entropy_eligible(r[1]):
-        return decode_record_jpeg(rec, train_key)
+        return decode_record_jpeg(rec, train_key, whole)
     _, info, scan, (off, length, text, seq_len, label, post_id, day) = r
-    img = JpegScan(rec[off:off + length], info, scan, cuts[:int(scan.cut_count)], _coefs(None, info, train_key), train_key)
+    img = JpegScan(rec[off:off + length], info, scan, cuts[:int(scan.cut_count)], _coefs(None, info, train_key, whole), train_key)
     return img, text, int(seq_len), int(label), int(post_id), int(day)
 
 
@@ -360,7 +377,7 @@ class _Staging:
     """One pinned staging set: ragged image bytes + descriptor table + the int64 fields, with the device byte buffer and
     descriptor table they are uploaded into and the event of the last upload."""
 
-    def __init__(self, batch_size, post_size, device, cuda, train=False, jpeg=False, entropy=False):
+    def __init__(self, batch_size, post_size, device, cuda, train=False, jpeg=False, entropy=False, cache=False):
         import torch
         from . import ops
         preprocess_desc_dtype = ops.preprocess_train_desc_dtype if train else ops.preprocess_desc_dtype
@@ -388,6 +405,11 @@ class _Staging:
                 self.sdesc_dev = torch.empty(self.sdesc.numel(), dtype=torch.uint8, device=device)
                 self.status_dev = torch.empty(batch_size, dtype=torch.int32, device=device)
             self.reserve_scan(1 << 20, 1 << 12)
+        self.spill_dev = None
+        if cache:                 # cache='device': the ds_ragged_gather table; the spill buffer appears with the first spilled image
+            self.gdesc = self._host(batch_size * ops.gather_desc_dtype().itemsize, torch.uint8)
+            self.gdesc_np = self.gdesc.numpy().view(ops.gather_desc_dtype())
+            self.gdesc_dev = torch.empty(self.gdesc.numel(), dtype=torch.uint8, device=device)
 
     def _host(self, n, dtype):
         return self.torch.empty(n, dtype=dtype, pin_memory=self.cuda)
@@ -405,6 +427,11 @@ class _Staging:
             if self.cuda:
                 self.coef_dev = self.torch.empty(cap, dtype=self.torch.int16, device=self.device)
                 self.scratch_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device)
+
+    def reserve_spill(self, nbytes):
+        if nbytes and (self.spill_dev is None or self.spill_dev.numel() < nbytes):
+            cap = -(-int(nbytes * 1.25) // 4096) * 4096
+            self.spill_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device)
 
     def reserve_scan(self, nbytes, nseg):
         from . import ops
@@ -434,6 +461,7 @@ class _State:
         self.out = None
         self.thread = None
         self.pool = None
+        self.cache = None                      # cache='device': the _Cache (arena + index); dropped by close()
 
 
 def _put(state, item):
@@ -473,8 +501,262 @@ def _record_stream(dataset, shuffle, rng, rank, world, loop):
         yield _EPOCH
 
 
+# ---- cache='device': decoded images resident in HBM ----------------------------------------------------------------------------
+CACHE_ALIGN = 16                      # every image of the arena (and of a spill buffer) starts on a multiple of this
+
+
+def _round_up(n, m):
+    return -(-n // m) * m
+
+
+def source_has_miss(source, count, first_index, rank, world, cached):
+    """One source file of a pass: `count` records whose global indices start at first_index.  True when a record of this
+    rank (index % world == rank) is not in `cached`, a container of (source, record) keys: the file has to be opened."""
+    return any((first_index + r) % world == rank and (source, r) not in cached for r in range(count))
+
+
+def sources_to_open(counts, order, rank, world, cached):
+    """The plan of one pass.  counts[s]: the records of source s, None while unknown; order: the pass's (shuffled) sequence
+    of source indices; cached: the (source, record) keys that are resident.  Returns the sources that must be opened, in
+    pass order: those holding a record of this rank that is not resident -- none for a fully cached pass -- and, from the
+    first source of unknown size on, every source (the global indices behind it are unknown until it has been read)."""
+    out, first = [], 0
+    for k, s in enumerate(order):
+        if counts[s] is None:
+            return out + list(order[k:])
+        if source_has_miss(s, counts[s], first, rank, world, cached):
+            out.append(s)
+        first += counts[s]
+    return out
+
+
+class _Cache:
+    """The arena (one uint8 device tensor, a bump allocator, nothing is ever evicted or rewritten) and the host's index:
+    (source file, record in it) -> (arena offset, height, width, text, seq_len, label, post_id, day) of a record that
+    decoded and passed the max_token_id / num_classes checks."""
+
+    def __init__(self, nbytes, device):
+        import torch
+        self.arena = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        self.capacity, self.used, self.full = int(nbytes), 0, False
+        self.entries = {}
+        self.counts = {}                       # source -> records in the file, once it has been read to its end
+
+    def reserve(self, nbytes):
+        """The arena offset of a new image, or None: once an image has found no room nothing more is inserted."""
+        if self.full or self.used + nbytes > self.capacity:
+            self.full = True
+            return None
+        off = self.used
+        self.used = _round_up(off + nbytes, CACHE_ALIGN)
+        return off
+
+
+class _CacheItem:
+    """One image of a batch under cache='device'.  off: its arena offset, None = spilled (this batch's spill buffer);
+    h, w: the resident region (the central crop, at train time the whole image); fill: what still has to be written there
+    (a decoded array, JpegCoefs or JpegScan), None for a hit; box: the window ds_ragged_gather copies; p: its TrainParams."""
+    __slots__ = ("off", "h", "w", "fill", "p", "box", "hit")
+
+    def __init__(self, off, h, w, fill, p, box):
+        self.off, self.h, self.w, self.fill, self.p, self.box, self.hit = off, h, w, fill, p, box, fill is None
+
+
+def _cached_record_stream(dataset, shuffle, rng, rank, world, loop, cache):
+    """_record_stream under cache='device': (pass number, global index, (source, record) key, raw record or None), the
+    same records in the same order with the same draws.  A source whose size is known and whose records of this rank are
+    all resident is not opened: its records are counted off instead; a resident record of an opened file carries None."""
+    from .datasets.tfrecord import read_records
+    index = {}
+    for i, path in enumerate(dataset.data_sources):
+        index.setdefault(path, i)
+    pass_no = -1
+    while True:
+        pass_no += 1
+        sources = list(dataset.data_sources)
+        if shuffle:
+            rng.shuffle(sources)
+        idx, n = -1, 0
+        for path in sources:
+            s = index[path]
+            count = cache.counts.get(s)
+            if count is not None and not source_has_miss(s, count, idx + 1, rank, world, cache.entries):
+                for r in range(count):
+                    idx += 1
+                    if idx % world == rank:
+                        n += 1
+                        yield pass_no, idx, (s, r), None
+                continue
+            r = -1
+            for rec in read_records(path):
+                idx += 1
+                r += 1
+                if idx % world != rank:
+                    continue
+                n += 1
+                yield pass_no, idx, (s, r), None if (s, r) in cache.entries else rec
+            cache.counts[s] = r + 1
+        if not loop or n == 0:
+            return
+        yield _EPOCH
+
+
+def _check_record(text, label, max_token_id, num_classes):
+    if max_token_id is not None and int(np.max(text)) > max_token_id:
+        raise ValueError("token id %d in the dataset exceeds the embedding table (%d rows + <ukn>): the "
+                         "dataset was converted with a different vocabulary" % (int(np.max(text)), max_token_id))
+    if num_classes is not None and not 0 <= label < num_classes:
+        raise ValueError("label %d outside [0, %d)" % (label, num_classes))
+
+
+def _cache_pop(cache, entry, train, seed, max_token_id, num_classes):
+    """The next record of the stream under cache='device': a hit comes from the index; a miss is awaited, checked and given
+    its place in the arena (it is resident from here on: its pixels are written by the batch it belongs to, ahead of every
+    gather that reads them on the one copy stream).  A record that raises is never inserted.  Returns the feeder's tuple,
+    its first item a _CacheItem."""
+    slot, pass_no, idx, key = entry
+    e = cache.entries.get(key)
+    fill = None
+    if e is None:
+        fill, text, seq_len, label, post_id, day = slot.result()
+        _check_record(text, label, max_token_id, num_classes)
+        h, w = (fill.box[2], fill.box[3]) if isinstance(fill, (JpegCoefs, JpegScan)) else fill.shape[:2]
+        off = cache.reserve(h * w * 3)
+        if off is not None:
+            cache.entries[key] = (off, h, w, text, seq_len, label, post_id, day)
+    else:
+        off, h, w, text, seq_len, label, post_id, day = e
+    p, box = None, (0, 0, h, w)
+    if train:                                      # the host generator's draws: they need the image's size only
+        from .preprocessing.inception_preprocessing import record_rng, sample_train_params
+        p = sample_train_params(h, w, record_rng(seed, pass_no, idx))
+        box = (p.y0, p.x0, p.crop_h, p.crop_w)
+    return _CacheItem(off, h, w, fill, p, box), text, seq_len, label, post_id, day
+
+
+def _pack_cached(items, out_h, out_w, st):
+    """The host half of a batch under cache='device' (items in output-slot order): the ds_ragged_gather table and the
+    preprocessing descriptors of ALL images (st.gdesc_np, st.desc_np; the ragged layout is pack_ragged's), and for the
+    misses what puts their pixels where the gather reads them -- decoded arrays into pinned staging (st.bytes), coefficients
+    and ds_jpeg_desc rows as pack_ragged_jpeg lays them out, the rows that write the arena in front of those that write the
+    spill buffer.  Returns (ragged bytes, int16 used, arena rows, rows, [(src, destination offset, staging offset, size)
+    of every staged array], (first, one past the last) arena byte the rows write, staging offset free for fallbacks)."""
+    pos = spos = stage = room = 0
+    pix, rows_of = [], ([], [])
+    for i, it in enumerate(items):
+        size = it.h * it.w * 3
+        if it.off is None:
+            src, soff = 1, spos
+            spos += _round_up(size, CACHE_ALIGN)
+        else:
+            src, soff = 0, it.off
+        y0, x0, wh, ww = it.box
+        st.gdesc_np[i] = (soff, pos, src, 3 * it.w, y0, x0, wh, ww)
+        st.desc_np[i] = _desc_record(pos, wh, ww, out_h, out_w, it.p)
+        pos = _round_up(pos + wh * ww * 3, 4)
+        f, it.fill = it.fill, None
+        if isinstance(f, (JpegCoefs, JpegScan)):
+            rows_of[src].append((soff, f))
+            if isinstance(f, JpegScan):
+                room += _round_up(size, CACHE_ALIGN)           # for the PIL decode of an image the kernel flags
+        elif f is not None:
+            if f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8 or f.shape[0] < 1 or f.shape[1] < 1:
+                raise ValueError("input cache: images must be non-empty uint8 [h, w, 3] arrays")
+            pix.append((src, soff, stage, f))
+            stage += _round_up(size, CACHE_ALIGN)
+    st.reserve(max(pos, stage + room))
+    st.reserve_spill(spos)
+    out = st.bytes.numpy()
+    copies = []
+    for src, doff, sp, f in pix:
+        out[sp:sp + f.size].reshape(f.shape)[...] = f
+        if copies and copies[-1][0] == src and doff - copies[-1][1] == sp - copies[-1][2] == _round_up(copies[-1][3], CACHE_ALIGN):
+            copies[-1] = (src, copies[-1][1], copies[-1][2], doff - copies[-1][1] + f.size)     # neighbours in both buffers: one copy
+        else:
+            copies.append((src, doff, sp, f.size))
+    rows, na = rows_of[0] + rows_of[1], len(rows_of[0])
+    abase = min((off for off, _ in rows_of[0]), default=0)
+    aend = max((off + f.box[2] * f.box[3] * 3 for off, f in rows_of[0]), default=0)
+    cpos = nscan = nseg = 0
+    for _, f in rows:
+        if isinstance(f, JpegCoefs):
+            cpos = _round_up(cpos, 8) + f.coef.size
+        else:
+            cpos = _round_up(cpos, 8) + f.coef_count
+            nscan += int(f.cuts[-1]) - int(f.scan.scan_begin)
+            nseg += f.cuts.size
+    st.scans, st.coef_copies = [], []
+    if rows:
+        st.reserve_coef(cpos)
+        if nseg:
+            st.reserve_scan(nscan, nseg)
+        coef, cpos = st.coef.numpy(), 0
+        for nj, (doff, f) in enumerate(rows):
+            cpos = _round_up(cpos, 8)
+            if isinstance(f, JpegCoefs):
+                size = f.coef.size
+                coef[cpos:cpos + size] = f.coef
+                st.coef_copies.append((cpos, size))
+            else:                                  # (descriptor row, item, (src, destination offset), first coefficient)
+                size = f.coef_count
+                st.scans.append((nj, f, (0 if nj < na else 1, doff), cpos))
+            st.jdesc_np[nj] = (cpos, doff - abase if nj < na else doff, f.width, f.height, f.sampling, f.box[0], f.box[1],
+                               f.box[2], f.box[3], 0, f.quant)
+            cpos += size
+        if st.scans:
+            from . import ops
+            ops.fill_jpeg_scan_tables([(f.data, f.info, f.scan, f.cuts) for _, f, _, _ in st.scans],
+                                      [c for _, _, _, c in st.scans], st.scan.numpy(), st.sdesc_np, st.segs_np)
+            st.scan_used, st.segs_used = nscan, nseg
+    return pos, cpos, na, len(rows), copies, (abase, aend), stage
+
+
+def _fill_cached(st, cache, plan, stream, train, batch_size):
+    """The device half, on the copy stream (the current one): the misses' pixels into the arena -- or, for a spilled image,
+    into this staging set's spill buffer -- by H2D copies and ds_jpeg_reconstruct, then ONE ds_ragged_gather that moves
+    every image's window, hit or miss, into the ragged buffer the preprocessing kernel reads.  Returns (images of the
+    batch PIL decoded because the Huffman kernel flagged them, images whose coefficients the device produced)."""
+    from . import ops
+    used, ncoef, na, nj, copies, (abase, aend), free = plan
+    arena = cache.arena
+    for src, doff, sp, size in copies:
+        (st.spill_dev if src else arena)[doff:doff + size].copy_(st.bytes[sp:sp + size], non_blocking=True)
+    flagged = on_device = 0
+    if st.scans:
+        bad = _device_entropy_launch(st, stream, ncoef)
+        keep = np.ones(nj, bool)
+        out = st.bytes.numpy()
+        for k in bad:
+            row, it, (src, doff), _ = st.scans[k]
+            im = decode_pixels(it.data, None, whole=train)             # the resident region, as a miss of the PIL path has it
+            if im.shape[:2] != (it.box[2], it.box[3]):
+                raise ValueError("a JPEG decodes to another size than its header states")
+            out[free:free + im.size].reshape(im.shape)[...] = im
+            (st.spill_dev if src else arena)[doff:doff + im.size].copy_(st.bytes[free:free + im.size], non_blocking=True)
+            free += _round_up(im.size, CACHE_ALIGN)
+            keep[row] = False
+        flagged, on_device = int(bad.size), len(st.scans) - int(bad.size)
+        if flagged:
+            st.jdesc_np[:int(keep.sum())] = st.jdesc_np[:nj][keep]
+            na, nj = int(keep[:na].sum()), int(keep.sum())
+    elif nj:
+        st.coef_dev[:ncoef].copy_(st.coef[:ncoef], non_blocking=True)
+    if nj:
+        st.jdesc_dev.copy_(st.jdesc, non_blocking=True)
+        item = ops.jpeg_desc_dtype().itemsize
+        if na:
+            ops.jpeg_reconstruct(st.coef_dev[:ncoef], st.jdesc_np[:na], arena[abase:aend], scratch=st.scratch_dev,
+                                 desc_dev=st.jdesc_dev)
+        if nj > na:
+            ops.jpeg_reconstruct(st.coef_dev[:ncoef], st.jdesc_np[na:nj], st.spill_dev, scratch=st.scratch_dev,
+                                 desc_dev=st.jdesc_dev[na * item:])
+    st.gdesc_dev.copy_(st.gdesc, non_blocking=True)
+    ops.ragged_gather(arena, st.spill_dev, st.gdesc_np[:batch_size], st.bytes_dev[:used], desc_dev=st.gdesc_dev)
+    return flagged, on_device
+
+
 def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, world, seed, loop, max_token_id,
-            num_classes, decode_images, prefetch, inflight, train=False, jpeg=False, entropy=False):
+            num_classes, decode_images, prefetch, inflight, train=False, jpeg=False, entropy=False, cache_bytes=None):
     import collections
     try:
         import torch
@@ -491,7 +773,12 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
         rng = np.random.RandomState(seed)
         stagings, turn = [], 0
         pending = collections.deque()
-        records = _record_stream(dataset, shuffle, rng, rank, world, loop)
+        cache = None
+        if cache_bytes and decode_images:          # cache='device': the arena lives as long as the feeder state
+            cache = state.cache = _Cache(cache_bytes, dev)
+            records = _cached_record_stream(dataset, shuffle, rng, rank, world, loop, cache)
+        else:
+            records = _record_stream(dataset, shuffle, rng, rank, world, loop)
         exhausted = boundary = False
         buf = []
         while not state.stop.is_set():
@@ -499,8 +786,9 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             # are the batch permutations (made below as batches complete); the next draw after the last record of a pass is
             # the next pass's source shuffle.  So with shuffling on, the next pass starts only once every record of the
             # finished one has been consumed (a short bubble per epoch); without shuffling nothing is drawn at all.
+            # With the cache a pass always waits for the one before it: what is resident is known once its records are in.
             while not exhausted and len(pending) < inflight:
-                if boundary and shuffle and pending:
+                if boundary and (shuffle or cache is not None) and pending:
                     break
                 boundary = False
                 rec = next(records, None)
@@ -508,6 +796,14 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                     exhausted = True
                 elif rec is _EPOCH:
                     boundary = True
+                elif cache is not None:
+                    pass_no, idx, ckey, payload = rec
+                    slot = None                    # a hit: no file was read for it, nothing goes to the pool
+                    if payload is not None and jpeg:
+                        slot = state.pool.submit(decode_record_jpeg_scan if entropy else decode_record_jpeg, payload, None, train)
+                    elif payload is not None:
+                        slot = state.pool.submit(decode_record, payload, True, None, train)
+                    pending.append((slot, pass_no, idx, ckey))
                 else:
                     pass_no, idx, payload = rec
                     key = (seed, pass_no, idx) if train and decode_images else None
@@ -517,19 +813,19 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                         pending.append(state.pool.submit(decode_record, payload, decode_images, key))
             if not pending:
                 break
-            img, text, seq_len, label, post_id, day = pending.popleft().result()
-            if max_token_id is not None and int(np.max(text)) > max_token_id:
-                raise ValueError("token id %d in the dataset exceeds the embedding table (%d rows + <ukn>): the "
-                                 "dataset was converted with a different vocabulary" % (int(np.max(text)), max_token_id))
-            if num_classes is not None and not 0 <= label < num_classes:
-                raise ValueError("label %d outside [0, %d)" % (label, num_classes))
+            if cache is not None:
+                img, text, seq_len, label, post_id, day = _cache_pop(cache, pending.popleft(), train, seed, max_token_id, num_classes)
+            else:
+                img, text, seq_len, label, post_id, day = pending.popleft().result()
+                _check_record(text, label, max_token_id, num_classes)
             buf.append((img, text, seq_len, label, post_id, day))
             if len(buf) < batch_size:
                 continue
             order = rng.permutation(batch_size) if shuffle else np.arange(batch_size)
             if post_size is None:
                 post_size = len(buf[0][1])
-                stagings = [_Staging(batch_size, post_size, dev, cuda, train and decode_images, jpeg and decode_images, entropy)
+                stagings = [_Staging(batch_size, post_size, dev, cuda, train and decode_images, jpeg and decode_images, entropy,
+                                     cache is not None)
                             for _ in range(max(2, prefetch + 1))]
             st = stagings[turn]
             turn = (turn + 1) % len(stagings)
@@ -541,7 +837,17 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                 ints[nt + k * batch_size:nt + (k + 1) * batch_size] = np.asarray([b[2 + k] for b in buf], np.int64)[order]
             used = ncoef = njpeg = 0
             copies = []
-            if decode_images and jpeg:
+            plan = cstats = None
+            if cache is not None:
+                items = [buf[j][0] for j in order]
+                fresh = [it for it in items if not it.hit]
+                kept = [it for it in fresh if it.off is not None]
+                cstats = (len(items) - len(fresh), len(fresh), len(fresh) - len(kept), len(kept),
+                          max((it.off + it.h * it.w * 3 for it in kept), default=0), sum(isinstance(it.fill, np.ndarray) for it in fresh))
+                plan = _pack_cached(items, height, width, st)
+                used = plan[0]
+                (ops.check_preprocess_train_descs if train else ops.check_preprocess_descs)(st.desc_np[:batch_size], used)
+            elif decode_images and jpeg:
                 used, ncoef, njpeg, copies = pack_ragged_jpeg([buf[j][0] for j in order], height, width, st, train)
                 (ops.check_preprocess_train_descs if train else ops.check_preprocess_descs)(st.desc_np[:batch_size], used)
                 if njpeg:
@@ -559,7 +865,9 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             flagged = on_device = 0
             if cuda:
                 with torch.cuda.stream(stream):
-                    if decode_images and jpeg:
+                    if cache is not None:
+                        flagged, on_device = _fill_cached(st, cache, plan, stream, train, batch_size)
+                    elif decode_images and jpeg:
                         for off, size in copies:                 # the images PIL decoded: their slots only
                             st.bytes_dev[off:off + size].copy_(st.bytes[off:off + size], non_blocking=True)
                         if st.scans:
@@ -586,18 +894,18 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             out["texts"] = ints_dev[:nt].view(batch_size, post_size)
             for k, (name, _) in enumerate(_FIELDS):
                 out[name] = ints_dev[nt + k * batch_size:nt + (k + 1) * batch_size]
-            if not _put(state, ("batch", out, event, stream, len(copies) + flagged if jpeg else 0, on_device)):
+            fallbacks = (cstats[5] if cache is not None else len(copies)) + flagged if jpeg else 0
+            if not _put(state, ("batch", out, event, stream, fallbacks, on_device, cstats)):
                 return
         _put(state, ("end",))
     except BaseException as e:
         _put(state, ("error", e))
 
 
-def _device_entropy(st, stream, ncoef, njpeg, train):
+def _device_entropy_launch(st, stream, ncoef):
     """The Huffman decode of the batch's JpegScan images on the copy stream (the current one), into their ranges of
     st.coef_dev; host-decoded images' coefficients are uploaded into theirs.  The status words come back to pinned memory
-    and the FEEDER waits for them; a flagged image is decoded with PIL from the bytes it holds, its crop uploaded into its
-    slot of the ragged buffer and its row dropped from the reconstruct table.  Returns (rows left in st.jdesc_np, flagged)."""
+    and the FEEDER waits for them.  Returns the indices into st.scans of the images the kernel flagged."""
     import torch
     from . import ops
     for off, size in st.coef_copies:
@@ -613,7 +921,14 @@ def _device_entropy(st, stream, ncoef, njpeg, train):
     done = torch.cuda.Event()
     done.record(stream)
     done.synchronize()
-    bad = np.nonzero(st.status.numpy()[:ns])[0]
+    return np.nonzero(st.status.numpy()[:ns])[0]
+
+
+def _device_entropy(st, stream, ncoef, njpeg, train):
+    """_device_entropy_launch for a batch without the cache: a flagged image is decoded with PIL from the bytes it holds,
+    its crop uploaded into its slot of the ragged buffer and its row dropped from the reconstruct table.  Returns (rows
+    left in st.jdesc_np, flagged)."""
+    bad = _device_entropy_launch(st, stream, ncoef)
     if not bad.size:
         return njpeg, 0
     keep = np.ones(njpeg, bool)
@@ -640,6 +955,7 @@ def _shutdown(state):
         state.thread.join()
     if state.pool is not None:
         state.pool.close()
+    state.cache = None
     try:                                       # drop queued batches (device tensors, events)
         while True:
             state.out.get_nowait()
@@ -657,11 +973,19 @@ class DeviceLoader:
     decode_images=False); jpeg_fallbacks counts the images of the batches handed out so far that took the PIL path.
     jpeg_entropy='device' (with jpeg_decode='device' only, a ValueError otherwise): the Huffman decode of restart-segmented
     streams in ds_jpeg_entropy_decode_device as well; jpeg_device_entropy counts the images whose coefficients the device
-    produced, and an image the kernel flags is a fallback."""
+    produced, and an image the kernel flags is a fallback.  cache='device' with cache_bytes (a positive number of bytes, no
+    default; a ValueError without it, and on a device that is not CUDA/HIP unless decode_images=False, where the switch does
+    nothing): decoded images stay in an arena of that size and later passes are assembled from it by ds_ragged_gather --
+    the same batches; cache_stats() reports, close() frees the arena."""
 
     def __init__(self, dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False, device="cuda",
                  rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None, workers=8, prefetch=2,
-                 decode_images=True, jpeg_decode='host', jpeg_entropy='host'):
+                 decode_images=True, jpeg_decode='host', jpeg_entropy='host', cache='none', cache_bytes=None):
+        if cache not in ('none', 'device'):
+            raise ValueError("cache must be 'none' or 'device', not %r" % (cache,))
+        if cache == 'device' and (cache_bytes is None or isinstance(cache_bytes, bool) or int(cache_bytes) < 1):
+            raise ValueError("cache='device' needs an explicit positive cache_bytes: the decoded size of a dataset is not "
+                             "known before it is decoded, and no share of the device memory is taken silently")
         if jpeg_decode not in ('host', 'device'):
             raise ValueError("jpeg_decode must be 'host' or 'device', not %r" % (jpeg_decode,))
         if jpeg_entropy not in ('host', 'device'):
@@ -671,6 +995,9 @@ class DeviceLoader:
         self.jpeg_decode, self.jpeg_entropy = jpeg_decode, jpeg_entropy
         self.jpeg_fallbacks = 0
         self.jpeg_device_entropy = 0
+        self.cache = cache
+        self._cache_stats = {'hits': 0, 'misses': 0, 'spilled': 0, 'bytes_used': 0, 'records': 0,
+                             'bytes_capacity': int(cache_bytes) if cache == 'device' and decode_images else 0}
         if batch_size < 1 or height < 1 or width < 1 or world < 1 or not 0 <= rank < world:
             raise ValueError("DeviceLoader: bad batch_size / height / width / rank / world")
         self.workers = clamp_workers(workers)
@@ -681,6 +1008,8 @@ class DeviceLoader:
         device = torch.device(device)
         if device.type == "cuda" and device.index is None and torch.cuda.is_available():
             device = torch.device("cuda", torch.cuda.current_device())      # the caller's current device, not the feeder thread's
+        if cache == 'device' and self.decode_images and device.type != "cuda":
+            raise ValueError("cache='device' needs a CUDA/HIP device: the arena is device memory")
         st = self._state = _State()
         st.out = queue.Queue(maxsize=self.prefetch)
         st.pool = OrderedPool(self.workers)
@@ -689,7 +1018,8 @@ class DeviceLoader:
                                      args=(st, dataset, int(batch_size), bool(shuffle), int(height), int(width), device, rank,
                                            world, seed, bool(loop), max_token_id, num_classes, self.decode_images,
                                            self.prefetch, inflight, bool(is_training), jpeg_decode == 'device',
-                                           jpeg_entropy == 'device'))
+                                           jpeg_entropy == 'device',
+                                           int(cache_bytes) if cache == 'device' and self.decode_images else None))
         self._finalizer = weakref.finalize(self, _shutdown, st)
         st.thread.start()
 
@@ -701,9 +1031,16 @@ class DeviceLoader:
             raise StopIteration
         item = self._state.out.get()
         if item[0] == "batch":
-            _, out, event, stream, fallbacks, on_device = item
+            _, out, event, stream, fallbacks, on_device, cstats = item
             self.jpeg_fallbacks += fallbacks
             self.jpeg_device_entropy += on_device
+            if cstats is not None:
+                c = self._cache_stats
+                c['hits'] += cstats[0]
+                c['misses'] += cstats[1]
+                c['spilled'] += cstats[2]
+                c['records'] += cstats[3]
+                c['bytes_used'] = max(c['bytes_used'], cstats[4])
             if event is not None:
                 import torch
                 cur = torch.cuda.current_stream(stream.device)
@@ -719,6 +1056,12 @@ class DeviceLoader:
     def close(self):
         self._done = True
         self._finalizer()
+
+    def cache_stats(self):
+        """The decoded-image cache over the batches handed out so far: images served from the arena (hits), images decoded
+        (misses), of those the ones that found no room and went through a spill buffer (spilled), the arena bytes in use
+        and its size, and the records resident.  All zero with cache='none' (or decode_images=False)."""
+        return dict(self._cache_stats)
 
     def threads(self):
         """The loader's live threads (feeder + decode workers); empty after close()."""

@@ -1412,3 +1412,82 @@ def jpeg_entropy_decode_device(scan, images, segs, coef, images_dev=None, segs_d
     _lib.check(_lib.load().ds_jpeg_entropy_decode_device(_p(scan), scan.numel(), _p(images_dev), B, _p(segs_dev), S, _p(coef),
                                                          coef.numel(), _p(status), _stream()), "ds_jpeg_entropy_decode_device")
     return status[:B]
+
+
+# ---- the decoded-image cache: batch assembly from resident images (ds_ragged_gather) -------------------------------------------
+def gather_desc_dtype():
+    """NumPy view of ds_gather_desc (40 bytes): one record per image of a ds_ragged_gather launch."""
+    import numpy as np
+    return np.dtype([("src_offset", np.int64), ("out_offset", np.int64), ("src", np.int32), ("pitch", np.int32),
+                     ("y0", np.int32), ("x0", np.int32), ("height", np.int32), ("width", np.int32)], align=True)
+
+
+def check_gather_descs(desc, narena, nspill, nout):
+    """Every record of the table names a source that exists (0 = arena of `narena` bytes, 1 = spill of `nspill` bytes; pass
+    nspill = 0 when there is no spill buffer), its window lies inside its source row and its source buffer, its
+    destination range lies inside `nout` bytes at a multiple of 4, and no two windows share output bytes: raises
+    ValueError before anything is launched (the launch skips a record that does not fit and cannot see an overlap)."""
+    import numpy as np
+    desc = np.asarray(desc)
+    if desc.dtype != gather_desc_dtype() or desc.ndim != 1 or desc.size == 0:
+        raise ValueError("ragged_gather: descriptors must be a non-empty 1-D array of ops.gather_desc_dtype()")
+    i64 = lambda k: desc[k].astype(np.int64)
+    src, pitch, y0, x0, h, w = i64("src"), i64("pitch"), i64("y0"), i64("x0"), i64("height"), i64("width")
+    so, oo = desc["src_offset"], desc["out_offset"]
+    if ((src != 0) & (src != 1)).any():
+        raise ValueError("ragged_gather: src must be 0 (arena) or 1 (spill)")
+    n = h * w * 3
+    if ((h < 1) | (w < 1) | (y0 < 0) | (x0 < 0) | (pitch < 1) | (n > 0x7fffffff)).any():
+        raise ValueError("ragged_gather: a window must be at least 1 x 1 pixels, at a non-negative origin, below 2**31 bytes")
+    nsrc = np.where(src == 1, int(nspill), int(narena))
+    last = (y0 + h - 1) * pitch + (x0 + w) * 3
+    if (((x0 + w) * 3 > pitch) | (so < 0) | (so > nsrc) | (last > nsrc - so)).any():
+        i = int(np.flatnonzero(((x0 + w) * 3 > pitch) | (so < 0) | (so > nsrc) | (last > nsrc - so))[0])
+        raise ValueError("ragged_gather: the window of record %d leaves its source (%s of %d bytes)"
+                         % (i, "spill" if src[i] else "arena", int(nsrc[i])))
+    if ((oo < 0) | (oo + n > int(nout))).any():
+        raise ValueError("ragged_gather: a window outside the output buffer of %d bytes" % int(nout))
+    if (oo % 4 != 0).any():
+        raise ValueError("ragged_gather: out_offset must be a multiple of 4")
+    order = np.argsort(oo, kind="stable")
+    if ((oo + n)[order][:-1] > oo[order][1:]).any():
+        raise ValueError("ragged_gather: two windows overlap in the output buffer")
+    return desc
+
+
+def ragged_gather_host(arena, spill, desc, out):
+    """ds_ragged_gather_host on NumPy arrays: arena / spill (uint8; spill may be None) -> the windows of `desc` in out
+    (uint8, in place).  Returns out."""
+    import numpy as np
+    for a in (arena, spill, out):
+        if a is not None and (a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous):
+            raise ValueError("ragged_gather_host: arena, spill and out must be contiguous 1-D uint8 arrays")
+    desc = np.ascontiguousarray(check_gather_descs(desc, arena.size, 0 if spill is None else spill.size, out.size))
+    rc = _lib.load().ds_ragged_gather_host(_host_ptr(arena), arena.size, None if spill is None else _host_ptr(spill),
+                                           0 if spill is None else spill.size, _host_ptr(desc), desc.size, _host_ptr(out), out.size)
+    if rc != 0:
+        raise ValueError("ds_ragged_gather_host: bad argument (%d)" % rc)
+    return out
+
+
+def ragged_gather(arena, spill, desc, out, desc_dev=None):
+    """ds_ragged_gather: arena / spill (device uint8; spill may be None when no record names it), desc (HOST array of
+    ops.gather_desc_dtype(), checked here), out (device uint8, written in place: only the windows' bytes), desc_dev (the
+    table already on the device; uploaded here when None).  Returns out."""
+    import numpy as np
+    for t in (arena, spill, out):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("ragged_gather: arena, spill and out must be contiguous uint8 tensors")
+    desc = check_gather_descs(desc, arena.numel(), 0 if spill is None else spill.numel(), out.numel())
+    B = int(desc.size)
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8)).to(out.device)
+    if not desc_dev.is_cuda or not desc_dev.is_contiguous() or desc_dev.numel() * desc_dev.element_size() < B * gather_desc_dtype().itemsize:
+        raise ValueError("ragged_gather: desc_dev is smaller than the descriptor table")
+    _lib.check(_lib.load().ds_ragged_gather(_p(arena), arena.numel(), _p(spill), 0 if spill is None else spill.numel(),
+                                            _p(desc_dev), B, _p(out), out.numel(), _stream()), "ds_ragged_gather")
+    return out

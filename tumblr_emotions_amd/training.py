@@ -146,7 +146,11 @@ class SyntheticInput:
     same batches bit for bit) -- honoured only with config['input_pipeline'] = 'device'; with the host pipeline the key is
     a ValueError: that pipeline decodes with PIL.
     config['jpeg_entropy']: 'host' (default) or 'device' (the Huffman decode of restart-segmented JPEGs on the GPU too) --
-    honoured only with config['jpeg_decode'] = 'device'; with anything else the key is a ValueError."""
+    honoured only with config['jpeg_decode'] = 'device'; with anything else the key is a ValueError.
+    config['input_cache']: 'none' (default) or 'device' (every record is decoded once and its pixels stay in an arena of
+    config['input_cache_gb'] GB of device memory, a positive number without a default; later passes are assembled from
+    there by ds_ragged_gather, the same batches bit for bit) -- honoured only with config['input_pipeline'] = 'device';
+    with the host pipeline or config['synthetic'] the key is a ValueError."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
@@ -166,6 +170,18 @@ class SyntheticInput:
         if config.get("jpeg_entropy", "host") == "device" and config.get("jpeg_decode", "host") != "device":
             raise ValueError("config['jpeg_entropy'] = 'device' needs config['jpeg_decode'] = 'device': the coefficients go "
                              "to ds_jpeg_reconstruct")
+        if config.get("input_cache", "none") not in ("none", "device"):
+            raise ValueError("config['input_cache'] must be 'none' or 'device', not %r" % (config["input_cache"],))
+        if config.get("input_cache", "none") == "device":
+            if config.get("synthetic", False):
+                raise ValueError("config['input_cache'] = 'device' needs a real dataset: synthetic batches are not decoded")
+            if config.get("input_pipeline", "host") != "device":
+                raise ValueError("config['input_cache'] = 'device' needs config['input_pipeline'] = 'device': the arena "
+                                 "feeds the device preprocessing")
+            gb = config.get("input_cache_gb")
+            if isinstance(gb, bool) or not isinstance(gb, (int, float)) or not gb > 0:
+                raise ValueError("config['input_cache'] = 'device' needs config['input_cache_gb'], a positive number of GB: "
+                                 "there is no default")
         ddir = config.get("dataset_dir")
         split = os.path.join(ddir or "", "photos", "train_valid_split.txt")
         if config.get("synthetic", False):
@@ -196,6 +212,9 @@ class SyntheticInput:
                                                      workers=self.config.get("input_workers", 8),
                                                      jpeg_decode=self.config.get("jpeg_decode", "host"),
                                                      jpeg_entropy=self.config.get("jpeg_entropy", "host"),
+                                                     cache=self.config.get("input_cache", "none"),
+                                                     cache_bytes=(int(self.config["input_cache_gb"] * 1e9)
+                                                                  if self.config.get("input_cache", "none") == "device" else None),
                                                      decode_images=with_images)     # text-only: no JPEG is decoded
             b = next(self._records)
         else:
