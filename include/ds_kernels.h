@@ -589,6 +589,24 @@ int ds_bn_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t 
  * alias z.  fp32 only.                                                                                                      */
 int ds_bn_infer_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *rstd,
                           const float *shift, float *dz, void *stream);
+/* Frozen-BatchNorm TRAINING (moving statistics inside the train step, slim's batch_norm(is_training=False) around a tower
+ * that trains): beta keeps its gradient dbeta = sum_rows g, g = dy * [z*rstd + shift > 0].  ds_bn_infer_bwd_apply_sums writes
+ * the dz of ds_bn_infer_bwd_apply, bit for bit (same launch shape, same arguments), and in the same pass the column sums of g
+ * as partials float[C][P], P = ds_bn_infer_bwd_partials(M, C): fixed summation order, no atomics, every slot written.
+ * dz NULL: only the sums (a layer nothing below wants dz of; also the pooled stem, whose z and dy ARE the pooled tensors:
+ * sum over windows of dpool * [rstd*zmax + shift > 0]).                                                                   */
+int ds_bn_infer_bwd_partials(int64_t M, int32_t C);
+int ds_bn_infer_bwd_apply_sums(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *rstd,
+                               const float *shift, float *dz, float *partials, void *stream);
+/* ... and ONE launch that adds the partials of many layers into their beta gradients (slices of the flat gradient):
+ * dbeta[c] = sum_p partials[c * P + p], combined in double in a fixed order.  A layer of a column range of a wider partials
+ * tensor passes partials offset by P * its first column.                                                                   */
+typedef struct ds_bn_sum_job {
+    const float *partials;      /* float[C][P] */
+    int32_t P, C;
+    float *dbeta;               /* out, C floats */
+} ds_bn_sum_job;
+int ds_bn_dbeta_reduce_multi(const ds_bn_sum_job *jobs, int32_t njobs, void *stream);
 /* The same with dz written to a SEPARATE bf16 tensor (pixel stride lddz) and z left as it is: the 16-bit configurations' 1x1  */
 /* input gradients (ds_conv_bf16 with x_dtype = DS_DTYPE_BF16) read 2 instead of 4 bytes per element and get exactly the values */
 /* they would have rounded on load (RNE), so Conv2DBackpropInput has the same bits                                            */
@@ -628,6 +646,11 @@ int ds_bn_pool_bwd_apply(const float *z, const float *dpool, const uint8_t *argm
 int ds_bn_pool_infer_bwd_apply(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H, int32_t W,
                                int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW, const float *rstd,
                                const float *shift, float *dz, void *stream);
+/* ... and its frozen-BatchNorm TRAINING form (see ds_bn_infer_bwd_apply_sums): the same dz (NULL: none) plus the column sums
+ * of g as partials float[C][P], P = ds_bn_pool_bwd_partials(N, OH, OW, C)                                                   */
+int ds_bn_pool_infer_bwd_apply_sums(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H, int32_t W,
+                                    int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW, const float *rstd,
+                                    const float *shift, float *dz, float *partials, void *stream);
 int ds_maxpool_bwd(const float *dy, const uint8_t *argmax, float *dx, int32_t accumulate, int32_t N,
                    int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
                    int32_t OH, int32_t OW, void *stream);

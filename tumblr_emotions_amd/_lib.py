@@ -96,6 +96,11 @@ class BnInferJob(C.Structure):
                 ("rstd", C.c_void_p), ("shift", C.c_void_p)]
 
 
+class BnSumJob(C.Structure):
+    """ds_bn_sum_job"""
+    _fields_ = [("partials", C.c_void_p), ("P", C.c_int32), ("C", C.c_int32), ("dbeta", C.c_void_p)]
+
+
 class SumSegments(C.Structure):
     _fields_ = [("nseg", C.c_int32), ("c_begin", C.c_int32 * 4), ("c_end", C.c_int32 * 4), ("P", C.c_int32 * 4),
                 ("kind", C.c_int32 * 4), ("s", C.c_void_p * 4), ("q", C.c_void_p * 4), ("P2", C.c_int32 * 4),
@@ -238,6 +243,9 @@ SIGNATURES = {
     "ds_bn_bwd_finalize_apply": (C.c_int, [_SS, _P, _P, _P, _P, _P, _P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _i32, _i32, _P, _P, _P]),
     "ds_bn_bwd_apply": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _P, _P]),
     "ds_bn_infer_bwd_apply": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P]),
+    "ds_bn_infer_bwd_partials": (C.c_int, [_i64, _i32]),
+    "ds_bn_infer_bwd_apply_sums": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P]),
+    "ds_bn_dbeta_reduce_multi": (C.c_int, [_P, _i32, _P]),
     "ds_bn_bwd_apply_bf16": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _i32, _P, _P]),
     "ds_maxpool_fwd": (C.c_int, [_P, _P, _P] + [_i32] * 11 + [_P]),
     "ds_maxpool_bn_relu_fwd": (C.c_int, [_P, _P, _P, _P, _P] + [_i32] * 11 + [_P, _P]),
@@ -245,6 +253,7 @@ SIGNATURES = {
     "ds_bn_pool_bwd_reduce": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P, _P]),
     "ds_bn_pool_bwd_apply": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P, _P, _P]),
     "ds_bn_pool_infer_bwd_apply": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P]),
+    "ds_bn_pool_infer_bwd_apply_sums": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P, _P]),
     "ds_maxpool_bwd": (C.c_int, [_P, _P, _P] + [_i32] * 11 + [_P]),
     "ds_maxpool3_bwd_sums_partials": (C.c_int, [_i32, _i32, _i32]),
     "ds_maxpool3_bwd_sums": (C.c_int, [_P, _P, _P, _i32, _P, _i32, _i32, _i32, _i32, _i32, _P, _P]),

@@ -608,6 +608,114 @@ __global__ __launch_bounds__(256) void bn_infer_bwd_apply_kernel(const float *z,
     }
 }
 
+// ---- frozen-BatchNorm TRAINING backward (moving statistics in the train step) ----------------------------------------------
+// The same pointwise pass when beta still trains: dz as above, bit for bit, and in the same walk the column sums of
+// g = dy * [z*rstd + shift > 0] -- dbeta = sum g is all that is left of the batch-statistics backward.  A thread keeps its
+// float4 column group, so its four sums stay in registers (rows in walk order); one LDS combine per workgroup adds the
+// threads of a column group in thread order and stores partials[c][blockIdx.x] -- float[C][P], P = gridDim.x, the layout of
+// the other sum producers without the second (g*xhat) plane.  A workgroup covers 256 consecutive (row, column group) slots:
+// with C / 4 > 256 it meets only some column groups and stores an exact 0 for the others, so every slot of the tensor is
+// written by every launch.  No atomics: ds_bn_dbeta_reduce_multi adds the P partials in a fixed order.
+// WRITE = false: dz is not wanted (a frozen layer with nothing below it: the stem), the pass only sums.
+template <bool ADD2, bool WRITE>
+__global__ __launch_bounds__(256) void bn_infer_bwd_apply_sums_kernel(const float *z, int ldz, SegDev dy, int64_t M, int C,
+                                                                      const float *rstd, const float *shift, float *dz, int drow,
+                                                                      float *partials) {
+    __shared__ float sh[256][4];
+    const int C4 = C >> 2;
+    const int t0 = (int)blockIdx.x * 256 + threadIdx.x;
+    const int row0 = t0 / C4, c = (t0 - row0 * C4) * 4;
+    const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c), s4 = *reinterpret_cast<const float4 *>(shift + c);
+    const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+    int sgi = 0;
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (i < dy.nseg && c >= dy.c_begin[i] && c < dy.c_end[i]) sgi = i;
+    const float *const dyp = dy.ptr[sgi] + (c - dy.c_begin[sgi]);
+    const int64_t dyld = dy.ld[sgi];
+    const float *const dyp2 = (ADD2 && dy.ptr2[sgi]) ? dy.ptr2[sgi] + (c - dy.c_begin[sgi]) : nullptr;
+    float sum[4] = {0.f, 0.f, 0.f, 0.f};
+    constexpr int NR = DS_BN_ROWS;          // rows per pass: every load of the pass before any of its stores
+    for (int64_t row = row0; row < M; row += NR * (int64_t)drow) {
+        int64_t rws[NR];
+        bool ok[NR];
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            ok[u] = row + u * (int64_t)drow < M;
+            rws[u] = ok[u] ? row + u * (int64_t)drow : row;
+        }
+        float4 zv[NR], dv[NR];
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            zv[u] = ds::ld_stream4(z + rws[u] * ldz + c);
+            dv[u] = ds::ld_stream4(dyp + rws[u] * dyld);
+        }
+        if (ADD2 && dyp2) {
+#pragma unroll
+            for (int u = 0; u < NR; ++u) {
+                const float4 e = ds::ld_stream4(dyp2 + rws[u] * dyld);
+                dv[u].x += e.x; dv[u].y += e.y; dv[u].z += e.z; dv[u].w += e.w;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            if (u > 0 && !ok[u]) break;
+            const float zz[4] = {zv[u].x, zv[u].y, zv[u].z, zv[u].w}, dd[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
+            f32x4_t o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool on = __builtin_fmaf(zz[j], rr[j], ss[j]) > 0.f;
+                sum[j] += on ? dd[j] : 0.f;
+                o[j] = on ? rr[j] * dd[j] : 0.f;
+            }
+            if constexpr (WRITE) __builtin_nontemporal_store(o, reinterpret_cast<f32x4_t *>(dz + rws[u] * ldz + c));
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sh[threadIdx.x][j] = sum[j];
+    __syncthreads();
+    const int P = gridDim.x;
+    const int head = (int)(((int64_t)blockIdx.x * 256) % C4);      // column group of this workgroup's thread 0
+    for (int cg = threadIdx.x; cg < C4; cg += 256) {               // owner of column group cg: its threads in thread order
+        int first = cg - head;
+        if (first < 0) first += C4;
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int t = first; t < 256; t += C4)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] += sh[t][j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) partials[(int64_t)(cg * 4 + j) * P + blockIdx.x] = a[j];
+    }
+}
+
+// ds_bn_dbeta_reduce_multi: the partial sums of many layers into their beta gradients as one launch -- one workgroup per
+// channel (workgroup -> job by the running channel count), the P partials combined in double in the fixed order of
+// bn_bwd_finalize_kernel: strided per thread, butterfly per wave, waves 0..3
+constexpr int kSumJobsMax = 64;
+struct SumJobsDev {
+    int njobs;
+    int first[kSumJobsMax + 1];          // first workgroup of the job; [njobs]: the grid
+    int P[kSumJobsMax];
+    const float *partials[kSumJobsMax];
+    float *dbeta[kSumJobsMax];
+};
+
+__global__ __launch_bounds__(256) void bn_dbeta_reduce_multi_kernel(const SumJobsDev jb) {
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int j = 0;
+    for (int i = 1; i < jb.njobs; ++i)
+        if ((int)blockIdx.x >= jb.first[i]) j = i;
+    const int c = (int)blockIdx.x - jb.first[j], P = jb.P[j];
+    const float *p0 = jb.partials[j] + (int64_t)c * P;
+    double s = 0.0;
+    for (int p = threadIdx.x; p < P; p += 256) s += (double)p0[p];
+    s = wave_sum_f64(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) jb.dbeta[j][c] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
+}
+
 // ds_bn_bwd_finalize_apply: the backward finalize (segments, per-segment beta / dbeta) and the apply pass as one launch
 // (see bn_finalize_apply_relu_kernel)
 struct BwdFinApplyArgs {
@@ -991,4 +1099,57 @@ extern "C" int ds_bn_infer_bwd_apply(const float *z, int32_t ldz, const ds_segme
         hipLaunchKernelGGL(bn_infer_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, rstd,
                            shift, dz, drow);
     return ds::check_launch("ds_bn_infer_bwd_apply");
+}
+
+extern "C" int ds_bn_infer_bwd_partials(int64_t M, int32_t C) {
+    if (M <= 0 || C <= 0 || C % 4) return 0;
+    int drow;
+    return column_grid(M, C / 4, &drow);
+}
+
+extern "C" int ds_bn_infer_bwd_apply_sums(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C,
+                                          const float *rstd, const float *shift, float *dz, float *partials, void *stream) {
+    DS_REQUIRE(z && rstd && shift && partials && M > 0 && C > 0 && C % 4 == 0 && ldz >= C && ldz % 4 == 0 &&
+                   ((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)rstd) | ((uintptr_t)shift)) & 15) == 0 &&
+                   (((uintptr_t)partials) & 3) == 0,
+               "ds_bn_infer_bwd_apply_sums: bad argument (need C %% 4 == 0, ldz >= C, ldz %% 4 == 0, 16-byte aligned z / dz / rstd / "
+               "shift, partials)");
+    if (int e = check_segments(dy, C, "ds_bn_infer_bwd_apply_sums")) return e;
+    int drow;
+    const int grid = column_grid(M, C / 4, &drow);
+    const bool add2 = has_second_addend(dy);
+    hipStream_t st = (hipStream_t)stream;
+    if (add2 && dz)
+        hipLaunchKernelGGL((bn_infer_bwd_apply_sums_kernel<true, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+                           dz, drow, partials);
+    else if (add2)
+        hipLaunchKernelGGL((bn_infer_bwd_apply_sums_kernel<true, false>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+                           dz, drow, partials);
+    else if (dz)
+        hipLaunchKernelGGL((bn_infer_bwd_apply_sums_kernel<false, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+                           dz, drow, partials);
+    else
+        hipLaunchKernelGGL((bn_infer_bwd_apply_sums_kernel<false, false>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+                           dz, drow, partials);
+    return ds::check_launch("ds_bn_infer_bwd_apply_sums");
+}
+
+extern "C" int ds_bn_dbeta_reduce_multi(const ds_bn_sum_job *jobs, int32_t njobs, void *stream) {
+    DS_REQUIRE(jobs && njobs >= 1, "ds_bn_dbeta_reduce_multi: at least one job required");
+    for (int i = 0; i < njobs; ++i)
+        DS_REQUIRE(jobs[i].partials && jobs[i].dbeta && jobs[i].P > 0 && jobs[i].C > 0, "ds_bn_dbeta_reduce_multi: job %d is malformed", i);
+    for (int i0 = 0; i0 < njobs; i0 += kSumJobsMax) {      // (one launch for up to 64 layers: the tower has 57)
+        SumJobsDev jb = {};
+        jb.njobs = njobs - i0 < kSumJobsMax ? njobs - i0 : kSumJobsMax;
+        int total = 0;
+        for (int i = 0; i < jb.njobs; ++i) {
+            const ds_bn_sum_job &j = jobs[i0 + i];
+            jb.first[i] = total;
+            jb.P[i] = j.P; jb.partials[i] = j.partials; jb.dbeta[i] = j.dbeta;
+            total += j.C;
+        }
+        jb.first[jb.njobs] = total;
+        hipLaunchKernelGGL(bn_dbeta_reduce_multi_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, jb);
+    }
+    return ds::check_launch("ds_bn_dbeta_reduce_multi");
 }

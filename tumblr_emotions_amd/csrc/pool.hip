@@ -819,6 +819,79 @@ __global__ __launch_bounds__(256) void bn_pool_infer_bwd_apply_kernel(const floa
     }
 }
 
+// ds_bn_pool_infer_bwd_apply_sums: the frozen-BatchNorm TRAINING twin (moving statistics in the train step, beta still trains):
+// the same dz, bit for bit, and in the same patch walk the column sums of g = dy_full * [z*rstd + shift > 0] (dbeta = sum g) as
+// fixed-order partials float[C][P], P = gridDim.x -- a thread keeps its channel group over its grid-stride walk (256 * gridDim.x
+// is a multiple of C / 4, as for bn_pool_bwd_reduce_kernel), one LDS combine per workgroup in thread order, no atomics.
+// WRITE = false: nothing below the layer wants dz (the unpooled stem), the pass only sums.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void bn_pool_infer_bwd_apply_sums_kernel(const float *z, const float *dpool, const uint8_t *am,
+                                                                           int N, int H, int W, int C, int pad_t, int pad_l, int OH,
+                                                                           int OW, const float *rstd, const float *shift, float *dz,
+                                                                           float *partials) {
+    __shared__ float sh[256][4];
+    const int C4 = C >> 2;
+    const int PH = OH + 1, PW = OW + 1;
+    const int64_t total = (int64_t)N * PH * PW * C4;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = (int)(first % C4) * 4;
+    const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c);
+    const float4 s4 = *reinterpret_cast<const float4 *>(shift + c);
+    const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+    float sum[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = first; i < total; i += (int64_t)gridDim.x * 256) {
+        int64_t r = i / C4;
+        const int q = (int)(r % PW) - 1;
+        r /= PW;
+        const int p = (int)(r % PH) - 1;
+        const int n = (int)(r / PH);
+        const PatchGrad pg = patch_grad(dpool, am, n, p, q, c, C, OH, OW);
+        float4 zv[2][2];
+        bool ok[2][2];
+        int64_t offs[2][2];
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                const int ih = 2 * p - pad_t + 1 + y, iw = 2 * q - pad_l + 1 + x;
+                ok[y][x] = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
+                offs[y][x] = (((int64_t)n * H + ih) * W + iw) * C + c;
+                zv[y][x] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ok[y][x]) zv[y][x] = ds::ld_stream4(z + offs[y][x]);
+            }
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                if (!ok[y][x]) continue;
+                const float zz[4] = {zv[y][x].x, zv[y][x].y, zv[y][x].z, zv[y][x].w};
+                ds::f32x4_nt o;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool on = __builtin_fmaf(zz[j], rr[j], ss[j]) > 0.f;
+                    sum[j] += on ? pg.g[y][x][j] : 0.f;
+                    o[j] = on ? rr[j] * pg.g[y][x][j] : 0.f;
+                }
+                if constexpr (WRITE) __builtin_nontemporal_store(o, reinterpret_cast<ds::f32x4_nt *>(dz + offs[y][x]));
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sh[threadIdx.x][j] = sum[j];
+    __syncthreads();
+    const int P = gridDim.x;
+    const int head = (int)(((int64_t)blockIdx.x * 256) % C4);      // channel group of this workgroup's thread 0
+    for (int cg = threadIdx.x; cg < C4; cg += 256) {               // owner of channel group cg: its threads in thread order
+        int t0 = cg - head;
+        if (t0 < 0) t0 += C4;
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int t = t0; t < 256; t += C4)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] += sh[t][j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) partials[(int64_t)(cg * 4 + j) * P + blockIdx.x] = a[j];
+    }
+}
+
 }  // namespace
 
 namespace {
@@ -1018,4 +1091,22 @@ extern "C" int ds_bn_pool_infer_bwd_apply(const float *z, const float *dpool, co
     hipLaunchKernelGGL(bn_pool_infer_bwd_apply_kernel, dim3(pool_bwd_grid(N, OH, OW, C)), dim3(256), 0, (hipStream_t)stream, z,
                        dpool, argmax, N, H, W, C, pad_t, pad_l, OH, OW, rstd, shift, dz);
     return ds::check_launch("ds_bn_pool_infer_bwd_apply");
+}
+
+extern "C" int ds_bn_pool_infer_bwd_apply_sums(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H,
+                                               int32_t W, int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW,
+                                               const float *rstd, const float *shift, float *dz, float *partials, void *stream) {
+    DS_REQUIRE(z && dpool && argmax && rstd && shift && partials && N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 &&
+                   C % 4 == 0 && H <= 2 * OH && W <= 2 * OW && pad_t >= 0 && pad_t <= 1 && pad_l >= 0 && pad_l <= 1 &&
+                   ((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)dpool) | ((uintptr_t)rstd) | ((uintptr_t)shift)) & 15) == 0 &&
+                   (((uintptr_t)partials) & 3) == 0,
+               "ds_bn_pool_infer_bwd_apply_sums: bad argument (3x3 stride-2 SAME pools, C %% 4 == 0, 16-byte aligned tensors, partials)");
+    const int grid = pool_bwd_grid(N, OH, OW, C);
+    if (dz)
+        hipLaunchKernelGGL(bn_pool_infer_bwd_apply_sums_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, dpool, argmax, N,
+                           H, W, C, pad_t, pad_l, OH, OW, rstd, shift, dz, partials);
+    else
+        hipLaunchKernelGGL(bn_pool_infer_bwd_apply_sums_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, dpool, argmax, N,
+                           H, W, C, pad_t, pad_l, OH, OW, rstd, shift, dz, partials);
+    return ds::check_launch("ds_bn_pool_infer_bwd_apply_sums");
 }

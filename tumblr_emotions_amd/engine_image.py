@@ -13,6 +13,7 @@ slim/nets/inception_utils.py:32-71); how is MI355X-first:
     layers (SURVEY A4);
   * all buffers are allocated once per batch size; nothing is allocated or synchronised per step.
 """
+import contextlib
 import ctypes as C
 import os
 from collections import namedtuple
@@ -152,6 +153,9 @@ class ConvBN:
         self.bnb = False              # the dgrad forms dz from z and dy as it loads (enable_bnb): no ds_bn_bwd_apply pass
         self.dx_y = None
         self._sum_segs = None
+        self.fz_job = None            # frozen-BatchNorm step: (address, P) of this layer's partial sums of g (frozen_partials)
+        self._fz_part = None
+        self._fz_segs = None
         if self.trainable:
             if self.fold:      # stem (train_all only): KW folded into the channel axis like the forward conv
                 self.wgrad = WgradPlan(B, self.H, self.W, 7 * 4, 4, 7, 1, self.stride, cout, cout, fold_cin=4)
@@ -448,7 +452,7 @@ class ConvBN:
                 x_amax = self.amax[0]
                 ops.absmax(x_ptr, self.B * self.H * self.W * ldx, x_amax, x_dtype)
             amax_p = ops._p(x_amax)
-        if eng.training:       # batch statistics (slim.batch_norm is_training=True)
+        if eng.batch_stats:    # batch statistics (slim.batch_norm is_training=True)
             # the column sums are taken about a pivot near the mean -- the previous step's batch mean, the
             # moving mean before the first step (bind) -- so channels with |mean| >> std keep their variance
             plan.d.flags = DS_EPI_STATS
@@ -495,7 +499,8 @@ class ConvBN:
             plan.d.flags = 0
             # (z16: z centred about the moving mean; with it the shift is beta itself: infer_prepare on a zero mean)
             plan.run(x_ptr, self.w_ptr, ops._p(self.z), x_amax=amax_p, pivot=ops._p(self.mm) if self.z16 else None)
-            ops.bn_infer_prepare(self.beta, self.mm, self.mv, BN_EPS, self.cout, self.rstd, self.shift)
+            if not eng.frozen_step:      # (a frozen-BatchNorm training step prepared all 57 layers in one launch: _frozen_prepare)
+                ops.bn_infer_prepare(self.beta, self.mm, self.mv, BN_EPS, self.cout, self.rstd, self.shift)
             if self.z16:
                 ops.bn_infer_prepare(self.beta, eng.zeros, self.mv, BN_EPS, self.cout, self.rstd, self.shift_c)
         if segs is not None and not self.skip_apply:
@@ -529,7 +534,7 @@ class ConvBN:
         if need_dx:
             self._run_dgrad(dx_ptr)
 
-    def backward_infer(self, dx_ptr, pool=None, apply=True):
+    def backward_infer(self, dx_ptr, pool=None, apply=True, run_dgrad=True):
         """Moving-statistics backward (InceptionV1Engine.input_backward(eval_mode=True)): BatchNorm with fixed statistics is a
         per-channel affine map, so dz = rstd * dy * [z*rstd + shift > 0] is ONE pointwise pass over z (ds_bn_infer_bwd_apply;
         pool: from the pooled gradient, ds_bn_pool_infer_bwd_apply) -- no sums, no finalize -- and then the plain dgrad.
@@ -541,7 +546,70 @@ class ConvBN:
             else:
                 ops.bn_infer_bwd_apply(self.z, self.dy_segs, self.M, self.cout, self.rstd, self.shift, self.z, ldz=self.ldz)
         self._dz_amax_live = False
-        self._run_dgrad(dx_ptr)
+        if run_dgrad:
+            self._run_dgrad(dx_ptr)
+
+    def frozen_partials(self, pool=None):
+        """This layer's partial sums of g for the frozen-BatchNorm step, float[cout][P] (allocated at the first such step; kept
+        until the step's ds_bn_dbeta_reduce_multi has read them, so every layer has its own)."""
+        if self._fz_part is None:
+            if self.pool_inside:
+                P = ops.bn_infer_bwd_partials(self.z.shape[0], self.cout)
+            elif pool is not None:
+                P = ops.bn_pool_bwd_partials(self.B, self.OH, self.OW, self.cout)
+            else:
+                P = ops.bn_infer_bwd_partials(self.M, self.cout)
+            self._fz_part = torch.empty(self.cout * P, device=self.eng.device)
+            self.fz_job = (self._fz_part.data_ptr(), P)
+        return self._fz_part
+
+    def backward_frozen(self, x_ptr=None, ldx=0, dx_ptr=None, need_dx=True, pool=None, apply=True):
+        """Backward of a frozen-BatchNorm TRAINING step (SentimentNet(frozen_bn=True)): the pointwise pass of backward_infer,
+        but the layer keeps what a training step owes -- its beta gradient, dbeta = sum g, from partial sums the SAME pass emits
+        (ds_bn_infer_bwd_apply_sums / ds_bn_pool_infer_bwd_apply_sums; reduced once per step by
+        InceptionV1Engine._frozen_dbeta), and its weight gradient where it is trainable.  apply=False: the block has run the
+        pointwise pass over this layer's concat columns already (MixedStage zcat)."""
+        if self.gbeta is None and not need_dx and not self.trainable:
+            return
+        want_dz = need_dx or self.trainable
+        dz = self.z if want_dz else None
+        if apply and self.gbeta is None:
+            if want_dz:
+                self.backward_infer(None, pool, run_dgrad=False)
+        elif apply:
+            part = self.frozen_partials(pool)
+            if self.pool_inside:
+                # only the window maxima of z exist, and every window hands its gradient to ONE pixel whose z is that maximum:
+                # sum_pixels g = sum_windows dpool * [rstd * zmax + shift > 0] -- the pointwise pass on the POOLED tensors
+                assert pool is not None and not want_dz          # (a frozen stem: nothing below it)
+                if self._fz_segs is None:
+                    self._fz_segs = make_segments([(0, self.cout, pool.dout.data_ptr(), self.cout)])
+                ops.bn_infer_bwd_apply_sums(self.z, self._fz_segs, self.z.shape[0], self.cout, self.rstd, self.shift, None, part)
+            elif pool is not None:
+                ops.bn_pool_infer_bwd_apply_sums(self.z, pool.dout, pool.argmax, self.B, self.OH, self.OW, self.cout, self.rstd,
+                                                 self.shift, dz, part)
+            else:
+                ops.bn_infer_bwd_apply_sums(self.z, self.dy_segs, self.M, self.cout, self.rstd, self.shift, dz, part, ldz=self.ldz)
+        self._dz_amax_live = False
+        if self.trainable:
+            self._run_wgrad(x_ptr, ldx)
+        if need_dx:
+            self._run_dgrad(dx_ptr)
+
+    def _run_wgrad(self, x_ptr, ldx):
+        eng = self.eng
+        self.wgrad.d.ldx = ldx
+        if eng.wgrad_stream is not None:
+            # Conv2DBackpropFilter is a leaf of the backward graph (only the optimiser and the all-reduce wait for
+            # it): off the chain that the next layer's dgrad waits on, onto the weight-gradient stream
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())          # dz is complete here
+            eng.wgrad_stream.wait_event(ev)
+            with torch.cuda.stream(eng.wgrad_stream):
+                self.wgrad.run(x_ptr, ops._p(self.z), self.gw_ptr, ops._p(eng.ws_set[3]), eng.ws_bytes)
+            eng.wgrad_pending = True
+        else:
+            self.wgrad.run(x_ptr, ops._p(self.z), self.gw_ptr, ops._p(self.ws_buf), eng.ws_bytes)
 
     def _run_dgrad(self, dx_ptr, use16=False):
         sums = ops._p(self.dx_sums) if self.dx_sums is not None else None
@@ -600,18 +668,7 @@ class ConvBN:
                              amax=self.dz_amax if track else None, ldz=self.ldz)
         self._dz_amax_live = track
         if self.trainable:
-            self.wgrad.d.ldx = ldx
-            if eng.wgrad_stream is not None:
-                # Conv2DBackpropFilter is a leaf of the backward graph (only the optimiser and the all-reduce wait for
-                # it): off the chain that the next layer's dgrad waits on, onto the weight-gradient stream
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream())          # dz is complete here
-                eng.wgrad_stream.wait_event(ev)
-                with torch.cuda.stream(eng.wgrad_stream):
-                    self.wgrad.run(x_ptr, ops._p(self.z), self.gw_ptr, ops._p(eng.ws_set[3]), eng.ws_bytes)
-                eng.wgrad_pending = True
-            else:
-                self.wgrad.run(x_ptr, ops._p(self.z), self.gw_ptr, ops._p(self.ws_buf), eng.ws_bytes)
+            self._run_wgrad(x_ptr, ldx)
         if need_dx:
             self._run_dgrad(dx_ptr, use16=self.dz16 is not None)
 
@@ -714,6 +771,10 @@ class ConvStage(Stage):
     def backward(self, need_dx):
         need_dx = need_dx and (not self.layer.fold or self.eng.input_grad)      # (the stem: the image gradient, input_backward)
         dx = ops._p(self.prev.dout) if need_dx else None
+        if self.eng.frozen_step:
+            self.layer.backward_frozen(ops._p(self.prev.out), self.prev.C, dx, need_dx,
+                                       self.pool if (self.fused_into_pool and self.pool.stride == 2) else None)
+            return
         if self.eng.infer_bwd:
             self.layer.backward_infer(dx, self.pool if (self.fused_into_pool and self.pool.stride == 2) else None)
             return
@@ -895,6 +956,7 @@ class MixedStage(Stage):
         # critical path per block -- so it is on up to 128 samples only (bit 0 forward, bit 1 backward)
         self.batch_bn = 0
         self._infer_close = None
+        self._fz_close = None        # frozen-BatchNorm step: the partial sums of g over the closing columns [b0, Ct)
         if self.zcat:
             self.rs_cat = torch.empty(2, Ct, device=dev)
             self.rs_cat[0].fill_(1.0)
@@ -1066,7 +1128,7 @@ class MixedStage(Stage):
     def _batch_forward(self):
         """One ds_bn_finalize_multi for the block-closing layers?  (training with per-rank statistics, no in-launch finalize)"""
         eng = self.eng
-        return bool((self.batch_bn & 1) and eng.training and not eng.sync_bn
+        return bool((self.batch_bn & 1) and eng.batch_stats and not eng.sync_bn
                     and all(l.fin is None for l in (self.c1, self.c2, self.c3)))
 
     def _finalize_closing(self):
@@ -1156,10 +1218,23 @@ class MixedStage(Stage):
             if self._infer_close is None:
                 self._infer_close = (make_segments([(0, Ct - b0, self.dout.data_ptr() + 4 * b0, Ct)]), self.out.view(M, Ct)[:, b0:])
             dy, z = self._infer_close
-            ops.bn_infer_bwd_apply(z, dy, M, Ct - b0, self.rs_cat[0, b0:], self.rs_cat[1, b0:], z, ldz=Ct)
+            if eng.frozen_step and self.c1.gbeta is not None:
+                # ... which also emits the column sums of g: the three layers' beta gradients are column ranges of them
+                if self._fz_close is None:
+                    P = ops.bn_infer_bwd_partials(M, Ct - b0)
+                    self._fz_close = torch.empty((Ct - b0) * P, device=eng.device)
+                    off = 0
+                    for l in (self.c1, self.c2, self.c3):
+                        l.fz_job = (self._fz_close.data_ptr() + 4 * off * P, P)
+                        off += l.cout
+                ops.bn_infer_bwd_apply_sums(z, dy, M, Ct - b0, self.rs_cat[0, b0:], self.rs_cat[1, b0:], z, self._fz_close, ldz=Ct)
+            else:
+                ops.bn_infer_bwd_apply(z, dy, M, Ct - b0, self.rs_cat[0, b0:], self.rs_cat[1, b0:], z, ldz=Ct)
 
         def closing(layer, x_ptr, ldx, dx_ptr, ndx):
-            if infer:
+            if eng.frozen_step:
+                layer.backward_frozen(x_ptr, ldx, dx_ptr, ndx, apply=not self.zcat)
+            elif infer:
                 layer.backward_infer(dx_ptr, apply=not self.zcat)
             elif batched:
                 layer._run_dgrad(dx_ptr)
@@ -1179,8 +1254,13 @@ class MixedStage(Stage):
         self._fork_join(None, lambda: closing(self.c1, ops._p(self.r1), b1a, ops._p(self.dr1), True),
                         lambda: closing(self.c2, ops._p(self.r2), b2a, ops._p(self.dr2), True), branch3)
         if infer:
-            self.fused.backward_infer(ops._p(p.dout))
-            if not pool_first and not self.split_dout:
+            if eng.frozen_step:
+                self.fused.backward_frozen(x, p.C, ops._p(p.dout) if need_dx else None, need_dx)
+            else:
+                self.fused.backward_infer(ops._p(p.dout))
+            # (need_dx: always set in input_backward's walk; a frozen-BatchNorm step with trainable_bn_beta=False ends at
+            # Mixed_5c, whose input gradient nobody reads)
+            if need_dx and not pool_first and not self.split_dout:
                 ops.maxpool_bwd(self.dpooled, self.argmax, p.dout, True, self.B, p.H, p.W, p.C, 3, 1, "SAME")
             return
         self.fused.backward(x, p.C, ops._p(p.dout) if need_dx else None, need_dx)
@@ -1311,6 +1391,13 @@ class InceptionV1Engine:
         # _pivots keeps the statistics pivots of the training state that was left, so the next training step is unchanged
         self.input_grad = False
         self.infer_bwd = False       # inside input_backward(eval_mode=True): the stages run their moving-statistics backward
+        # frozen-BatchNorm training (SentimentNet(frozen_bn=True)): the STATISTICS mode of a pass, apart from `training` (which
+        # keeps dropout on): while frozen_step is set -- SentimentNet.train_step sets it around its forward and backward --
+        # every BatchNorm normalises with the moving statistics, the backward is the pointwise one with beta and weight
+        # gradients live, and neither the moving statistics nor the pivots are written
+        self.frozen_step = False
+        self._frozen_prep = None
+        self._frozen_jobs = {}
         self._input_grad_training = True     # was the last forward(input_grad=True) a batch-statistics pass?
         self._pivots = None
         self._restore_pivots = None
@@ -1347,6 +1434,11 @@ class InceptionV1Engine:
         self.lg = lg
         # first stage (from the top) below which nothing is trainable -> backward can stop there
         self.layers = [l for s in self.stages for l in s.layers]
+
+    @property
+    def batch_stats(self):
+        """Does this pass normalise with the batch's own statistics?  (training, and not a frozen-BatchNorm step)"""
+        return bool(self.training and not self.frozen_step)
 
     @property
     def arith(self):
@@ -1540,6 +1632,27 @@ class InceptionV1Engine:
                 ops.fill(l.shift, l.cout, 0.0)
         self._fused_key = (self.weights_version, self.alloc_gen)
 
+    def _frozen_prepare(self):
+        """(rstd, shift) of all 57 layers from the moving statistics and the CURRENT beta as one launch (every step: Adam moves
+        beta), into the vectors the apply passes, the pools and the on-load normalising consumers read."""
+        if self._frozen_prep is None or self._frozen_prep[0] != self.alloc_gen:
+            jobs = [(l.beta, l.mm, l.mv, l.cout, l.rstd, l.shift) for l in self.layers]
+            self._frozen_prep = (self.alloc_gen, ops.BnInferJobs(jobs))
+        self._frozen_prep[1].run(BN_EPS)
+
+    def _frozen_dbeta(self, top):
+        """dbeta of the layers of the trainable end points (top; their betas lie in bucket 1 of the flat gradient) or of all
+        the others, from the partial sums their pointwise backward passes left: ONE ds_bn_dbeta_reduce_multi launch."""
+        if not self.trainable_bn_beta:
+            return
+        key = (self.alloc_gen, top)
+        jobs = self._frozen_jobs.get(key)
+        if jobs is None:
+            layers = [l for s in self.stages if (s.name in TRAINABLE_ENDPOINTS) == top for l in s.layers]
+            assert all(l.fz_job is not None for l in layers)
+            jobs = self._frozen_jobs[key] = ops.BnSumJobs([(l.fz_job[0], l.fz_job[1], l.cout, l.gbeta) for l in layers])
+        jobs.run()
+
     def fused_report(self):
         """[(layer key, reason)] of the layers that kept conv -> ds_bn_apply_relu (or a pool-stage BatchNorm) in the last fused
         forward; every other conv layer ran with BatchNorm + ReLU in its epilogue."""
@@ -1585,6 +1698,12 @@ class InceptionV1Engine:
         if not stem.stem_direct or (stem.trainable and self.training):
             # the generic stem kernel and the stem's wgrad (train_all) read a zero-padded 4-channel copy
             ops.pad_channels(images, 3, self.input.out, 4, B * self.input.H * self.input.W)
+        if self.frozen_step:
+            if not self.training or input_grad or fused:
+                raise ValueError("a frozen-BatchNorm step is a plain training pass")
+            if self.dtype != "f32" or self.train_all or self.sync_bn:
+                raise NotImplementedError("frozen-BatchNorm training is the fp32 configuration without train_all / sync_bn")
+            self._frozen_prepare()
         if self.fused_infer:
             self._fused_prepare()
         else:
@@ -1617,9 +1736,45 @@ class InceptionV1Engine:
             stop = min(i for i, s in enumerate(self.stages) if any(l.trainable for l in s.layers))
         self.wgrad_stream = self.side_w if (self.wgrad_side and self.side_w is not None) else None
         self.wgrad_pending = False
+        if self.frozen_step:
+            self._backward_frozen(n, stop)
+            return
+        self._backward_walk(n, stop)
+
+    def _backward_frozen(self, n, stop):
+        """The stage walk of a frozen-BatchNorm training step: the stages run their pointwise moving-statistics backward
+        (infer_bwd) -- the dgrads plain, their DS_EPI_BNSUMS epilogues and on-load BatchNorm backward taken off the descriptors
+        for the pass as input_backward(eval_mode=True) does -- but weight gradients, beta gradients and the reducer's calls stay."""
+        with self._pointwise_backward():
+            self._backward_walk(n, stop)
+
+    @contextlib.contextmanager
+    def _pointwise_backward(self, on=True):
+        """The moving-statistics backward of the stages (infer_bwd) for the body: the dgrads run plain -- their DS_EPI_BNSUMS
+        epilogues and on-load BatchNorm backward (bnb) are taken off the descriptors and put back behind it.  on=False: nothing."""
+        plans = [l.dgrad for l in self.layers if l.dgrad is not None] if on else []
+        saved_plans = [(pl.d.flags, pl.d.bnb, pl.d.mask_rstd, pl.d.mask_shift) for pl in plans]
+        try:
+            for pl in plans:
+                pl.d.flags &= ~ops.DS_EPI_BNSUMS
+                pl.d.bnb = pl.d.mask_rstd = pl.d.mask_shift = None
+            self.infer_bwd = bool(on)
+            yield
+        finally:
+            self.infer_bwd = False
+            for pl, (fl, bnb, mr, ms) in zip(plans, saved_plans):
+                pl.d.flags, pl.d.bnb, pl.d.mask_rstd, pl.d.mask_shift = fl, bnb, mr, ms
+
+    def _backward_walk(self, n, stop):
+        frozen = self.frozen_step
         for i in range(n - 1, stop - 1, -1):
             self.stages[i].backward(need_dx=(i > stop))
-            if self.reducer is not None and not self.train_all and self.stages[i].name in TRAINABLE_ENDPOINTS:
+            top = self.stages[i].name in TRAINABLE_ENDPOINTS
+            if frozen and top:
+                self._frozen_dbeta(True)      # (bucket 1 holds these betas: complete before the stage reports)
+                if self.wgrad_pending:
+                    self.wgrad_stream.wait_stream(torch.cuda.current_stream())
+            if self.reducer is not None and not self.train_all and top:
                 # every conv-weight gradient and the Logits gradients now sit in bucket 1 of the flat
                 # gradient: its all-reduce can start while dgrad continues through the frozen blocks
                 if self.wgrad_pending:      # ... once the weight-gradient stream is through: report from there
@@ -1627,6 +1782,8 @@ class InceptionV1Engine:
                         self.reducer.stage_done(self.stages[i].name)
                 else:
                     self.reducer.stage_done(self.stages[i].name)
+        if frozen and stop == 0:
+            self._frozen_dbeta(False)
         if self.wgrad_pending:              # the optimiser (and the next forward pass, which rewrites z) wait for it
             torch.cuda.current_stream().wait_stream(self.wgrad_stream)
         if self.reducer is not None and self.train_all:
@@ -1656,26 +1813,17 @@ class InceptionV1Engine:
         if stem.dgrad is None:
             stem.make_dgrad(3)
         saved = [(l.trainable, l.gbeta) for l in self.layers]
-        # eval_mode: the dgrads run plain -- their DS_EPI_BNSUMS epilogues and on-load BatchNorm backward (bnb) are taken off
-        # the descriptors for the pass and put back behind it
-        plans = [l.dgrad for l in self.layers if l.dgrad is not None] if eval_mode else []
-        saved_plans = [(pl.d.flags, pl.d.bnb, pl.d.mask_rstd, pl.d.mask_shift) for pl in plans]
         self.input.dout = dimages
         try:
             for l in self.layers:
                 l.trainable, l.gbeta = False, None
-            for pl in plans:
-                pl.d.flags &= ~ops.DS_EPI_BNSUMS
-                pl.d.bnb = pl.d.mask_rstd = pl.d.mask_shift = None
-            self.infer_bwd = bool(eval_mode)
-            self.wgrad_stream, self.wgrad_pending = None, False
-            for s in reversed(self.stages):
-                s.backward(need_dx=True)
+            # eval_mode: the dgrads run plain for the pass (_pointwise_backward)
+            with self._pointwise_backward(bool(eval_mode)):
+                self.wgrad_stream, self.wgrad_pending = None, False
+                for s in reversed(self.stages):
+                    s.backward(need_dx=True)
         finally:
-            self.infer_bwd = False
             for l, (tr, gb) in zip(self.layers, saved):
                 l.trainable, l.gbeta = tr, gb
-            for pl, (fl, bnb, mr, ms) in zip(plans, saved_plans):
-                pl.d.flags, pl.d.bnb, pl.d.mask_rstd, pl.d.mask_shift = fl, bnb, mr, ms
             self.input.dout = None
         return dimages

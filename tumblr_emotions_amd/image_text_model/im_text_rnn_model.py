@@ -35,7 +35,7 @@ class DeepSentiment(SyntheticInput):
         embedding, vocab, dim, self.word_to_id = resolve_embedding(config, embedding)
         self._init_input(config, post, vocab, nb_emotions, True, device)
         self.nb_emotions = self.dataset.num_classes
-        for key in ("train_all", "trainable_embedding"):      # optional fine-tuning switches (not in the reference _CONFIG)
+        for key in ("train_all", "trainable_embedding", "frozen_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
             if key in config:
                 net_kw.setdefault(key, bool(config[key]))
         self.net = SentimentNet(mode="joint", nb_emotions=self.nb_emotions,

@@ -30,9 +30,22 @@ class SentimentNet:
                  vocab_size=10000, embedding_dim=300, post_size=32, image_size=224, dropout_keep_prob=0.8,
                  trainable_bn_beta=True, device="cuda", process_group=None, overlap_comm=True,
                  concurrent_towers=True, train_all=False, trainable_embedding=False, dtype="f32",
-                 force_dp_buckets=False, sync_bn=False):
+                 force_dp_buckets=False, sync_bn=False, frozen_bn=False):
         assert mode in ("joint", "image", "text")
         self.dtype = dtype
+        # frozen_bn (opt-in): train_step normalises with the MOVING statistics -- slim.arg_scope([slim.batch_norm],
+        # is_training=False) around a tower that otherwise trains (dropout on, the same trainable set, beta's gradient is the
+        # plain column sum) -- and never writes them; everything but train_step is that of any other net
+        self.frozen_bn = bool(frozen_bn)
+        if self.frozen_bn:
+            if mode == "text":
+                raise ValueError("frozen_bn: mode 'text' has no BatchNorm")
+            if sync_bn:
+                raise ValueError("frozen_bn with sync_bn: fixed statistics leave nothing to synchronise")
+            if dtype != "f32":
+                raise NotImplementedError("frozen_bn is implemented for the fp32 configuration, not %r" % dtype)
+            if train_all:
+                raise NotImplementedError("frozen_bn with train_all is not implemented")
         if not torch.cuda.is_available():
             raise RuntimeError("tumblr_emotions_amd needs an MI355X (HIP) device: the training path has no CPU fallback")
         self.mode, self.nb_emotions, self.device = mode, nb_emotions, torch.device(device)
@@ -455,12 +468,18 @@ class SentimentNet:
                 self.release_graph()     # buffers re-allocated or weights reloaded since the capture: the graph is stale
         for p in self.leaves.values():
             p.grad = None
-        logits = self.forward(batch, dropout_mask, seed)
-        ce = self.cross_entropy(logits, batch["labels"])
-        if st.n_l2 > 0:      # trainable part of the L2 loss, on the pre-update weights
-            ops.sumsq(st.theta, st.n_l2, self.l2_scratch, self.l2_buf)
-        self.reducer.begin_step()
-        ce.backward()          # engines call reducer.stage_done(...): bucket 1 is all-reduced under the backward
+        if self.frozen_bn:     # the statistics mode of this forward and backward: moving statistics, read-only
+            self.image.frozen_step = True
+        try:
+            logits = self.forward(batch, dropout_mask, seed)
+            ce = self.cross_entropy(logits, batch["labels"])
+            if st.n_l2 > 0:      # trainable part of the L2 loss, on the pre-update weights
+                ops.sumsq(st.theta, st.n_l2, self.l2_scratch, self.l2_buf)
+            self.reducer.begin_step()
+            ce.backward()          # engines call reducer.stage_done(...): bucket 1 is all-reduced under the backward
+        finally:
+            if self.frozen_bn:
+                self.image.frozen_step = False
         grad_scale = self.reducer.finish()
         ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
                     ADAM_B1, ADAM_B2, ADAM_EPS)
@@ -531,6 +550,8 @@ class SentimentNet:
         of ~900 kernel launches, which is what bounds the step below ~64 samples per GPU.  Per-step scalars (Adam's
         lr_t, the dropout seed) are read from device memory.  Single rank only: with data parallelism the RCCL
         all-reduce stays outside a graph and the eager step is used."""
+        if self.frozen_bn:
+            raise NotImplementedError("capture_step is not implemented for a frozen_bn net")
         if self.reducer.active:
             return False
         st = self.store

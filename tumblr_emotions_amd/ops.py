@@ -752,6 +752,35 @@ def bn_infer_bwd_apply(z, segs, M, C_, rstd, shift, dz, ldz=0):
                                                  _stream()), "ds_bn_infer_bwd_apply")
 
 
+def bn_infer_bwd_partials(M, C_):
+    return _lib.load().ds_bn_infer_bwd_partials(M, C_)
+
+
+def bn_infer_bwd_apply_sums(z, segs, M, C_, rstd, shift, dz, partials, ldz=0):
+    """ds_bn_infer_bwd_apply that also emits the column sums of g = dy * [z*rstd + shift > 0] as partials [C, P],
+    P = bn_infer_bwd_partials(M, C) (frozen-BatchNorm training: dbeta).  dz None: the sums only."""
+    ptr = lambda t: t if isinstance(t, C.c_void_p) else _p(t)
+    _lib.check(_lib.load().ds_bn_infer_bwd_apply_sums(ptr(z), ldz or C_, C.byref(segs), M, C_, ptr(rstd), ptr(shift), ptr(dz),
+                                                      ptr(partials), _stream()), "ds_bn_infer_bwd_apply_sums")
+
+
+class BnSumJobs:
+    """ds_bn_dbeta_reduce_multi: the beta gradients of every listed layer from its partial sums as ONE launch.
+    jobs: (partials address or tensor, P, C, dbeta tensor)."""
+
+    def __init__(self, jobs):
+        self.n = len(jobs)
+        self.arr = (_lib.BnSumJob * self.n)()
+        self._keep = jobs
+        for a, (partials, P, C_, dbeta) in zip(self.arr, jobs):
+            a.partials = partials if isinstance(partials, int) else partials.data_ptr()
+            a.P, a.C, a.dbeta = P, C_, dbeta.data_ptr()
+
+    def run(self):
+        _lib.check(_lib.load().ds_bn_dbeta_reduce_multi(C.cast(self.arr, C.c_void_p), self.n, _stream()),
+                   "ds_bn_dbeta_reduce_multi")
+
+
 def maxpool_fwd(x, y, argmax, N, H, W, C_, k, stride, mode="SAME"):
     if mode == "SAME":
         OH, pt = same_pad(H, k, stride)
@@ -801,6 +830,16 @@ def bn_pool_infer_bwd_apply(z, dpool, argmax, N, H, W, C_, rstd, shift, dz):
     OW, pl = same_pad(W, 3, 2)
     _lib.check(_lib.load().ds_bn_pool_infer_bwd_apply(_p(z), _p(dpool), _p(argmax), N, H, W, C_, pt, pl, OH, OW, _p(rstd),
                                                       _p(shift), _p(dz), _stream()), "ds_bn_pool_infer_bwd_apply")
+
+
+def bn_pool_infer_bwd_apply_sums(z, dpool, argmax, N, H, W, C_, rstd, shift, dz, partials):
+    """ds_bn_pool_infer_bwd_apply that also emits the column sums of g as partials [C, P], P = bn_pool_bwd_partials(N, H, W, C)
+    (frozen-BatchNorm training: dbeta).  dz None: the sums only."""
+    OH, pt = same_pad(H, 3, 2)
+    OW, pl = same_pad(W, 3, 2)
+    _lib.check(_lib.load().ds_bn_pool_infer_bwd_apply_sums(_p(z), _p(dpool), _p(argmax), N, H, W, C_, pt, pl, OH, OW, _p(rstd),
+                                                           _p(shift), _p(dz), _p(partials), _stream()),
+               "ds_bn_pool_infer_bwd_apply_sums")
 
 
 def maxpool_bwd(dy, argmax, dx, accumulate, N, H, W, C_, k, stride, mode="SAME"):

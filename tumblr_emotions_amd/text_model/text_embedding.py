@@ -22,6 +22,8 @@ _POST_SIZE = 50                                 # datasets/convert_to_dataset.py
 class TextModel(SyntheticInput):
     def __init__(self, config, nb_emotions=15, embedding=None, device="cuda", **net_kw):
         self.config = config
+        if config.get('frozen_bn'):
+            raise ValueError("config['frozen_bn']: the text model has no BatchNorm")
         self.learning_rate = config['initial_lr']
         post = config.get('post_size', _POST_SIZE)
         # GloVe file -> [V, D] + zero <ukn> row; V and D come from the file (:61-66)
