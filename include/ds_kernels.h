@@ -583,6 +583,14 @@ int ds_bn_bwd_finalize_apply(const ds_bn_sum_segments *sg, const float *beta, fl
 /* Inception concat buffer is differentiated in place there                                                          */
 int ds_bn_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *mean,
                     const float *rstd, const float *shift, const float *coef, float *dz, float *amax, void *stream);
+/* ds_bn_bwd_apply over a COLUMN RANGE of a layer: z / dz / mean / rstd / shift point at the range's first column, dy's
+ * segments count from it, and the two coefficient vectors come separately -- coef_g = coef + c0, coef_gx = coef + C + c0 of the
+ * layer's float[2][C] -- because the second no longer follows the first at + ncols.  fp32, no second addend, no amax.  The
+ * fused 1x1 layer of a Mixed block in front of a stride-2 pool: its reduce columns here, its Branch_0 columns through
+ * ds_bn_pool_bwd_apply_cols.  The same kernel and per-element arithmetic as ds_bn_bwd_apply: bit-identical.              */
+int ds_bn_bwd_apply_cols(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t ncols, const float *mean,
+                         const float *rstd, const float *shift, const float *coef_g, const float *coef_gx, float *dz,
+                         void *stream);
 /* The moving-statistics twin (is_training=False: BatchNorm is a fixed per-channel affine map, its backward pointwise):
  * dz = rstd * dy * [z*rstd + shift > 0], the predicate evaluated as ds_bn_apply_relu evaluates it.  No mean, no coef, no
  * sums.  dy as for ds_bn_bwd_apply (up to four segments, ptr2 second addends honoured); ldz: row stride of z AND dz; dz may
@@ -641,6 +649,19 @@ int ds_bn_pool_bwd_reduce(const float *z, const float *dpool, const uint8_t *arg
 int ds_bn_pool_bwd_apply(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H, int32_t W,
                          int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW, const float *mean,
                          const float *rstd, const float *shift, const float *coef, float *dz, void *stream);
+/* ... and the apply for a COLUMN RANGE of a layer whose output gradient is the gradient of a stride-2 SAME max pool of a
+ * wider tensor: the concat of an Inception block in front of MaxPool_4a_3x3 (k = 3: 3x3/2) or MaxPool_5a_2x2 (k = 2: 2x2/2;
+ * inception_v1.py:118,208).  dpool / argmax: the pool's gradient and winners [N, OH, OW, Cp]; the range is their columns
+ * [c0, c0 + ncols).  z [N, H, W, ldz] and dz [N, H, W, lddz] point at the range's first column in their own tensors, as do
+ * mean / rstd / shift / coef_g / coef_gx (the two column means of ds_bn_bwd_finalize*).  dz may alias z: every input pixel
+ * belongs to exactly one patch and a patch's z values are loaded before its stores.  ncols, c0 and the strides are multiples of
+ * 4, pointers 16-byte aligned, H <= 2 OH, W <= 2 OW (k = 2: H + pad_t <= 2 OH too, so that no pixel is left out).  The pool
+ * gradient is rebuilt with ds_maxpool_bwd's own order of addends and dz formed as ds_bn_bwd_apply forms it: the bits of
+ * those two launches, without the full-resolution gradient between them.                                                  */
+int ds_bn_pool_bwd_apply_cols(const float *z, int32_t ldz, float *dz, int32_t lddz, const float *dpool, const uint8_t *argmax,
+                              int32_t Cp, int32_t c0, int32_t N, int32_t H, int32_t W, int32_t pad_t, int32_t pad_l, int32_t OH,
+                              int32_t OW, int32_t ncols, const float *mean, const float *rstd, const float *shift,
+                              const float *coef_g, const float *coef_gx, int32_t k, void *stream);
 /* ... and the moving-statistics twin of the apply: dz = rstd * g * [z*rstd + shift > 0], g the pool's gradient rebuilt per
  * patch from the pooled gradient and the arg-max record (dz may alias z)                                                    */
 int ds_bn_pool_infer_bwd_apply(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H, int32_t W,

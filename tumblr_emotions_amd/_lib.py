@@ -242,6 +242,7 @@ SIGNATURES = {
     "ds_bn_finalize_apply_relu": (C.c_int, [_P, _i32, _i64, _i32, _P, _P, _f32, _f32, _P, _P, _P, _P, _P, _P, _i64, _SG, _P, _P]),
     "ds_bn_bwd_finalize_apply": (C.c_int, [_SS, _P, _P, _P, _P, _P, _P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _i32, _i32, _P, _P, _P]),
     "ds_bn_bwd_apply": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _P, _P]),
+    "ds_bn_bwd_apply_cols": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _P, _P]),
     "ds_bn_infer_bwd_apply": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P]),
     "ds_bn_infer_bwd_partials": (C.c_int, [_i64, _i32]),
     "ds_bn_infer_bwd_apply_sums": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P]),
@@ -252,6 +253,7 @@ SIGNATURES = {
     "ds_bn_pool_bwd_partials": (C.c_int, [_i32, _i32, _i32, _i32]),
     "ds_bn_pool_bwd_reduce": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P, _P]),
     "ds_bn_pool_bwd_apply": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P, _P, _P]),
+    "ds_bn_pool_bwd_apply_cols": (C.c_int, [_P, _i32, _P, _i32, _P, _P] + [_i32] * 10 + [_P, _P, _P, _P, _P, _i32, _P]),
     "ds_bn_pool_infer_bwd_apply": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P]),
     "ds_bn_pool_infer_bwd_apply_sums": (C.c_int, [_P, _P, _P] + [_i32] * 8 + [_P, _P, _P, _P, _P]),
     "ds_maxpool_bwd": (C.c_int, [_P, _P, _P] + [_i32] * 11 + [_P]),

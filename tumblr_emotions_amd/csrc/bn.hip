@@ -482,14 +482,16 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_segs_kernel(SumSegDev sg,
 template <bool OUT16, bool COH = false, bool ADD2 = false, bool Z16 = false>
 __device__ __forceinline__ void bwd_apply_body(int bid, const float *z, int ldz, const SegDev &dy, int64_t M, int C,
                                                const float *mean, const float *rstd, const float *shift,
-                                               const float *coef, float *dz, float *amax, int drow, int lddz) {
+                                               const float *coef, float *dz, float *amax, int drow, int lddz,
+                                               const float *coef_gx = nullptr) {
     // (thread = one float4 column group, rows row0, row0 + drow, ...: see bn_apply_relu_kernel)
+    // coef_gx: the second coefficient vector where it does not follow the first at + C (ds_bn_bwd_apply_cols)
     const int C4 = C >> 2;
     const int t0 = bid * 256 + threadIdx.x;
     const int row0 = t0 / C4, c = (t0 - row0 * C4) * 4;
     const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c), s4 = *reinterpret_cast<const float4 *>(shift + c);
     const float4 m4 = *reinterpret_cast<const float4 *>(mean + c);
-    const float4 k14 = ld_res4<COH>(coef + c), k24 = ld_res4<COH>(coef + C + c);
+    const float4 k14 = ld_res4<COH>(coef + c), k24 = ld_res4<COH>((coef_gx ? coef_gx : coef + C) + c);
     const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
     const float a1[4] = {k14.x, k14.y, k14.z, k14.w}, a2[4] = {k24.x, k24.y, k24.z, k24.w};
     int sgi = 0;
@@ -550,8 +552,9 @@ __device__ __forceinline__ void bwd_apply_body(int bid, const float *z, int ldz,
 template <bool OUT16, bool ADD2 = false, bool Z16 = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *z, int ldz, SegDev dy, int64_t M, int C,
                                                            const float *mean, const float *rstd, const float *shift,
-                                                           const float *coef, float *dz, float *amax, int drow, int lddz) {
-    bwd_apply_body<OUT16, false, ADD2, Z16>((int)blockIdx.x, z, ldz, dy, M, C, mean, rstd, shift, coef, dz, amax, drow, lddz);
+                                                           const float *coef, float *dz, float *amax, int drow, int lddz,
+                                                           const float *coef_gx = nullptr) {
+    bwd_apply_body<OUT16, false, ADD2, Z16>((int)blockIdx.x, z, ldz, dy, M, C, mean, rstd, shift, coef, dz, amax, drow, lddz, coef_gx);
 }
 
 // ---- moving-statistics (is_training=False) backward ------------------------------------------------------------------------
@@ -1045,6 +1048,21 @@ extern "C" int ds_bn_bwd_apply(const float *z, int32_t ldz, const ds_segments *d
         hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, mean, rstd,
                            shift, coef, dz, amax, drow, ldz);
     return ds::check_launch("ds_bn_bwd_apply");
+}
+
+extern "C" int ds_bn_bwd_apply_cols(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t ncols, const float *mean,
+                                    const float *rstd, const float *shift, const float *coef_g, const float *coef_gx, float *dz,
+                                    void *stream) {
+    DS_REQUIRE(z && mean && rstd && shift && coef_g && coef_gx && dz && M > 0 && ncols > 0 && ncols % 4 == 0 && ldz >= ncols &&
+                   ldz % 4 == 0 && ((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)coef_g) | ((uintptr_t)coef_gx)) & 15) == 0,
+               "ds_bn_bwd_apply_cols: bad argument (need ncols %% 4 == 0, ldz >= ncols, ldz %% 4 == 0, 16-byte aligned z / dz / coef)");
+    if (int e = check_segments(dy, ncols, "ds_bn_bwd_apply_cols")) return e;
+    DS_REQUIRE(!has_second_addend(dy), "ds_bn_bwd_apply_cols: no second addend");
+    int drow;
+    const int grid = column_grid(M, ncols / 4, &drow);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, ncols, mean, rstd,
+                       shift, coef_g, dz, (float *)nullptr, drow, ldz, coef_gx);
+    return ds::check_launch("ds_bn_bwd_apply_cols");
 }
 
 extern "C" int ds_bn_bwd_apply_z16(const void *z16, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *mean,

@@ -773,6 +773,83 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const float *z, 
     }
 }
 
+// ds_bn_pool_bwd_apply_cols: the same pass for a COLUMN RANGE of a layer behind a stride-2 pool of a wider tensor -- the
+// concat of a Mixed block in front of MaxPool_4a_3x3 / MaxPool_5a_2x2.  dpool / am point at the range's first column of the
+// pooled tensors (pixel stride Cp), z and dz have pixel strides of their own, c runs over [0, ncols).  K = 3: the 2x2 patches of
+// the 3x3/2 pool (patch_grad: maxpool3s2_bwd_patch's order of the up to four addends); K = 2: the 2x2/2 pool, whose windows
+// do not overlap -- the patch IS window (p, q) and a pixel has the one addend of maxpool_bwd_kernel<2, 2> or none.  dz by
+// ds::bn_bwd_dz: the bits of ds_maxpool_bwd followed by ds_bn_bwd_apply.
+template <int K>
+__global__ __launch_bounds__(256) void bn_pool_bwd_apply_cols_kernel(const float *z, int ldz, float *dz, int lddz,
+                                                                     const float *dpool, const uint8_t *am, int Cp, int N,
+                                                                     int H, int W, int pad_t, int pad_l, int OH, int OW,
+                                                                     int ncols, const float *mean, const float *rstd,
+                                                                     const float *shift, const float *coef_g,
+                                                                     const float *coef_gx) {
+    constexpr int E = K == 3 ? 1 : 0;      // 3x3/2: one patch more than windows per axis, the first one at p = -1
+    const int C4 = ncols >> 2;
+    const int PH = OH + E, PW = OW + E;
+    const int64_t total = (int64_t)N * PH * PW * C4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i % C4) * 4;
+        int64_t r = i / C4;
+        const int q = (int)(r % PW) - E;
+        r /= PW;
+        const int p = (int)(r % PH) - E;
+        const int n = (int)(r / PH);
+        PatchGrad pg;
+        if constexpr (K == 3) {
+            pg = patch_grad(dpool, am, n, p, q, c, Cp, OH, OW);
+        } else {
+            const int64_t o = (((int64_t)n * OH + p) * OW + q) * Cp + c;
+            const unsigned a = *reinterpret_cast<const unsigned *>(am + o);
+            const float4 t = *reinterpret_cast<const float4 *>(dpool + o);
+            const float d[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (int y = 0; y < 2; ++y)
+#pragma unroll
+                for (int x = 0; x < 2; ++x)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        pg.g[y][x][j] = 0.f;
+                        if (((a >> (8 * j)) & 0xFFu) == (unsigned)(y * 2 + x)) pg.g[y][x][j] += d[j];
+                    }
+        }
+        const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c);
+        const float4 s4 = *reinterpret_cast<const float4 *>(shift + c);
+        const float4 m4 = *reinterpret_cast<const float4 *>(mean + c);
+        const float4 k1 = *reinterpret_cast<const float4 *>(coef_g + c);
+        const float4 k2 = *reinterpret_cast<const float4 *>(coef_gx + c);
+        const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
+        const float a1[4] = {k1.x, k1.y, k1.z, k1.w}, a2[4] = {k2.x, k2.y, k2.z, k2.w};
+        // (the patch's four z loads before its four stores, as in bn_pool_bwd_apply_kernel; dz may lie over z)
+        float4 zv[2][2];
+        bool ok[2][2];
+        int64_t pix[2][2];
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                const int ih = 2 * p - pad_t + E + y, iw = 2 * q - pad_l + E + x;
+                ok[y][x] = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
+                pix[y][x] = ((int64_t)n * H + ih) * W + iw;
+                zv[y][x] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ok[y][x]) zv[y][x] = ds::ld_stream4(z + pix[y][x] * ldz + c);
+            }
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                if (!ok[y][x]) continue;
+                const float zz[4] = {zv[y][x].x, zv[y][x].y, zv[y][x].z, zv[y][x].w};
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = ds::bn_bwd_dz(zz[j], pg.g[y][x][j], rr[j], ss[j], mm[j], a1[j], a2[j]);
+                *reinterpret_cast<float4 *>(dz + pix[y][x] * lddz + c) = make_float4(o[0], o[1], o[2], o[3]);
+            }
+    }
+}
+
 // ds_bn_pool_infer_bwd_apply: the same patch walk for the moving-statistics backward -- dz = rstd * g * [z*rstd + shift > 0]
 // with g the pool's gradient rebuilt per 2x2 patch; no mean, no coef
 __global__ __launch_bounds__(256) void bn_pool_infer_bwd_apply_kernel(const float *z, const float *dpool, const uint8_t *am,
@@ -1079,6 +1156,40 @@ extern "C" int ds_bn_pool_bwd_apply(const float *z, const float *dpool, const ui
     hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3(pool_bwd_grid(N, OH, OW, C)), dim3(256), 0, (hipStream_t)stream, z,
                        dpool, argmax, N, H, W, C, pad_t, pad_l, OH, OW, mean, rstd, shift, coef, dz);
     return ds::check_launch("ds_bn_pool_bwd_apply");
+}
+
+extern "C" int ds_bn_pool_bwd_apply_cols(const float *z, int32_t ldz, float *dz, int32_t lddz, const float *dpool,
+                                         const uint8_t *argmax, int32_t Cp, int32_t c0, int32_t N, int32_t H, int32_t W,
+                                         int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW, int32_t ncols,
+                                         const float *mean, const float *rstd, const float *shift, const float *coef_g,
+                                         const float *coef_gx, int32_t k, void *stream) {
+    DS_REQUIRE(z && dz && dpool && argmax && mean && rstd && shift && coef_g && coef_gx,
+               "ds_bn_pool_bwd_apply_cols: null pointer");
+    DS_REQUIRE(k == 2 || k == 3, "ds_bn_pool_bwd_apply_cols: kernel size %d (3: 3x3/2, 2: 2x2/2 pools only)", k);
+    DS_REQUIRE(ncols > 0 && ncols % 4 == 0 && c0 >= 0 && c0 % 4 == 0 && Cp % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0,
+               "ds_bn_pool_bwd_apply_cols: ncols %d, first column %d and the strides %d / %d / %d must be multiples of 4", ncols, c0,
+               ldz, lddz, Cp);
+    DS_REQUIRE(ldz >= ncols && lddz >= ncols && Cp >= c0 + ncols,
+               "ds_bn_pool_bwd_apply_cols: stride smaller than the column range (ldz %d, lddz %d, pool %d < %d + %d)", ldz, lddz, Cp,
+               c0, ncols);
+    DS_REQUIRE(N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && pad_t >= 0 && pad_t <= 1 && pad_l >= 0 && pad_l <= 1,
+               "ds_bn_pool_bwd_apply_cols: bad geometry");
+    // every input pixel in exactly one patch: 3x3/2 patches reach row 2 OH - pad_t, 2x2/2 windows row 2 OH - pad_t - 1
+    DS_REQUIRE(H <= 2 * OH && W <= 2 * OW && (k == 3 || (H + pad_t <= 2 * OH && W + pad_l <= 2 * OW)),
+               "ds_bn_pool_bwd_apply_cols: H > 2 OH or W > 2 OW (stride-2 SAME pools only)");
+    DS_REQUIRE(((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)dpool) | ((uintptr_t)mean) | ((uintptr_t)rstd) | ((uintptr_t)shift) |
+                 ((uintptr_t)coef_g) | ((uintptr_t)coef_gx)) & 15) == 0 && (((uintptr_t)argmax) & 3) == 0,
+               "ds_bn_pool_bwd_apply_cols: 16-byte aligned tensors and vectors, 4-byte aligned winners");
+    // (the neighbours' grid: sized for the (OH + 1)(OW + 1) patches of k = 3 and rounded for the reduce kernel's fixed channel
+    // group per thread; this kernel needs neither -- k = 2 has OH * OW patches -- and its grid-stride loop makes both harmless)
+    const dim3 grid(pool_bwd_grid(N, OH, OW, ncols));
+    if (k == 3)
+        hipLaunchKernelGGL(bn_pool_bwd_apply_cols_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, z, ldz, dz, lddz, dpool + c0,
+                           argmax + c0, Cp, N, H, W, pad_t, pad_l, OH, OW, ncols, mean, rstd, shift, coef_g, coef_gx);
+    else
+        hipLaunchKernelGGL(bn_pool_bwd_apply_cols_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, z, ldz, dz, lddz, dpool + c0,
+                           argmax + c0, Cp, N, H, W, pad_t, pad_l, OH, OW, ncols, mean, rstd, shift, coef_g, coef_gx);
+    return ds::check_launch("ds_bn_pool_bwd_apply_cols");
 }
 
 extern "C" int ds_bn_pool_infer_bwd_apply(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H,

@@ -226,6 +226,7 @@ class ConvBN:
         self.dy2 = False                         # some part has a second addend (dy_segs.ptr2): see MixedStage.alloc, split_dout
         self.part_pool = [None] * len(parts)     # (pool stage, first column): the part feeds nothing but that max pool
         self._sum_segs = None
+        self._rest_segs = None                   # parts 1.. counted from part 0's end (_bwd_apply_pooled)
 
     def sums_from(self, part, src, src2=None):
         """Part `part` takes its sums from the dgrad epilogue that writes its gradient (src2: its second addend's, dy2)."""
@@ -628,7 +629,22 @@ class ConvBN:
         self.dgrad.d.x_dtype = ops.DS_DTYPE_F32
         self.dgrad.run(ops._p(self.z), self.w_ptr, dx_ptr, mask=y, stats=sums, x_amax=ops._p(am))
 
-    def backward(self, x_ptr=None, ldx=0, dx_ptr=None, need_dx=True):
+    def _bwd_apply_pooled(self, pool):
+        """ds_bn_bwd_apply of a Mixed block's fused 1x1 layer whose part 0 (Branch_0, the concat's columns [0, b0)) feeds nothing
+        but the stride-2 max pool `pool`: part 0 from the pooled gradient and the winners (ds_bn_pool_bwd_apply_cols; the
+        concat's gradient is not read), the reduce outputs' parts from their dense gradients as before."""
+        b0, nf = self.dy_parts[0][1], self.cout
+        if self._rest_segs is None:
+            self._rest_segs = make_segments([(c0 - b0, c1 - b0, ptr, ld) for (c0, c1, ptr, ld) in self.dy_parts[1:]])
+        ops.bn_pool_bwd_apply_cols(self.z, nf, self.z, nf, pool.dout, pool.argmax, pool.C, 0, self.B, self.OH, self.OW, b0,
+                                   self.mean, self.rstd, self.shift, self.coef[0], self.coef[1], pool.k)
+        zr = self.z[:, b0:]
+        ops.bn_bwd_apply_cols(zr, self._rest_segs, self.M, nf - b0, self.mean[b0:], self.rstd[b0:], self.shift[b0:],
+                              self.coef[0, b0:], self.coef[1, b0:], zr, ldz=nf)
+
+    def backward(self, x_ptr=None, ldx=0, dx_ptr=None, need_dx=True, pool=None):
+        """pool: the stride-2 max pool that is the only consumer of part 0 of this layer's output, whose full-resolution gradient
+        was NOT written (MixedStage pooled_bwd; the sums of that part come from the pooled tensors, sums_from_pool)."""
         eng = self.eng
         M, Cc = self.M, self.cout
         dy_segs = self.dy_segs
@@ -639,6 +655,7 @@ class ConvBN:
         dz = self.z if self.dz16 is None else self.dz16          # dz over z, or into its own bf16 tensor
         if eng.fuse_fin_apply and not eng.sync_bn and (need_dx or self.trainable) and not self.bnb and not self.dy2 and not self.z16:
             # the finalize and the apply pass behind it as ONE launch (ds_bn_bwd_finalize_apply)
+            assert pool is None
             if from_parts:
                 sg = self._sum_plan()
                 self._run_reduce_jobs()
@@ -664,8 +681,12 @@ class ConvBN:
             if self.bnb:              # z stays as it is: the dgrad's loader forms dz
                 self._run_dgrad(dx_ptr)
                 return
-            ops.bn_bwd_apply(self.z, dy_segs, M, Cc, self.zmean, self.rstd, self.zshift, self.coef, dz,
-                             amax=self.dz_amax if track else None, ldz=self.ldz)
+            if pool is not None:
+                assert from_parts and not self.bnb and not track and dz is self.z and self.ldz == Cc
+                self._bwd_apply_pooled(pool)
+            else:
+                ops.bn_bwd_apply(self.z, dy_segs, M, Cc, self.zmean, self.rstd, self.zshift, self.coef, dz,
+                                 amax=self.dz_amax if track else None, ldz=self.ldz)
         self._dz_amax_live = track
         if self.trainable:
             self._run_wgrad(x_ptr, ldx)
@@ -685,6 +706,7 @@ class Stage:
     raw = False                # PoolStage: `out` holds raw window maxima of the stem's z
     out_amax = None            # fp8: the device record of max|out|
     fused_into_pool = False    # ConvStage: feeds nothing but the next max pool, which applies BatchNorm + ReLU
+    pooled_bwd = False         # MixedStage in front of a stride-2 pool: its backward reads the POOLED gradient (PoolStage.alloc)
     track_amax = True          # PoolStage (fp8): some fp8 conv reads `out` (InceptionV1Engine._prune_amax)
 
 
@@ -829,6 +851,15 @@ class PoolStage(Stage):
             targets = p.concat_layers()
         for layer, off in targets:
             layer.sums_from_pool(0, self, off)
+        # ... and such a block (Mixed_3c, Mixed_4f) also APPLIES its BatchNorm backward from the pooled tensors
+        # (ds_bn_pool_bwd_apply_cols): this stage launches no MaxPoolGrad and the block's full-resolution `dout` is neither
+        # written nor read.  fp32 zcat blocks with the block-batched backward; MixedStage.backward keeps the former path for the
+        # passes that cannot take it (moving statistics, sync_bn, DS_FIN_APPLY).  `dout` stays allocated for those.
+        eng = self.eng
+        p.pooled_bwd = bool(eng.pool_apply and isinstance(p, MixedStage) and targets and self.stride == 2 and self.k in (2, 3)
+                            and eng.dtype == "f32" and not eng.act16 and p.fused.dgrad.family != ops.DS_FAM_FP8D
+                            and p.zcat and (p.batch_bn & 2) and not eng.split_dout and not p.fused.bnb and p.fused.dz16 is None
+                            and not p.fused.z16 and p.b[0] % 4 == 0)
 
     @property
     def out_amax(self):
@@ -862,7 +893,7 @@ class PoolStage(Stage):
         p = self.prev
         if p.fused_into_pool and self.stride == 2:
             return          # the conv in front consumes self.dout / self.argmax directly (ConvBN.backward_pooled)
-        if need_dx:
+        if need_dx and not p.pooled_bwd:      # (pooled_bwd: the block in front takes self.dout / self.argmax itself, MixedStage.backward)
             ops.maxpool_bwd(self.dout, self.argmax, p.dout, False, self.B, p.H, p.W, p.C, self.k, self.stride, "SAME")
 
 
@@ -1146,9 +1177,10 @@ class MixedStage(Stage):
         return bool((self.batch_bn & 2) and need_dx and not eng.sync_bn
                     and all(l.dz16 is None and not l.bnb and l.dgrad.family != ops.DS_FAM_FP8D for l in (self.c1, self.c2, self.c3)))
 
-    def _bn_backward_closing(self):
+    def _bn_backward_closing(self, from_pool=False):
         """BatchNorm + ReLU backward of the three block-closing layers as one pass over the columns [b0, Ct) of the concat:
-        their sums (from the next block's dgrad epilogue, or reduced per layer), ONE finalize, ONE apply that leaves dz over z."""
+        their sums (from the next block's dgrad epilogue, or reduced per layer), ONE finalize, ONE apply that leaves dz over z.
+        from_pool: the apply rebuilds the gradient from the stride-2 pool behind the block (pooled_bwd); self.dout is not read."""
         b0 = self.b[0]
         Ct, Cb = self.C, self.C - b0
         M = self.B * self.H * self.W
@@ -1175,7 +1207,12 @@ class MixedStage(Stage):
                                       dbetas=[l.gbeta for l in layers])
         else:
             ops.bn_bwd_finalize_multi(sg, M, Cb, [l.beta for l in layers], [l.gbeta for l in layers], self.coef_cat)
-            ops.bn_bwd_apply(z, dy, M, Cb, self.mean_cat[b0:], self.rs_cat[0, b0:], self.rs_cat[1, b0:], self.coef_cat, z, ldz=Ct)
+            if from_pool:
+                nx = self.next
+                ops.bn_pool_bwd_apply_cols(z, Ct, z, Ct, nx.dout, nx.argmax, Ct, b0, self.B, self.H, self.W, Cb, self.mean_cat[b0:],
+                                           self.rs_cat[0, b0:], self.rs_cat[1, b0:], self.coef_cat[0], self.coef_cat[1], nx.k)
+            else:
+                ops.bn_bwd_apply(z, dy, M, Cb, self.mean_cat[b0:], self.rs_cat[0, b0:], self.rs_cat[1, b0:], self.coef_cat, z, ldz=Ct)
         for l in layers:
             l._dz_amax_live = False
 
@@ -1211,8 +1248,14 @@ class MixedStage(Stage):
 
         infer = eng.infer_bwd        # moving-statistics backward: pointwise BatchNorm passes, plain pool gradients, no sums
         batched = self._batch_backward(need_dx) and not infer
+        # pooled_bwd (Mixed_3c / 4f): the gradient of this block's output exists only pooled, behind the stride-2 pool -- both
+        # apply passes that would read self.dout rebuild it from there.  A pass that cannot has the pool gradient written first
+        from_pool = self.pooled_bwd and batched and not eng.fuse_fin_apply
+        if self.pooled_bwd and not from_pool:
+            nx = self.next
+            ops.maxpool_bwd(nx.dout, nx.argmax, self.dout, False, self.B, self.H, self.W, self.C, nx.k, nx.stride, "SAME")
         if batched:                  # BatchNorm backward of the three block-closing layers: two launches in front of the fork
-            self._bn_backward_closing()
+            self._bn_backward_closing(from_pool)
         if infer and self.zcat:      # the block-closing layers' z are the columns [b0, Ct) of the concat: ONE pointwise pass
             M, Ct = self.B * self.H * self.W, self.C
             if self._infer_close is None:
@@ -1263,7 +1306,7 @@ class MixedStage(Stage):
             if need_dx and not pool_first and not self.split_dout:
                 ops.maxpool_bwd(self.dpooled, self.argmax, p.dout, True, self.B, p.H, p.W, p.C, 3, 1, "SAME")
             return
-        self.fused.backward(x, p.C, ops._p(p.dout) if need_dx else None, need_dx)
+        self.fused.backward(x, p.C, ops._p(p.dout) if need_dx else None, need_dx, pool=self.next if from_pool else None)
         if need_dx and self.split_dout:             # the sums of the dgrad's addend (the pool gradient's came with it: branch3)
             ops.bn_bwd_reduce(p.out, self._dgrad_sum_segs, self.B * p.H * p.W, p.C, eng.zeros, eng.ones, eng.zeros, self.dgrad_sums,
                               ldz=p.C)
@@ -1338,6 +1381,11 @@ class InceptionV1Engine:
         self.mul3 = _lib.tuning_env("DS_MUL3", "0") == "1"     # opt-in: forward 1x1 convs with fp32 products on the bf16 matrix cores
         self.bnb_on_load = int(_lib.tuning_env("DS_BNB", "1"))      # BatchNorm backward formed by the 1x1 dgrad's loader: see ConvBN.make_dgrad
         self.zcat = _lib.tuning_env("DS_ZCAT", "1") != "0"     # 3x3 / Branch_3 convs write z into the concat, consumers normalise on load
+        # Mixed_3c / Mixed_4f: BatchNorm backward apply straight from the stride-2 pool's gradient, no full-resolution concat
+        # gradient (PoolStage.alloc, MixedStage.backward): bit-identical (tests), -1.10 GB of HBM traffic per step at B = 256 by the
+        # shapes, the two MaxPoolGrad launches (0.18 ms alone on the chip, profiles/r06h_timeline.txt) off the chain.  The step-time
+        # effect is NOT measured yet (profiles/pool_apply_notes.md says what is and what is not).  DS_POOL_APPLY=0: A/B
+        self.pool_apply = _lib.tuning_env("DS_POOL_APPLY", "1") != "0"
         # ds_bn_finalize inside the conv launch where the library can (ConvBN.plan_finalize; ds_conv_desc.fin).  Built, bit-identical
         # (tests), measured, OFF: the last arriver of a column tile re-reads up to 256 columns x 196 partials alone while the
         # separate launch spreads them over one workgroup per channel -- B = 32: 3.89 -> 4.36 ms, B = 64: 5.29 -> 5.59

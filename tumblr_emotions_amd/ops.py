@@ -744,6 +744,13 @@ def bn_bwd_apply(z, segs, M, C_, mean, rstd, shift, coef, dz, amax=None, ldz=0):
                                            _p(dz), _p(amax), _stream()), "ds_bn_bwd_apply")
 
 
+def bn_bwd_apply_cols(z, segs, M, ncols, mean, rstd, shift, coef_g, coef_gx, dz, ldz):
+    """ds_bn_bwd_apply over a column range of a layer (fp32): every tensor / vector points at the range's first column, the
+    two coefficient vectors come separately (their distance is the LAYER's column count, not the range's)."""
+    _lib.check(_lib.load().ds_bn_bwd_apply_cols(_p(z), ldz, C.byref(segs), M, ncols, _p(mean), _p(rstd), _p(shift), _p(coef_g),
+                                                _p(coef_gx), _p(dz), _stream()), "ds_bn_bwd_apply_cols")
+
+
 def bn_infer_bwd_apply(z, segs, M, C_, rstd, shift, dz, ldz=0):
     """Moving-statistics BatchNorm + ReLU backward, pointwise: dz = rstd * dy * [z*rstd + shift > 0] (dz over z, or any fp32
     tensor with z's row stride).  z .. dz: tensors or raw device addresses."""
@@ -822,6 +829,18 @@ def bn_pool_bwd_apply(z, dpool, argmax, N, H, W, C_, mean, rstd, shift, coef, dz
     OW, pl = same_pad(W, 3, 2)
     _lib.check(_lib.load().ds_bn_pool_bwd_apply(_p(z), _p(dpool), _p(argmax), N, H, W, C_, pt, pl, OH, OW, _p(mean),
                                                 _p(rstd), _p(shift), _p(coef), _p(dz), _stream()), "ds_bn_pool_bwd_apply")
+
+
+def bn_pool_bwd_apply_cols(z, ldz, dz, lddz, dpool, argmax, Cp, c0, N, H, W, ncols, mean, rstd, shift, coef_g, coef_gx, k):
+    """BatchNorm + ReLU backward apply of the columns [c0, c0 + ncols) of a k x k / 2 SAME max pool's input (k = 3 or 2) from the
+    POOLED gradient dpool and the winners argmax [N, OH, OW, Cp]: ds_maxpool_bwd + ds_bn_bwd_apply without the full-resolution
+    gradient between them, bit for bit.  z (pixel stride ldz), dz (lddz; may be z) and the per-column vectors point at the range's
+    first column."""
+    OH, pt = same_pad(H, k, 2)
+    OW, pl = same_pad(W, k, 2)
+    _lib.check(_lib.load().ds_bn_pool_bwd_apply_cols(_p(z), ldz, _p(dz), lddz, _p(dpool), _p(argmax), Cp, c0, N, H, W, pt, pl,
+                                                     OH, OW, ncols, _p(mean), _p(rstd), _p(shift), _p(coef_g), _p(coef_gx), k,
+                                                     _stream()), "ds_bn_pool_bwd_apply_cols")
 
 
 def bn_pool_infer_bwd_apply(z, dpool, argmax, N, H, W, C_, rstd, shift, dz):
