@@ -304,9 +304,14 @@ def part_jpeg(ds, args, results):
         recs.append(bytes(rec))
         if len(recs) == B:
             break
-    items = [P.decode_record_jpeg(r)[0] for r in recs]
-    st = P._Staging(B, 50, torch.device("cuda"), True, False, True)
-    used, ncoef, nj, copies = P.pack_ragged_jpeg(items, OUT, OUT, st)
+    cfg = P._Config(B, OUT, OUT, torch.device("cuda"), jpeg=True)
+    pool = P.OrderedPool(8)
+    pending = [(pool.submit(P.decode_record_jpeg, r), 0, i, None) for i, r in enumerate(recs)]
+    items = [P._next_item(e, cfg)[0] for e in pending]
+    pool.close()
+    st = P._Staging(cfg, 50)
+    plan = P.pack_batch(items, OUT, OUT, st)
+    used, ncoef, nj = plan.used, plan.ncoef, sum(rows for _, _, _, _, rows in plan.groups)
     coef = st.coef[:ncoef].cuda()
     ddesc = st.jdesc.cuda()
     out = torch.empty(used, dtype=torch.uint8, device="cuda")
@@ -414,7 +419,7 @@ def part_cache(ds, args, results):
     rng = np.random.RandomState(0)
     ch, cw = P.crop_box(H, W)[2:]
     for train in (False, True):
-        st = P._Staging(B, 50, torch.device("cuda"), True, train, False, False, True)
+        st = P._Staging(P._Config(B, OUT, OUT, torch.device("cuda"), train=train, cache_bytes=1), 50)
         t0 = time.perf_counter()
         for rep in range(20):
             items = []
@@ -424,8 +429,8 @@ def part_cache(ds, args, results):
                 if train:
                     p = sample_train_params(h, w, record_rng(0, rep, i))
                     box = (p.y0, p.x0, p.crop_h, p.crop_w)
-                items.append(P._CacheItem(i * (-(-h * w * 3 // 16) * 16), h, w, None, p, box))
-            P._pack_cached(items, OUT, OUT, st)
+                items.append(P._Item(i * (-(-h * w * 3 // 16) * 16), h, w, None, p, box))
+            P.pack_batch(items, OUT, OUT, st, cached=True)
         emit(results, what="cache_feeder_host_time", is_training=train, B=B,
              ms_per_batch=round((time.perf_counter() - t0) / 20 * 1e3, 3))
     # the kernel alone

@@ -180,7 +180,7 @@ def test_cached_record_stream_opens_only_what_the_plan_names(tmp_path, monkeypat
         Index.entries, Index.counts = {}, {}
         rng_a, rng_b = np.random.RandomState(5), np.random.RandomState(5)
         plain = P._record_stream(ds, True, rng_a, rank, world, True)
-        cached = P._cached_record_stream(ds, True, rng_b, rank, world, True, Index)
+        cached = P._record_stream(ds, True, rng_b, rank, world, True, Index)
         opens = []
         for pass_no in range(4):
             del opened[:]
@@ -189,11 +189,11 @@ def test_cached_record_stream_opens_only_what_the_plan_names(tmp_path, monkeypat
                 if a is P._EPOCH:
                     assert b is P._EPOCH
                     break
-                assert a[:2] == b[:2]
+                assert a[:3] == b[:3] and a[3] is not None
                 if b[3] is None:
                     assert b[2] in Index.entries
                 else:
-                    assert bytes(a[2]) == bytes(b[3])
+                    assert bytes(a[3]) == bytes(b[3])
                     Index.entries[b[2]] = True
             opens.append(len(opened) - 2)                     # the plain stream opens both files on every pass
         assert opens[0] == 2 and (opens[1:] == [0, 0, 0] if world == 1 else opens[-1] <= 2)

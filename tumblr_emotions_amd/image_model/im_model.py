@@ -113,20 +113,13 @@ def load_batch_with_text(dataset, batch_size=32, shuffle=True, height=299, width
     every record is decoded once, its uint8 pixels stay in an arena of cache_bytes bytes of device memory, and from the
     second pass on the batches are assembled from there by ds_ragged_gather -- the same batches bit for bit, no file read
     for a resident record; what does not fit is decoded again on every pass.  DeviceLoader.cache_stats() reports."""
-    if cache not in ('none', 'device'):
-        raise ValueError("cache must be 'none' or 'device', not %r" % (cache,))
+    from ..input_pipeline import DeviceLoader, check_switches
+    check_switches(jpeg_decode, jpeg_entropy, cache, cache_bytes)
     if cache == 'device' and pipeline != 'device':
         raise ValueError("cache='device' needs pipeline='device': the arena feeds the device preprocessing")
-    if jpeg_entropy not in ('host', 'device'):
-        raise ValueError("jpeg_entropy must be 'host' or 'device', not %r" % (jpeg_entropy,))
-    if jpeg_entropy == 'device' and jpeg_decode != 'device':
-        raise ValueError("jpeg_entropy='device' needs jpeg_decode='device': the coefficients go to ds_jpeg_reconstruct")
-    if jpeg_decode not in ('host', 'device'):
-        raise ValueError("jpeg_decode must be 'host' or 'device', not %r" % (jpeg_decode,))
     if jpeg_decode == 'device' and pipeline != 'device':
         raise ValueError("jpeg_decode='device' needs pipeline='device': the host pipeline decodes with PIL")
     if pipeline == 'device':
-        from ..input_pipeline import DeviceLoader
         return DeviceLoader(dataset, batch_size, shuffle, height, width, is_training, device, rank, world, seed, loop,
                             max_token_id, num_classes, workers=workers, prefetch=prefetch, decode_images=decode_images, jpeg_decode=jpeg_decode,
                             jpeg_entropy=jpeg_entropy, cache=cache, cache_bytes=cache_bytes)

@@ -48,7 +48,19 @@ record stream opens a file only when it does not know its size yet or a record o
 cached pass opens nothing and submits nothing to the pool; a pass starts only when the one before it has been consumed, so what
 is resident is known.  Nothing is evicted: once an image finds no room, nothing more is inserted, and such records are decoded
 on every pass into the staging set's spill buffer, which the same gather reads.
+
+Whatever the switches, a batch ends in the same two things -- the ragged byte buffer, laid out as pack_ragged lays it out, and
+the preprocessing descriptor table -- and is made by the same three steps.  _next_item turns a record of the stream into an
+_Item: what still has to be written for the image (a decoded array, JpegCoefs, JpegScan; nothing for a hit of the cache), the
+region that produces and the window of it that goes to the ragged buffer.  pack_batch, host only, lays the items out and
+returns a BatchPlan: the H2D copies, the ds_jpeg_desc rows grouped by the buffer they write (the ragged buffer; with the cache
+the arena and the spill buffer, followed by the gather), the coefficient uploads and the scan tables.  _run_plan issues the
+plan on the copy stream -- copies, entropy launch or coefficient upload, flagged_fallback (host only as well: it amends the
+plan for the images the Huffman kernel flagged), ds_jpeg_reconstruct once per buffer, the gather -- in front of the
+preprocessing kernel.  tests/test_input_batch_plan_cpu.py executes the same plans with the kernels' host statements.
 """
+import collections
+import functools
 import io
 import queue
 import threading
@@ -81,6 +93,27 @@ def clamp_workers(workers):
     return max(1, min(int(workers), MAX_WORKERS))
 
 
+def _round_up(n, m):
+    return -(-n // m) * m
+
+
+def _check_image(im, what):
+    if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
+        raise ValueError("%s: images must be non-empty uint8 [h, w, 3] arrays" % what)
+
+
+def _crop(h, w, train_key=None, whole=False):
+    """(box, TrainParams or None) of an h x w image: the whole image, the central crop, or the crop sample_train_params
+    draws from record_rng(*train_key)."""
+    if whole:
+        return (0, 0, h, w), None
+    if train_key is None:
+        return crop_box(h, w), None
+    from .preprocessing.inception_preprocessing import record_rng, sample_train_params
+    p = sample_train_params(h, w, record_rng(*train_key))
+    return (p.y0, p.x0, p.crop_h, p.crop_w), p
+
+
 def _desc_record(off, h, w, out_h, out_w, p=None):
     """One ds_preprocess_desc record (p None) or ds_preprocess_train_desc record of a crop of h x w pixels at byte `off`."""
     geom = (off, h, w, resize_scale(h, out_h), resize_scale(w, out_w))
@@ -104,10 +137,9 @@ def pack_ragged(images, out_h, out_w, out=None, desc=None, align=4, params=None)
         desc = np.zeros(n, preprocess_desc_dtype() if params is None else preprocess_train_desc_dtype())
     offsets, pos = [], 0
     for im in images:
-        if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
-            raise ValueError("pack_ragged: images must be non-empty uint8 [h, w, 3] arrays")
+        _check_image(im, "pack_ragged")
         offsets.append(pos)
-        pos = -(-(pos + im.size) // align) * align
+        pos = _round_up(pos + im.size, align)
     if out is None:
         out = np.zeros(max(pos, align), np.uint8)
     if out.size < pos:
@@ -178,7 +210,7 @@ class OrderedPool:
         self._threads = []
 
 
-def decode_record(rec, decode_image=True, train_key=None, whole=False):
+def decode_record(rec, train_key=None, whole=False, *, decode_image=True):
     """One TFRecord payload -> (cropped uint8 image or None, text int64[50], seq_len, label, post_id, day): the work of
     Dataset.examples for one record plus central_crop (only the cropped region is ever uploaded).  train_key = (seed, pass,
     global record index): the crop is the one sample_train_params draws from record_rng(*train_key), and the first item
@@ -201,14 +233,9 @@ def decode_pixels(data, train_key=None, whole=False):
     -- no crop at all."""
     from PIL import Image
     img = np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))
-    if whole:
-        return np.ascontiguousarray(img)
-    if train_key is None:
-        y0, x0, ch, cw = crop_box(img.shape[0], img.shape[1])
-        return np.ascontiguousarray(img[y0:y0 + ch, x0:x0 + cw])
-    from .preprocessing.inception_preprocessing import record_rng, sample_train_params
-    p = sample_train_params(img.shape[0], img.shape[1], record_rng(*train_key))
-    return np.ascontiguousarray(img[p.y0:p.y0 + p.crop_h, p.x0:p.x0 + p.crop_w]), p
+    (y0, x0, ch, cw), p = _crop(img.shape[0], img.shape[1], train_key, whole)
+    crop = np.ascontiguousarray(img[y0:y0 + ch, x0:x0 + cw])
+    return crop if p is None else (crop, p)
 
 
 # ---- jpeg_decode='device': coefficients instead of pixels ----------------------------------------------------------------------
@@ -262,14 +289,7 @@ def decode_jpeg_bytes(data, train_key=None):
 def _coefs(coef, info, train_key, whole=False):
     from . import ops
     h, w = int(info.height), int(info.width)
-    if whole:
-        box, p = (0, 0, h, w), None
-    elif train_key is None:
-        box, p = crop_box(h, w), None
-    else:
-        from .preprocessing.inception_preprocessing import record_rng, sample_train_params
-        p = sample_train_params(h, w, record_rng(*train_key))
-        box = (p.y0, p.x0, p.crop_h, p.crop_w)
+    box, p = _crop(h, w, train_key, whole)
     return JpegCoefs(coef, h, w, int(info.sampling), ops.jpeg_quant(info), box, p)
 
 
@@ -287,7 +307,7 @@ def decode_record_jpeg(rec, train_key=None, whole=False):
         buf = np.empty(size, np.int16)
         r = ops.jpeg_record_decode(rec, buf)
     if r is None:
-        return decode_record(rec, True, train_key, whole)
+        return decode_record(rec, train_key, whole)
     status, info, (off, length, text, seq_len, label, post_id, day) = r
     if status == 0:
         img = _coefs(buf[:int(info.coef_count)], info, train_key, whole)
@@ -314,73 +334,29 @@ def decode_record_jpeg_scan(rec, train_key=None, whole=False):
     return img, text, int(seq_len), int(label), int(post_id), int(day)
 
 
-def pack_ragged_jpeg(items, out_h, out_w, st, train=False):
-    """pack_ragged for a batch whose items are JpegCoefs or decoded crops (train: (crop, TrainParams)): the preprocessing
-    descriptors of ALL images and the pixels of the decoded ones go where pack_ragged puts them (st.desc_np, st.bytes);
-    coefficients go to st.coef back to back (starts rounded up to 8 int16) with one st.jdesc_np record each.  Returns
-    (bytes used, int16 used, JpegCoefs count, [(offset, size) of every decoded crop])."""
-    shapes, pos, cpos, spos, nseg = [], 0, 0, 0, 0
-    for it in items:
-        if isinstance(it, JpegCoefs):
-            ch, cw = it.box[2], it.box[3]
-            cpos = -(-cpos // 8) * 8 + it.coef.size
-        elif isinstance(it, JpegScan):
-            ch, cw = it.box[2], it.box[3]
-            cpos = -(-cpos // 8) * 8 + it.coef_count
-            spos += int(it.cuts[-1]) - int(it.scan.scan_begin)
-            nseg += it.cuts.size
-        else:
-            im = it[0] if train else it
-            if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
-                raise ValueError("pack_ragged_jpeg: images must be non-empty uint8 [h, w, 3] arrays")
-            ch, cw = im.shape[:2]
-        shapes.append((pos, ch, cw))
-        pos = -(-(pos + ch * cw * 3) // 4) * 4
-    st.reserve(pos)
-    st.reserve_coef(cpos)
-    if nseg:
-        st.reserve_scan(spos, nseg)
-    out, coef = st.bytes.numpy(), st.coef.numpy()
-    cpos, nj, copies = 0, 0, []
-    st.scans, st.coef_copies = [], []
-    for i, (it, (off, ch, cw)) in enumerate(zip(items, shapes)):
-        if isinstance(it, (JpegCoefs, JpegScan)):
-            p = it.params
-            cpos = -(-cpos // 8) * 8
-            if isinstance(it, JpegCoefs):
-                size = it.coef.size
-                coef[cpos:cpos + size] = it.coef
-                st.coef_copies.append((cpos, size))
-            else:                                  # the device writes these coefficients: (descriptor row, item, byte offset)
-                size = it.coef_count
-                st.scans.append((nj, it, off, cpos))
-            st.jdesc_np[nj] = (cpos, off, it.width, it.height, it.sampling, it.box[0], it.box[1], ch, cw, 0, it.quant)
-            cpos += size
-            nj += 1
-        else:
-            im, p = it if train else (it, None)
-            out[off:off + im.size].reshape(im.shape)[...] = im
-            copies.append((off, im.size))
-        if train and (p.crop_h, p.crop_w) != (ch, cw):
-            raise ValueError("pack_ragged_jpeg: image %d is not the crop its parameters describe" % i)
-        st.desc_np[i] = _desc_record(off, ch, cw, out_h, out_w, p if train else None)
-    if st.scans:
-        from . import ops
-        ops.fill_jpeg_scan_tables([(it.data, it.info, it.scan, it.cuts) for _, it, _, _ in st.scans],
-                                  [c for _, _, _, c in st.scans], st.scan.numpy(), st.sdesc_np, st.segs_np)
-        st.scan_used, st.segs_used = spos, nseg
-    return pos, cpos, nj, copies
+# ---- configuration and staging ------------------------------------------------------------------------------------------------
+# What the feeder and its staging sets are built from, made once by DeviceLoader.__init__.  train, jpeg, entropy and
+# cache_bytes are normalised there: all off with decode_images=False, entropy only with jpeg, cache_bytes None without the cache.
+_Config = collections.namedtuple(
+    "_Config", "batch_size height width device decode_images train jpeg entropy cache_bytes shuffle rank world seed loop "
+               "max_token_id num_classes prefetch inflight",
+    defaults=(True, False, False, False, None, False, 0, 1, 0, True, None, None, 2, 256))
+
+# What the feeder hands DeviceLoader.__next__ per batch, and the cache's share of it (None without the cache).
+_Batch = collections.namedtuple("_Batch", "out event stream fallbacks on_device stats")
+_CacheStats = collections.namedtuple("_CacheStats", "hits misses spilled records bytes_used")
 
 
-# ---- staging ----------------------------------------------------------------------------------------------------------------
 class _Staging:
     """One pinned staging set: ragged image bytes + descriptor table + the int64 fields, with the device byte buffer and
     descriptor table they are uploaded into and the event of the last upload."""
 
-    def __init__(self, batch_size, post_size, device, cuda, train=False, jpeg=False, entropy=False, cache=False):
+    def __init__(self, cfg, post_size):
         import torch
         from . import ops
-        preprocess_desc_dtype = ops.preprocess_train_desc_dtype if train else ops.preprocess_desc_dtype
+        batch_size, device = cfg.batch_size, cfg.device
+        preprocess_desc_dtype = ops.preprocess_train_desc_dtype if cfg.train else ops.preprocess_desc_dtype
+        cuda = device.type == "cuda"
         self.torch, self.device, self.cuda = torch, device, cuda
         self.event = None
         self.ints = self._host(batch_size * (post_size + len(_FIELDS)), torch.int64)
@@ -390,14 +366,13 @@ class _Staging:
         self.bytes = self.bytes_dev = None
         self.reserve(1 << 20)
         self.coef = self.coef_dev = self.scratch_dev = None
-        if jpeg:                  # jpeg_decode='device': coefficients, their descriptors, the planes of ds_jpeg_reconstruct
+        if cfg.jpeg:              # jpeg_decode='device': coefficients, their descriptors, the planes of ds_jpeg_reconstruct
             self.jdesc = self._host(batch_size * ops.jpeg_desc_dtype().itemsize, torch.uint8)
             self.jdesc_np = self.jdesc.numpy().view(ops.jpeg_desc_dtype())
             self.jdesc_dev = torch.empty(self.jdesc.numel(), dtype=torch.uint8, device=device) if cuda else None
             self.reserve_coef(1 << 20)
-        self.scans, self.coef_copies = [], []     # pack_ragged_jpeg: the JpegScan images, the ranges of host-decoded coefficients
         self.scan = self.scan_dev = self.segs = self.segs_np = self.segs_dev = None
-        if jpeg and entropy:      # jpeg_entropy='device': entropy-coded bytes, the two tables, the status words
+        if cfg.entropy:           # jpeg_entropy='device': entropy-coded bytes, the two tables, the status words
             self.sdesc = self._host(batch_size * ops.jpeg_scan_desc_dtype().itemsize, torch.uint8)
             self.sdesc_np = self.sdesc.numpy().view(ops.jpeg_scan_desc_dtype())
             self.status = self._host(batch_size, torch.int32)
@@ -406,7 +381,7 @@ class _Staging:
                 self.status_dev = torch.empty(batch_size, dtype=torch.int32, device=device)
             self.reserve_scan(1 << 20, 1 << 12)
         self.spill_dev = None
-        if cache:                 # cache='device': the ds_ragged_gather table; the spill buffer appears with the first spilled image
+        if cfg.cache_bytes:       # cache='device': the ds_ragged_gather table; the spill buffer appears with the first spilled image
             self.gdesc = self._host(batch_size * ops.gather_desc_dtype().itemsize, torch.uint8)
             self.gdesc_np = self.gdesc.numpy().view(ops.gather_desc_dtype())
             self.gdesc_dev = torch.empty(self.gdesc.numel(), dtype=torch.uint8, device=device)
@@ -416,13 +391,13 @@ class _Staging:
 
     def reserve(self, nbytes):
         if self.bytes is None or self.bytes.numel() < nbytes:
-            cap = -(-int(nbytes * 1.25) // 4096) * 4096
+            cap = _round_up(int(nbytes * 1.25), 4096)
             self.bytes = self._host(cap, self.torch.uint8)
             self.bytes_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device) if self.cuda else None
 
     def reserve_coef(self, n):
         if self.coef is None or self.coef.numel() < n:
-            cap = -(-int(n * 1.25) // 4096) * 4096
+            cap = _round_up(int(n * 1.25), 4096)
             self.coef = self._host(cap, self.torch.int16)
             if self.cuda:
                 self.coef_dev = self.torch.empty(cap, dtype=self.torch.int16, device=self.device)
@@ -430,18 +405,18 @@ class _Staging:
 
     def reserve_spill(self, nbytes):
         if nbytes and (self.spill_dev is None or self.spill_dev.numel() < nbytes):
-            cap = -(-int(nbytes * 1.25) // 4096) * 4096
+            cap = _round_up(int(nbytes * 1.25), 4096)
             self.spill_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device)
 
     def reserve_scan(self, nbytes, nseg):
         from . import ops
         if self.scan is None or self.scan.numel() < nbytes:
-            cap = -(-int(nbytes * 1.25) // 4096) * 4096
+            cap = _round_up(int(nbytes * 1.25), 4096)
             self.scan = self._host(cap, self.torch.uint8)
             self.scan_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device) if self.cuda else None
         item = ops.jpeg_segment_dtype().itemsize
         if self.segs is None or self.segs.numel() < nseg * item:
-            cap = -(-int(nseg * 1.25) // 256) * 256 * item
+            cap = _round_up(int(nseg * 1.25), 256) * item
             self.segs = self._host(cap, self.torch.uint8)
             self.segs_np = self.segs.numpy().view(ops.jpeg_segment_dtype())
             self.segs_dev = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device) if self.cuda else None
@@ -474,39 +449,8 @@ def _put(state, item):
     return False
 
 
-_EPOCH = object()
-
-
-def _record_stream(dataset, shuffle, rng, rank, world, loop):
-    """(pass number, global index within the pass, raw record) for the records of this rank in the host generator's order,
-    _EPOCH between passes.  The source shuffle of a pass is drawn when the first record of that pass is asked for, never
-    earlier."""
-    from .datasets.tfrecord import read_records
-    pass_no = -1
-    while True:
-        pass_no += 1
-        sources = list(dataset.data_sources)
-        if shuffle:
-            rng.shuffle(sources)
-        idx, n = -1, 0
-        for path in sources:
-            for rec in read_records(path):
-                idx += 1
-                if idx % world != rank:
-                    continue                   # other ranks' records: never parsed, never decoded
-                n += 1
-                yield pass_no, idx, rec
-        if not loop or n == 0:
-            return
-        yield _EPOCH
-
-
 # ---- cache='device': decoded images resident in HBM ----------------------------------------------------------------------------
 CACHE_ALIGN = 16                      # every image of the arena (and of a spill buffer) starts on a multiple of this
-
-
-def _round_up(n, m):
-    return -(-n // m) * m
 
 
 def source_has_miss(source, count, first_index, rank, world, cached):
@@ -552,20 +496,16 @@ class _Cache:
         return off
 
 
-class _CacheItem:
-    """One image of a batch under cache='device'.  off: its arena offset, None = spilled (this batch's spill buffer);
-    h, w: the resident region (the central crop, at train time the whole image); fill: what still has to be written there
-    (a decoded array, JpegCoefs or JpegScan), None for a hit; box: the window ds_ragged_gather copies; p: its TrainParams."""
-    __slots__ = ("off", "h", "w", "fill", "p", "box", "hit")
-
-    def __init__(self, off, h, w, fill, p, box):
-        self.off, self.h, self.w, self.fill, self.p, self.box, self.hit = off, h, w, fill, p, box, fill is None
+# ---- records ------------------------------------------------------------------------------------------------------------------
+_EPOCH = object()
 
 
-def _cached_record_stream(dataset, shuffle, rng, rank, world, loop, cache):
-    """_record_stream under cache='device': (pass number, global index, (source, record) key, raw record or None), the
-    same records in the same order with the same draws.  A source whose size is known and whose records of this rank are
-    all resident is not opened: its records are counted off instead; a resident record of an opened file carries None."""
+def _record_stream(dataset, shuffle, rng, rank, world, loop, cache=None):
+    """(pass number, global index within the pass, (source, record) key, raw record or None) for the records of this rank
+    in the host generator's order, _EPOCH between passes.  The source shuffle of a pass is drawn when the first record of
+    that pass is asked for, never earlier.  With a cache (its `entries` and `counts`) a source whose size is known and
+    whose records of this rank are all resident is not opened: its records are counted off instead; a resident record of
+    an opened file carries None.  The records, their order and the draws are the same either way."""
     from .datasets.tfrecord import read_records
     index = {}
     for i, path in enumerate(dataset.data_sources):
@@ -579,7 +519,7 @@ def _cached_record_stream(dataset, shuffle, rng, rank, world, loop, cache):
         idx, n = -1, 0
         for path in sources:
             s = index[path]
-            count = cache.counts.get(s)
+            count = cache.counts.get(s) if cache is not None else None
             if count is not None and not source_has_miss(s, count, idx + 1, rank, world, cache.entries):
                 for r in range(count):
                     idx += 1
@@ -592,10 +532,11 @@ def _cached_record_stream(dataset, shuffle, rng, rank, world, loop, cache):
                 idx += 1
                 r += 1
                 if idx % world != rank:
-                    continue
+                    continue                   # other ranks' records: never parsed, never decoded
                 n += 1
-                yield pass_no, idx, (s, r), None if (s, r) in cache.entries else rec
-            cache.counts[s] = r + 1
+                yield pass_no, idx, (s, r), None if cache is not None and (s, r) in cache.entries else rec
+            if cache is not None:
+                cache.counts[s] = r + 1
         if not loop or n == 0:
             return
         yield _EPOCH
@@ -609,176 +550,268 @@ def _check_record(text, label, max_token_id, num_classes):
         raise ValueError("label %d outside [0, %d)" % (label, num_classes))
 
 
-def _cache_pop(cache, entry, train, seed, max_token_id, num_classes):
-    """The next record of the stream under cache='device': a hit comes from the index; a miss is awaited, checked and given
-    its place in the arena (it is resident from here on: its pixels are written by the batch it belongs to, ahead of every
-    gather that reads them on the one copy stream).  A record that raises is never inserted.  Returns the feeder's tuple,
-    its first item a _CacheItem."""
+class _Item:
+    """One image of a batch.  fill: what still has to be written for it (a decoded array, JpegCoefs or JpegScan), None for
+    a hit of the cache; h, w: the region the fill produces -- the crop, or under cache='device' the resident region (the
+    central crop, at train time the whole image); box: the window of that region that goes to the ragged buffer (all of
+    it without the cache); p: the window's TrainParams; off (cache='device'): the region's arena offset, None = spilled
+    (this batch's spill buffer)."""
+    __slots__ = ("off", "h", "w", "fill", "p", "box")
+
+    def __init__(self, off, h, w, fill, p, box):
+        self.off, self.h, self.w, self.fill, self.p, self.box = off, h, w, fill, p, box
+
+
+def _next_item(entry, cfg, cache=None):
+    """The next record of the stream, entry = (decode slot or None, pass number, global index, (source, record) key):
+    awaited and checked, its image as an _Item (None with decode_images=False).  Under cache='device' a hit comes from the
+    index; a miss is given its place in the arena (it is resident from here on: its pixels are written by the batch it
+    belongs to, ahead of every gather that reads them on the one copy stream; a record that raises is never inserted),
+    and at train time the window is drawn here -- the host generator's draws need the image's size only.  Returns the
+    feeder's tuple (item, text, seq_len, label, post_id, day)."""
     slot, pass_no, idx, key = entry
-    e = cache.entries.get(key)
-    fill = None
-    if e is None:
-        fill, text, seq_len, label, post_id, day = slot.result()
-        _check_record(text, label, max_token_id, num_classes)
-        h, w = (fill.box[2], fill.box[3]) if isinstance(fill, (JpegCoefs, JpegScan)) else fill.shape[:2]
-        off = cache.reserve(h * w * 3)
-        if off is not None:
-            cache.entries[key] = (off, h, w, text, seq_len, label, post_id, day)
-    else:
+    e = cache.entries.get(key) if cache is not None else None
+    if e is not None:
         off, h, w, text, seq_len, label, post_id, day = e
-    p, box = None, (0, 0, h, w)
-    if train:                                      # the host generator's draws: they need the image's size only
-        from .preprocessing.inception_preprocessing import record_rng, sample_train_params
-        p = sample_train_params(h, w, record_rng(seed, pass_no, idx))
-        box = (p.y0, p.x0, p.crop_h, p.crop_w)
-    return _CacheItem(off, h, w, fill, p, box), text, seq_len, label, post_id, day
-
-
-def _pack_cached(items, out_h, out_w, st):
-    """The host half of a batch under cache='device' (items in output-slot order): the ds_ragged_gather table and the
-    preprocessing descriptors of ALL images (st.gdesc_np, st.desc_np; the ragged layout is pack_ragged's), and for the
-    misses what puts their pixels where the gather reads them -- decoded arrays into pinned staging (st.bytes), coefficients
-    and ds_jpeg_desc rows as pack_ragged_jpeg lays them out, the rows that write the arena in front of those that write the
-    spill buffer.  Returns (ragged bytes, int16 used, arena rows, rows, [(src, destination offset, staging offset, size)
-    of every staged array], (first, one past the last) arena byte the rows write, staging offset free for fallbacks)."""
-    pos = spos = stage = room = 0
-    pix, rows_of = [], ([], [])
-    for i, it in enumerate(items):
-        size = it.h * it.w * 3
-        if it.off is None:
-            src, soff = 1, spos
-            spos += _round_up(size, CACHE_ALIGN)
+        fill = p = None
+    else:
+        fill, text, seq_len, label, post_id, day = slot.result()
+        _check_record(text, label, cfg.max_token_id, cfg.num_classes)
+        if fill is None:
+            return None, text, seq_len, label, post_id, day
+        fill, p = fill if isinstance(fill, tuple) else (fill, None)
+        if isinstance(fill, (JpegCoefs, JpegScan)):
+            h, w, p = fill.box[2], fill.box[3], fill.params
         else:
-            src, soff = 0, it.off
+            _check_image(fill, "input pipeline")
+            h, w = fill.shape[:2]
+        if p is not None and (p.crop_h, p.crop_w) != (h, w):
+            raise ValueError("input pipeline: record %d is not the crop its parameters describe" % idx)
+        off = None
+        if cache is not None:
+            off = cache.reserve(h * w * 3)
+            if off is not None:
+                cache.entries[key] = (off, h, w, text, seq_len, label, post_id, day)
+    box = (0, 0, h, w)
+    if cache is not None and cfg.train:
+        box, p = _crop(h, w, (cfg.seed, pass_no, idx))
+    return _Item(off, h, w, fill, p, box), text, seq_len, label, post_id, day
+
+
+# ---- the batch plan: the host half of a batch -------------------------------------------------------------------------------------
+_ARENA, _SPILL, _RAGGED = 0, 1, 2     # the buffers pixels are written to; the first two are the `src` values of ds_gather_desc
+
+# used: bytes of the ragged buffer; copies: [(destination buffer, destination offset, staging offset, size)], coalesced;
+# groups: [(destination buffer, first byte, one past the last byte the rows write, first ds_jpeg_desc row, rows)], arena rows
+# ahead of spill rows; ncoef: int16 of coefficient storage; coef_copies: [(offset, size)] of the host-decoded coefficients;
+# scans: [(ds_jpeg_desc row, JpegScan, destination buffer, destination offset, staging offset of a PIL decode, first
+# coefficient)] with nscan bytes and nseg segments in the scan tables; gather: rows of the ds_ragged_gather table; arrays:
+# images that arrived decoded; flagged: images the Huffman kernel flagged (flagged_fallback); stats: _CacheStats or None.
+BatchPlan = collections.namedtuple("BatchPlan", "used copies groups ncoef coef_copies scans nscan nseg gather arrays flagged stats")
+
+
+def pack_batch(items, out_h, out_w, st, cached=False):
+    """The host half of a batch (items: _Item in output-slot order): the preprocessing descriptors of ALL images
+    (st.desc_np; the ragged layout is pack_ragged's) and what puts the pixels there.  Without the cache every image is
+    written straight to its ragged slot -- a decoded array is staged at the same offset of st.bytes and copied with its
+    padding, so a batch of arrays is one copy of [0, used).  With it (cached) the misses are written to their place in
+    the arena or the spill buffer, the arrays staged back to back, and st.gdesc_np moves every window, hit or miss, from
+    there.  Coefficients go to st.coef back to back (starts rounded up to 8 int16) with one st.jdesc_np row each, the rows
+    that write the arena in front of those that write the spill buffer; a JpegScan's entropy-coded bytes go to the scan
+    tables (st.scan, st.sdesc_np, st.segs_np) instead.  Launches nothing; returns the BatchPlan."""
+    pos = spos = stage = misses = spilled = top = 0
+    pix, rows_of = [], ([], [], [])
+    for i, it in enumerate(items):
         y0, x0, wh, ww = it.box
-        st.gdesc_np[i] = (soff, pos, src, 3 * it.w, y0, x0, wh, ww)
         st.desc_np[i] = _desc_record(pos, wh, ww, out_h, out_w, it.p)
+        size = it.h * it.w * 3
+        if not cached:
+            dst, doff = _RAGGED, pos
+        else:
+            if it.off is None:
+                dst, doff = _SPILL, spos
+                spos += _round_up(size, CACHE_ALIGN)
+            else:
+                dst, doff = _ARENA, it.off
+            st.gdesc_np[i] = (doff, pos, dst, 3 * it.w, y0, x0, wh, ww)
         pos = _round_up(pos + wh * ww * 3, 4)
-        f, it.fill = it.fill, None
-        if isinstance(f, (JpegCoefs, JpegScan)):
-            rows_of[src].append((soff, f))
-            if isinstance(f, JpegScan):
-                room += _round_up(size, CACHE_ALIGN)           # for the PIL decode of an image the kernel flags
-        elif f is not None:
-            if f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8 or f.shape[0] < 1 or f.shape[1] < 1:
-                raise ValueError("input cache: images must be non-empty uint8 [h, w, 3] arrays")
-            pix.append((src, soff, stage, f))
+        f = it.fill
+        if f is None:                              # a hit: nothing is written
+            continue
+        misses += 1
+        if dst == _SPILL:
+            spilled += 1
+        elif dst == _ARENA:
+            top = max(top, doff + size)
+        if not isinstance(f, np.ndarray):
+            rows_of[dst].append((doff, size, f))
+        elif cached:
+            pix.append((dst, doff, stage, size, f))
             stage += _round_up(size, CACHE_ALIGN)
-    st.reserve(max(pos, stage + room))
+        else:
+            pix.append((dst, doff, doff, _round_up(size, 4), f))
+    # coefficient storage, ds_jpeg_desc rows and the scan list, destination buffer by destination buffer
+    groups, host_coefs, scans = [], [], []
+    cpos = nscan = nseg = nj = 0
+    for dst in (_ARENA, _SPILL, _RAGGED):
+        if not rows_of[dst]:
+            continue
+        base, end = 0, (spos if dst == _SPILL else pos)
+        if dst == _ARENA:                          # the rows see only the bytes of the arena that this batch writes
+            base, end = min(doff for doff, _, _ in rows_of[dst]), max(doff + size for doff, size, _ in rows_of[dst])
+        groups.append((dst, base, end, nj, len(rows_of[dst])))
+        for doff, size, f in rows_of[dst]:
+            c = _round_up(cpos, 8)
+            if isinstance(f, JpegScan):            # the device writes these coefficients; the PIL decode of a flagged
+                soff = doff                        # image is staged at its ragged offset or, cached, behind the arrays
+                if cached:
+                    soff, stage = stage, stage + _round_up(size, CACHE_ALIGN)
+                scans.append((nj, f, dst, doff, soff, c))
+                cpos = c + f.coef_count
+                nscan += int(f.cuts[-1]) - int(f.scan.scan_begin)
+                nseg += f.cuts.size
+            else:
+                host_coefs.append((c, f.coef))
+                cpos = c + f.coef.size
+            st.jdesc_np[nj] = (c, doff - base, f.width, f.height, f.sampling, f.box[0], f.box[1], f.box[2], f.box[3], 0, f.quant)
+            nj += 1
+    st.reserve(max(pos, stage))
     st.reserve_spill(spos)
     out = st.bytes.numpy()
     copies = []
-    for src, doff, sp, f in pix:
-        out[sp:sp + f.size].reshape(f.shape)[...] = f
-        if copies and copies[-1][0] == src and doff - copies[-1][1] == sp - copies[-1][2] == _round_up(copies[-1][3], CACHE_ALIGN):
-            copies[-1] = (src, copies[-1][1], copies[-1][2], doff - copies[-1][1] + f.size)     # neighbours in both buffers: one copy
+    for dst, doff, soff, size, f in pix:
+        out[soff:soff + f.size].reshape(f.shape)[...] = f
+        align = 4 if dst == _RAGGED else CACHE_ALIGN
+        if copies and copies[-1][0] == dst and doff - copies[-1][1] == soff - copies[-1][2] == _round_up(copies[-1][3], align):
+            copies[-1] = (dst, copies[-1][1], copies[-1][2], doff - copies[-1][1] + size)     # neighbours in both buffers: one copy
         else:
-            copies.append((src, doff, sp, f.size))
-    rows, na = rows_of[0] + rows_of[1], len(rows_of[0])
-    abase = min((off for off, _ in rows_of[0]), default=0)
-    aend = max((off + f.box[2] * f.box[3] * 3 for off, f in rows_of[0]), default=0)
-    cpos = nscan = nseg = 0
-    for _, f in rows:
-        if isinstance(f, JpegCoefs):
-            cpos = _round_up(cpos, 8) + f.coef.size
-        else:
-            cpos = _round_up(cpos, 8) + f.coef_count
-            nscan += int(f.cuts[-1]) - int(f.scan.scan_begin)
-            nseg += f.cuts.size
-    st.scans, st.coef_copies = [], []
-    if rows:
-        st.reserve_coef(cpos)
-        if nseg:
-            st.reserve_scan(nscan, nseg)
-        coef, cpos = st.coef.numpy(), 0
-        for nj, (doff, f) in enumerate(rows):
-            cpos = _round_up(cpos, 8)
-            if isinstance(f, JpegCoefs):
-                size = f.coef.size
-                coef[cpos:cpos + size] = f.coef
-                st.coef_copies.append((cpos, size))
-            else:                                  # (descriptor row, item, (src, destination offset), first coefficient)
-                size = f.coef_count
-                st.scans.append((nj, f, (0 if nj < na else 1, doff), cpos))
-            st.jdesc_np[nj] = (cpos, doff - abase if nj < na else doff, f.width, f.height, f.sampling, f.box[0], f.box[1],
-                               f.box[2], f.box[3], 0, f.quant)
-            cpos += size
-        if st.scans:
-            from . import ops
-            ops.fill_jpeg_scan_tables([(f.data, f.info, f.scan, f.cuts) for _, f, _, _ in st.scans],
-                                      [c for _, _, _, c in st.scans], st.scan.numpy(), st.sdesc_np, st.segs_np)
-            st.scan_used, st.segs_used = nscan, nseg
-    return pos, cpos, na, len(rows), copies, (abase, aend), stage
-
-
-def _fill_cached(st, cache, plan, stream, train, batch_size):
-    """The device half, on the copy stream (the current one): the misses' pixels into the arena -- or, for a spilled image,
-    into this staging set's spill buffer -- by H2D copies and ds_jpeg_reconstruct, then ONE ds_ragged_gather that moves
-    every image's window, hit or miss, into the ragged buffer the preprocessing kernel reads.  Returns (images of the
-    batch PIL decoded because the Huffman kernel flagged them, images whose coefficients the device produced)."""
-    from . import ops
-    used, ncoef, na, nj, copies, (abase, aend), free = plan
-    arena = cache.arena
-    for src, doff, sp, size in copies:
-        (st.spill_dev if src else arena)[doff:doff + size].copy_(st.bytes[sp:sp + size], non_blocking=True)
-    flagged = on_device = 0
-    if st.scans:
-        bad = _device_entropy_launch(st, stream, ncoef)
-        keep = np.ones(nj, bool)
-        out = st.bytes.numpy()
-        for k in bad:
-            row, it, (src, doff), _ = st.scans[k]
-            im = decode_pixels(it.data, None, whole=train)             # the resident region, as a miss of the PIL path has it
-            if im.shape[:2] != (it.box[2], it.box[3]):
-                raise ValueError("a JPEG decodes to another size than its header states")
-            out[free:free + im.size].reshape(im.shape)[...] = im
-            (st.spill_dev if src else arena)[doff:doff + im.size].copy_(st.bytes[free:free + im.size], non_blocking=True)
-            free += _round_up(im.size, CACHE_ALIGN)
-            keep[row] = False
-        flagged, on_device = int(bad.size), len(st.scans) - int(bad.size)
-        if flagged:
-            st.jdesc_np[:int(keep.sum())] = st.jdesc_np[:nj][keep]
-            na, nj = int(keep[:na].sum()), int(keep.sum())
-    elif nj:
-        st.coef_dev[:ncoef].copy_(st.coef[:ncoef], non_blocking=True)
+            copies.append((dst, doff, soff, size))
     if nj:
+        st.reserve_coef(cpos)
+        coef = st.coef.numpy()
+        for c, a in host_coefs:
+            coef[c:c + a.size] = a
+    if scans:
+        from . import ops
+        st.reserve_scan(nscan, nseg)
+        ops.fill_jpeg_scan_tables([(f.data, f.info, f.scan, f.cuts) for _, f, _, _, _, _ in scans],
+                                  [c for _, _, _, _, _, c in scans], st.scan.numpy(), st.sdesc_np, st.segs_np)
+    stats = _CacheStats(len(items) - misses, misses, spilled, misses - spilled, top) if cached else None
+    return BatchPlan(pos, copies, groups, cpos, [(c, a.size) for c, a in host_coefs], scans, nscan, nseg,
+                     len(items) if cached else 0, len(pix), 0, stats)
+
+
+def flagged_fallback(plan, st, bad, whole=False):
+    """Amend the plan for the images the Huffman kernel flagged (bad: their indices into plan.scans): each is decoded with
+    PIL from the bytes its JpegScan holds -- the region a PIL miss has: its crop, or (whole) the uncropped image -- the
+    pixels are staged in st.bytes, a copy to the image's destination is appended and its row leaves the ds_jpeg_desc
+    table.  Host only: the caller issues plan.copies[len(old copies):].  Returns the new plan."""
+    if not len(bad):
+        return plan
+    out = st.bytes.numpy()
+    copies = list(plan.copies)
+    keep = np.ones(sum(g[4] for g in plan.groups), bool)
+    for k in bad:
+        row, f, dst, doff, soff, _ = plan.scans[k]
+        im = decode_pixels(f.data, f.train_key, whole)
+        im = im[0] if isinstance(im, tuple) else im
+        if im.shape[:2] != (f.box[2], f.box[3]):
+            raise ValueError("a JPEG decodes to another size than its header states")
+        out[soff:soff + im.size].reshape(im.shape)[...] = im
+        copies.append((dst, doff, soff, im.size))
+        keep[row] = False
+    st.jdesc_np[:int(keep.sum())] = st.jdesc_np[:keep.size][keep]
+    groups, nj = [], 0
+    for dst, base, end, first, n in plan.groups:
+        left = int(keep[first:first + n].sum())
+        if left:
+            groups.append((dst, base, end, nj, left))
+        nj += left
+    return plan._replace(copies=copies, groups=groups, flagged=len(bad))
+
+
+# ---- the device half of a batch ---------------------------------------------------------------------------------------------------
+def _device_entropy_launch(plan, st, stream):
+    """The Huffman decode of the batch's JpegScan images on the copy stream (the current one), into their ranges of
+    st.coef_dev; host-decoded images' coefficients are uploaded into theirs.  The status words come back to pinned memory
+    and the FEEDER waits for them.  Returns the indices into plan.scans of the images the kernel flagged."""
+    import torch
+    from . import ops
+    for off, size in plan.coef_copies:
+        st.coef_dev[off:off + size].copy_(st.coef[off:off + size], non_blocking=True)
+    ns, nscan, nseg = len(plan.scans), plan.nscan, plan.nseg
+    st.scan_dev[:nscan].copy_(st.scan[:nscan], non_blocking=True)
+    st.sdesc_dev.copy_(st.sdesc, non_blocking=True)
+    nb = nseg * ops.jpeg_segment_dtype().itemsize
+    st.segs_dev[:nb].copy_(st.segs[:nb], non_blocking=True)
+    ops.jpeg_entropy_decode_device(st.scan_dev[:nscan], st.sdesc_np[:ns], st.segs_np[:nseg], st.coef_dev[:plan.ncoef],
+                                   images_dev=st.sdesc_dev, segs_dev=st.segs_dev, status=st.status_dev)
+    st.status[:ns].copy_(st.status_dev[:ns], non_blocking=True)
+    done = torch.cuda.Event()
+    done.record(stream)
+    done.synchronize()
+    return np.nonzero(st.status.numpy()[:ns])[0]
+
+
+def _run_plan(plan, st, arena, stream, whole):
+    """The device half, on the copy stream (the current one): the H2D copies of the staged pixels; the Huffman decode of
+    the JpegScan images (or, without any, the upload of the coefficients); the PIL decode and upload of the images that
+    kernel flagged; ds_jpeg_reconstruct once per buffer it writes -- the ragged buffer or, under cache='device', the arena
+    and this staging set's spill buffer -- and then ONE ds_ragged_gather that moves every image's window, hit or miss,
+    into the ragged buffer the preprocessing kernel reads.  Returns the plan as amended for the flagged images."""
+    from . import ops
+    bufs = (arena, st.spill_dev, st.bytes_dev)
+
+    def upload(copies):
+        for dst, doff, soff, size in copies:
+            bufs[dst][doff:doff + size].copy_(st.bytes[soff:soff + size], non_blocking=True)
+
+    upload(plan.copies)
+    if plan.scans:
+        issued = len(plan.copies)
+        plan = flagged_fallback(plan, st, _device_entropy_launch(plan, st, stream), whole)
+        upload(plan.copies[issued:])
+    elif plan.groups:
+        st.coef_dev[:plan.ncoef].copy_(st.coef[:plan.ncoef], non_blocking=True)
+    if plan.groups:
         st.jdesc_dev.copy_(st.jdesc, non_blocking=True)
         item = ops.jpeg_desc_dtype().itemsize
-        if na:
-            ops.jpeg_reconstruct(st.coef_dev[:ncoef], st.jdesc_np[:na], arena[abase:aend], scratch=st.scratch_dev,
-                                 desc_dev=st.jdesc_dev)
-        if nj > na:
-            ops.jpeg_reconstruct(st.coef_dev[:ncoef], st.jdesc_np[na:nj], st.spill_dev, scratch=st.scratch_dev,
-                                 desc_dev=st.jdesc_dev[na * item:])
-    st.gdesc_dev.copy_(st.gdesc, non_blocking=True)
-    ops.ragged_gather(arena, st.spill_dev, st.gdesc_np[:batch_size], st.bytes_dev[:used], desc_dev=st.gdesc_dev)
-    return flagged, on_device
+        for dst, base, end, first, n in plan.groups:
+            ops.jpeg_reconstruct(st.coef_dev[:plan.ncoef], st.jdesc_np[first:first + n], bufs[dst][base:end],
+                                 scratch=st.scratch_dev, desc_dev=st.jdesc_dev[first * item:])
+    if plan.gather:
+        st.gdesc_dev.copy_(st.gdesc, non_blocking=True)
+        ops.ragged_gather(arena, st.spill_dev, st.gdesc_np[:plan.gather], st.bytes_dev[:plan.used], desc_dev=st.gdesc_dev)
+    return plan
 
 
-def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, world, seed, loop, max_token_id,
-            num_classes, decode_images, prefetch, inflight, train=False, jpeg=False, entropy=False, cache_bytes=None):
-    import collections
+def _feeder(state, dataset, cfg):
     try:
         import torch
         from . import ops
-        dev = torch.device(device)
+        dev, batch_size, shuffle = cfg.device, cfg.batch_size, cfg.shuffle
         cuda = dev.type == "cuda"
-        if decode_images and not cuda:
+        if cfg.decode_images and not cuda:
             raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
         post_size = None
         stream = None
         if cuda:
             torch.cuda.set_device(dev)
             stream = torch.cuda.Stream(device=dev)
-        rng = np.random.RandomState(seed)
+        rng = np.random.RandomState(cfg.seed)
         stagings, turn = [], 0
         pending = collections.deque()
         cache = None
-        if cache_bytes and decode_images:          # cache='device': the arena lives as long as the feeder state
-            cache = state.cache = _Cache(cache_bytes, dev)
-            records = _cached_record_stream(dataset, shuffle, rng, rank, world, loop, cache)
-        else:
-            records = _record_stream(dataset, shuffle, rng, rank, world, loop)
+        if cfg.cache_bytes:                        # cache='device': the arena lives as long as the feeder state
+            cache = state.cache = _Cache(cfg.cache_bytes, dev)
+        records = _record_stream(dataset, shuffle, rng, cfg.rank, cfg.world, cfg.loop, cache)
+        # What a worker does with a record.  With the cache it decodes the resident region -- at train time the whole
+        # image -- and the feeder draws the window (_next_item); without it the worker draws the crop from the record's key.
+        decode = (decode_record_jpeg_scan if cfg.entropy else decode_record_jpeg if cfg.jpeg else
+                  decode_record if cfg.decode_images else functools.partial(decode_record, decode_image=False))
+        whole = cfg.train and cache is not None
+        check_descs = ops.check_preprocess_train_descs if cfg.train else ops.check_preprocess_descs
+        preprocess = ops.preprocess_train if cfg.train else ops.preprocess_eval
         exhausted = boundary = False
         buf = []
         while not state.stop.is_set():
@@ -787,7 +820,7 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             # the next pass's source shuffle.  So with shuffling on, the next pass starts only once every record of the
             # finished one has been consumed (a short bubble per epoch); without shuffling nothing is drawn at all.
             # With the cache a pass always waits for the one before it: what is resident is known once its records are in.
-            while not exhausted and len(pending) < inflight:
+            while not exhausted and len(pending) < cfg.inflight:
                 if boundary and (shuffle or cache is not None) and pending:
                     break
                 boundary = False
@@ -796,37 +829,21 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
                     exhausted = True
                 elif rec is _EPOCH:
                     boundary = True
-                elif cache is not None:
-                    pass_no, idx, ckey, payload = rec
-                    slot = None                    # a hit: no file was read for it, nothing goes to the pool
-                    if payload is not None and jpeg:
-                        slot = state.pool.submit(decode_record_jpeg_scan if entropy else decode_record_jpeg, payload, None, train)
-                    elif payload is not None:
-                        slot = state.pool.submit(decode_record, payload, True, None, train)
-                    pending.append((slot, pass_no, idx, ckey))
                 else:
-                    pass_no, idx, payload = rec
-                    key = (seed, pass_no, idx) if train and decode_images else None
-                    if jpeg and decode_images:
-                        pending.append(state.pool.submit(decode_record_jpeg_scan if entropy else decode_record_jpeg, payload, key))
-                    else:
-                        pending.append(state.pool.submit(decode_record, payload, decode_images, key))
+                    pass_no, idx, key, payload = rec
+                    slot = None                    # a hit: no file was read for it, nothing goes to the pool
+                    if payload is not None:
+                        slot = state.pool.submit(decode, payload, (cfg.seed, pass_no, idx) if cfg.train and cache is None else None, whole)
+                    pending.append((slot, pass_no, idx, key))
             if not pending:
                 break
-            if cache is not None:
-                img, text, seq_len, label, post_id, day = _cache_pop(cache, pending.popleft(), train, seed, max_token_id, num_classes)
-            else:
-                img, text, seq_len, label, post_id, day = pending.popleft().result()
-                _check_record(text, label, max_token_id, num_classes)
-            buf.append((img, text, seq_len, label, post_id, day))
+            buf.append(_next_item(pending.popleft(), cfg, cache))
             if len(buf) < batch_size:
                 continue
             order = rng.permutation(batch_size) if shuffle else np.arange(batch_size)
             if post_size is None:
                 post_size = len(buf[0][1])
-                stagings = [_Staging(batch_size, post_size, dev, cuda, train and decode_images, jpeg and decode_images, entropy,
-                                     cache is not None)
-                            for _ in range(max(2, prefetch + 1))]
+                stagings = [_Staging(cfg, post_size) for _ in range(max(2, cfg.prefetch + 1))]
             st = stagings[turn]
             turn = (turn + 1) % len(stagings)
             st.wait_free()
@@ -835,56 +852,19 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             ints[:nt].reshape(batch_size, post_size)[...] = np.stack([b[1] for b in buf])[order]
             for k in range(len(_FIELDS)):
                 ints[nt + k * batch_size:nt + (k + 1) * batch_size] = np.asarray([b[2 + k] for b in buf], np.int64)[order]
-            used = ncoef = njpeg = 0
-            copies = []
-            plan = cstats = None
-            if cache is not None:
-                items = [buf[j][0] for j in order]
-                fresh = [it for it in items if not it.hit]
-                kept = [it for it in fresh if it.off is not None]
-                cstats = (len(items) - len(fresh), len(fresh), len(fresh) - len(kept), len(kept),
-                          max((it.off + it.h * it.w * 3 for it in kept), default=0), sum(isinstance(it.fill, np.ndarray) for it in fresh))
-                plan = _pack_cached(items, height, width, st)
-                used = plan[0]
-                (ops.check_preprocess_train_descs if train else ops.check_preprocess_descs)(st.desc_np[:batch_size], used)
-            elif decode_images and jpeg:
-                used, ncoef, njpeg, copies = pack_ragged_jpeg([buf[j][0] for j in order], height, width, st, train)
-                (ops.check_preprocess_train_descs if train else ops.check_preprocess_descs)(st.desc_np[:batch_size], used)
-                if njpeg:
-                    ops.check_jpeg_descs(st.jdesc_np[:njpeg], ncoef, used)
-            elif decode_images:
-                images = [buf[j][0] for j in order]          # descriptor j = output slot j: the permutation costs nothing
-                params = None
-                if train:
-                    images, params = [im for im, _ in images], [p for _, p in images]
-                st.reserve(sum(-(-im.size // 4) * 4 for im in images))
-                _, _, used = pack_ragged(images, height, width, out=st.bytes.numpy(), desc=st.desc_np, params=params)
-                (ops.check_preprocess_train_descs if train else ops.check_preprocess_descs)(st.desc_np[:batch_size], used)
+            plan = None
+            if cfg.decode_images:                  # descriptor j = output slot j: the permutation costs nothing
+                plan = pack_batch([buf[j][0] for j in order], cfg.height, cfg.width, st, cache is not None)
+                check_descs(st.desc_np[:batch_size], plan.used)
             buf = []
             out = {}
-            flagged = on_device = 0
             if cuda:
                 with torch.cuda.stream(stream):
-                    if cache is not None:
-                        flagged, on_device = _fill_cached(st, cache, plan, stream, train, batch_size)
-                    elif decode_images and jpeg:
-                        for off, size in copies:                 # the images PIL decoded: their slots only
-                            st.bytes_dev[off:off + size].copy_(st.bytes[off:off + size], non_blocking=True)
-                        if st.scans:
-                            njpeg, flagged = _device_entropy(st, stream, ncoef, njpeg, train)
-                            on_device = len(st.scans) - flagged
-                        elif njpeg:
-                            st.coef_dev[:ncoef].copy_(st.coef[:ncoef], non_blocking=True)
-                        if njpeg:
-                            st.jdesc_dev.copy_(st.jdesc, non_blocking=True)
-                            ops.jpeg_reconstruct(st.coef_dev[:ncoef], st.jdesc_np[:njpeg], st.bytes_dev[:used],
-                                                 scratch=st.scratch_dev, desc_dev=st.jdesc_dev)
-                    elif decode_images:
-                        st.bytes_dev[:used].copy_(st.bytes[:used], non_blocking=True)
-                    if decode_images:
+                    if plan is not None:
+                        plan = _run_plan(plan, st, cache.arena if cache is not None else None, stream, whole)
                         st.desc_dev.copy_(st.desc, non_blocking=True)
-                        run = ops.preprocess_train if train else ops.preprocess_eval
-                        out["images"] = run(st.bytes_dev[:used], st.desc_np[:batch_size], height, width, desc_dev=st.desc_dev)
+                        out["images"] = preprocess(st.bytes_dev[:plan.used], st.desc_np[:batch_size], cfg.height, cfg.width,
+                                                   desc_dev=st.desc_dev)
                     ints_dev = st.ints.to(dev, non_blocking=True)
                     st.event = torch.cuda.Event()
                     st.event.record(stream)
@@ -894,59 +874,15 @@ def _feeder(state, dataset, batch_size, shuffle, height, width, device, rank, wo
             out["texts"] = ints_dev[:nt].view(batch_size, post_size)
             for k, (name, _) in enumerate(_FIELDS):
                 out[name] = ints_dev[nt + k * batch_size:nt + (k + 1) * batch_size]
-            fallbacks = (cstats[5] if cache is not None else len(copies)) + flagged if jpeg else 0
-            if not _put(state, ("batch", out, event, stream, fallbacks, on_device, cstats)):
+            batch = _Batch(out, event, stream, 0, 0, None)
+            if plan is not None:                   # under jpeg_decode='device' an image that PIL decoded is a fallback
+                batch = batch._replace(fallbacks=plan.arrays + plan.flagged if cfg.jpeg else 0,
+                                       on_device=len(plan.scans) - plan.flagged, stats=plan.stats)
+            if not _put(state, batch):
                 return
-        _put(state, ("end",))
+        _put(state, None)                          # the end of the stream; an exception is handed over as itself
     except BaseException as e:
-        _put(state, ("error", e))
-
-
-def _device_entropy_launch(st, stream, ncoef):
-    """The Huffman decode of the batch's JpegScan images on the copy stream (the current one), into their ranges of
-    st.coef_dev; host-decoded images' coefficients are uploaded into theirs.  The status words come back to pinned memory
-    and the FEEDER waits for them.  Returns the indices into st.scans of the images the kernel flagged."""
-    import torch
-    from . import ops
-    for off, size in st.coef_copies:
-        st.coef_dev[off:off + size].copy_(st.coef[off:off + size], non_blocking=True)
-    ns, nscan, nseg = len(st.scans), st.scan_used, st.segs_used
-    st.scan_dev[:nscan].copy_(st.scan[:nscan], non_blocking=True)
-    st.sdesc_dev.copy_(st.sdesc, non_blocking=True)
-    nb = nseg * ops.jpeg_segment_dtype().itemsize
-    st.segs_dev[:nb].copy_(st.segs[:nb], non_blocking=True)
-    ops.jpeg_entropy_decode_device(st.scan_dev[:nscan], st.sdesc_np[:ns], st.segs_np[:nseg], st.coef_dev[:ncoef],
-                                   images_dev=st.sdesc_dev, segs_dev=st.segs_dev, status=st.status_dev)
-    st.status[:ns].copy_(st.status_dev[:ns], non_blocking=True)
-    done = torch.cuda.Event()
-    done.record(stream)
-    done.synchronize()
-    return np.nonzero(st.status.numpy()[:ns])[0]
-
-
-def _device_entropy(st, stream, ncoef, njpeg, train):
-    """_device_entropy_launch for a batch without the cache: a flagged image is decoded with PIL from the bytes it holds,
-    its crop uploaded into its slot of the ragged buffer and its row dropped from the reconstruct table.  Returns (rows
-    left in st.jdesc_np, flagged)."""
-    bad = _device_entropy_launch(st, stream, ncoef)
-    if not bad.size:
-        return njpeg, 0
-    keep = np.ones(njpeg, bool)
-    out = st.bytes.numpy()
-    for k in bad:
-        row, it, off, _ = st.scans[k]
-        im = decode_pixels(it.data, it.train_key)
-        im = im[0] if train else im
-        if im.shape[:2] != (it.box[2], it.box[3]):
-            raise ValueError("a JPEG decodes to another size than its header states")
-        out[off:off + im.size].reshape(im.shape)[...] = im
-        st.bytes_dev[off:off + im.size].copy_(st.bytes[off:off + im.size], non_blocking=True)
-        keep[row] = False
-    left = int(keep.sum())
-    st.jdesc_np[:left] = st.jdesc_np[:njpeg][keep]
-    return left, int(bad.size)
-
-
+        _put(state, e)
 
 
 def _shutdown(state):
@@ -961,6 +897,21 @@ def _shutdown(state):
             state.out.get_nowait()
     except queue.Empty:
         pass
+
+
+def check_switches(jpeg_decode='host', jpeg_entropy='host', cache='none', cache_bytes=None):
+    """The values and combinations of the device pipeline's switches, for DeviceLoader and load_batch_with_text alike."""
+    if cache not in ('none', 'device'):
+        raise ValueError("cache must be 'none' or 'device', not %r" % (cache,))
+    if cache == 'device' and (cache_bytes is None or isinstance(cache_bytes, bool) or int(cache_bytes) < 1):
+        raise ValueError("cache='device' needs an explicit positive cache_bytes: the decoded size of a dataset is not "
+                         "known before it is decoded, and no share of the device memory is taken silently")
+    if jpeg_decode not in ('host', 'device'):
+        raise ValueError("jpeg_decode must be 'host' or 'device', not %r" % (jpeg_decode,))
+    if jpeg_entropy not in ('host', 'device'):
+        raise ValueError("jpeg_entropy must be 'host' or 'device', not %r" % (jpeg_entropy,))
+    if jpeg_entropy == 'device' and jpeg_decode != 'device':
+        raise ValueError("jpeg_entropy='device' needs jpeg_decode='device': the coefficients go to ds_jpeg_reconstruct")
 
 
 class DeviceLoader:
@@ -981,23 +932,11 @@ class DeviceLoader:
     def __init__(self, dataset, batch_size=32, shuffle=True, height=299, width=299, is_training=False, device="cuda",
                  rank=0, world=1, seed=0, loop=True, max_token_id=None, num_classes=None, workers=8, prefetch=2,
                  decode_images=True, jpeg_decode='host', jpeg_entropy='host', cache='none', cache_bytes=None):
-        if cache not in ('none', 'device'):
-            raise ValueError("cache must be 'none' or 'device', not %r" % (cache,))
-        if cache == 'device' and (cache_bytes is None or isinstance(cache_bytes, bool) or int(cache_bytes) < 1):
-            raise ValueError("cache='device' needs an explicit positive cache_bytes: the decoded size of a dataset is not "
-                             "known before it is decoded, and no share of the device memory is taken silently")
-        if jpeg_decode not in ('host', 'device'):
-            raise ValueError("jpeg_decode must be 'host' or 'device', not %r" % (jpeg_decode,))
-        if jpeg_entropy not in ('host', 'device'):
-            raise ValueError("jpeg_entropy must be 'host' or 'device', not %r" % (jpeg_entropy,))
-        if jpeg_entropy == 'device' and jpeg_decode != 'device':
-            raise ValueError("jpeg_entropy='device' needs jpeg_decode='device': the coefficients go to ds_jpeg_reconstruct")
+        check_switches(jpeg_decode, jpeg_entropy, cache, cache_bytes)
         self.jpeg_decode, self.jpeg_entropy = jpeg_decode, jpeg_entropy
         self.jpeg_fallbacks = 0
         self.jpeg_device_entropy = 0
         self.cache = cache
-        self._cache_stats = {'hits': 0, 'misses': 0, 'spilled': 0, 'bytes_used': 0, 'records': 0,
-                             'bytes_capacity': int(cache_bytes) if cache == 'device' and decode_images else 0}
         if batch_size < 1 or height < 1 or width < 1 or world < 1 or not 0 <= rank < world:
             raise ValueError("DeviceLoader: bad batch_size / height / width / rank / world")
         self.workers = clamp_workers(workers)
@@ -1010,16 +949,19 @@ class DeviceLoader:
             device = torch.device("cuda", torch.cuda.current_device())      # the caller's current device, not the feeder thread's
         if cache == 'device' and self.decode_images and device.type != "cuda":
             raise ValueError("cache='device' needs a CUDA/HIP device: the arena is device memory")
+        jpeg = self.decode_images and jpeg_decode == 'device'
+        cfg = _Config(int(batch_size), int(height), int(width), device, self.decode_images,
+                      train=self.decode_images and bool(is_training), jpeg=jpeg, entropy=jpeg and jpeg_entropy == 'device',
+                      cache_bytes=int(cache_bytes) if cache == 'device' and self.decode_images else None,
+                      shuffle=bool(shuffle), rank=rank, world=world, seed=seed, loop=bool(loop), max_token_id=max_token_id,
+                      num_classes=num_classes, prefetch=self.prefetch,
+                      inflight=max(4 * self.workers, min(int(batch_size), 256)))
+        self._cache_stats = {'hits': 0, 'misses': 0, 'spilled': 0, 'bytes_used': 0, 'records': 0,
+                             'bytes_capacity': cfg.cache_bytes or 0}
         st = self._state = _State()
         st.out = queue.Queue(maxsize=self.prefetch)
         st.pool = OrderedPool(self.workers)
-        inflight = max(4 * self.workers, min(int(batch_size), 256))
-        st.thread = threading.Thread(target=_feeder, name="ds-input-feeder", daemon=True,
-                                     args=(st, dataset, int(batch_size), bool(shuffle), int(height), int(width), device, rank,
-                                           world, seed, bool(loop), max_token_id, num_classes, self.decode_images,
-                                           self.prefetch, inflight, bool(is_training), jpeg_decode == 'device',
-                                           jpeg_entropy == 'device',
-                                           int(cache_bytes) if cache == 'device' and self.decode_images else None))
+        st.thread = threading.Thread(target=_feeder, name="ds-input-feeder", daemon=True, args=(st, dataset, cfg))
         self._finalizer = weakref.finalize(self, _shutdown, st)
         st.thread.start()
 
@@ -1030,27 +972,24 @@ class DeviceLoader:
         if self._done:
             raise StopIteration
         item = self._state.out.get()
-        if item[0] == "batch":
-            _, out, event, stream, fallbacks, on_device, cstats = item
-            self.jpeg_fallbacks += fallbacks
-            self.jpeg_device_entropy += on_device
-            if cstats is not None:
+        if isinstance(item, _Batch):
+            self.jpeg_fallbacks += item.fallbacks
+            self.jpeg_device_entropy += item.on_device
+            if item.stats is not None:
                 c = self._cache_stats
-                c['hits'] += cstats[0]
-                c['misses'] += cstats[1]
-                c['spilled'] += cstats[2]
-                c['records'] += cstats[3]
-                c['bytes_used'] = max(c['bytes_used'], cstats[4])
-            if event is not None:
+                for k in ('hits', 'misses', 'spilled', 'records'):
+                    c[k] += getattr(item.stats, k)
+                c['bytes_used'] = max(c['bytes_used'], item.stats.bytes_used)
+            if item.event is not None:
                 import torch
-                cur = torch.cuda.current_stream(stream.device)
-                cur.wait_event(event)
-                for t in out.values():          # allocated on the copy stream, consumed (and later freed) on this one
+                cur = torch.cuda.current_stream(item.stream.device)
+                cur.wait_event(item.event)
+                for t in item.out.values():     # allocated on the copy stream, consumed (and later freed) on this one
                     t.record_stream(cur)
-            return out
+            return item.out
         self.close()
-        if item[0] == "error":
-            raise item[1]
+        if item is not None:                    # the feeder's exception; None is the end of the stream
+            raise item
         raise StopIteration
 
     def close(self):
