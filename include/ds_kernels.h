@@ -1066,6 +1066,28 @@ int ds_ragged_gather(const uint8_t *arena, int64_t narena, const uint8_t *spill,
 int ds_ragged_gather_host(const uint8_t *arena, int64_t narena, const uint8_t *spill, int64_t nspill,
                           const ds_gather_desc *desc, int32_t batch, uint8_t *out, int64_t nout);
 
+/* ---- streaming evaluation metrics (csrc/metrics.hip) ----------------------------------------------------------------------
+ * ds_eval_metrics_update adds one batch to two accumulators that stay on the device; the caller zeroes them once and reads
+ * them back when the evaluation is over.  logits: fp32 [B, C], row stride ldl >= C floats; labels: int64 [B].
+ * counts: C*C + C + 4 int64 --
+ *   confusion[C*C]   row = label, column = prediction (the LOWEST index among the maximal logits)
+ *   rank_hist[C]     rank = #{ j : z_j > z_y, or z_j == z_y and j < y }: rank == 0 exactly when the prediction is the label,
+ *                    top-k accuracy = sum(rank_hist[:k]) / n
+ *   n, n_nonfinite, n_bad_label, one reserved 0
+ * A row with any NaN or +-inf logit counts in n_nonfinite and nowhere else; otherwise a row whose label is outside [0, C)
+ * counts in n_bad_label and nowhere else (no address is formed from such a label); every other row counts in n, in one
+ * confusion bin and one rank bin, and adds logsumexp(z) - z_y (natural logarithm, computed in double from the fp32 logits
+ * after subtracting the maximum) to loss_sum[0], one double.
+ * Bitwise reproducible from run to run: the integer bins are combined per workgroup in LDS and take at most one integer
+ * atomic add per non-zero bin and workgroup; the batch's loss goes through per-workgroup double partials in `scratch`
+ * (ds_eval_metrics_workspace(B, C) bytes, 8-byte aligned, private to the stream) and a second small launch that adds them in
+ * index order.  No float atomic, no hand-off between workgroups.
+ * DS_ERR_ARG before any launch: a null pointer, B outside [1, 65536], C outside [1, 1024], ldl < C, logits not 4-byte or
+ * labels / counts / loss_sum / scratch not 8-byte aligned.  ds_eval_metrics_workspace is host-only: bytes, < 0 on a bad B or C. */
+int ds_eval_metrics_workspace(int32_t B, int32_t C);
+int ds_eval_metrics_update(const float *logits, int32_t ldl, const int64_t *labels, int32_t B, int32_t C, int64_t *counts,
+                           double *loss_sum, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -299,6 +299,8 @@ SIGNATURES = {
     "ds_jpeg_entropy_decode_device": (C.c_int, [_P, _i64, _P, _i32, _P, _i64, _P, _i64, _P, _P]),
     "ds_ragged_gather": (C.c_int, [_P, _i64, _P, _i64, _P, _i32, _P, _i64, _P]),
     "ds_ragged_gather_host": (C.c_int, [_P, _i64, _P, _i64, _P, _i32, _P, _i64]),
+    "ds_eval_metrics_workspace": (C.c_int, [_i32, _i32]),
+    "ds_eval_metrics_update": (C.c_int, [_P, _i32, _P, _i32, _i32, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1003,6 +1003,33 @@ def fill(dst, n, value):
     _lib.check(_lib.load().ds_fill(_p(dst), n, value, _stream()), "ds_fill")
 
 
+# ---- streaming evaluation metrics (ds_eval_metrics_update) ------------------------------------------------------------------
+def eval_metrics_workspace(B, C_):
+    """Bytes of scratch ds_eval_metrics_update needs for a [B, C_] batch (host only)."""
+    n = _lib.load().ds_eval_metrics_workspace(B, C_)
+    _lib.check(min(n, 0), "ds_eval_metrics_workspace")
+    return n
+
+
+def eval_metrics_update(logits, labels, counts, loss_sum, scratch):
+    """Add the batch (fp32 logits [B, C], unit column stride; int64 labels [B]) to counts (int64 [C*C + C + 4]) and loss_sum
+    (float64 [1]) on the current stream: include/ds_kernels.h has the layout.  Nothing is read back."""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("eval_metrics_update: logits must be fp32 [B, C] with unit column stride")
+    B, C_ = logits.shape
+    if labels.dtype != torch.int64 or labels.shape != (B,) or not labels.is_contiguous():
+        raise ValueError("eval_metrics_update: labels must be contiguous int64 [B]")
+    if counts.dtype != torch.int64 or counts.numel() != C_ * C_ + C_ + 4 or not counts.is_contiguous():
+        raise ValueError("eval_metrics_update: counts must be contiguous int64 [C*C + C + 4]")
+    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise ValueError("eval_metrics_update: loss_sum must be one float64")
+    need = eval_metrics_workspace(B, C_)
+    if scratch.numel() * scratch.element_size() < need or not scratch.is_contiguous():
+        raise ValueError("eval_metrics_update: scratch is smaller than eval_metrics_workspace(B, C) = %d bytes" % need)
+    _lib.check(_lib.load().ds_eval_metrics_update(_p(logits), logits.stride(0), _p(labels), B, C_, _p(counts), _p(loss_sum),
+                                                  _p(scratch), _stream()), "ds_eval_metrics_update")
+
+
 # ---- eval-time image preprocessing (ds_preprocess_eval) ---------------------------------------------------------------------
 def preprocess_desc_dtype():
     """NumPy view of ds_preprocess_desc (24 bytes): one record per image of a ragged uint8 batch."""

@@ -17,6 +17,7 @@ import time
 
 import torch
 
+from .metrics import check_metrics_config
 from .synthetic import synthetic_batch_numpy, to_device
 
 
@@ -26,15 +27,19 @@ def _rank_world():
     return 0, 1
 
 
-def save_checkpoint(model, train_dir, step):
-    """Variables under their TF names + Adam slots + step, as one torch file per checkpoint."""
+def _write_checkpoint(model, path, step):
     net = model.net
     torch.cuda.synchronize()
-    path = os.path.join(train_dir, "model.ckpt-%d.pt" % step)
     # plain tensors / numbers / strings only, so that the file loads with weights_only=True
     torch.save({"variables": {k: torch.from_numpy(v) for k, v in net.state_dict().items()},
                 "adam_m": net.store.m.cpu(), "adam_v": net.store.v.cpu(), "global_step": int(step),
                 "config": json.dumps(model.config, default=str)}, path)
+
+
+def save_checkpoint(model, train_dir, step):
+    """Variables under their TF names + Adam slots + step, as one torch file per checkpoint."""
+    path = os.path.join(train_dir, "model.ckpt-%d.pt" % step)
+    _write_checkpoint(model, path, step)
     with open(os.path.join(train_dir, "checkpoint"), "w") as f:
         json.dump({"model_checkpoint_path": os.path.basename(path), "global_step": step}, f)
     return path
@@ -46,6 +51,53 @@ def latest_checkpoint(checkpoint_dir):
         return None
     with open(idx) as f:
         return os.path.join(checkpoint_dir, json.load(f)["model_checkpoint_path"])
+
+
+class Validator:
+    """config['validate_every'] = N: held-out metrics during training (rank 0 only; no collective is involved).  run() feeds
+    model.validation_batches(config['validate_batches']) -- the same batches every time -- through net.predict(is_training=
+    False), which writes no variable, moving statistic, pivot or step counter, into a freshly reset StreamingMetrics, and
+    appends result() + global_step + learning_rate to <train_dir>/validation.jsonl.  config['keep_best']: an accuracy strictly
+    above the best so far also writes model.best.pt (what save_checkpoint writes; the `checkpoint` index is left alone, so
+    latest_checkpoint does not see it) and best.json."""
+
+    def __init__(self, model, train_dir):
+        from .metrics import DEFAULT_TOP_K, StreamingMetrics
+        cfg = model.config
+        self.model, self.train_dir = model, train_dir
+        self.every = int(cfg["validate_every"])
+        self.batches = int(cfg.get("validate_batches", 10))
+        self.keep_best = bool(cfg.get("keep_best", False))
+        self.fused = bool(cfg.get("fused_inference", False))
+        self.best = None
+        self.metrics = StreamingMetrics(model.net.nb_emotions, model.net.device, cfg.get("metrics_top_k", DEFAULT_TOP_K))
+
+    def due(self, step, num_steps):
+        return step % self.every == 0 or step == num_steps
+
+    def run(self, step, lr, quiet=False):
+        net = self.model.net
+        self.metrics.reset()
+        for batch in self.model.validation_batches(self.batches):
+            self.metrics.update(net.predict(batch, is_training=False, fused=self.fused), batch["labels"])
+        res = self.metrics.result()
+        _warn_uncounted(res, "validation at step %d" % step)
+        with open(os.path.join(self.train_dir, "validation.jsonl"), "a") as f:
+            f.write(json.dumps(dict(res, global_step=step, learning_rate=lr)) + "\n")
+        if not quiet:
+            print("global step %d: validation accuracy = %.4f, loss = %.4f (%d samples)" % (step, res["accuracy"], res["loss"], res["n"]))
+        if self.keep_best and (self.best is None or res["accuracy"] > self.best):
+            self.best = res["accuracy"]
+            _write_checkpoint(self.model, os.path.join(self.train_dir, "model.best.pt"), step)
+            with open(os.path.join(self.train_dir, "best.json"), "w") as f:
+                json.dump({"global_step": step, "accuracy": res["accuracy"]}, f)
+        return res
+
+
+def _warn_uncounted(res, what):
+    if res["n_nonfinite"] or res["n_bad_label"]:
+        print("WARNING: %s: %d rows with non-finite logits and %d rows with a label out of range are not in the metrics"
+              % (what, res["n_nonfinite"], res["n_bad_label"]))
 
 
 def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_interval_secs=600,
@@ -61,6 +113,7 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
     # python-2 integer division, :140; under data parallelism one step consumes batch_size * world samples
     nb_batches = max(1, model.dataset.num_samples // (batch_size * world))
     net = model.net
+    validator = Validator(model, train_dir) if rank == 0 and cfg.get("validate_every") is not None else None
     epoch, lr = 0, initial_lr
     last_save = time.time()
     loss_val = float("nan")
@@ -82,6 +135,8 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
             t0 = time.time()
             if rank == 0 and not quiet:
                 print("global step %d: loss = %.4f (%.3f sec/step)" % (step + 1, loss_val, dt))
+        if validator is not None and validator.due(step + 1, num_steps):
+            validator.run(step + 1, lr, quiet=quiet)
         if rank == 0 and time.time() - last_save >= save_interval_secs:
             save_checkpoint(model, train_dir, step + 1)
             last_save = time.time()
@@ -108,23 +163,40 @@ def run_evaluation(model, checkpoint_dir, log_dir, mode, num_evals, batch_fn=Non
     returned, printed and appended to <log_dir>/<mode>/accuracy.jsonl.
     As in the reference the graph is built with is_training = (mode == 'train') (:65).  config['fused_inference'] = True:
     the moving-statistics evaluation runs SentimentNet.predict(fused=True) (same logits bit for bit; ignored for mode 'train',
-    which keeps batch statistics)."""
+    which keeps batch statistics).  config['eval_metrics'] = True: the batches are accumulated on the device by
+    metrics.StreamingMetrics instead of argmax + .item() per batch (one read-back at the end), and its result() -- confusion
+    matrix, per-class precision / recall / F1, top-k accuracy, cross-entropy -- is appended with global_step, num_evals and
+    mode to <log_dir>/<mode>/metrics.jsonl; the returned accuracy and accuracy.jsonl are what they are without the key."""
     path = latest_checkpoint(checkpoint_dir)
     if path is None:
         raise FileNotFoundError("no checkpoint in %s" % checkpoint_dir)
     step = load_checkpoint(model, path)
     is_training = mode == "train"
     fused = bool(getattr(model, "config", {}).get("fused_inference", False)) and not is_training
+    metrics = None
+    if getattr(model, "config", {}).get("eval_metrics", False):
+        from .metrics import DEFAULT_TOP_K, StreamingMetrics
+        metrics = StreamingMetrics(model.net.nb_emotions, model.net.device, model.config.get("metrics_top_k", DEFAULT_TOP_K))
     correct = total = 0
     for i in range(num_evals):
         batch = batch_fn(i) if batch_fn is not None else model.next_batch(10 ** 6 + i)
         logits = model.net.predict(batch, is_training=is_training, fused=fused)
         model.logits, model.labels = logits, batch["labels"]
-        correct += int((logits.argmax(dim=1) == batch["labels"]).sum().item())     # streaming_accuracy
+        if metrics is not None:
+            metrics.update(logits, batch["labels"])       # enqueued: nothing is read back until the loop is over
+        else:
+            correct += int((logits.argmax(dim=1) == batch["labels"]).sum().item())     # streaming_accuracy
         total += int(batch["labels"].shape[0])
-    acc = correct / max(total, 1)
     out_dir = os.path.join(log_dir, mode)
     os.makedirs(out_dir, exist_ok=True)
+    if metrics is not None:
+        res = metrics.result()
+        _warn_uncounted(res, "evaluation of step %d" % step)
+        # streaming_accuracy's denominator is every row; a row the metrics leave out was not a correct prediction
+        correct = sum(row[c] for c, row in enumerate(res["confusion"]))
+        with open(os.path.join(out_dir, "metrics.jsonl"), "a") as f:
+            f.write(json.dumps(dict(res, global_step=step, num_evals=num_evals, mode=mode)) + "\n")
+    acc = correct / max(total, 1)
     with open(os.path.join(out_dir, "accuracy.jsonl"), "a") as f:
         f.write(json.dumps({"global_step": step, "accuracy": acc, "num_evals": num_evals, "mode": mode}) + "\n")
     if not quiet:
@@ -150,7 +222,10 @@ class SyntheticInput:
     config['input_cache']: 'none' (default) or 'device' (every record is decoded once and its pixels stay in an arena of
     config['input_cache_gb'] GB of device memory, a positive number without a default; later passes are assembled from
     there by ds_ragged_gather, the same batches bit for bit) -- honoured only with config['input_pipeline'] = 'device';
-    with the host pipeline or config['synthetic'] the key is a ValueError."""
+    with the host pipeline or config['synthetic'] the key is a ValueError.
+    config['eval_metrics'], config['validate_every'], config['validate_batches'], config['keep_best'], config['metrics_top_k']:
+    streaming metrics in evaluate_* and validation during train_* (metrics.check_metrics_config lists what each takes;
+    a bad value or a key that would do nothing is a ValueError)."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
@@ -158,6 +233,8 @@ class SyntheticInput:
         self.post_ids = self.days = self.labels = None
         self._records = None
         self._augment = False
+        self._validation = None
+        check_metrics_config(config)
         if config.get("augment", False) and config.get("synthetic", False):
             raise ValueError("config['augment'] needs a real dataset: synthetic batches have no JPEG to augment")
         if config.get("jpeg_decode", "host") not in ("host", "device"):
@@ -198,6 +275,41 @@ class SyntheticInput:
         if self._records is not None:
             raise RuntimeError("use_augmentation() must precede the first batch")
         self._augment = bool(self.config.get("augment", False))
+
+    def validation_batches(self, count):
+        """The held-out batches of config['validate_every']: the same `count` batches of config['batch_size'] at every call,
+        in global order (rank 0, world 1), independent of the training stream, which is not consumed.  Synthetic: the
+        batches a single-process evaluate_* reads (seed 10**6 + i), built once and kept on the device.  A real dataset: a
+        fresh loader on the 'validation' split -- shuffle=False, the eval preprocessing, the configured 'input_pipeline' /
+        'jpeg_*' arms, no 'input_cache', no augmentation -- that is closed when the batches are drawn; it makes one pass at
+        most, so a split shorter than count * batch_size gives fewer batches (the ragged tail is dropped as in training)."""
+        post_size, vocab, nb, with_images, device = self._in
+        bs = self.config["batch_size"]
+        if not hasattr(self.dataset, "data_sources"):
+            if self._validation is None or len(self._validation) != count:
+                self._validation = [to_device(synthetic_batch_numpy(bs, post_size, vocab, nb, seed=10 ** 6 + i,
+                                                                    with_images=with_images), device) for i in range(count)]
+            yield from self._validation
+            return
+        from .datasets.convert_to_dataset import get_split_with_text
+        from .image_model.im_model import load_batch_with_text
+        if self._validation is None:
+            self._validation = get_split_with_text("validation", self.config["dataset_dir"])
+        if self._validation.num_samples < bs:
+            raise ValueError("config['validate_every']: the validation split has %d records, fewer than one batch of %d"
+                             % (self._validation.num_samples, bs))
+        records = load_batch_with_text(self._validation, bs, shuffle=False, height=224, width=224, is_training=False,
+                                       device=device, rank=0, world=1, loop=False, max_token_id=vocab,
+                                       num_classes=getattr(self.dataset, "num_classes", nb),
+                                       pipeline=self.config.get("input_pipeline", "host"),
+                                       workers=self.config.get("input_workers", 8),
+                                       jpeg_decode=self.config.get("jpeg_decode", "host"),
+                                       jpeg_entropy=self.config.get("jpeg_entropy", "host"), decode_images=with_images)
+        try:
+            for _, batch in zip(range(count), records):
+                yield batch
+        finally:
+            records.close()
 
     def next_batch(self, step):
         post_size, vocab, nb, with_images, device = self._in
