@@ -809,6 +809,14 @@ int ds_adam_tf(float *theta, const float *g, float *m, float *v, int64_t n, int6
                float grad_scale, float lr_t, const float *lr_t_dev, float beta1, float beta2, float eps,
                void *stream);
 
+/* Clone-gradient accumulation over the flat gradient buffer (slim/deployment/model_deploy.py:414-444, _sum_clones_gradients).
+ * mode 0: acc[i] = g[i]            (first clone)
+ * mode 1: acc[i] = acc[i] + g[i]   (middle clones)
+ * mode 2: g[i]   = acc[i] + g[i]   (last clone: the sum lands where the all-reduce, Adam and grads_state_dict read it)
+ * The running sum is always the LEFT operand: ((g0 + g1) + g2) + ... in clone order, plain fp32 adds, no atomics.
+ * n % 4 == 0, both pointers 16-byte aligned (what ParamStore lays out); anything else is DS_ERR_ARG before any launch. */
+int ds_grad_accumulate(float *acc, float *g, int64_t n, int32_t mode, void *stream);
+
 /* small helpers (deterministic two-stage reductions; scratch is caller-provided) */
 /* out[0] = sum x^2 (= 2*tf.nn.l2_loss); scratch >= 256 floats                                */
 int ds_sumsq(const float *x, int64_t n, float *scratch, float *out, void *stream);

@@ -275,6 +275,28 @@ __global__ __launch_bounds__(256) void adam_tf_kernel(float *theta, const float 
     }
 }
 
+// ---- clone-gradient accumulation over the flat gradient buffer -----------------------------------------
+// One float4 per thread and trip: element i is read and written by the same thread only, so acc and g may be any two
+// buffers (or the same one) and the result does not depend on the launch shape.  The running sum is the LEFT operand of a
+// plain fp32 add (no contraction is possible: there is no multiply).  Plain loads and stores: the sum is read next by the
+// all-reduce / Adam, the running sum by the next clone -- both want it in L2 / the Infinity Cache.
+constexpr int kAccumVecPerBlock = 256 * 4;       // four 16-byte trips per thread before the grid cap takes over
+
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float4 *acc, float4 *g, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 b = g[i];
+        if (MODE == 0) {
+            acc[i] = b;
+        } else {
+            const float4 a = acc[i];
+            const float4 s = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+            if (MODE == 1) acc[i] = s;
+            else g[i] = s;
+        }
+    }
+}
+
 // ---- reductions / plumbing ---------------------------------------------------------------------------
 constexpr int kSumsqBlocks = 256;
 
@@ -510,6 +532,20 @@ extern "C" int ds_adam_tf(float *theta, const float *g, float *m, float *v, int6
     hipLaunchKernelGGL(adam_tf_kernel, dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
                        n, n_wd, wd, grad_scale, lr_t, lr_t_dev, beta1, beta2, eps);
     return ds::check_launch("ds_adam_tf");
+}
+
+extern "C" int ds_grad_accumulate(float *acc, float *g, int64_t n, int32_t mode, void *stream) {
+    DS_REQUIRE(acc && g, "ds_grad_accumulate: null pointer");
+    DS_REQUIRE(n > 0 && n % 4 == 0, "ds_grad_accumulate: n must be a positive multiple of 4 (got %lld)", (long long)n);
+    DS_REQUIRE(mode >= 0 && mode <= 2, "ds_grad_accumulate: mode must be 0 (first), 1 (middle) or 2 (last), not %d", (int)mode);
+    DS_REQUIRE(((uintptr_t)acc | (uintptr_t)g) % 16 == 0, "ds_grad_accumulate: acc and g must be 16-byte aligned");
+    const int64_t n4 = n / 4;
+    const dim3 grid(ds::stream_grid(n4, kAccumVecPerBlock)), block(256);
+    float4 *a4 = reinterpret_cast<float4 *>(acc), *g4 = reinterpret_cast<float4 *>(g);
+    if (mode == 0) hipLaunchKernelGGL(grad_accumulate_kernel<0>, grid, block, 0, (hipStream_t)stream, a4, g4, n4);
+    else if (mode == 1) hipLaunchKernelGGL(grad_accumulate_kernel<1>, grid, block, 0, (hipStream_t)stream, a4, g4, n4);
+    else hipLaunchKernelGGL(grad_accumulate_kernel<2>, grid, block, 0, (hipStream_t)stream, a4, g4, n4);
+    return ds::check_launch("ds_grad_accumulate");
 }
 
 extern "C" int ds_sumsq(const float *x, int64_t n, float *scratch, float *out, void *stream) {

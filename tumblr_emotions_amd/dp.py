@@ -15,6 +15,9 @@ BatchNorm statistics and moving averages per clone (:353-355).  Here that become
   * the 1/world scale and the L2 gradient are applied inside the fused Adam kernel, after the
     reduction (L2 counted once, like slim);
   * BatchNorm uses per-rank batch statistics (slim keeps them per clone).
+  * a rank may itself train several clones per step, one after the other (SentimentNet.train_step(num_clones=K)): the flat
+    gradient is then complete only after the last clone's accumulation, the reducer runs deferred (begin_step(defer=True))
+    and both buckets are reduced at the end -- one all-reduce per step, not per clone.
 
 Nothing here needs a GPU: the same functions run under gloo on CPU tensors (tests/test_dp_cpu.py).
 """
@@ -92,6 +95,7 @@ class GradientReducer:
         self._ready = set()
         self._needed = set()
         self._events = []
+        self._defer = False
         # timing=True (bench.py): event pairs around the early bucket-1 reduce on the side stream and at the end of
         # the backward pass on the main stream, so the first multi-GPU run says whether the overlap is real
         self.timing = False
@@ -102,14 +106,17 @@ class GradientReducer:
         """Names of the backward stages that must have finished before bucket 1 is complete."""
         self._needed = set(names)
 
-    def begin_step(self):
+    def begin_step(self, defer=False):
+        """defer=True (a step of several clones, SentimentNet.train_step(num_clones=K)): the flat gradient is complete only
+        after the last clone's accumulation, so stage_done records and launches nothing and finish() reduces both buckets."""
         self._ready.clear()
         self._events = []
         self._pending = None
+        self._defer = bool(defer)
 
     def stage_done(self, name):
         """Called by the engines from inside backward(); launches bucket 1 when the last stage reports."""
-        if not self.active:
+        if not self.active or self._defer:
             return
         self._ready.add(name)
         if self.overlap:       # stages may run on different streams (text tower): remember where each finished

@@ -4,7 +4,7 @@ import os
 import numpy as np
 
 from ..net import SentimentNet
-from ..training import SyntheticInput, run_training
+from ..training import SyntheticInput, check_clones_config, run_training
 
 _RANDOM_SEED = 0
 _CONFIG = {'mode': 'train',
@@ -57,9 +57,11 @@ class ImageModel(SyntheticInput):
         self.learning_rate = config['initial_lr']
         self._init_input(config, config.get('post_size', 50), config.get('vocab_size', 400000), nb_emotions, True, device)
         self.nb_emotions = self.dataset.num_classes
-        for key in ("train_all", "trainable_embedding", "frozen_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
+        for key in ("train_all", "trainable_embedding", "frozen_bn", "sync_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
             if key in config:
                 net_kw.setdefault(key, bool(config[key]))
+        if "dtype" in config:
+            net_kw.setdefault("dtype", config["dtype"])
         self.net = SentimentNet(mode="image", nb_emotions=self.nb_emotions, device=device, **net_kw)
         self.net.initialize(seed=config.get('seed', 1))
         self.logits = None
@@ -67,7 +69,10 @@ class ImageModel(SyntheticInput):
 
 def train_image_model(checkpoints_dir, train_dir, num_steps, *, config=None, quiet=False):
     """Fine tune the Image model, retraining Mixed_5c (im_model.py:166-225)."""
-    model = ImageModel(dict(_CONFIG, **(config or {})))
+    config = dict(_CONFIG, **(config or {}))
+    check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
+    model = ImageModel(config)
+    model.use_clones()
     model.use_augmentation()
     init_fn = get_init_fn(checkpoints_dir)
     if init_fn is not None:

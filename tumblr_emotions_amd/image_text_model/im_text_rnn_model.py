@@ -7,7 +7,7 @@ from .. import ops
 from ..image_model.im_model import get_init_fn
 from ..net import SentimentNet
 from ..text_model.text_preprocessing import resolve_embedding
-from ..training import SyntheticInput, run_training
+from ..training import SyntheticInput, check_clones_config, run_training
 
 _POST_SIZE = 50
 _CONFIG = {'mode': 'train',
@@ -35,9 +35,11 @@ class DeepSentiment(SyntheticInput):
         embedding, vocab, dim, self.word_to_id = resolve_embedding(config, embedding)
         self._init_input(config, post, vocab, nb_emotions, True, device)
         self.nb_emotions = self.dataset.num_classes
-        for key in ("train_all", "trainable_embedding", "frozen_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
+        for key in ("train_all", "trainable_embedding", "frozen_bn", "sync_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
             if key in config:
                 net_kw.setdefault(key, bool(config[key]))
+        if "dtype" in config:
+            net_kw.setdefault("dtype", config["dtype"])
         self.net = SentimentNet(mode="joint", nb_emotions=self.nb_emotions,
                                 im_features_size=config['im_features_size'], rnn_size=config['rnn_size'],
                                 fc_size=config['fc_size'], vocab_size=vocab, embedding_dim=dim, post_size=post,
@@ -61,7 +63,10 @@ class DeepSentiment(SyntheticInput):
 
 def train_deep_sentiment(checkpoints_dir, train_dir, num_steps, *, config=None, quiet=False):
     """Fine tune the inception model, retraining the last layer (im_text_rnn_model.py:107-169)."""
-    model = DeepSentiment(dict(_CONFIG, **(config or {})))
+    config = dict(_CONFIG, **(config or {}))
+    check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
+    model = DeepSentiment(config)
+    model.use_clones()
     model.use_augmentation()
     init_fn = get_init_fn(checkpoints_dir)
     if init_fn is not None:

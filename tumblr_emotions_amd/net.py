@@ -101,6 +101,7 @@ class SentimentNet:
         # sync_bn: BatchNorm over the global batch (off by default: slim's clones -- and the DP parity tests -- keep the
         # statistics per rank, model_deploy.py:353-355)
         self.sync_bn = bool(sync_bn and self.world > 1 and self.image is not None)
+        self.sync_bn_requested = bool(sync_bn)      # (train_step(num_clones > 1) refuses the request itself, whatever the world)
         if self.sync_bn:
             if dtype != "f32":
                 raise ValueError("sync_bn is implemented for the fp32 configuration")
@@ -434,7 +435,14 @@ class SentimentNet:
         reg = 0.0
         if self.store.n_l2 > 0 or self.frozen_l2_sumsq:
             reg = 0.5 * WEIGHT_DECAY * (self.frozen_l2_sumsq + float(self.l2_buf.item()))
-        loss = float(self.loss_buf.item()) + reg
+        if getattr(self, "_clone_count", 1) > 1:      # slim's total loss of this rank's clones: the mean of their cross-entropies
+            ce = 0.0
+            for x in self.clone_loss.cpu().tolist():      # summed in clone order, in double
+                ce += x
+            ce /= self._clone_count
+        else:
+            ce = float(self.loss_buf.item())
+        loss = ce + reg
         self.check_status()
         return loss
 
@@ -448,7 +456,18 @@ class SentimentNet:
         return int(seed) * 4096 + self.reducer.rank
 
     # ---- one training step -----------------------------------------------------------------------
-    def train_step(self, batch, lr, dropout_mask=None, seed=None):
+    def train_step(self, batch, lr, dropout_mask=None, seed=None, num_clones=1, after_clone=None):
+        """One optimiser step on `batch`.  num_clones = K > 1: the step of K of slim's in-graph clones on this device, run back
+        to back -- clone c is rows [c B/K, (c+1) B/K) of every tensor of `batch` (and of `dropout_mask`), has
+        its own BatchNorm batch statistics and the dropout stream of virtual rank rank*K + c; the clone gradients are summed in
+        clone order by ds_grad_accumulate, all-reduced once, and Adam runs once with grad_scale 1 / (world * K); the L2 term is
+        counted once, the moving statistics are clone 0's, `step` advances once.  `logits` then holds all B rows in order and
+        total_loss_value() the mean of the K cross-entropies + the L2 term.  after_clone(c), a test and diagnostic hook, is
+        called once clone c's backward pass and accumulation are enqueued, before clone c + 1 starts.  num_clones = 1 is the
+        plain step, launch for launch."""
+        if type(num_clones) is not int or num_clones != 1:
+            return self._train_step_clones(batch, lr, dropout_mask, seed, num_clones, after_clone)
+        self._clone_count = 1
         st = self.store
         self.step += 1
         t = self.step
@@ -484,6 +503,93 @@ class SentimentNet:
         ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
                     ADAM_B1, ADAM_B2, ADAM_EPS)
         return ce
+
+    # ---- one training step of several clones ---------------------------------------------------------
+    def check_clones(self, num_clones, batch_rows=None, seed=None):
+        """The combinations train_step(num_clones=K > 1) refuses, before anything is enqueued or counted."""
+        K = num_clones
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+            raise ValueError("num_clones must be a positive int, not %r" % (K,))
+        K = int(K)
+        if K == 1:
+            return K
+        if self.sync_bn_requested:
+            raise ValueError("num_clones = %d with sync_bn: clones have their own BatchNorm statistics by definition" % K)
+        if self.dtype != "f32":
+            raise NotImplementedError("num_clones = %d with dtype %r: clones are implemented for the fp32 configuration"
+                                      % (K, self.dtype))
+        if self._graph is not None:
+            raise NotImplementedError("num_clones = %d with a captured step: release_graph() first, a step of several "
+                                      "clones is not captured" % K)
+        if seed is not None:
+            raise ValueError("num_clones = %d with an explicit seed: every clone draws its own dropout stream" % K)
+        if K * self.world > 4096:
+            raise ValueError("num_clones * world = %d exceeds the 4096 dropout streams of a step" % (K * self.world))
+        if batch_rows is not None and batch_rows % K != 0:
+            raise ValueError("num_clones = %d does not divide the batch of %d rows" % (K, batch_rows))
+        return K
+
+    @staticmethod
+    def _clone_rows(t, lo, hi):
+        """Rows [lo, hi) of a batch tensor: a view where it keeps the 16-byte alignment the kernels load with."""
+        v = t[lo:hi]
+        return v if v.data_ptr() % 16 == 0 and v.is_contiguous() else v.clone(memory_format=torch.contiguous_format)
+
+    def _train_step_clones(self, batch, lr, dropout_mask, seed, num_clones, after_clone):
+        B = int(batch["labels"].shape[0])
+        K = self.check_clones(num_clones, B, seed)
+        if K == 1:
+            return self.train_step(batch, lr, dropout_mask=dropout_mask, seed=seed)
+        st = self.store
+        b = B // K
+        nc = self.nb_emotions
+        if getattr(self, "grad_acc", None) is None:
+            self.grad_acc = torch.zeros_like(st.grad)
+        if getattr(self, "clone_loss", None) is None or self.clone_loss.shape[0] != K:
+            self.clone_loss = torch.zeros(K, device=self.device)
+        if getattr(self, "clone_logits", None) is None or tuple(self.clone_logits.shape) != (B, nc):
+            self.clone_logits = torch.empty(B, nc, device=self.device)
+        self.step += 1
+        t = self.step
+        if self.image is not None:
+            self.image.invalidate_fused()
+        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
+        if self.frozen_bn:
+            self.image.frozen_step = True
+        try:
+            self.reducer.begin_step(defer=True)      # store.grad is complete only after the last accumulation
+            for c in range(K):
+                lo, hi = c * b, (c + 1) * b
+                sub = {k: self._clone_rows(v, lo, hi) for k, v in batch.items()}
+                mask = None if dropout_mask is None else self._clone_rows(dropout_mask, lo, hi)
+                # the dropout stream of virtual rank rank * K + c: the numbering of a (K * world)-rank run
+                clone_seed = int(self.step) * 4096 + self.reducer.rank * K + c
+                for p in self.leaves.values():
+                    p.grad = None
+                if self.image is not None:
+                    self.image.update_moving = c == 0      # the moving averages are clone 0's (model_deploy.py:353-355)
+                logits = self.forward(sub, mask, clone_seed)
+                if self.dlogits is None or self.dlogits.shape != logits.shape:
+                    self.dlogits = torch.empty(logits.shape, device=self.device)
+                ce = SoftmaxCrossEntropyFunction.apply(logits, sub["labels"], self.clone_loss[c:c + 1], self.dlogits)
+                if c == 0 and st.n_l2 > 0:      # trainable part of the L2 loss, once, on the pre-update weights
+                    ops.sumsq(st.theta, st.n_l2, self.l2_scratch, self.l2_buf)
+                ce.backward()
+                self.clone_logits[lo:hi].copy_(logits.detach())
+                ops.grad_accumulate(self.grad_acc, st.grad, st.n_trainable_padded, 0 if c == 0 else (2 if c == K - 1 else 1))
+                if after_clone is not None:
+                    after_clone(c)
+        finally:
+            if self.image is not None:
+                self.image.update_moving = True
+            if self.frozen_bn:
+                self.image.frozen_step = False
+        self.reducer.finish()
+        self.logits = self.clone_logits
+        self._clone_count = K
+        ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, 1.0 / (self.world * K), lr_t,
+                    ADAM_B1, ADAM_B2, ADAM_EPS)
+        return self.clone_loss
 
     # ---- the same step as one hipGraph ---------------------------------------------------------------
     def _batch_key(self, batch, dropout_mask):
@@ -544,12 +650,16 @@ class SentimentNet:
                 self.text.backward(d_tx)
                 self.image.backward(d_im)
 
-    def capture_step(self, batch, dropout_mask=None):
+    def capture_step(self, batch, dropout_mask=None, num_clones=1):
         """Capture one whole training step on `batch`'s tensors (static addresses: refill them in place between
         steps) into a hipGraph; later train_step calls with the same tensors replay it -- one graph launch instead
         of ~900 kernel launches, which is what bounds the step below ~64 samples per GPU.  Per-step scalars (Adam's
         lr_t, the dropout seed) are read from device memory.  Single rank only: with data parallelism the RCCL
         all-reduce stays outside a graph and the eager step is used."""
+        if type(num_clones) is not int or num_clones != 1:
+            if self.check_clones(num_clones) > 1:
+                raise NotImplementedError("capture_step with num_clones = %d: a step of several clones is not captured"
+                                          % num_clones)
         if self.frozen_bn:
             raise NotImplementedError("capture_step is not implemented for a frozen_bn net")
         if self.reducer.active:

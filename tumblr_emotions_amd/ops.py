@@ -983,6 +983,12 @@ def adam_tf(theta, g, m, v, n, n_wd, wd, grad_scale, lr_t, b1, b2, eps, lr_t_dev
                                       b1, b2, eps, _stream()), "ds_adam_tf")
 
 
+def grad_accumulate(acc, g, n, mode):
+    """Clone-gradient accumulation over the first n floats of two flat buffers: mode 0 acc = g, 1 acc = acc + g,
+    2 g = acc + g (the running sum is the left operand; n % 4 == 0, 16-byte aligned)."""
+    _lib.check(_lib.load().ds_grad_accumulate(_p(acc), _p(g), n, mode, _stream()), "ds_grad_accumulate")
+
+
 def sumsq(x, n, scratch, out):
     _lib.check(_lib.load().ds_sumsq(_p(x), n, _p(scratch), _p(out), _stream()), "ds_sumsq")
 

@@ -4,7 +4,7 @@ import torch
 
 from ..net import SentimentNet
 from .text_preprocessing import resolve_embedding
-from ..training import SyntheticInput, run_training
+from ..training import SyntheticInput, check_clones_config, run_training
 
 _RANDOM_SEED = 0
 _CONFIG = {'mode': 'train',
@@ -30,9 +30,11 @@ class TextModel(SyntheticInput):
         embedding, vocab, dim, self.word_to_id = resolve_embedding(config, embedding)
         self._init_input(config, post, vocab, nb_emotions, False, device)
         self.nb_emotions = self.dataset.num_classes
-        for key in ("train_all", "trainable_embedding"):      # optional fine-tuning switches (not in the reference _CONFIG)
+        for key in ("train_all", "trainable_embedding", "sync_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
             if key in config:
                 net_kw.setdefault(key, bool(config[key]))
+        if "dtype" in config:
+            net_kw.setdefault("dtype", config["dtype"])
         self.net = SentimentNet(mode="text", nb_emotions=self.nb_emotions, rnn_size=config['rnn_size'],
                                 vocab_size=vocab, embedding_dim=dim, post_size=post, device=device, **net_kw)
         self.net.initialize(seed=config.get('seed', 1))
@@ -44,7 +46,10 @@ class TextModel(SyntheticInput):
 
 def train_text_model(train_dir, num_steps, *, config=None, quiet=False):
     """Train rnn text model (text_embedding.py:89-150)."""
-    model = TextModel(dict(_CONFIG, **(config or {})))
+    config = dict(_CONFIG, **(config or {}))
+    check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
+    model = TextModel(config)
+    model.use_clones()
     return run_training(model, train_dir, num_steps, quiet=quiet)
 
 

@@ -15,10 +15,31 @@ import os
 import shutil
 import time
 
+import numpy as np
 import torch
 
 from .metrics import check_metrics_config
 from .synthetic import synthetic_batch_numpy, to_device
+
+
+def check_clones_config(config):
+    """config['num_clones'] = K (default 1; train_*): every rank trains K of slim's in-graph clones per step, one after the
+    other, with their gradients accumulated (SentimentNet.train_step(num_clones=K)).  config['batch_size']
+    stays the batch of ONE clone, so a rank reads batch_size * K samples per step.  Returns K.  Needs no device.  ValueError
+    for anything but a positive int (a bool is not one); with K > 1, config['sync_bn'] is a ValueError (clones have their own
+    BatchNorm statistics by definition) and a config['dtype'] other than 'f32' a NotImplementedError."""
+    K = config.get("num_clones", 1)
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 1:
+        raise ValueError("config['num_clones'] must be a positive int, not %r" % (K,))
+    K = int(K)
+    if K > 1:
+        if config.get("sync_bn", False):
+            raise ValueError("config['num_clones'] = %d with config['sync_bn']: clones have their own BatchNorm statistics "
+                             "by definition" % K)
+        if config.get("dtype", "f32") != "f32":
+            raise NotImplementedError("config['num_clones'] = %d with config['dtype'] = %r: clones are implemented for the "
+                                      "fp32 configuration" % (K, config["dtype"]))
+    return K
 
 
 def _rank_world():
@@ -110,8 +131,9 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
         os.makedirs(train_dir)
     cfg = model.config
     batch_size, initial_lr, decay = cfg["batch_size"], cfg["initial_lr"], cfg["decay_factor"]
-    # python-2 integer division, :140; under data parallelism one step consumes batch_size * world samples
-    nb_batches = max(1, model.dataset.num_samples // (batch_size * world))
+    num_clones = check_clones_config(cfg)      # batch_size is the batch of ONE clone, as in slim
+    # python-2 integer division, :140; under data parallelism one step consumes batch_size * num_clones * world samples
+    nb_batches = max(1, model.dataset.num_samples // (batch_size * num_clones * world))
     net = model.net
     validator = Validator(model, train_dir) if rank == 0 and cfg.get("validate_every") is not None else None
     epoch, lr = 0, initial_lr
@@ -127,7 +149,10 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
         model.learning_rate = lr
         batch = batch_fn(step) if batch_fn is not None else model.next_batch(step)
         model.labels = batch["labels"]
-        net.train_step(batch, lr, dropout_mask=dropout_mask)
+        if num_clones > 1:
+            net.train_step(batch, lr, dropout_mask=dropout_mask, num_clones=num_clones)
+        else:
+            net.train_step(batch, lr, dropout_mask=dropout_mask)
         model.logits = net.logits
         if (step + 1) % log_every == 0 or step + 1 == num_steps:
             loss_val = net.total_loss_value()                        # syncs: only on logging steps
@@ -225,7 +250,9 @@ class SyntheticInput:
     with the host pipeline or config['synthetic'] the key is a ValueError.
     config['eval_metrics'], config['validate_every'], config['validate_batches'], config['keep_best'], config['metrics_top_k']:
     streaming metrics in evaluate_* and validation during train_* (metrics.check_metrics_config lists what each takes;
-    a bad value or a key that would do nothing is a ValueError)."""
+    a bad value or a key that would do nothing is a ValueError).
+    config['num_clones'] = K (default 1): train_* run K clones per rank and step with config['batch_size'] rows each
+    (check_clones_config; the trainers call use_clones() before the first batch); evaluate_* and the analyses ignore it."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
@@ -270,6 +297,13 @@ class SyntheticInput:
             raise IOError("no converted dataset under config['dataset_dir'] = %r (expected %s).  Set "
                           "config['synthetic'] = True for synthetic batches" % (ddir, split))
 
+    def use_clones(self):
+        """Called by the trainers before the first batch: config['num_clones'] takes effect on next_batch()."""
+        if self._records is not None:
+            raise RuntimeError("use_clones() must precede the first batch")
+        self._train_clones = check_clones_config(self.config)
+        return self._train_clones
+
     def use_augmentation(self):
         """Called by the trainers of the models that read images, before the first batch: config['augment'] takes effect."""
         if self._records is not None:
@@ -312,12 +346,15 @@ class SyntheticInput:
             records.close()
 
     def next_batch(self, step):
+        """The batch of one training step on this rank: config['batch_size'] * config['num_clones'] samples (clone (r, c) is
+        slice r * K + c of the global batch); evaluate_* and the analyses never set _train_clones and read batch_size."""
         post_size, vocab, nb, with_images, device = self._in
         rank, world = _rank_world()
+        rows = self.config["batch_size"] * getattr(self, "_train_clones", 1)
         if hasattr(self.dataset, "data_sources"):            # real TFRecords
             if self._records is None:
                 from .image_model.im_model import load_batch_with_text
-                self._records = load_batch_with_text(self.dataset, self.config["batch_size"], height=224, width=224,
+                self._records = load_batch_with_text(self.dataset, rows, height=224, width=224,
                                                      is_training=self._augment, device=device, rank=rank, world=world, max_token_id=vocab,
                                                      num_classes=getattr(self.dataset, "num_classes", nb),
                                                      pipeline=self.config.get("input_pipeline", "host"),
@@ -330,7 +367,7 @@ class SyntheticInput:
                                                      decode_images=with_images)     # text-only: no JPEG is decoded
             b = next(self._records)
         else:
-            gb = self.config["batch_size"] * world
+            gb = rows * world
             b = synthetic_batch_numpy(gb, post_size, vocab, nb, seed=step, with_images=with_images)
             b = to_device(b, device, rank, world)
         self.post_ids, self.days = b["post_ids"], b["days"]
