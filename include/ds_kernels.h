@@ -641,7 +641,9 @@ int ds_maxpool_bn_relu_fwd(const float *z, const float *rstd, const float *shift
 /* ... and its backward: BatchNorm(+ReLU) backward of that conv straight from the POOLED gradient (3x3 stride-2
  * SAME pools).  MaxPoolGrad's full-resolution result is rebuilt per 2x2 input patch on the fly instead of being
  * written and re-read twice.  reduce -> partials float[2][C][P] (P = ds_bn_pool_bwd_partials), then
- * ds_bn_bwd_finalize as usual, then apply (dz may alias z).                                                   */
+ * ds_bn_bwd_finalize as usual, then apply (dz may alias z).  Every ds_bn_pool_* pass checks the same things before
+ * it launches (DS_ERR_ARG otherwise): N, H, W, OH, OW > 0, pads in {0, 1}, H <= 2 OH, W <= 2 OW, C % 4 == 0 (reduce:
+ * C <= 1024), 16-byte aligned z / dz / dpool / per-channel vectors, 4-byte aligned argmax.                     */
 int ds_bn_pool_bwd_partials(int32_t N, int32_t OH, int32_t OW, int32_t C);
 int ds_bn_pool_bwd_reduce(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H, int32_t W,
                           int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW, const float *mean,

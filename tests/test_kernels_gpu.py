@@ -2147,7 +2147,8 @@ def test_batch_norm_finalize_inside_the_conv_launch_is_bit_identical(case):
     close(res[1][2], 1.0 / np.sqrt(zr.var(0) + 1e-3), 1e-5)
 
 
-@pytest.mark.parametrize("case", [(2, 17, 24), (3, 12, 64), (1, 30, 192)])
+# (1, 5, 1024): C / 4 = 256, every thread of a workgroup owns a column group in the combine, and C is the reduce's upper limit
+@pytest.mark.parametrize("case", [(2, 17, 24), (3, 12, 64), (1, 30, 192), (1, 5, 1024)])
 def test_batch_norm_backward_from_the_pooled_gradient(case):
     """ds_bn_pool_bwd_reduce/_apply (BN+ReLU backward of a conv behind a 3x3/2 SAME pool, straight from the pool's
     output gradient) against the oracle's MaxPoolGrad followed by the oracle's BatchNorm backward."""
@@ -2189,6 +2190,10 @@ def test_batch_norm_backward_from_the_pooled_gradient(case):
     ops.bn_pool_bwd_reduce(zd, dpd, am, N, H, H, Cc, mean_d, rstd_d, shift_d, again)
     torch.cuda.synchronize()
     assert torch.equal(part, again)                      # fixed summation order
+    inplace = zd.clone()                                 # the engine's call: dz over z
+    ops.bn_pool_bwd_apply(inplace, dpd, am, N, H, H, Cc, mean_d, rstd_d, shift_d, coef, inplace)
+    torch.cuda.synchronize()
+    assert torch.equal(inplace.view(M, Cc), dz)
 
 
 def test_avgpool_dropout():

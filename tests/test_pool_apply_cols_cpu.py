@@ -64,6 +64,33 @@ def test_bn_pool_bwd_apply_cols_refuses_bad_arguments(lib):
     _refused(l, f(*_pool_args(z=C.c_void_p(0x10004))), name, "aligned")
 
 
+def _full_pool_args(tail, **kw):
+    """A ds_bn_pool_bwd_reduce / _apply call nothing is wrong with (2 x 9 x 9 x 8 behind a 3x3/2 pool), one argument replaced."""
+    a = dict(z=FAKE, dpool=FAKE, argmax=FAKE, N=2, H=9, W=9, C=8, pad_t=1, pad_l=1, OH=5, OW=5, mean=FAKE, rstd=FAKE, shift=FAKE)
+    a.update(kw)
+    return list(a.values()) + [FAKE] * tail + [None]
+
+
+@pytest.mark.parametrize("name,tail", [("ds_bn_pool_bwd_reduce", 1), ("ds_bn_pool_bwd_apply", 2)])
+def test_bn_pool_bwd_reduce_and_apply_refuse_what_their_siblings_refuse(lib, name, tail):
+    l = lib.load()
+    call = getattr(l, name)
+
+    def f(*a):
+        rc = call(*a)
+        assert rc == -1, "%s returned %d, not DS_ERR_ARG" % (name, rc)
+        return rc
+
+    _refused(l, f(*_full_pool_args(tail, z=C.c_void_p(0x10004))), name, "aligned")          # a pointer off by 4 bytes
+    _refused(l, f(*_full_pool_args(tail, dpool=C.c_void_p(0x10004))), name, "aligned")
+    _refused(l, f(*_full_pool_args(tail, rstd=C.c_void_p(0x10004))), name, "aligned")
+    _refused(l, f(*_full_pool_args(tail, N=0)), name, "geometry")
+    _refused(l, f(*_full_pool_args(tail, pad_t=2)), name, "geometry")
+    _refused(l, f(*_full_pool_args(tail, H=12)), name, "H > 2 OH")                          # (refused before, too)
+    _refused(l, f(*_full_pool_args(tail, C=6)), name)
+    _refused(l, f(*_full_pool_args(tail, z=None)), name, "null")
+
+
 def test_bn_bwd_apply_cols_refuses_bad_arguments(lib):
     l = lib.load()
     f, name = l.ds_bn_bwd_apply_cols, "ds_bn_bwd_apply_cols"

@@ -476,47 +476,39 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_segs_kernel(SumSegDev sg,
     bwd_finalize_segs_channel(sg, inv_count, C, coef, (int)blockIdx.x);
 }
 
-// OUT16: dz goes to a SEPARATE bf16 tensor (pixel stride lddz) instead of over z -- the 16-bit configurations' 1x1 input
-// gradients read it with one 16-byte load per eight channels (conv_bf16d_kernel<.., XB = true>); the values are the ones that
-// kernel would have rounded on load (RNE), so the dgrad's result has the same bits
-template <bool OUT16, bool COH = false, bool ADD2 = false, bool Z16 = false>
-__device__ __forceinline__ void bwd_apply_body(int bid, const float *z, int ldz, const SegDev &dy, int64_t M, int C,
-                                               const float *mean, const float *rstd, const float *shift,
-                                               const float *coef, float *dz, float *amax, int drow, int lddz,
-                                               const float *coef_gx = nullptr) {
-    // (thread = one float4 column group, rows row0, row0 + drow, ...: see bn_apply_relu_kernel)
-    // coef_gx: the second coefficient vector where it does not follow the first at + C (ds_bn_bwd_apply_cols)
+// THE row walk of the BatchNorm-backward passes over z [M, ldz] and the gradient of the layer's activation in up to four
+// column segments.  Thread = one float4 column group c, rows row0, row0 + drow, ... (see bn_apply_relu_kernel): f.channel(c)
+// once, then f.element(z[4], dy[4], c, row, offset of the z element) per row.  DS_BN_ROWS rows per pass, every load of the pass
+// before any of its stores.  ADD2: the gradient is the sum of two tensors of the same layout (ds_segments.ptr2); a segment
+// without one adds nothing.  Z16: z is stored as bf16.
+template <bool ADD2, bool Z16, class F>
+__device__ __forceinline__ void bn_row_walk(int bid, const float *z, int ldz, const SegDev &dy, int64_t M, int C, int drow, F &f) {
     const int C4 = C >> 2;
     const int t0 = bid * 256 + threadIdx.x;
     const int row0 = t0 / C4, c = (t0 - row0 * C4) * 4;
-    const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c), s4 = *reinterpret_cast<const float4 *>(shift + c);
-    const float4 m4 = *reinterpret_cast<const float4 *>(mean + c);
-    const float4 k14 = ld_res4<COH>(coef + c), k24 = ld_res4<COH>((coef_gx ? coef_gx : coef + C) + c);
-    const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
-    const float a1[4] = {k14.x, k14.y, k14.z, k14.w}, a2[4] = {k24.x, k24.y, k24.z, k24.w};
+    f.channel(c);
     int sgi = 0;
 #pragma unroll
     for (int i = 1; i < 4; ++i)
         if (i < dy.nseg && c >= dy.c_begin[i] && c < dy.c_end[i]) sgi = i;
     const float *const dyp = dy.ptr[sgi] + (c - dy.c_begin[sgi]);
     const int64_t dyld = dy.ld[sgi];
-    // ADD2: the gradient is the sum of two tensors of the same layout (ds_segments.ptr2); a segment without one adds nothing
     const float *const dyp2 = (ADD2 && dy.ptr2[sgi]) ? dy.ptr2[sgi] + (c - dy.c_begin[sgi]) : nullptr;
-    float am = 0.f;
-    constexpr int NR = DS_BN_ROWS;          // rows per pass: every load of the pass before any of its stores
+    constexpr int NR = DS_BN_ROWS;
     for (int64_t row = row0; row < M; row += NR * (int64_t)drow) {
-        int64_t rws[NR];
+        int64_t rws[NR], zo[NR];
         bool ok[NR];
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
             ok[u] = row + u * (int64_t)drow < M;
             rws[u] = ok[u] ? row + u * (int64_t)drow : row;
+            zo[u] = rws[u] * ldz + c;
         }
         float4 zv[NR], dv[NR];
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
-            if constexpr (Z16) zv[u] = ldz4<__bf16>(reinterpret_cast<const __bf16 *>(z) + rws[u] * ldz + c);
-            else zv[u] = ds::ld_stream4(z + rws[u] * ldz + c);
+            if constexpr (Z16) zv[u] = ldz4<__bf16>(reinterpret_cast<const __bf16 *>(z) + zo[u]);
+            else zv[u] = ds::ld_stream4(z + zo[u]);
             dv[u] = ds::ld_stream4(dyp + rws[u] * dyld);
         }
         if (ADD2 && dyp2) {
@@ -530,19 +522,54 @@ __device__ __forceinline__ void bwd_apply_body(int bid, const float *z, int ldz,
         for (int u = 0; u < NR; ++u) {
             if (u > 0 && !ok[u]) break;
             const float zz[4] = {zv[u].x, zv[u].y, zv[u].z, zv[u].w}, dd[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = ds::bn_bwd_dz(zz[j], dd[j], rr[j], ss[j], mm[j], a1[j], a2[j]);
-            if (OUT16) {
-                const f32x4_t ov = {o[0], o[1], o[2], o[3]};
-                *reinterpret_cast<bf16x4_t *>(reinterpret_cast<__bf16 *>(dz) + rws[u] * lddz + c) = __builtin_convertvector(ov, bf16x4_t);
-            } else {
-                *reinterpret_cast<float4 *>(dz + rws[u] * ldz + c) = make_float4(o[0], o[1], o[2], o[3]);
-            }
-            am = fmaxf(am, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
+            f.element(zz, dd, c, rws[u], zo[u]);
         }
     }
+}
+
+// The batch-statistics apply, dz = ds::bn_bwd_dz, and max|dz| of the thread.
+// OUT16: dz goes to a SEPARATE bf16 tensor (pixel stride lddz) instead of over z -- the 16-bit configurations' 1x1 input
+// gradients read it with one 16-byte load per eight channels (conv_bf16d_kernel<.., XB = true>); the values are the ones that
+// kernel would have rounded on load (RNE), so the dgrad's result has the same bits
+// coef_gx: the second coefficient vector where it does not follow the first at + C (ds_bn_bwd_apply_cols)
+template <bool OUT16, bool COH>
+struct BwdApply {
+    const float *mean, *rstd, *shift, *coef_g, *coef_gx;
+    float *dz;
+    int lddz;
+    float rr[4], ss[4], mm[4], a1[4], a2[4], am;
+    __device__ __forceinline__ void channel(int c) {
+        ds::ld_vec4(rr, rstd + c);
+        ds::ld_vec4(ss, shift + c);
+        ds::ld_vec4(mm, mean + c);
+        const float4 k14 = ld_res4<COH>(coef_g + c), k24 = ld_res4<COH>(coef_gx + c);
+        a1[0] = k14.x; a1[1] = k14.y; a1[2] = k14.z; a1[3] = k14.w;
+        a2[0] = k24.x; a2[1] = k24.y; a2[2] = k24.z; a2[3] = k24.w;
+        am = 0.f;
+    }
+    __device__ __forceinline__ void element(const float (&z)[4], const float (&dy)[4], int c, int64_t row, int64_t zoff) {
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = ds::bn_bwd_dz(z[j], dy[j], rr[j], ss[j], mm[j], a1[j], a2[j]);
+        if (OUT16) {
+            const f32x4_t ov = {o[0], o[1], o[2], o[3]};
+            *reinterpret_cast<bf16x4_t *>(reinterpret_cast<__bf16 *>(dz) + row * lddz + c) = __builtin_convertvector(ov, bf16x4_t);
+        } else {
+            *reinterpret_cast<float4 *>(dz + zoff) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+        am = fmaxf(am, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
+    }
+};
+
+template <bool OUT16, bool COH = false, bool ADD2 = false, bool Z16 = false>
+__device__ __forceinline__ void bwd_apply_body(int bid, const float *z, int ldz, const SegDev &dy, int64_t M, int C,
+                                               const float *mean, const float *rstd, const float *shift,
+                                               const float *coef, float *dz, float *amax, int drow, int lddz,
+                                               const float *coef_gx = nullptr) {
+    BwdApply<OUT16, COH> f{mean, rstd, shift, coef, coef_gx ? coef_gx : coef + C, dz, lddz};
+    bn_row_walk<ADD2, Z16>(bid, z, ldz, dy, M, C, drow, f);
     if (amax) {
+        float am = f.am;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
         if ((threadIdx.x & 63) == 0) ds::atomic_max_nonneg(amax, am);
@@ -559,135 +586,23 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *z, int l
 
 // ---- moving-statistics (is_training=False) backward ------------------------------------------------------------------------
 // BatchNorm with fixed statistics is a per-channel affine map, so its backward with the ReLU behind it is pointwise:
-// dz = rstd * dy * [z*rstd + shift > 0].  No column sums, no mean, no coef: one streaming pass (12 B per element, in place)
-// in the launch shape of bn_bwd_apply_kernel.  The predicate is the fused multiply-add bn_apply_relu_kernel evaluates
-// (the compiler contracts its v*r + s), so the mask has the decision bits of the activation the forward pass wrote.
-template <bool ADD2>
-__global__ __launch_bounds__(256) void bn_infer_bwd_apply_kernel(const float *z, int ldz, SegDev dy, int64_t M, int C,
-                                                                 const float *rstd, const float *shift, float *dz, int drow) {
-    const int C4 = C >> 2;
-    const int t0 = (int)blockIdx.x * 256 + threadIdx.x;
-    const int row0 = t0 / C4, c = (t0 - row0 * C4) * 4;
-    const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c), s4 = *reinterpret_cast<const float4 *>(shift + c);
-    const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-    int sgi = 0;
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (i < dy.nseg && c >= dy.c_begin[i] && c < dy.c_end[i]) sgi = i;
-    const float *const dyp = dy.ptr[sgi] + (c - dy.c_begin[sgi]);
-    const int64_t dyld = dy.ld[sgi];
-    const float *const dyp2 = (ADD2 && dy.ptr2[sgi]) ? dy.ptr2[sgi] + (c - dy.c_begin[sgi]) : nullptr;
-    constexpr int NR = DS_BN_ROWS;          // rows per pass: every load of the pass before any of its stores
-    for (int64_t row = row0; row < M; row += NR * (int64_t)drow) {
-        int64_t rws[NR];
-        bool ok[NR];
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            ok[u] = row + u * (int64_t)drow < M;
-            rws[u] = ok[u] ? row + u * (int64_t)drow : row;
-        }
-        float4 zv[NR], dv[NR];
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            zv[u] = ds::ld_stream4(z + rws[u] * ldz + c);
-            dv[u] = ds::ld_stream4(dyp + rws[u] * dyld);
-        }
-        if (ADD2 && dyp2) {
-#pragma unroll
-            for (int u = 0; u < NR; ++u) {
-                const float4 e = ds::ld_stream4(dyp2 + rws[u] * dyld);
-                dv[u].x += e.x; dv[u].y += e.y; dv[u].z += e.z; dv[u].w += e.w;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            if (u > 0 && !ok[u]) break;
-            const float zz[4] = {zv[u].x, zv[u].y, zv[u].z, zv[u].w}, dd[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
-            f32x4_t o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = __builtin_fmaf(zz[j], rr[j], ss[j]) > 0.f ? rr[j] * dd[j] : 0.f;
-            __builtin_nontemporal_store(o, reinterpret_cast<f32x4_t *>(dz + rws[u] * ldz + c));
-        }
-    }
-}
-
-// ---- frozen-BatchNorm TRAINING backward (moving statistics in the train step) ----------------------------------------------
+// dz = rstd * dy * [z*rstd + shift > 0] (ds::InferBwd).  No column sums, no mean, no coef: one streaming pass (12 B per
+// element, in place) in the launch shape of bn_bwd_apply_kernel.
+// ---- frozen-BatchNorm TRAINING backward (moving statistics in the train step): SUMS ------------------------------------------
 // The same pointwise pass when beta still trains: dz as above, bit for bit, and in the same walk the column sums of
 // g = dy * [z*rstd + shift > 0] -- dbeta = sum g is all that is left of the batch-statistics backward.  A thread keeps its
-// float4 column group, so its four sums stay in registers (rows in walk order); one LDS combine per workgroup adds the
-// threads of a column group in thread order and stores partials[c][blockIdx.x] -- float[C][P], P = gridDim.x, the layout of
-// the other sum producers without the second (g*xhat) plane.  A workgroup covers 256 consecutive (row, column group) slots:
-// with C / 4 > 256 it meets only some column groups and stores an exact 0 for the others, so every slot of the tensor is
-// written by every launch.  No atomics: ds_bn_dbeta_reduce_multi adds the P partials in a fixed order.
+// float4 column group, so its four sums stay in registers (rows in walk order); ds::combine_column_groups stores
+// partials[c][blockIdx.x] -- float[C][P], P = gridDim.x, the layout of the other sum producers without the second (g*xhat)
+// plane.  No atomics: ds_bn_dbeta_reduce_multi adds the P partials in a fixed order.
 // WRITE = false: dz is not wanted (a frozen layer with nothing below it: the stem), the pass only sums.
-template <bool ADD2, bool WRITE>
-__global__ __launch_bounds__(256) void bn_infer_bwd_apply_sums_kernel(const float *z, int ldz, SegDev dy, int64_t M, int C,
-                                                                      const float *rstd, const float *shift, float *dz, int drow,
-                                                                      float *partials) {
-    __shared__ float sh[256][4];
-    const int C4 = C >> 2;
-    const int t0 = (int)blockIdx.x * 256 + threadIdx.x;
-    const int row0 = t0 / C4, c = (t0 - row0 * C4) * 4;
-    const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c), s4 = *reinterpret_cast<const float4 *>(shift + c);
-    const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-    int sgi = 0;
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (i < dy.nseg && c >= dy.c_begin[i] && c < dy.c_end[i]) sgi = i;
-    const float *const dyp = dy.ptr[sgi] + (c - dy.c_begin[sgi]);
-    const int64_t dyld = dy.ld[sgi];
-    const float *const dyp2 = (ADD2 && dy.ptr2[sgi]) ? dy.ptr2[sgi] + (c - dy.c_begin[sgi]) : nullptr;
-    float sum[4] = {0.f, 0.f, 0.f, 0.f};
-    constexpr int NR = DS_BN_ROWS;          // rows per pass: every load of the pass before any of its stores
-    for (int64_t row = row0; row < M; row += NR * (int64_t)drow) {
-        int64_t rws[NR];
-        bool ok[NR];
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            ok[u] = row + u * (int64_t)drow < M;
-            rws[u] = ok[u] ? row + u * (int64_t)drow : row;
-        }
-        float4 zv[NR], dv[NR];
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            zv[u] = ds::ld_stream4(z + rws[u] * ldz + c);
-            dv[u] = ds::ld_stream4(dyp + rws[u] * dyld);
-        }
-        if (ADD2 && dyp2) {
-#pragma unroll
-            for (int u = 0; u < NR; ++u) {
-                const float4 e = ds::ld_stream4(dyp2 + rws[u] * dyld);
-                dv[u].x += e.x; dv[u].y += e.y; dv[u].z += e.z; dv[u].w += e.w;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            if (u > 0 && !ok[u]) break;
-            const float zz[4] = {zv[u].x, zv[u].y, zv[u].z, zv[u].w}, dd[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
-            f32x4_t o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool on = __builtin_fmaf(zz[j], rr[j], ss[j]) > 0.f;
-                sum[j] += on ? dd[j] : 0.f;
-                o[j] = on ? rr[j] * dd[j] : 0.f;
-            }
-            if constexpr (WRITE) __builtin_nontemporal_store(o, reinterpret_cast<f32x4_t *>(dz + rws[u] * ldz + c));
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh[threadIdx.x][j] = sum[j];
-    __syncthreads();
-    const int P = gridDim.x;
-    const int head = (int)(((int64_t)blockIdx.x * 256) % C4);      // column group of this workgroup's thread 0
-    for (int cg = threadIdx.x; cg < C4; cg += 256) {               // owner of column group cg: its threads in thread order
-        int first = cg - head;
-        if (first < 0) first += C4;
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int t = first; t < 256; t += C4)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] += sh[t][j];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) partials[(int64_t)(cg * 4 + j) * P + blockIdx.x] = a[j];
+template <bool ADD2, bool WRITE, bool SUMS>
+__global__ __launch_bounds__(256) void bn_infer_bwd_kernel(const float *z, int ldz, SegDev dy, int64_t M, int C, const float *rstd,
+                                                           const float *shift, float *dz, int drow, float *partials) {
+    ds::InferBwd<WRITE, SUMS> f{rstd, shift, dz};
+    bn_row_walk<ADD2, false>((int)blockIdx.x, z, ldz, dy, M, C, drow, f);
+    if constexpr (SUMS) {
+        __shared__ float sh[256][4];
+        ds::combine_column_groups<1>(sh, f.sum, C >> 2, C, partials);
     }
 }
 
@@ -1111,11 +1026,11 @@ extern "C" int ds_bn_infer_bwd_apply(const float *z, int32_t ldz, const ds_segme
     int drow;
     const int grid = column_grid(M, C / 4, &drow);
     if (has_second_addend(dy))
-        hipLaunchKernelGGL(bn_infer_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, rstd,
-                           shift, dz, drow);
+        hipLaunchKernelGGL((bn_infer_bwd_kernel<true, true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C,
+                           rstd, shift, dz, drow, (float *)nullptr);
     else
-        hipLaunchKernelGGL(bn_infer_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, rstd,
-                           shift, dz, drow);
+        hipLaunchKernelGGL((bn_infer_bwd_kernel<false, true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C,
+                           rstd, shift, dz, drow, (float *)nullptr);
     return ds::check_launch("ds_bn_infer_bwd_apply");
 }
 
@@ -1138,16 +1053,16 @@ extern "C" int ds_bn_infer_bwd_apply_sums(const float *z, int32_t ldz, const ds_
     const bool add2 = has_second_addend(dy);
     hipStream_t st = (hipStream_t)stream;
     if (add2 && dz)
-        hipLaunchKernelGGL((bn_infer_bwd_apply_sums_kernel<true, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+        hipLaunchKernelGGL((bn_infer_bwd_kernel<true, true, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
                            dz, drow, partials);
     else if (add2)
-        hipLaunchKernelGGL((bn_infer_bwd_apply_sums_kernel<true, false>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+        hipLaunchKernelGGL((bn_infer_bwd_kernel<true, false, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
                            dz, drow, partials);
     else if (dz)
-        hipLaunchKernelGGL((bn_infer_bwd_apply_sums_kernel<false, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+        hipLaunchKernelGGL((bn_infer_bwd_kernel<false, true, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
                            dz, drow, partials);
     else
-        hipLaunchKernelGGL((bn_infer_bwd_apply_sums_kernel<false, false>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+        hipLaunchKernelGGL((bn_infer_bwd_kernel<false, false, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
                            dz, drow, partials);
     return ds::check_launch("ds_bn_infer_bwd_apply_sums");
 }

@@ -136,6 +136,71 @@ __device__ __forceinline__ float bn_bwd_dz(float z, float dy, float r, float s, 
     return r * __builtin_fmaf(-xh, a2, g - a1);
 }
 
+__device__ __forceinline__ void ld_vec4(float (&v)[4], const float *p) {
+    const float4 t = *reinterpret_cast<const float4 *>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+}
+
+// Per-element functor of the BatchNorm-backward walks (bn.hip: bn_row_walk over dense rows, pool.hip: pool_patch_walk over
+// the 2x2 patches of a stride-2 pool) for the moving-statistics backward: dz = rstd * g * [z*rstd + shift > 0], stored
+// non-temporally where z has the element (dz has z's layout; it may be z).  The predicate is the fused multiply-add
+// bn_apply_relu_kernel evaluates, so the mask has the decision bits of the activation the forward pass wrote.
+// SUMS: also the thread's column sums of g * [..] in walk order (frozen-BatchNorm training: dbeta), for
+// combine_column_groups.  WRITE = false: only the sums are wanted.
+// A walk calls channel(c) for the thread's float4 column group and element(z[4], g[4], c, row / pixel index, offset of the z
+// element) once per row / pixel.
+template <bool WRITE, bool SUMS>
+struct InferBwd {
+    static constexpr bool kStreamZ = true, kHoist = SUMS;      // (pool_patch_walk)
+    const float *rstd, *shift;
+    float *dz;
+    float rr[4], ss[4], sum[4];
+    __device__ __forceinline__ void channel(int c) {
+        ld_vec4(rr, rstd + c);
+        ld_vec4(ss, shift + c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sum[j] = 0.f;
+    }
+    __device__ __forceinline__ void element(const float (&z)[4], const float (&g)[4], int, int64_t, int64_t zoff) {
+        f32x4_nt o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool on = __builtin_fmaf(z[j], rr[j], ss[j]) > 0.f;
+            if (SUMS) sum[j] += on ? g[j] : 0.f;
+            o[j] = on ? rr[j] * g[j] : 0.f;
+        }
+        if (WRITE) __builtin_nontemporal_store(o, reinterpret_cast<f32x4_nt *>(dz + zoff));
+    }
+};
+
+// The workgroup's column sums of a walk in which thread t of workgroup b keeps column group (256 b + t) mod C4: `mine` holds
+// the thread's PLANES x 4 sums (plane k in [4k, 4k + 4)).  The owner of a column group -- thread cg, cg + 256, ... -- adds the
+// group's threads in thread order and stores partials[k][4 cg + j][b]: float[PLANES][C][P], P = gridDim.x.  A column group the
+// workgroup does not meet (C4 > 256) gets an exact 0, so every slot is written by every launch.  No atomics.
+template <int PLANES>
+__device__ __forceinline__ void combine_column_groups(float (*sh)[4 * PLANES], const float (&mine)[4 * PLANES], int C4, int C,
+                                                      float *partials) {
+#pragma unroll
+    for (int j = 0; j < 4 * PLANES; ++j) sh[threadIdx.x][j] = mine[j];
+    __syncthreads();
+    const int P = gridDim.x;
+    const int head = (int)(((int64_t)blockIdx.x * 256) % C4);      // column group of this workgroup's thread 0
+    for (int cg = threadIdx.x; cg < C4; cg += 256) {
+        int t0 = cg - head;
+        if (t0 < 0) t0 += C4;
+        float a[4 * PLANES];
+#pragma unroll
+        for (int j = 0; j < 4 * PLANES; ++j) a[j] = 0.f;
+        for (int t = t0; t < 256; t += C4)
+#pragma unroll
+            for (int j = 0; j < 4 * PLANES; ++j) a[j] += sh[t][j];
+#pragma unroll
+        for (int k = 0; k < PLANES; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) partials[((int64_t)k * C + cg * 4 + j) * P + blockIdx.x] = a[4 * k + j];
+    }
+}
+
 }  // namespace ds
 
 #define DS_REQUIRE(cond, ...)                 \

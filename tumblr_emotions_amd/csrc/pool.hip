@@ -604,7 +604,7 @@ __global__ __launch_bounds__(256) void avgpool_dropout_bwd_kernel(const float *d
 }
 
 // ---- BatchNorm backward of a conv that feeds only a 3x3/2 max pool, straight from the POOLED gradient -------
-// The pool's gradient w.r.t. its full-resolution input is never written: these two kernels rebuild it per 2x2
+// The pool's gradient w.r.t. its full-resolution input is never written: these kernels rebuild it per 2x2
 // input patch from the four windows that can name it (same walk as maxpool3s2_bwd_patch) and feed it into the
 // BatchNorm(+ReLU) backward formulas,
 //     g = dy_full * (z*rstd + shift > 0),   dbeta = sum g,   dz = rstd * (g - mean(g) - xhat * mean(g*xhat)).
@@ -652,320 +652,165 @@ __device__ __forceinline__ PatchGrad patch_grad(const float *dpool, const uint8_
     return r;
 }
 
-// partials laid out [2][C][P], P = gridDim.x; the launch makes 256*gridDim.x a multiple of C/4 so that a thread
-// keeps its channel group over its whole grid-stride walk
-__global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const float *z, const float *dpool, const uint8_t *am,
-                                                                 int N, int H, int W, int C, int pad_t, int pad_l, int OH,
-                                                                 int OW, const float *mean, const float *rstd,
-                                                                 const float *shift, float *partials) {
-    __shared__ float sh[256][8];
-    const int C4 = C >> 2;
-    const int PH = OH + 1, PW = OW + 1;
-    const int64_t total = (int64_t)N * PH * PW * C4;
-    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c = (int)(first % C4) * 4;
-    const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c);
-    const float4 s4 = *reinterpret_cast<const float4 *>(shift + c);
-    const float4 m4 = *reinterpret_cast<const float4 *>(mean + c);
-    const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
-    float sg[4] = {0.f, 0.f, 0.f, 0.f}, sx[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t i = first; i < total; i += (int64_t)gridDim.x * 256) {
-        int64_t r = i / C4;
-        const int q = (int)(r % PW) - 1;
-        r /= PW;
-        const int p = (int)(r % PH) - 1;
-        const int n = (int)(r / PH);
-        const PatchGrad pg = patch_grad(dpool, am, n, p, q, c, C, OH, OW);
+// K = 2 (the 2x2/2 pool): windows do not overlap -- the patch IS window (p, q) and a pixel has the one addend of
+// maxpool_bwd_kernel<2, 2> or none
+__device__ __forceinline__ PatchGrad window_grad(const float *dpool, const uint8_t *am, int n, int p, int q, int c, int C,
+                                                 int OH, int OW) {
+    const int64_t o = (((int64_t)n * OH + p) * OW + q) * C + c;
+    const unsigned a = *reinterpret_cast<const unsigned *>(am + o);
+    float d[4];
+    ds::ld_vec4(d, dpool + o);
+    PatchGrad r;
 #pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            const int ih = 2 * p - pad_t + 1 + y;
-            if ((unsigned)ih >= (unsigned)H) continue;
+    for (int y = 0; y < 2; ++y)
 #pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                const int iw = 2 * q - pad_l + 1 + x;
-                if ((unsigned)iw >= (unsigned)W) continue;
-                const float4 zv = *reinterpret_cast<const float4 *>(z + (((int64_t)n * H + ih) * W + iw) * C + c);
-                const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
+        for (int x = 0; x < 2; ++x)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float g = (zz[j] * rr[j] + ss[j] > 0.f) ? pg.g[y][x][j] : 0.f;
-                    sg[j] += g;
-                    sx[j] += g * ((zz[j] - mm[j]) * rr[j]);
-                }
+            for (int j = 0; j < 4; ++j) {
+                r.g[y][x][j] = 0.f;
+                if (((a >> (8 * j)) & 0xFFu) == (unsigned)(y * 2 + x)) r.g[y][x][j] += d[j];
             }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        sh[threadIdx.x][j] = sg[j];
-        sh[threadIdx.x][4 + j] = sx[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < C4) {      // owner of channel group threadIdx.x: add its threads of this block in index order
-        const int cg = threadIdx.x;
-        int t0 = (int)(((int64_t)cg - (int64_t)blockIdx.x * 256) % C4);
-        if (t0 < 0) t0 += C4;
-        float a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int t = t0; t < 256; t += C4)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += sh[t][j];
-        const int P = gridDim.x;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            partials[(int64_t)(cg * 4 + j) * P + blockIdx.x] = a[j];
-            partials[((int64_t)C + cg * 4 + j) * P + blockIdx.x] = a[4 + j];
-        }
-    }
+    return r;
 }
 
-__global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const float *z, const float *dpool, const uint8_t *am,
-                                                                int N, int H, int W, int C, int pad_t, int pad_l, int OH,
-                                                                int OW, const float *mean, const float *rstd,
-                                                                const float *shift, const float *coef, float *dz) {
-    const int C4 = C >> 2;
-    const int PH = OH + 1, PW = OW + 1;
-    const int64_t total = (int64_t)N * PH * PW * C4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)(i % C4) * 4;
-        int64_t r = i / C4;
-        const int q = (int)(r % PW) - 1;
-        r /= PW;
-        const int p = (int)(r % PH) - 1;
-        const int n = (int)(r / PH);
-        const PatchGrad pg = patch_grad(dpool, am, n, p, q, c, C, OH, OW);
-        const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c);
-        const float4 s4 = *reinterpret_cast<const float4 *>(shift + c);
-        const float4 m4 = *reinterpret_cast<const float4 *>(mean + c);
-        const float4 k1 = *reinterpret_cast<const float4 *>(coef + c);
-        const float4 k2 = *reinterpret_cast<const float4 *>(coef + C + c);
-        const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
-        const float a1[4] = {k1.x, k1.y, k1.z, k1.w}, a2[4] = {k2.x, k2.y, k2.z, k2.w};
-        // the patch's four z values first, then the four stores: a load behind a store waits for it (one in-order memory
-        // counter), which made the patch a chain of four round trips; z is read once (dz overwrites it): non-temporal
-        float4 zv[2][2];
-        bool ok[2][2];
-        int64_t offs[2][2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                const int ih = 2 * p - pad_t + 1 + y, iw = 2 * q - pad_l + 1 + x;
-                ok[y][x] = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-                offs[y][x] = (((int64_t)n * H + ih) * W + iw) * C + c;
-                zv[y][x] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (ok[y][x]) zv[y][x] = ds::ld_stream4(z + offs[y][x]);
-            }
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                if (!ok[y][x]) continue;
-                const float zz[4] = {zv[y][x].x, zv[y][x].y, zv[y][x].z, zv[y][x].w};
-                float o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float g = (zz[j] * rr[j] + ss[j] > 0.f) ? pg.g[y][x][j] : 0.f;
-                    const float xhat = (zz[j] - mm[j]) * rr[j];
-                    o[j] = rr[j] * (g - a1[j] - xhat * a2[j]);
-                }
-                *reinterpret_cast<float4 *>(dz + offs[y][x]) = make_float4(o[0], o[1], o[2], o[3]);
-            }
-    }
-}
+struct PoolGeom {
+    int N, H, W, pad_t, pad_l, OH, OW;
+};
 
-// ds_bn_pool_bwd_apply_cols: the same pass for a COLUMN RANGE of a layer behind a stride-2 pool of a wider tensor -- the
-// concat of a Mixed block in front of MaxPool_4a_3x3 / MaxPool_5a_2x2.  dpool / am point at the range's first column of the
-// pooled tensors (pixel stride Cp), z and dz have pixel strides of their own, c runs over [0, ncols).  K = 3: the 2x2 patches of
-// the 3x3/2 pool (patch_grad: maxpool3s2_bwd_patch's order of the up to four addends); K = 2: the 2x2/2 pool, whose windows
-// do not overlap -- the patch IS window (p, q) and a pixel has the one addend of maxpool_bwd_kernel<2, 2> or none.  dz by
-// ds::bn_bwd_dz: the bits of ds_maxpool_bwd followed by ds_bn_bwd_apply.
-template <int K>
-__global__ __launch_bounds__(256) void bn_pool_bwd_apply_cols_kernel(const float *z, int ldz, float *dz, int lddz,
-                                                                     const float *dpool, const uint8_t *am, int Cp, int N,
-                                                                     int H, int W, int pad_t, int pad_l, int OH, int OW,
-                                                                     int ncols, const float *mean, const float *rstd,
-                                                                     const float *shift, const float *coef_g,
-                                                                     const float *coef_gx) {
-    constexpr int E = K == 3 ? 1 : 0;      // 3x3/2: one patch more than windows per axis, the first one at p = -1
+// THE walk of these passes: over the 2x2 input patches of a stride-2 pool -- K = 3: the (OH + 1)(OW + 1) patches of a 3x3/2
+// pool, the first at p = q = -1 (patch_grad: maxpool3s2_bwd_patch's order of the up to four addends); K = 2: the OH * OW
+// windows of a 2x2/2 pool -- and the float4 groups of `ncols` columns.  z has pixel stride ldz; dpool / am point at the first
+// of the columns in the pooled tensors (pixel stride Cp).  Per patch, for each pixel of it that lies inside the tensor:
+// f.element(z[4], g[4], c, pixel index, offset of the z element), g the pool's gradient routed to that pixel.
+// All four z loads of a patch stand before its first element() call and the store that may make: a load behind a store
+// waits for it (one in-order memory counter), which made the patch a chain of four round trips.  F::kStreamZ: z is read for
+// the last time (dz overwrites it): non-temporal loads.
+// Every launch has pool_bwd_grid's shape, so a thread keeps its column group c over its grid-stride walk.  F::kHoist: the
+// functor's per-channel vectors are loaded once, in front of the walk (f.channel(c); the summing passes, whose sums need the
+// fixed group anyway); otherwise per patch behind the pooled loads, with c decoded from the index -- hoisted, the
+// batch-statistics apply holds 1 - 4 registers more and loses a wave of occupancy (scripts/kres.sh).
+template <int K, class F>
+__device__ __forceinline__ void pool_patch_walk(const PoolGeom &gm, int ncols, const float *z, int ldz, const float *dpool,
+                                                const uint8_t *am, int Cp, F &f) {
+    constexpr int E = K == 3 ? 1 : 0;
     const int C4 = ncols >> 2;
-    const int PH = OH + E, PW = OW + E;
-    const int64_t total = (int64_t)N * PH * PW * C4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)(i % C4) * 4;
+    const int PH = gm.OH + E, PW = gm.OW + E;
+    const int64_t total = (int64_t)gm.N * PH * PW * C4;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c0 = (int)(first % C4) * 4;
+    if (F::kHoist) f.channel(c0);
+    for (int64_t i = first; i < total; i += (int64_t)gridDim.x * 256) {
+        const int c = F::kHoist ? c0 : (int)(i % C4) * 4;
         int64_t r = i / C4;
         const int q = (int)(r % PW) - E;
         r /= PW;
         const int p = (int)(r % PH) - E;
         const int n = (int)(r / PH);
-        PatchGrad pg;
-        if constexpr (K == 3) {
-            pg = patch_grad(dpool, am, n, p, q, c, Cp, OH, OW);
-        } else {
-            const int64_t o = (((int64_t)n * OH + p) * OW + q) * Cp + c;
-            const unsigned a = *reinterpret_cast<const unsigned *>(am + o);
-            const float4 t = *reinterpret_cast<const float4 *>(dpool + o);
-            const float d[4] = {t.x, t.y, t.z, t.w};
+        const PatchGrad pg = K == 3 ? patch_grad(dpool, am, n, p, q, c, Cp, gm.OH, gm.OW)
+                                    : window_grad(dpool, am, n, p, q, c, Cp, gm.OH, gm.OW);
+        if (!F::kHoist) f.channel(c);
+        float4 zv[2][2];
+        bool ok[2][2];
+        int64_t pix[2][2], zo[2][2];
 #pragma unroll
-            for (int y = 0; y < 2; ++y)
+        for (int y = 0; y < 2; ++y)
 #pragma unroll
-                for (int x = 0; x < 2; ++x)
+            for (int x = 0; x < 2; ++x) {
+                const int ih = 2 * p - gm.pad_t + E + y, iw = 2 * q - gm.pad_l + E + x;
+                ok[y][x] = (unsigned)ih < (unsigned)gm.H && (unsigned)iw < (unsigned)gm.W;
+                pix[y][x] = ((int64_t)n * gm.H + ih) * gm.W + iw;
+                zo[y][x] = pix[y][x] * ldz + c;
+                zv[y][x] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ok[y][x]) zv[y][x] = F::kStreamZ ? ds::ld_stream4(z + zo[y][x]) : *reinterpret_cast<const float4 *>(z + zo[y][x]);
+            }
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        pg.g[y][x][j] = 0.f;
-                        if (((a >> (8 * j)) & 0xFFu) == (unsigned)(y * 2 + x)) pg.g[y][x][j] += d[j];
-                    }
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                if (!ok[y][x]) continue;
+                const float zz[4] = {zv[y][x].x, zv[y][x].y, zv[y][x].z, zv[y][x].w};
+                f.element(zz, pg.g[y][x], c, pix[y][x], zo[y][x]);
+            }
+    }
+}
+
+// ds_bn_pool_bwd_reduce: sum g and sum g * xhat as partials [2][C][P], P = gridDim.x (z is read again by the apply pass)
+struct PoolBwdSums {
+    static constexpr bool kStreamZ = false, kHoist = true;
+    const float *mean, *rstd, *shift;
+    float rr[4], ss[4], mm[4], sum[8];
+    __device__ __forceinline__ void channel(int c) {
+        ds::ld_vec4(rr, rstd + c);
+        ds::ld_vec4(ss, shift + c);
+        ds::ld_vec4(mm, mean + c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum[j] = 0.f;
+    }
+    __device__ __forceinline__ void element(const float (&z)[4], const float (&dy)[4], int, int64_t, int64_t) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float g = (z[j] * rr[j] + ss[j] > 0.f) ? dy[j] : 0.f;
+            sum[j] += g;
+            sum[4 + j] += g * ((z[j] - mm[j]) * rr[j]);
         }
-        const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c);
-        const float4 s4 = *reinterpret_cast<const float4 *>(shift + c);
-        const float4 m4 = *reinterpret_cast<const float4 *>(mean + c);
-        const float4 k1 = *reinterpret_cast<const float4 *>(coef_g + c);
-        const float4 k2 = *reinterpret_cast<const float4 *>(coef_gx + c);
-        const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
-        const float a1[4] = {k1.x, k1.y, k1.z, k1.w}, a2[4] = {k2.x, k2.y, k2.z, k2.w};
-        // (the patch's four z loads before its four stores, as in bn_pool_bwd_apply_kernel; dz may lie over z)
-        float4 zv[2][2];
-        bool ok[2][2];
-        int64_t pix[2][2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                const int ih = 2 * p - pad_t + E + y, iw = 2 * q - pad_l + E + x;
-                ok[y][x] = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-                pix[y][x] = ((int64_t)n * H + ih) * W + iw;
-                zv[y][x] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (ok[y][x]) zv[y][x] = ds::ld_stream4(z + pix[y][x] * ldz + c);
-            }
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                if (!ok[y][x]) continue;
-                const float zz[4] = {zv[y][x].x, zv[y][x].y, zv[y][x].z, zv[y][x].w};
-                float o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = ds::bn_bwd_dz(zz[j], pg.g[y][x][j], rr[j], ss[j], mm[j], a1[j], a2[j]);
-                *reinterpret_cast<float4 *>(dz + pix[y][x] * lddz + c) = make_float4(o[0], o[1], o[2], o[3]);
-            }
     }
+};
+
+__global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(PoolGeom gm, int C, const float *z, const float *dpool,
+                                                                 const uint8_t *am, const float *mean, const float *rstd,
+                                                                 const float *shift, float *partials) {
+    __shared__ float sh[256][8];
+    PoolBwdSums f{mean, rstd, shift};
+    pool_patch_walk<3>(gm, C, z, C, dpool, am, C, f);
+    ds::combine_column_groups<2>(sh, f.sum, C >> 2, C, partials);
 }
 
-// ds_bn_pool_infer_bwd_apply: the same patch walk for the moving-statistics backward -- dz = rstd * g * [z*rstd + shift > 0]
-// with g the pool's gradient rebuilt per 2x2 patch; no mean, no coef
-__global__ __launch_bounds__(256) void bn_pool_infer_bwd_apply_kernel(const float *z, const float *dpool, const uint8_t *am,
-                                                                      int N, int H, int W, int C, int pad_t, int pad_l, int OH,
-                                                                      int OW, const float *rstd, const float *shift, float *dz) {
-    const int C4 = C >> 2;
-    const int PH = OH + 1, PW = OW + 1;
-    const int64_t total = (int64_t)N * PH * PW * C4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)(i % C4) * 4;
-        int64_t r = i / C4;
-        const int q = (int)(r % PW) - 1;
-        r /= PW;
-        const int p = (int)(r % PH) - 1;
-        const int n = (int)(r / PH);
-        const PatchGrad pg = patch_grad(dpool, am, n, p, q, c, C, OH, OW);
-        const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c);
-        const float4 s4 = *reinterpret_cast<const float4 *>(shift + c);
-        const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-        float4 zv[2][2];
-        bool ok[2][2];
-        int64_t offs[2][2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                const int ih = 2 * p - pad_t + 1 + y, iw = 2 * q - pad_l + 1 + x;
-                ok[y][x] = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-                offs[y][x] = (((int64_t)n * H + ih) * W + iw) * C + c;
-                zv[y][x] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (ok[y][x]) zv[y][x] = ds::ld_stream4(z + offs[y][x]);
-            }
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                if (!ok[y][x]) continue;
-                const float zz[4] = {zv[y][x].x, zv[y][x].y, zv[y][x].z, zv[y][x].w};
-                ds::f32x4_nt o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = __builtin_fmaf(zz[j], rr[j], ss[j]) > 0.f ? rr[j] * pg.g[y][x][j] : 0.f;
-                __builtin_nontemporal_store(o, reinterpret_cast<ds::f32x4_nt *>(dz + offs[y][x]));
-            }
+// ds_bn_pool_bwd_apply / ds_bn_pool_bwd_apply_cols: dz by ds::bn_bwd_dz -- the bits of ds_maxpool_bwd followed by
+// ds_bn_bwd_apply.  The second entry point is the pass for a COLUMN RANGE of a layer behind a stride-2 pool of a wider tensor
+// (the concat of a Mixed block in front of MaxPool_4a_3x3 / MaxPool_5a_2x2): z and dz have pixel strides of their own, dz may
+// lie over z.
+struct PoolBwdApply {
+    static constexpr bool kStreamZ = true, kHoist = false;
+    const float *mean, *rstd, *shift, *coef_g, *coef_gx;
+    float *dz;
+    int lddz;
+    float rr[4], ss[4], mm[4], a1[4], a2[4];
+    __device__ __forceinline__ void channel(int c) {
+        ds::ld_vec4(rr, rstd + c);
+        ds::ld_vec4(ss, shift + c);
+        ds::ld_vec4(mm, mean + c);
+        ds::ld_vec4(a1, coef_g + c);
+        ds::ld_vec4(a2, coef_gx + c);
     }
+    __device__ __forceinline__ void element(const float (&z)[4], const float (&dy)[4], int c, int64_t pix, int64_t) {
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = ds::bn_bwd_dz(z[j], dy[j], rr[j], ss[j], mm[j], a1[j], a2[j]);
+        *reinterpret_cast<float4 *>(dz + pix * lddz + c) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(PoolGeom gm, int ncols, const float *z, int ldz, float *dz,
+                                                                int lddz, const float *dpool, const uint8_t *am, int Cp,
+                                                                const float *mean, const float *rstd, const float *shift,
+                                                                const float *coef_g, const float *coef_gx) {
+    PoolBwdApply f{mean, rstd, shift, coef_g, coef_gx, dz, lddz};
+    pool_patch_walk<K>(gm, ncols, z, ldz, dpool, am, Cp, f);
 }
 
-// ds_bn_pool_infer_bwd_apply_sums: the frozen-BatchNorm TRAINING twin (moving statistics in the train step, beta still trains):
-// the same dz, bit for bit, and in the same patch walk the column sums of g = dy_full * [z*rstd + shift > 0] (dbeta = sum g) as
-// fixed-order partials float[C][P], P = gridDim.x -- a thread keeps its channel group over its grid-stride walk (256 * gridDim.x
-// is a multiple of C / 4, as for bn_pool_bwd_reduce_kernel), one LDS combine per workgroup in thread order, no atomics.
-// WRITE = false: nothing below the layer wants dz (the unpooled stem), the pass only sums.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void bn_pool_infer_bwd_apply_sums_kernel(const float *z, const float *dpool, const uint8_t *am,
-                                                                           int N, int H, int W, int C, int pad_t, int pad_l, int OH,
-                                                                           int OW, const float *rstd, const float *shift, float *dz,
-                                                                           float *partials) {
-    __shared__ float sh[256][4];
-    const int C4 = C >> 2;
-    const int PH = OH + 1, PW = OW + 1;
-    const int64_t total = (int64_t)N * PH * PW * C4;
-    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c = (int)(first % C4) * 4;
-    const float4 r4 = *reinterpret_cast<const float4 *>(rstd + c);
-    const float4 s4 = *reinterpret_cast<const float4 *>(shift + c);
-    const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-    float sum[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t i = first; i < total; i += (int64_t)gridDim.x * 256) {
-        int64_t r = i / C4;
-        const int q = (int)(r % PW) - 1;
-        r /= PW;
-        const int p = (int)(r % PH) - 1;
-        const int n = (int)(r / PH);
-        const PatchGrad pg = patch_grad(dpool, am, n, p, q, c, C, OH, OW);
-        float4 zv[2][2];
-        bool ok[2][2];
-        int64_t offs[2][2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                const int ih = 2 * p - pad_t + 1 + y, iw = 2 * q - pad_l + 1 + x;
-                ok[y][x] = (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-                offs[y][x] = (((int64_t)n * H + ih) * W + iw) * C + c;
-                zv[y][x] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (ok[y][x]) zv[y][x] = ds::ld_stream4(z + offs[y][x]);
-            }
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                if (!ok[y][x]) continue;
-                const float zz[4] = {zv[y][x].x, zv[y][x].y, zv[y][x].z, zv[y][x].w};
-                ds::f32x4_nt o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool on = __builtin_fmaf(zz[j], rr[j], ss[j]) > 0.f;
-                    sum[j] += on ? pg.g[y][x][j] : 0.f;
-                    o[j] = on ? rr[j] * pg.g[y][x][j] : 0.f;
-                }
-                if constexpr (WRITE) __builtin_nontemporal_store(o, reinterpret_cast<ds::f32x4_nt *>(dz + offs[y][x]));
-            }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh[threadIdx.x][j] = sum[j];
-    __syncthreads();
-    const int P = gridDim.x;
-    const int head = (int)(((int64_t)blockIdx.x * 256) % C4);      // channel group of this workgroup's thread 0
-    for (int cg = threadIdx.x; cg < C4; cg += 256) {               // owner of channel group cg: its threads in thread order
-        int t0 = cg - head;
-        if (t0 < 0) t0 += C4;
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int t = t0; t < 256; t += C4)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] += sh[t][j];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) partials[(int64_t)(cg * 4 + j) * P + blockIdx.x] = a[j];
+// ds_bn_pool_infer_bwd_apply (moving statistics: no mean, no coef) and its frozen-BatchNorm TRAINING twin
+// ds_bn_pool_infer_bwd_apply_sums (SUMS: the same dz, bit for bit, and the column sums of g as fixed-order partials
+// float[C][P], P = gridDim.x; WRITE = false: nothing below the layer wants dz -- the unpooled stem -- the pass only sums)
+template <bool WRITE, bool SUMS>
+__global__ __launch_bounds__(256) void bn_pool_infer_bwd_kernel(PoolGeom gm, int C, const float *z, const float *dpool,
+                                                                const uint8_t *am, const float *rstd, const float *shift,
+                                                                float *dz, float *partials) {
+    ds::InferBwd<WRITE, SUMS> f{rstd, shift, dz};
+    pool_patch_walk<3>(gm, C, z, C, dpool, am, C, f);
+    if constexpr (SUMS) {
+        __shared__ float sh[256][4];
+        ds::combine_column_groups<1>(sh, f.sum, C >> 2, C, partials);
     }
 }
 
@@ -1131,6 +976,24 @@ int pool_bwd_grid(int N, int OH, int OW, int C) {
     g = (g + step - 1) / step * step;
     return g;
 }
+
+// What every ds_bn_pool_* pass asks of its pool and its pointers: a stride-2 SAME pool whose 2x2 patches cover the input
+// (H <= 2 OH, W <= 2 OW), float4 column groups, 16-byte loads of z / dz / dpool and the per-channel vectors (null: not used by
+// the entry point), 4-byte loads of the winners
+int check_pool_walk(const char *who, const PoolGeom &gm, int C, const void *z, const void *dz, const void *dpool,
+                    const void *argmax, const float *const (&vec)[5]) {
+    DS_REQUIRE(z && dpool && argmax, "%s: null pointer", who);
+    DS_REQUIRE(gm.N > 0 && gm.H > 0 && gm.W > 0 && gm.OH > 0 && gm.OW > 0 && gm.pad_t >= 0 && gm.pad_t <= 1 && gm.pad_l >= 0 &&
+                   gm.pad_l <= 1,
+               "%s: bad geometry", who);
+    DS_REQUIRE(gm.H <= 2 * gm.OH && gm.W <= 2 * gm.OW, "%s: H > 2 OH or W > 2 OW (stride-2 SAME pools only)", who);
+    DS_REQUIRE(C > 0 && C % 4 == 0, "%s: %d columns (C %% 4 == 0)", who, C);
+    uintptr_t bits = (uintptr_t)z | (uintptr_t)dz | (uintptr_t)dpool;
+    for (const float *v : vec) bits |= (uintptr_t)v;
+    DS_REQUIRE((bits & 15) == 0 && (((uintptr_t)argmax) & 3) == 0, "%s: 16-byte aligned tensors and vectors, 4-byte aligned winners",
+               who);
+    return DS_OK;
+}
 }  // namespace
 
 extern "C" int ds_bn_pool_bwd_partials(int32_t N, int32_t OH, int32_t OW, int32_t C) { return pool_bwd_grid(N, OH, OW, C); }
@@ -1139,11 +1002,11 @@ extern "C" int ds_bn_pool_bwd_reduce(const float *z, const float *dpool, const u
                                      int32_t W, int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW,
                                      const float *mean, const float *rstd, const float *shift, float *partials,
                                      void *stream) {
-    DS_REQUIRE(z && dpool && argmax && mean && rstd && shift && partials && C % 4 == 0 && C <= 1024 && H <= 2 * OH &&
-                   W <= 2 * OW,
-               "ds_bn_pool_bwd_reduce: bad argument (3x3 stride-2 SAME pools, C %% 4 == 0, C <= 1024)");
-    hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(pool_bwd_grid(N, OH, OW, C)), dim3(256), 0, (hipStream_t)stream, z,
-                       dpool, argmax, N, H, W, C, pad_t, pad_l, OH, OW, mean, rstd, shift, partials);
+    const PoolGeom gm{N, H, W, pad_t, pad_l, OH, OW};
+    DS_REQUIRE(mean && rstd && shift && partials && C <= 1024, "ds_bn_pool_bwd_reduce: bad argument (null vector, C <= 1024)");
+    if (int e = check_pool_walk("ds_bn_pool_bwd_reduce", gm, C, z, nullptr, dpool, argmax, {mean, rstd, shift})) return e;
+    hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(pool_bwd_grid(N, OH, OW, C)), dim3(256), 0, (hipStream_t)stream, gm, C, z,
+                       dpool, argmax, mean, rstd, shift, partials);
     return ds::check_launch("ds_bn_pool_bwd_reduce");
 }
 
@@ -1151,10 +1014,11 @@ extern "C" int ds_bn_pool_bwd_apply(const float *z, const float *dpool, const ui
                                     int32_t W, int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW,
                                     const float *mean, const float *rstd, const float *shift, const float *coef,
                                     float *dz, void *stream) {
-    DS_REQUIRE(z && dpool && argmax && mean && rstd && shift && coef && dz && C % 4 == 0 && H <= 2 * OH && W <= 2 * OW,
-               "ds_bn_pool_bwd_apply: bad argument (3x3 stride-2 SAME pools, C %% 4 == 0)");
-    hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3(pool_bwd_grid(N, OH, OW, C)), dim3(256), 0, (hipStream_t)stream, z,
-                       dpool, argmax, N, H, W, C, pad_t, pad_l, OH, OW, mean, rstd, shift, coef, dz);
+    const PoolGeom gm{N, H, W, pad_t, pad_l, OH, OW};
+    DS_REQUIRE(mean && rstd && shift && coef && dz, "ds_bn_pool_bwd_apply: null pointer");
+    if (int e = check_pool_walk("ds_bn_pool_bwd_apply", gm, C, z, dz, dpool, argmax, {mean, rstd, shift, coef})) return e;
+    hipLaunchKernelGGL(bn_pool_bwd_apply_kernel<3>, dim3(pool_bwd_grid(N, OH, OW, C)), dim3(256), 0, (hipStream_t)stream, gm, C, z,
+                       C, dz, C, dpool, argmax, C, mean, rstd, shift, coef, coef + C);
     return ds::check_launch("ds_bn_pool_bwd_apply");
 }
 
@@ -1163,8 +1027,8 @@ extern "C" int ds_bn_pool_bwd_apply_cols(const float *z, int32_t ldz, float *dz,
                                          int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW, int32_t ncols,
                                          const float *mean, const float *rstd, const float *shift, const float *coef_g,
                                          const float *coef_gx, int32_t k, void *stream) {
-    DS_REQUIRE(z && dz && dpool && argmax && mean && rstd && shift && coef_g && coef_gx,
-               "ds_bn_pool_bwd_apply_cols: null pointer");
+    const PoolGeom gm{N, H, W, pad_t, pad_l, OH, OW};
+    DS_REQUIRE(dz && mean && rstd && shift && coef_g && coef_gx, "ds_bn_pool_bwd_apply_cols: null pointer");
     DS_REQUIRE(k == 2 || k == 3, "ds_bn_pool_bwd_apply_cols: kernel size %d (3: 3x3/2, 2: 2x2/2 pools only)", k);
     DS_REQUIRE(ncols > 0 && ncols % 4 == 0 && c0 >= 0 && c0 % 4 == 0 && Cp % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0,
                "ds_bn_pool_bwd_apply_cols: ncols %d, first column %d and the strides %d / %d / %d must be multiples of 4", ncols, c0,
@@ -1172,52 +1036,46 @@ extern "C" int ds_bn_pool_bwd_apply_cols(const float *z, int32_t ldz, float *dz,
     DS_REQUIRE(ldz >= ncols && lddz >= ncols && Cp >= c0 + ncols,
                "ds_bn_pool_bwd_apply_cols: stride smaller than the column range (ldz %d, lddz %d, pool %d < %d + %d)", ldz, lddz, Cp,
                c0, ncols);
-    DS_REQUIRE(N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && pad_t >= 0 && pad_t <= 1 && pad_l >= 0 && pad_l <= 1,
-               "ds_bn_pool_bwd_apply_cols: bad geometry");
+    if (int e = check_pool_walk("ds_bn_pool_bwd_apply_cols", gm, ncols, z, dz, dpool, argmax, {mean, rstd, shift, coef_g, coef_gx}))
+        return e;
     // every input pixel in exactly one patch: 3x3/2 patches reach row 2 OH - pad_t, 2x2/2 windows row 2 OH - pad_t - 1
-    DS_REQUIRE(H <= 2 * OH && W <= 2 * OW && (k == 3 || (H + pad_t <= 2 * OH && W + pad_l <= 2 * OW)),
+    DS_REQUIRE(k == 3 || (H + pad_t <= 2 * OH && W + pad_l <= 2 * OW),
                "ds_bn_pool_bwd_apply_cols: H > 2 OH or W > 2 OW (stride-2 SAME pools only)");
-    DS_REQUIRE(((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)dpool) | ((uintptr_t)mean) | ((uintptr_t)rstd) | ((uintptr_t)shift) |
-                 ((uintptr_t)coef_g) | ((uintptr_t)coef_gx)) & 15) == 0 && (((uintptr_t)argmax) & 3) == 0,
-               "ds_bn_pool_bwd_apply_cols: 16-byte aligned tensors and vectors, 4-byte aligned winners");
-    // (the neighbours' grid: sized for the (OH + 1)(OW + 1) patches of k = 3 and rounded for the reduce kernel's fixed channel
-    // group per thread; this kernel needs neither -- k = 2 has OH * OW patches -- and its grid-stride loop makes both harmless)
+    // (the neighbours' grid: sized for the (OH + 1)(OW + 1) patches of k = 3; k = 2 has OH * OW patches and its grid-stride
+    // loop makes the surplus harmless)
     const dim3 grid(pool_bwd_grid(N, OH, OW, ncols));
     if (k == 3)
-        hipLaunchKernelGGL(bn_pool_bwd_apply_cols_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, z, ldz, dz, lddz, dpool + c0,
-                           argmax + c0, Cp, N, H, W, pad_t, pad_l, OH, OW, ncols, mean, rstd, shift, coef_g, coef_gx);
+        hipLaunchKernelGGL(bn_pool_bwd_apply_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, gm, ncols, z, ldz, dz, lddz,
+                           dpool + c0, argmax + c0, Cp, mean, rstd, shift, coef_g, coef_gx);
     else
-        hipLaunchKernelGGL(bn_pool_bwd_apply_cols_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, z, ldz, dz, lddz, dpool + c0,
-                           argmax + c0, Cp, N, H, W, pad_t, pad_l, OH, OW, ncols, mean, rstd, shift, coef_g, coef_gx);
+        hipLaunchKernelGGL(bn_pool_bwd_apply_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, gm, ncols, z, ldz, dz, lddz,
+                           dpool + c0, argmax + c0, Cp, mean, rstd, shift, coef_g, coef_gx);
     return ds::check_launch("ds_bn_pool_bwd_apply_cols");
 }
 
 extern "C" int ds_bn_pool_infer_bwd_apply(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H,
                                           int32_t W, int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW,
                                           const float *rstd, const float *shift, float *dz, void *stream) {
-    DS_REQUIRE(z && dpool && argmax && rstd && shift && dz && N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 && C % 4 == 0 &&
-                   H <= 2 * OH && W <= 2 * OW && pad_t >= 0 && pad_t <= 1 && pad_l >= 0 && pad_l <= 1 &&
-                   ((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)dpool) | ((uintptr_t)rstd) | ((uintptr_t)shift)) & 15) == 0,
-               "ds_bn_pool_infer_bwd_apply: bad argument (3x3 stride-2 SAME pools, C %% 4 == 0, 16-byte aligned tensors)");
-    hipLaunchKernelGGL(bn_pool_infer_bwd_apply_kernel, dim3(pool_bwd_grid(N, OH, OW, C)), dim3(256), 0, (hipStream_t)stream, z,
-                       dpool, argmax, N, H, W, C, pad_t, pad_l, OH, OW, rstd, shift, dz);
+    const PoolGeom gm{N, H, W, pad_t, pad_l, OH, OW};
+    DS_REQUIRE(rstd && shift && dz, "ds_bn_pool_infer_bwd_apply: null pointer");
+    if (int e = check_pool_walk("ds_bn_pool_infer_bwd_apply", gm, C, z, dz, dpool, argmax, {rstd, shift})) return e;
+    hipLaunchKernelGGL((bn_pool_infer_bwd_kernel<true, false>), dim3(pool_bwd_grid(N, OH, OW, C)), dim3(256), 0, (hipStream_t)stream,
+                       gm, C, z, dpool, argmax, rstd, shift, dz, (float *)nullptr);
     return ds::check_launch("ds_bn_pool_infer_bwd_apply");
 }
 
 extern "C" int ds_bn_pool_infer_bwd_apply_sums(const float *z, const float *dpool, const uint8_t *argmax, int32_t N, int32_t H,
                                                int32_t W, int32_t C, int32_t pad_t, int32_t pad_l, int32_t OH, int32_t OW,
                                                const float *rstd, const float *shift, float *dz, float *partials, void *stream) {
-    DS_REQUIRE(z && dpool && argmax && rstd && shift && partials && N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 &&
-                   C % 4 == 0 && H <= 2 * OH && W <= 2 * OW && pad_t >= 0 && pad_t <= 1 && pad_l >= 0 && pad_l <= 1 &&
-                   ((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)dpool) | ((uintptr_t)rstd) | ((uintptr_t)shift)) & 15) == 0 &&
-                   (((uintptr_t)partials) & 3) == 0,
-               "ds_bn_pool_infer_bwd_apply_sums: bad argument (3x3 stride-2 SAME pools, C %% 4 == 0, 16-byte aligned tensors, partials)");
-    const int grid = pool_bwd_grid(N, OH, OW, C);
+    const PoolGeom gm{N, H, W, pad_t, pad_l, OH, OW};
+    DS_REQUIRE(rstd && shift && partials && (((uintptr_t)partials) & 3) == 0, "ds_bn_pool_infer_bwd_apply_sums: null pointer (partials)");
+    if (int e = check_pool_walk("ds_bn_pool_infer_bwd_apply_sums", gm, C, z, dz, dpool, argmax, {rstd, shift})) return e;
+    const dim3 grid(pool_bwd_grid(N, OH, OW, C));
     if (dz)
-        hipLaunchKernelGGL(bn_pool_infer_bwd_apply_sums_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, dpool, argmax, N,
-                           H, W, C, pad_t, pad_l, OH, OW, rstd, shift, dz, partials);
+        hipLaunchKernelGGL((bn_pool_infer_bwd_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, gm, C, z, dpool, argmax,
+                           rstd, shift, dz, partials);
     else
-        hipLaunchKernelGGL(bn_pool_infer_bwd_apply_sums_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, dpool, argmax, N,
-                           H, W, C, pad_t, pad_l, OH, OW, rstd, shift, dz, partials);
+        hipLaunchKernelGGL((bn_pool_infer_bwd_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, gm, C, z, dpool, argmax,
+                           rstd, shift, dz, partials);
     return ds::check_launch("ds_bn_pool_infer_bwd_apply_sums");
 }

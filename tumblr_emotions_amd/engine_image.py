@@ -535,21 +535,6 @@ class ConvBN:
         if need_dx:
             self._run_dgrad(dx_ptr)
 
-    def backward_infer(self, dx_ptr, pool=None, apply=True, run_dgrad=True):
-        """Moving-statistics backward (InceptionV1Engine.input_backward(eval_mode=True)): BatchNorm with fixed statistics is a
-        per-channel affine map, so dz = rstd * dy * [z*rstd + shift > 0] is ONE pointwise pass over z (ds_bn_infer_bwd_apply;
-        pool: from the pooled gradient, ds_bn_pool_infer_bwd_apply) -- no sums, no finalize -- and then the plain dgrad.
-        rstd / shift are the vectors the forward pass applied (a zcat layer's: its slices of the block's on-load vectors)."""
-        if apply:
-            if pool is not None:
-                ops.bn_pool_infer_bwd_apply(self.z, pool.dout, pool.argmax, self.B, self.OH, self.OW, self.cout, self.rstd,
-                                            self.shift, self.z)
-            else:
-                ops.bn_infer_bwd_apply(self.z, self.dy_segs, self.M, self.cout, self.rstd, self.shift, self.z, ldz=self.ldz)
-        self._dz_amax_live = False
-        if run_dgrad:
-            self._run_dgrad(dx_ptr)
-
     def frozen_partials(self, pool=None):
         """This layer's partial sums of g for the frozen-BatchNorm step, float[cout][P] (allocated at the first such step; kept
         until the step's ds_bn_dbeta_reduce_multi has read them, so every layer has its own)."""
@@ -564,25 +549,32 @@ class ConvBN:
             self.fz_job = (self._fz_part.data_ptr(), P)
         return self._fz_part
 
-    def backward_frozen(self, x_ptr=None, ldx=0, dx_ptr=None, need_dx=True, pool=None, apply=True):
-        """Backward of a frozen-BatchNorm TRAINING step (SentimentNet(frozen_bn=True)): the pointwise pass of backward_infer,
-        but the layer keeps what a training step owes -- its beta gradient, dbeta = sum g, from partial sums the SAME pass emits
-        (ds_bn_infer_bwd_apply_sums / ds_bn_pool_infer_bwd_apply_sums; reduced once per step by
-        InceptionV1Engine._frozen_dbeta), and its weight gradient where it is trainable.  apply=False: the block has run the
-        pointwise pass over this layer's concat columns already (MixedStage zcat)."""
+    def backward_pointwise(self, x_ptr=None, ldx=0, dx_ptr=None, need_dx=True, pool=None, apply=True):
+        """Moving-statistics backward: BatchNorm with fixed statistics is a per-channel affine map, so
+        dz = rstd * dy * [z*rstd + shift > 0] is ONE pointwise pass over z -- no reduce pass, no finalize -- and then the plain
+        dgrad.  rstd / shift are the vectors the forward pass applied (a zcat layer's: its slices of the block's on-load vectors).
+        What the layer owes beyond dz is carried by its own gbeta and trainable:
+          InceptionV1Engine.input_backward(eval_mode=True): neither -- ds_bn_infer_bwd_apply (pool: from the pooled gradient,
+          ds_bn_pool_infer_bwd_apply);
+          a frozen-BatchNorm TRAINING step (SentimentNet(frozen_bn=True)): its beta gradient, dbeta = sum g, from partial sums the
+          SAME pass emits (ds_bn_infer_bwd_apply_sums / ds_bn_pool_infer_bwd_apply_sums; reduced once per step by
+          InceptionV1Engine._frozen_dbeta), and its weight gradient where it is trainable.
+        apply=False: the block has run the pointwise pass over this layer's concat columns already (MixedStage zcat)."""
         if self.gbeta is None and not need_dx and not self.trainable:
             return
-        want_dz = need_dx or self.trainable
-        dz = self.z if want_dz else None
-        if apply and self.gbeta is None:
-            if want_dz:
-                self.backward_infer(None, pool, run_dgrad=False)
+        dz = self.z if (need_dx or self.trainable) else None
+        if apply and self.gbeta is None:      # (dz is wanted, or the layer had returned)
+            if pool is not None:
+                ops.bn_pool_infer_bwd_apply(self.z, pool.dout, pool.argmax, self.B, self.OH, self.OW, self.cout, self.rstd,
+                                            self.shift, self.z)
+            else:
+                ops.bn_infer_bwd_apply(self.z, self.dy_segs, self.M, self.cout, self.rstd, self.shift, self.z, ldz=self.ldz)
         elif apply:
             part = self.frozen_partials(pool)
             if self.pool_inside:
                 # only the window maxima of z exist, and every window hands its gradient to ONE pixel whose z is that maximum:
                 # sum_pixels g = sum_windows dpool * [rstd * zmax + shift > 0] -- the pointwise pass on the POOLED tensors
-                assert pool is not None and not want_dz          # (a frozen stem: nothing below it)
+                assert pool is not None and dz is None           # (a frozen stem: nothing below it)
                 if self._fz_segs is None:
                     self._fz_segs = make_segments([(0, self.cout, pool.dout.data_ptr(), self.cout)])
                 ops.bn_infer_bwd_apply_sums(self.z, self._fz_segs, self.z.shape[0], self.cout, self.rstd, self.shift, None, part)
@@ -793,12 +785,9 @@ class ConvStage(Stage):
     def backward(self, need_dx):
         need_dx = need_dx and (not self.layer.fold or self.eng.input_grad)      # (the stem: the image gradient, input_backward)
         dx = ops._p(self.prev.dout) if need_dx else None
-        if self.eng.frozen_step:
-            self.layer.backward_frozen(ops._p(self.prev.out), self.prev.C, dx, need_dx,
-                                       self.pool if (self.fused_into_pool and self.pool.stride == 2) else None)
-            return
         if self.eng.infer_bwd:
-            self.layer.backward_infer(dx, self.pool if (self.fused_into_pool and self.pool.stride == 2) else None)
+            self.layer.backward_pointwise(ops._p(self.prev.out), self.prev.C, dx, need_dx,
+                                          self.pool if (self.fused_into_pool and self.pool.stride == 2) else None)
             return
         if self.fused_into_pool and self.pool.stride == 2:
             self.layer.backward_pooled(self.pool, ops._p(self.prev.out), self.prev.C, dx, need_dx)
@@ -1261,7 +1250,7 @@ class MixedStage(Stage):
             if self._infer_close is None:
                 self._infer_close = (make_segments([(0, Ct - b0, self.dout.data_ptr() + 4 * b0, Ct)]), self.out.view(M, Ct)[:, b0:])
             dy, z = self._infer_close
-            if eng.frozen_step and self.c1.gbeta is not None:
+            if self.c1.gbeta is not None:        # (a frozen-BatchNorm training step)
                 # ... which also emits the column sums of g: the three layers' beta gradients are column ranges of them
                 if self._fz_close is None:
                     P = ops.bn_infer_bwd_partials(M, Ct - b0)
@@ -1275,10 +1264,8 @@ class MixedStage(Stage):
                 ops.bn_infer_bwd_apply(z, dy, M, Ct - b0, self.rs_cat[0, b0:], self.rs_cat[1, b0:], z, ldz=Ct)
 
         def closing(layer, x_ptr, ldx, dx_ptr, ndx):
-            if eng.frozen_step:
-                layer.backward_frozen(x_ptr, ldx, dx_ptr, ndx, apply=not self.zcat)
-            elif infer:
-                layer.backward_infer(dx_ptr, apply=not self.zcat)
+            if infer:
+                layer.backward_pointwise(x_ptr, ldx, dx_ptr, ndx, apply=not self.zcat)
             elif batched:
                 layer._run_dgrad(dx_ptr)
             else:
@@ -1297,10 +1284,7 @@ class MixedStage(Stage):
         self._fork_join(None, lambda: closing(self.c1, ops._p(self.r1), b1a, ops._p(self.dr1), True),
                         lambda: closing(self.c2, ops._p(self.r2), b2a, ops._p(self.dr2), True), branch3)
         if infer:
-            if eng.frozen_step:
-                self.fused.backward_frozen(x, p.C, ops._p(p.dout) if need_dx else None, need_dx)
-            else:
-                self.fused.backward_infer(ops._p(p.dout))
+            self.fused.backward_pointwise(x, p.C, ops._p(p.dout) if need_dx else None, need_dx)
             # (need_dx: always set in input_backward's walk; a frozen-BatchNorm step with trainable_bn_beta=False ends at
             # Mixed_5c, whose input gradient nobody reads)
             if need_dx and not pool_first and not self.split_dout:
