@@ -831,6 +831,50 @@ int ds_colsum(const float *x, int64_t M, int32_t C, int32_t ld, float *scratch, 
  * image_model/inception_v1.py:302), whose single row tile would otherwise walk K serially. */
 int ds_slab_epilogue(const float *slabs, int32_t splits, int64_t slab_stride, int32_t lds, int64_t M, int32_t N, float *out,
                      int32_t ldo, const float *bias, const float *mask, int32_t ldmask, int32_t flags, void *stream);
+
+/* ---- grouped launches for the heads' small GEMMs --------------------------------------------------------------------------
+ * Between the two towers' forward and backward passes the step is a serial chain of GEMMs of one or two row tiles (MatMul /
+ * BiasAdd / Relu of im_text_rnn_model.py:95-105 and their gradients), each a dependent launch that fills a fraction of the chip.
+ * Launches that do not depend on each other are grouped.  Every result keeps the bits of the separate launches.
+ *
+ * ds_gemm_group: `count` (1..4) independent GEMMs as ONE launch.  Problem i is described exactly as for ds_conv_igemm --
+ * descs[i] (a plain GEMM: N = rows, H = W = OH = OW = KH = KW = 1, fp32, flags 0; splits > 1: slab s at z[i] + s *
+ * z_split_stride), x[i], w[i], z[i] -- and z[i] receives what ds_conv_igemm(descs[i], x[i], w[i], z[i], ...) writes, bit for
+ * bit: the grouped grid is the concatenation of the problems' grids and each workgroup looks its problem up once.  Problems
+ * whose own launch would not use the 128 x 32 tile of the small GEMMs are DS_ERR_ARG.  All four arrays are HOST arrays.       */
+int ds_gemm_group(const ds_conv_desc *const *descs, const float *const *x, const float *const *w, float *const *z,
+                  int32_t count, void *stream);
+/* One combine of ds_slab_epilogue_group: ds_slab_epilogue's arguments (out[m][n] = epilogue(sum_s slabs[s][m][n]), slabs added
+ * in index order, then BIAS, ACCUM, MASK, RELU in that order) plus
+ *   pre_slabs (nullable, needs DS_EPI_ACCUM): the accumulate operand is sum_s pre_slabs[s][m][n] (index order, from 0) instead
+ *             of the previous contents of out -- the bits of ds_slab_epilogue(pre_slabs -> out, flags 0) followed by this
+ *             combine with DS_EPI_ACCUM, without the intermediate pass: relu(x_tx W_tx + b + x_im W_im);
+ *   out2      (nullable): columns [n_split, N) are stored to out2[m * ldo2 + n - n_split], columns [0, n_split) to out --
+ *             one GEMM through the rows of W_fc, two gradients (d_im, d_tx).                                                  */
+typedef struct ds_slab_combine {
+    const float *slabs;
+    const float *pre_slabs;
+    int64_t slab_stride, pre_slab_stride;   /* floats between slabs                                      */
+    int64_t M;
+    int32_t N;
+    int32_t splits, pre_splits;
+    int32_t lds, pre_lds;                   /* row strides of the slabs                                  */
+    int32_t flags;                          /* DS_EPI_BIAS / DS_EPI_ACCUM / DS_EPI_MASK / DS_EPI_RELU    */
+    float *out;
+    float *out2;
+    int32_t ldo, ldo2, n_split;
+    int32_t ldmask;
+    const float *bias;
+    const float *mask;
+} ds_slab_combine;
+/* `count` (1..4) combines as ONE launch; `ops` is a HOST array. */
+int ds_slab_epilogue_group(const ds_slab_combine *ops, int32_t count, void *stream);
+/* The combine of a logits GEMM (M <= 512 rows, N <= 32 classes; bias nullable; logits packed [M][N]) and ds_softmax_ce of the
+ * result as ONE single-workgroup launch: logits, loss and dlogits are the bits of ds_slab_epilogue(flags = DS_EPI_BIAS) followed
+ * by ds_softmax_ce(logits, labels, M, N, grad_scale, grad_scale_dev, loss, dlogits).                                            */
+int ds_slab_epilogue_ce(const float *slabs, int32_t splits, int64_t slab_stride, int32_t lds, int32_t M, int32_t N,
+                        float *logits, const float *bias, const int64_t *labels, float grad_scale,
+                        const float *grad_scale_dev, float *loss, float *dlogits, void *stream);
 int ds_copy2d(const float *src, int32_t lds, float *dst, int32_t ldd, int64_t rows, int32_t cols,
               void *stream);
 int ds_pad_channels(const float *src, int32_t cs, float *dst, int32_t cd, int64_t pixels, void *stream);

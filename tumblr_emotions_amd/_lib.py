@@ -107,6 +107,14 @@ class SumSegments(C.Structure):
                 ("s2", C.c_void_p * 4), ("q2", C.c_void_p * 4)]
 
 
+class SlabCombine(C.Structure):
+    """ds_slab_combine"""
+    _fields_ = [("slabs", C.c_void_p), ("pre_slabs", C.c_void_p), ("slab_stride", C.c_int64), ("pre_slab_stride", C.c_int64),
+                ("M", C.c_int64), ("N", C.c_int32), ("splits", C.c_int32), ("pre_splits", C.c_int32), ("lds", C.c_int32),
+                ("pre_lds", C.c_int32), ("flags", C.c_int32), ("out", C.c_void_p), ("out2", C.c_void_p), ("ldo", C.c_int32),
+                ("ldo2", C.c_int32), ("n_split", C.c_int32), ("ldmask", C.c_int32), ("bias", C.c_void_p), ("mask", C.c_void_p)]
+
+
 class PreprocessDesc(C.Structure):
     """ds_preprocess_desc"""
     _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32), ("scale_y", C.c_float), ("scale_x", C.c_float)]
@@ -280,6 +288,9 @@ SIGNATURES = {
     "ds_sumsq": (C.c_int, [_P, _i64, _P, _P, _P]),
     "ds_colsum": (C.c_int, [_P, _i64, _i32, _i32, _P, _P, _P]),
     "ds_slab_epilogue": (C.c_int, [_P, _i32, _i64, _i32, _i64, _i32, _P, _i32, _P, _P, _i32, _i32, _P]),
+    "ds_gemm_group": (C.c_int, [C.POINTER(_CD), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _i32, _P]),
+    "ds_slab_epilogue_group": (C.c_int, [C.POINTER(SlabCombine), _i32, _P]),
+    "ds_slab_epilogue_ce": (C.c_int, [_P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _f32, _P, _P, _P, _P]),
     "ds_copy2d": (C.c_int, [_P, _i32, _P, _i32, _i64, _i32, _P]),
     "ds_pad_channels": (C.c_int, [_P, _i32, _P, _i32, _i64, _P]),
     "ds_fill": (C.c_int, [_P, _i64, _f32, _P]),

@@ -78,21 +78,23 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void *p, unsign
 struct TileId {
     int row, col, stride;      // first row tile, column tile, row-tile stride of the persistent loop
 };
-__device__ __forceinline__ TileId tile_id(const ConvParams &p) {
+// (bx, by) of a grid gx wide: the launch's own blockIdx / gridDim, or -- gemm_group_kernel -- a problem's share of a grouped launch
+__device__ __forceinline__ TileId tile_id(const ConvParams &p, int bx, int by, int gx) {
     TileId t;
     if (p.col_tiles > 0) {
-        const int id = blockIdx.x;
-        const int lin = (id & 7) * (int)(gridDim.x >> 3) + (id >> 3);      // position in the row-major tile list
+        const int id = bx;
+        const int lin = (id & 7) * (gx >> 3) + (id >> 3);      // position in the row-major tile list
         t.row = lin / p.col_tiles;
         t.col = lin - t.row * p.col_tiles;
         t.stride = p.row_tiles;            // exactly one tile per workgroup
     } else {
-        t.row = blockIdx.x;
-        t.col = blockIdx.y;
-        t.stride = gridDim.x;
+        t.row = bx;
+        t.col = by;
+        t.stride = gx;
     }
     return t;
 }
+__device__ __forceinline__ TileId tile_id(const ConvParams &p) { return tile_id(p, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x); }
 
 template <bool VEC>
 __device__ __forceinline__ f32x4 load4(__amdgpu_buffer_rsrc_t r, unsigned off, bool ok, int valid) {
@@ -112,16 +114,26 @@ __device__ __forceinline__ f32x4 load4(__amdgpu_buffer_rsrc_t r, unsigned off, b
 // are the workhorses and measured fastest at 3-4 resident workgroups per CU
 // BNR: the inference epilogue DS_EPI_BN_RELU, y = max(fma(acc, scale[col], shift[col]), 0) stored in place of z -- its own
 // instantiation (forward, vector loads, MT = 1), so the training kernels' code is untouched
+// floats of LDS one workgroup of conv_igemm_kernel<MT, NT, BNMAJOR, ..> stages its two K-tiles in
+template <int MT, int NT, bool BNMAJOR>
+constexpr int igemm_smem_floats() {
+    return 2 * (4 * MT * 32) * LDK + 2 * (BNMAJOR ? BK * (NT * 32 + 4) : NT * 32 * LDK);
+}
+
+// One workgroup's share of a launch: the tiles `tid0` names, K-tiles of split `split` of `nsplits`.  The body of
+// conv_igemm_kernel (its own blockIdx / gridDim) and of gemm_group_kernel (a problem's share of a grouped launch): the same
+// loads, MFMAs and stores in the same order, so what a tile receives does not depend on which of the two launched it.
+// `smem`: igemm_smem_floats<MT, NT, BNMAJOR>() floats, 16-byte aligned; wg_seq: the workgroup's number in dispatch order.
 template <int MT, int NT, bool BNMAJOR, bool FOLD, bool VEC, bool BNR = false>
-__global__ __launch_bounds__(256, (MT == 1 && NT == 1) ? 4 : (MT == 1 && NT == 2) ? 3 : 1) void conv_igemm_kernel(
-    const ConvParams p) {
+__device__ __forceinline__ void igemm_workgroup(const ConvParams &p, float *smem, const TileId tid0, const int split,
+                                                const int nsplits, const int wg_seq) {
     constexpr int WM = 4;
     constexpr int BM = WM * MT * 32, BN = NT * 32;
     constexpr int AR = BM / 64;                       // float4 A loads per thread per K-tile
     constexpr int BR = (BN * 4 + 255) / 256;          // float4 B loads per thread per K-tile
     constexpr int LDB = BNMAJOR ? (BN + 4) : LDK;     // B tile: [k][n] (n-contiguous weights) or [n][k]
     constexpr int BSZ = BNMAJOR ? BK * LDB : BN * LDK;
-    __shared__ __attribute__((aligned(16))) float smem[2 * BM * LDK + 2 * BSZ];
+    static_assert(igemm_smem_floats<MT, NT, BNMAJOR>() == 2 * BM * LDK + 2 * BSZ, "LDS size");
     float *As = smem;
     float *Bs = smem + 2 * BM * LDK;
 
@@ -129,16 +141,15 @@ __global__ __launch_bounds__(256, (MT == 1 && NT == 1) ? 4 : (MT == 1 && NT == 2
     const int tid = threadIdx.x, lane = tid & 63;
     const int wm = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform
     const int li = lane & 31, lk = lane >> 5;
-    const TileId tid0 = tile_id(p);
     const int n0 = tid0.col * BN;
     const int ohw = d.OH * d.OW;
     const int chunks = (d.Cin + BK - 1) / BK;
-    // split-K (small-M GEMMs): blockIdx.z owns K-tiles [kt0, kt1) and writes its own output slab
+    // split-K (small-M GEMMs): split `split` owns K-tiles [kt0, kt1) and writes its own output slab
     const int KT_all = p.taps * chunks;
-    const int kts = (KT_all + (int)gridDim.z - 1) / (int)gridDim.z;
-    const int kt0 = (int)blockIdx.z * kts;
+    const int kts = (KT_all + nsplits - 1) / nsplits;
+    const int kt0 = split * kts;
     const int KT = (kt0 + kts < KT_all ? kt0 + kts : KT_all) - kt0;     // K-tiles of this split (may be <= 0)
-    float *const zout = p.z + (int64_t)blockIdx.z * p.d.z_split_stride;
+    float *const zout = p.z + (int64_t)split * p.d.z_split_stride;
     const int flags = d.flags;
     const __amdgpu_buffer_rsrc_t srd_x = make_srd(p.x, p.x_bytes);
     const __amdgpu_buffer_rsrc_t srd_w = make_srd(p.w, p.w_bytes);
@@ -150,7 +161,7 @@ __global__ __launch_bounds__(256, (MT == 1 && NT == 1) ? 4 : (MT == 1 && NT == 2
     // arbitration unfair: the phases stagger and one wave's non-MFMA work hides under another's MFMAs.
     // Co-resident workgroups are ~256 apart in dispatch order (id % 8 -> XCD, (id / 8) % 32 -> CU); a
     // different placement only costs speed.  s_setprio is scalar: the switch is wave-uniform.
-    switch (p.prio_mode ? ((blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y) >> 8) & 3 : 0) {
+    switch (p.prio_mode ? (wg_seq >> 8) & 3 : 0) {
         case 1: __builtin_amdgcn_s_setprio(1); break;
         case 2: __builtin_amdgcn_s_setprio(2); break;
         case 3: __builtin_amdgcn_s_setprio(3); break;
@@ -399,6 +410,51 @@ __global__ __launch_bounds__(256, (MT == 1 && NT == 1) ? 4 : (MT == 1 && NT == 2
             p.stats[(int64_t)(n0 + tid) * tid0.stride + tid0.row] = s;
             p.stats[((int64_t)d.Cout + n0 + tid) * tid0.stride + tid0.row] = q;
         }
+    }
+}
+
+template <int MT, int NT, bool BNMAJOR, bool FOLD, bool VEC, bool BNR = false>
+__global__ __launch_bounds__(256, (MT == 1 && NT == 1) ? 4 : (MT == 1 && NT == 2) ? 3 : 1) void conv_igemm_kernel(
+    const ConvParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[igemm_smem_floats<MT, NT, BNMAJOR>()];
+    igemm_workgroup<MT, NT, BNMAJOR, FOLD, VEC, BNR>(
+        p, smem, tile_id(p), (int)blockIdx.z, (int)gridDim.z,
+        (int)(blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y));
+}
+
+// ---- grouped launch of up to four independent batch x features GEMMs (ds_gemm_group) ---------------------------------
+// The joint head's GEMMs are a row tile or two each: a launch of theirs fills a fraction of the chip and costs a dependent-launch
+// boundary.  Problems that do not depend on each other (W_fc's image and text halves) share ONE launch: the grid is the
+// concatenation of the problems' grids, every workgroup looks its problem up once -- scalar code, before the K loop -- and then
+// runs igemm_workgroup<1, 1, ..> on it exactly as that problem's own ds_conv_igemm launch would.
+constexpr int kGemmGroupMax = 4;
+struct GemmGroupParams {
+    ConvParams p[kGemmGroupMax];
+    int wg_end[kGemmGroupMax];       // first workgroup past problem i
+    int gx[kGemmGroupMax], gy[kGemmGroupMax], splits[kGemmGroupMax];      // the grid ds_conv_igemm launches for problem i
+    int variant[kGemmGroupMax];      // bit 0: n-contiguous weights (BNMAJOR), bit 1: 16-byte loads (VEC)
+    int count;
+};
+
+__global__ __launch_bounds__(256, 4) void gemm_group_kernel(const GemmGroupParams g) {
+    constexpr int kSmem = igemm_smem_floats<1, 1, true>() > igemm_smem_floats<1, 1, false>() ? igemm_smem_floats<1, 1, true>()
+                                                                                              : igemm_smem_floats<1, 1, false>();
+    __shared__ __attribute__((aligned(16))) float smem[kSmem];
+    const int id = (int)blockIdx.x;
+    int q = 0;
+    while (q + 1 < g.count && id >= g.wg_end[q]) ++q;
+    const int local = id - (q ? g.wg_end[q - 1] : 0);
+    const int gx = g.gx[q], gxy = gx * g.gy[q];
+    const int split = local / gxy;
+    const int by = (local - split * gxy) / gx;
+    const int bx = local - split * gxy - by * gx;
+    const ConvParams &p = g.p[q];
+    const TileId t = tile_id(p, bx, by, gx);
+    switch (g.variant[q]) {
+        case 0: igemm_workgroup<1, 1, false, false, false>(p, smem, t, split, g.splits[q], local); break;
+        case 1: igemm_workgroup<1, 1, true, false, false>(p, smem, t, split, g.splits[q], local); break;
+        case 2: igemm_workgroup<1, 1, false, false, true>(p, smem, t, split, g.splits[q], local); break;
+        default: igemm_workgroup<1, 1, true, false, true>(p, smem, t, split, g.splits[q], local); break;
     }
 }
 
@@ -2520,6 +2576,15 @@ int conv_igemm_bn_relu(const ds_conv_desc *d, const float *x, const float *w, fl
 }  // namespace ds
 
 namespace {
+int xcd_remap_on() {
+    static int xcd_remap = -1;
+    if (xcd_remap < 0) {
+        const char *e = ds::tune_env("DS_CONV_XCD_REMAP");      // A/B aid; default on
+        xcd_remap = e ? atoi(e) : 1;
+    }
+    return xcd_remap;
+}
+
 int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *bias, const float *mask,
                  float *stats, const float *pivot, const float *scale, const float *shift, void *stream) {
     DS_REQUIRE(d && x && w && z, "ds_conv_igemm: null argument");
@@ -2586,11 +2651,7 @@ int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z
                "ds_conv_igemm: the launch would write %d statistics partials but the plan was made for %d "
                "(a ds_debug_conv_set_* switch changed after planning?)", c.direct ? gx * 4 : gx, d->partials);
     p.row_tiles = rt;
-    static int xcd_remap = -1;
-    if (xcd_remap < 0) {
-        const char *e = ds::tune_env("DS_CONV_XCD_REMAP");      // A/B aid; default on
-        xcd_remap = e ? atoi(e) : 1;
-    }
+    const int xcd_remap = xcd_remap_on();
     dim3 grid(gx, gy, splits);
     p.col_tiles = 0;
     if (one && (c.wide || (xcd_remap && gy > 1)) && !c.direct) {    // one workgroup per tile: 1-D XCD-aware launch (TileId)
@@ -2634,6 +2695,64 @@ int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z
     return ds::check_launch("ds_conv_igemm");
 }
 }  // namespace
+
+// One launch for `count` (1..4) independent GEMMs, each described as for ds_conv_igemm (split-K descriptors write their slabs
+// at z[i] + s * z_split_stride).  Problem i's tiles receive exactly what ds_conv_igemm(descs[i], x[i], w[i], z[i]) writes: the
+// grid of that launch is laid into this one and the workgroups run the same code.  Plain 1x1 fp32 problems without epilogue
+// whose own launch is the 128 x 32 LDS-staged tile (the batch x features GEMMs of the heads); anything else is DS_ERR_ARG.
+extern "C" int ds_gemm_group(const ds_conv_desc *const *descs, const float *const *x, const float *const *w, float *const *z,
+                             int32_t count, void *stream) {
+    DS_REQUIRE(descs && x && w && z && count >= 1 && count <= kGemmGroupMax, "ds_gemm_group: 1..%d problems", kGemmGroupMax);
+    GemmGroupParams g{};
+    g.count = count;
+    int wgs = 0;
+    for (int i = 0; i < count; ++i) {
+        const ds_conv_desc *d = descs[i];
+        DS_REQUIRE(d && x[i] && w[i] && z[i], "ds_gemm_group: null argument (problem %d)", i);
+        DS_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->N > 0 && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->H == 1 && d->W == 1 &&
+                       d->OH == 1 && d->OW == 1 && d->pad_t == 0 && d->pad_l == 0 && d->fold_cin == 0 && d->flip == 0,
+                   "ds_gemm_group: problem %d is not a plain GEMM", i);
+        DS_REQUIRE(d->dtype == DS_DTYPE_F32 && d->flags == 0 && !d->bnb && !d->fin && !d->norm_rstd && !d->norm_shift &&
+                       !d->mask_rstd && !d->mask_shift && !d->pool_argmax,
+                   "ds_gemm_group: problem %d: fp32 without epilogue flags or on-load operands (combine with ds_slab_epilogue_group)", i);
+        DS_REQUIRE(d->w_n_stride == 1 || d->w_k_stride == 1, "ds_gemm_group: one weight stride must be 1");
+        DS_REQUIRE(d->ldx >= d->Cin && d->ldz >= d->Cout, "ds_gemm_group: problem %d: row strides below the row lengths", i);
+        const int splits = d->splits > 1 ? d->splits : 1;
+        DS_REQUIRE(splits == 1 || d->z_split_stride >= (int64_t)(d->N - 1) * d->ldz + d->Cout,
+                   "ds_gemm_group: problem %d: overlapping output slabs", i);
+        const Variant v = variant_of(d, x[i], w[i]);
+        const TileCfg c = pick_cfg(d, v.vec);
+        DS_REQUIRE(c.mt == 1 && c.nt == 1 && !c.direct && !c.glds && !c.bf16 && !c.wide,
+                   "ds_gemm_group: problem %d's own launch is not the 128 x 32 tile (run it through ds_conv_igemm)", i);
+        ConvParams &p = g.p[i];
+        p.d = *d;
+        if (splits == 1) p.d.z_split_stride = 0;
+        p.x = x[i]; p.w = w[i]; p.z = z[i];
+        p.M = d->N;
+        p.taps = 1;
+        const int64_t x_elems = (int64_t)(d->N - 1) * d->ldx + d->Cin;
+        const int64_t w_elems = (int64_t)(d->Cout - 1) * d->w_n_stride + (int64_t)(d->Cin - 1) * d->w_k_stride + 1;
+        DS_REQUIRE(x_elems * 4 < (1ll << 31) && w_elems * 4 < (1ll << 31), "ds_gemm_group: operand larger than 2 GiB");
+        p.x_bytes = (unsigned)(x_elems * 4);
+        p.w_bytes = (unsigned)(w_elems * 4);
+        int gx, gy, rt;
+        bool one;
+        grid_for(d, c, v, &gx, &gy, &rt, &one);
+        p.row_tiles = rt;
+        if (one && xcd_remap_on() && gy > 1) {      // the 1-D XCD-aware shape of ds_conv_igemm's launch (TileId)
+            p.col_tiles = gy;
+            gx = (rt * gy + 7) / 8 * 8;
+            gy = 1;
+        }
+        g.gx[i] = gx; g.gy[i] = gy; g.splits[i] = splits;
+        g.variant[i] = (v.bnmajor ? 1 : 0) | (v.vec ? 2 : 0);
+        DS_REQUIRE((int64_t)wgs + (int64_t)gx * gy * splits < (1 << 20), "ds_gemm_group: too many workgroups");
+        wgs += gx * gy * splits;
+        g.wg_end[i] = wgs;
+    }
+    hipLaunchKernelGGL(gemm_group_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, g);
+    return ds::check_launch("ds_gemm_group");
+}
 
 // ---- bf16 register-direct path -------------------------------------------------------------------------------------
 namespace {

@@ -225,10 +225,11 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float *acts, c
 }
 
 // ---- softmax cross entropy (+ gradient), one workgroup, fixed summation order -----------------------
-__global__ __launch_bounds__(256) void softmax_ce_kernel(const float *logits, const int64_t *labels, int B, int C,
-                                                         float grad_scale, const float *grad_scale_dev,
-                                                         float *loss, float *dlogits) {
-    __shared__ float red[256];
+// (the whole workgroup's work: softmax_ce_kernel, and slab_epilogue_ce_kernel behind its combine -- there thread t reads back
+// the rows t, t + 256 of `logits` that it has just stored itself)
+__device__ __forceinline__ void softmax_ce_workgroup(const float *logits, const int64_t *labels, int B, int C,
+                                                     float grad_scale, const float *grad_scale_dev,
+                                                     float *loss, float *dlogits, float *red) {
     if (grad_scale_dev) grad_scale *= grad_scale_dev[0];   // upstream d(loss) handed over on device
     float acc = 0.f;
     for (int b = threadIdx.x; b < B; b += 256) {
@@ -256,6 +257,13 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float *logits, co
         __syncthreads();
     }
     if (threadIdx.x == 0 && loss) loss[0] = red[0] / (float)B;
+}
+
+__global__ __launch_bounds__(256) void softmax_ce_kernel(const float *logits, const int64_t *labels, int B, int C,
+                                                         float grad_scale, const float *grad_scale_dev,
+                                                         float *loss, float *dlogits) {
+    __shared__ float red[256];
+    softmax_ce_workgroup(logits, labels, B, C, grad_scale, grad_scale_dev, loss, dlogits, red);
 }
 
 // ---- TF Adam over a flat buffer ------------------------------------------------------------------
@@ -659,6 +667,103 @@ extern "C" int ds_slab_epilogue(const float *slabs, int32_t splits, int64_t slab
     hipLaunchKernelGGL(slab_epilogue_kernel, dim3(ds::stream_grid(M * N, 256)), dim3(256), 0, (hipStream_t)stream, slabs, splits,
                        slab_stride, lds, M, N, out, ldo, bias, mask, ldmask, flags);
     return ds::check_launch("ds_slab_epilogue");
+}
+
+// ---- the combines of several split-K GEMMs as ONE launch (ds_slab_epilogue_group) -----------------------------------------
+// Combine i is slab_epilogue_kernel's arithmetic on its own slabs, with two extensions the joint head needs:
+//   * pre_slabs: the DS_EPI_ACCUM operand is not read from `out` but formed here, sum of pre_slabs in index order from 0 --
+//     what a plain ds_slab_epilogue of those slabs into `out` would have left there (W_fc's image half under its text half);
+//   * out2: columns [n_split, N) go to out2[m * ldo2 + n - n_split] (one dgrad through W_fc, the image and the text gradient).
+constexpr int kCombineMax = 4;
+struct SlabCombineParams {
+    ds_slab_combine op[kCombineMax];
+    int wg_end[kCombineMax];      // first workgroup past combine i
+    int count;
+};
+
+__global__ __launch_bounds__(256) void slab_epilogue_group_kernel(const SlabCombineParams g) {
+    const int id = (int)blockIdx.x;
+    int q = 0;
+    while (q + 1 < g.count && id >= g.wg_end[q]) ++q;
+    const int wg0 = q ? g.wg_end[q - 1] : 0;
+    const ds_slab_combine &c = g.op[q];
+    const int64_t total = c.M * c.N, step = (int64_t)(g.wg_end[q] - wg0) * 256;
+    const int N = c.N, flags = c.flags;
+    for (int64_t i = (int64_t)(id - wg0) * 256 + threadIdx.x; i < total; i += step) {
+        const int64_t m = i / N;
+        const int n = (int)(i - m * N);
+        float v = 0.f;
+        for (int k = 0; k < c.splits; ++k) v += c.slabs[(int64_t)k * c.slab_stride + m * c.lds + n];
+        if (flags & DS_EPI_BIAS) v += c.bias[n];
+        float *const o = (c.out2 && n >= c.n_split) ? c.out2 + m * c.ldo2 + (n - c.n_split) : c.out + m * c.ldo + n;
+        if (flags & DS_EPI_ACCUM) {
+            if (c.pre_slabs) {
+                float u = 0.f;
+                for (int k = 0; k < c.pre_splits; ++k) u += c.pre_slabs[(int64_t)k * c.pre_slab_stride + m * c.pre_lds + n];
+                v += u;
+            } else {
+                v += *o;
+            }
+        }
+        if (flags & DS_EPI_MASK) v = c.mask[m * c.ldmask + n] > 0.f ? v : 0.f;
+        if (flags & DS_EPI_RELU) v = fmaxf(v, 0.f);
+        *o = v;
+    }
+}
+
+extern "C" int ds_slab_epilogue_group(const ds_slab_combine *ops, int32_t count, void *stream) {
+    DS_REQUIRE(ops && count >= 1 && count <= kCombineMax, "ds_slab_epilogue_group: 1..%d combines", kCombineMax);
+    SlabCombineParams g{};
+    g.count = count;
+    int wgs = 0;
+    for (int i = 0; i < count; ++i) {
+        const ds_slab_combine &c = ops[i];
+        DS_REQUIRE(c.slabs && c.out && c.splits >= 1 && c.M > 0 && c.N > 0 && c.lds >= c.N, "ds_slab_epilogue_group: bad argument (combine %d)", i);
+        DS_REQUIRE((c.flags & ~(DS_EPI_BIAS | DS_EPI_ACCUM | DS_EPI_MASK | DS_EPI_RELU)) == 0 && (!(c.flags & DS_EPI_BIAS) || c.bias) &&
+                       (!(c.flags & DS_EPI_MASK) || (c.mask && c.ldmask >= c.N)),
+                   "ds_slab_epilogue_group: flags are BIAS / ACCUM / MASK / RELU (with their operands)");
+        DS_REQUIRE(!c.pre_slabs || ((c.flags & DS_EPI_ACCUM) && c.pre_splits >= 1 && c.pre_lds >= c.N),
+                   "ds_slab_epilogue_group: pre_slabs is the DS_EPI_ACCUM operand (pre_splits >= 1, pre_lds >= N)");
+        if (c.out2)
+            DS_REQUIRE(c.n_split > 0 && c.n_split < c.N && c.ldo >= c.n_split && c.ldo2 >= c.N - c.n_split,
+                       "ds_slab_epilogue_group: out2 takes columns [n_split, N), 0 < n_split < N");
+        else
+            DS_REQUIRE(c.ldo >= c.N, "ds_slab_epilogue_group: ldo below N (combine %d)", i);
+        g.op[i] = c;
+        wgs += ds::stream_grid(c.M * c.N, 256);
+        g.wg_end[i] = wgs;
+    }
+    hipLaunchKernelGGL(slab_epilogue_group_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, g);
+    return ds::check_launch("ds_slab_epilogue_group");
+}
+
+// The combine of the W_softmax GEMM's slabs (bias added: the logits) going straight on to the cross entropy and its gradient:
+// one workgroup, as ds_softmax_ce is -- thread t combines rows t and t + 256, stores them, and runs ds_softmax_ce's own
+// arithmetic on them (softmax_ce_workgroup), so logits, loss and dlogits are the bits of ds_slab_epilogue + ds_softmax_ce.
+__global__ __launch_bounds__(256) void slab_epilogue_ce_kernel(const float *slabs, int splits, int64_t slab_stride, int lds,
+                                                               int M, int N, float *logits, const float *bias,
+                                                               const int64_t *labels, float grad_scale,
+                                                               const float *grad_scale_dev, float *loss, float *dlogits) {
+    __shared__ float red[256];
+    for (int m = threadIdx.x; m < M; m += 256) {
+        for (int n = 0; n < N; ++n) {
+            float v = 0.f;
+            for (int k = 0; k < splits; ++k) v += slabs[(int64_t)k * slab_stride + (int64_t)m * lds + n];
+            if (bias) v += bias[n];
+            logits[(int64_t)m * N + n] = v;
+        }
+    }
+    softmax_ce_workgroup(logits, labels, M, N, grad_scale, grad_scale_dev, loss, dlogits, red);
+}
+
+extern "C" int ds_slab_epilogue_ce(const float *slabs, int32_t splits, int64_t slab_stride, int32_t lds, int32_t M, int32_t N,
+                                   float *logits, const float *bias, const int64_t *labels, float grad_scale,
+                                   const float *grad_scale_dev, float *loss, float *dlogits, void *stream) {
+    DS_REQUIRE(slabs && logits && labels && splits >= 1 && lds >= N, "ds_slab_epilogue_ce: bad argument");
+    DS_REQUIRE(M > 0 && M <= 512 && N > 0 && N <= 32, "ds_slab_epilogue_ce: M <= 512 rows of N <= 32 logits (packed, row stride N)");
+    hipLaunchKernelGGL(slab_epilogue_ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, slabs, splits, slab_stride, lds, M, N,
+                       logits, bias, labels, grad_scale, grad_scale_dev, loss, dlogits);
+    return ds::check_launch("ds_slab_epilogue_ce");
 }
 
 extern "C" int ds_copy2d(const float *src, int32_t lds, float *dst, int32_t ldd, int64_t rows, int32_t cols,

@@ -1351,6 +1351,11 @@ class InceptionV1Engine:
         self.wgrad_side = True       # Mixed_5c's weight gradients on their own stream, off the dgrad chain
         self.side_w = None
         self.wgrad_stream = None
+        # the Logits layer's weight and bias gradient (and side_job: the L2 term) on that stream too, its input gradient first
+        # on the chain (JointHeadEngine.group is the joint head's half of this).  Bit-identical (tests).  DS_HEAD_GROUP=0: A/B
+        self.head_group = _lib.tuning_env("DS_HEAD_GROUP", "1") != "0"
+        self.head_grads_pending = False      # JointHeadEngine left its parameter gradients on side_w: backward() joins it
+        self.side_job = None                 # callable run once behind the Logits gradients of the next backward() (SentimentNet)
         self.bwd_sums = True         # BatchNorm backward sums from the producing dgrad's epilogue (DS_EPI_BNSUMS) where it can
         self.stem_direct = True      # Conv2d_1a_7x7 from the packed RGB batch (ds_conv_stem; False: generic kernel on a 4-channel copy)
         self.stem_pool = _lib.tuning_env("DS_STEM_POOL", "1") != "0"      # ... with MaxPool_2a inside that kernel (ds_conv_stem_pool; ConvStage.alloc)
@@ -1757,17 +1762,39 @@ class InceptionV1Engine:
         B, nc, F = self.B, self.num_classes, self.feat
         last = self.last
         dl = ops._p(dlogits)
-        self.fc_wgrad.run(ops._p(self.pooled), dl, self.gw_fc, ops._p(self.ws), self.ws_bytes)
-        ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_fc)
-        self.fc_dgrad.run(dl, self.w_fc, ops._p(self.dpooled))
-        ops.avgpool_dropout_bwd(self.dpooled, self.mask, B, last.H * last.W, F, self.keep, last.dout)
+        self.wgrad_stream = self.side_w if (self.wgrad_side and self.side_w is not None) else None
+        # (the joint head's parameter gradients may already run on the weight-gradient stream: the walk below joins it)
+        self.wgrad_pending = bool(self.head_grads_pending) and self.wgrad_stream is not None
+        self.head_grads_pending = False
+        job, self.side_job = self.side_job, None
+        if self.head_group and self.wgrad_stream is not None:
+            # the chain first; the two Logits gradients are leaves of the backward graph (only the optimiser and the all-reduce
+            # read them): onto the weight-gradient stream, with its workspace
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())          # dlogits is complete here
+            self.fc_dgrad.run(dl, self.w_fc, ops._p(self.dpooled))
+            ops.avgpool_dropout_bwd(self.dpooled, self.mask, B, last.H * last.W, F, self.keep, last.dout)
+            self.wgrad_stream.wait_event(ev)
+            if not torch.cuda.is_current_stream_capturing():
+                dlogits.record_stream(self.wgrad_stream)      # (an autograd temporary must outlive its readers there)
+            with torch.cuda.stream(self.wgrad_stream):
+                self.fc_wgrad.run(ops._p(self.pooled), dl, self.gw_fc, ops._p(self.ws_set[3]), self.ws_bytes)
+                ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_fc)
+                if job is not None:
+                    job()
+            self.wgrad_pending = True
+        else:
+            self.fc_wgrad.run(ops._p(self.pooled), dl, self.gw_fc, ops._p(self.ws), self.ws_bytes)
+            ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_fc)
+            self.fc_dgrad.run(dl, self.w_fc, ops._p(self.dpooled))
+            ops.avgpool_dropout_bwd(self.dpooled, self.mask, B, last.H * last.W, F, self.keep, last.dout)
+            if job is not None:
+                job()
         n = len(self.stages)
         # below the last trainable stage only BatchNorm betas still need gradients
         stop = 0
         if not self.trainable_bn_beta:
             stop = min(i for i, s in enumerate(self.stages) if any(l.trainable for l in s.layers))
-        self.wgrad_stream = self.side_w if (self.wgrad_side and self.side_w is not None) else None
-        self.wgrad_pending = False
         if self.frozen_step:
             self._backward_frozen(n, stop)
             return

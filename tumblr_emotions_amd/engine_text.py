@@ -16,6 +16,7 @@ MI355X-first choices:
   * the concat of image and text features is never built: the dense layer is two GEMMs
     accumulating into one output.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -235,6 +236,15 @@ class JointHeadEngine:
         store.declare("b_softmax", (nb_emotions,), True, bucket=1)
         self.B = None
         self.reducer = None          # dp.GradientReducer, set by SentimentNet
+        # The chain between the towers' forward and backward passes, grouped (ops.GemmGroup): W_fc's two halves as one launch
+        # pair, the gradients of both features as one GEMM through W_fc with two outputs, and everything only the optimiser
+        # reads -- the four parameter gradients here, the L2 term (side_job) -- off the chain, on the image engine's
+        # weight-gradient stream (`image`, set by SentimentNet).  Bit-identical (tests).  DS_HEAD_GROUP=0: A/B
+        self.group = _lib.tuning_env("DS_HEAD_GROUP", "1") != "0"
+        self.image = None            # InceptionV1Engine whose side_w carries the parameter gradients (None: the current stream)
+        self.async_grads = False     # set by SentimentNet for its own steps, which join side_w before the optimiser
+        self.side_job = None         # callable run once behind the parameter gradients of the next backward() (SentimentNet)
+        self.fwd_group = None
 
     def alloc(self, B):
         if self.B == B:
@@ -255,7 +265,7 @@ class JointHeadEngine:
         self.b_fc, self.gb_fc = _vp(st.ptr("b_fc")), st.grad_view("b_fc")
         self.w_sm, self.gw_sm = _vp(st.ptr("W_softmax")), _vp(st.grad_ptr("W_softmax"))
         self.b_sm, self.gb_sm = _vp(st.ptr("b_softmax")), st.grad_view("b_softmax")
-        self.fc_im = None      # built on first forward (input strides are the callers')
+        self.fc_im = self.fwd_group = None      # built on first forward (input strides are the callers')
         self.ws_bytes = 0
         self.colsum_scratch = torch.empty(64 * max(fc, nc), device=dev)
 
@@ -273,22 +283,60 @@ class JointHeadEngine:
         self.ws_bytes = max(p.ws_bytes for p in (self.sm_wgrad, self.im_wgrad, self.tx_wgrad))
         self.ws = torch.empty(max(self.ws_bytes // 4, 4), device=self.device)
         self._lds = (ld_im, ld_tx)
+        # the grouped chain (self.group): needs the split-K form of the four GEMMs through W_fc (M <= 512 rows)
+        self.fwd_group = self.bwd_group = self.fc_dgrad = None
+        if all(isinstance(p, ops.SplitGemm) for p in (self.fc_im, self.fc_tx, self.im_dgrad, self.tx_dgrad)):
+            # dense = relu(tx W_tx + b + im W_im), summed in the order fc_im then fc_tx (ACCUM | BIAS | RELU) leave it
+            self.fwd_group = ops.GemmGroup([self.fc_im, self.fc_tx], [ops.slab_combine(
+                self.fc_tx, self.dense.data_ptr(), fc, flags=DS_EPI_ACCUM | DS_EPI_BIAS | DS_EPI_RELU, bias=self.b_fc.value,
+                pre=self.fc_im)])
+            # W_fc's image and text rows are contiguous: ddense W_fc^T is ONE GEMM, columns [0, im) d_im, [im, im + tx) d_tx
+            self.fc_dgrad = head_gemm_plan(B, fc, im + tx, fc, im + tx, fc, transposed_w=True, device=self.device)
+            self.bwd_group = ops.GemmGroup([self.fc_dgrad], [ops.slab_combine(
+                self.fc_dgrad, self.d_im.data_ptr(), im, out2=self.d_tx.data_ptr(), ldo2=tx, n_split=im)])
 
-    def forward(self, im_feat, tx_feat):
+    def grouped(self):
+        """Does the next forward / backward run the grouped chain?"""
+        return bool(self.group) and self.fwd_group is not None
+
+    def forward(self, im_feat, tx_feat, ce=None):
+        """ce: (labels, loss, dlogits) -- the cross entropy of the logits and its gradient (softmax_ce with grad_scale 1) from
+        the W_softmax combine's own launch (SentimentNet._step_kernels; the grouped chain only: see ce_fused)."""
         B = im_feat.shape[0]
         self.alloc(B)
         lds = (im_feat.stride(0), tx_feat.stride(0))
         if self.fc_im is None or self._lds != lds:
             self._plans(*lds)
         self.im_feat, self.tx_feat = im_feat, tx_feat
-        self.fc_im.run(ops._p(im_feat), self.w_im, ops._p(self.dense))
-        self.fc_tx.run(ops._p(tx_feat), self.w_tx, ops._p(self.dense), bias=self.b_fc)
-        self.sm.run(ops._p(self.dense), self.w_sm, ops._p(self.logits), bias=self.b_sm)
+        if self.grouped():
+            self.fwd_group.run((ops._p(im_feat), ops._p(tx_feat)), (self.w_im, self.w_tx))
+        else:
+            self.fc_im.run(ops._p(im_feat), self.w_im, ops._p(self.dense))
+            self.fc_tx.run(ops._p(tx_feat), self.w_tx, ops._p(self.dense), bias=self.b_fc)
+        if ce is not None:
+            if not self.ce_fused():
+                raise ValueError("JointHeadEngine.forward(ce=...) needs the grouped chain (ce_fused())")
+            ops.split_gemm_ce(self.sm, ops._p(self.dense), self.w_sm, self.logits, self.b_sm, *ce)
+        else:
+            self.sm.run(ops._p(self.dense), self.w_sm, ops._p(self.logits), bias=self.b_sm)
         return self.logits
+
+    def ce_fused(self):
+        """Can forward(ce=...) form the cross entropy in the W_softmax combine (ds_slab_epilogue_ce: one workgroup)?"""
+        return self.grouped() and isinstance(self.sm, ops.SplitGemm) and self.B <= 512 and self.nc <= 32
+
+    def _grad_stream(self):
+        im = self.image
+        if not self.async_grads or im is None or not im.wgrad_side or im.side_w is None:
+            return None
+        return im.side_w
 
     def backward(self, dlogits):
         B, fc, nc = self.B, self.fc, self.nc
         dl, ws = ops._p(dlogits), ops._p(self.ws)
+        job, self.side_job = self.side_job, None
+        if self.grouped():
+            return self._backward_grouped(dlogits, job)
         self.sm_wgrad.run(ops._p(self.dense), dl, self.gw_sm, ws, self.ws_bytes)
         ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_sm)
         self.sm_dgrad.run(dl, self.w_sm, ops._p(self.ddense), mask=ops._p(self.dense))      # ReluGrad fused
@@ -298,8 +346,42 @@ class JointHeadEngine:
         ops.colsum(self.ddense, B, fc, fc, self.colsum_scratch, self.gb_fc)
         self.im_dgrad.run(dd, self.w_im, ops._p(self.d_im))
         self.tx_dgrad.run(dd, self.w_tx, ops._p(self.d_tx))
+        if job is not None:
+            job()
         if self.reducer is not None:
             self.reducer.stage_done("head")
+        return self.d_im, self.d_tx
+
+    def _backward_grouped(self, dlogits, job):
+        """The same gradients, bit for bit.  On the chain: sm_dgrad -> one GEMM through W_fc -> (d_im, d_tx).  The weight and
+        bias gradients (and `job`) are leaves -- only the optimiser and the all-reduce read them -- and go to the image
+        engine's weight-gradient stream, which InceptionV1Engine.backward joins before either; without one they follow the
+        chain on this stream."""
+        B, fc, nc = self.B, self.fc, self.nc
+        dl, ws = ops._p(dlogits), ops._p(self.ws)
+        self.sm_dgrad.run(dl, self.w_sm, ops._p(self.ddense), mask=ops._p(self.dense))      # ReluGrad fused
+        dd = ops._p(self.ddense)
+        side = self._grad_stream()
+        if side is not None:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())          # dlogits and ddense are complete here
+        self.bwd_group.run((dd,), (self.w_im,))
+        if side is not None:
+            side.wait_event(ev)
+            if not torch.cuda.is_current_stream_capturing():
+                dlogits.record_stream(side)      # (an autograd temporary must outlive its readers on the other stream)
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            self.sm_wgrad.run(ops._p(self.dense), dl, self.gw_sm, ws, self.ws_bytes)
+            ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_sm)
+            self.im_wgrad.run(ops._p(self.im_feat), dd, self.gw_im, ws, self.ws_bytes)
+            self.tx_wgrad.run(ops._p(self.tx_feat), dd, self.gw_tx, ws, self.ws_bytes)
+            ops.colsum(self.ddense, B, fc, fc, self.colsum_scratch, self.gb_fc)
+            if job is not None:
+                job()
+            if self.reducer is not None:
+                self.reducer.stage_done("head")
+        if side is not None:
+            self.image.head_grads_pending = True      # InceptionV1Engine.backward joins side_w before the optimiser
         return self.d_im, self.d_tx
 
     def input_backward(self, dlogits, with_text=False):

@@ -60,6 +60,7 @@ class SentimentNet:
                                         trainable_embedding=trainable_embedding)
         if mode == "joint":
             self.head = JointHeadEngine(self.store, im_features_size, rnn_size, fc_size, nb_emotions, device)
+            self.head.image = self.image      # (its parameter gradients ride on the image engine's weight-gradient stream)
         elif mode == "text":
             self.head = TextHeadEngine(self.store, rnn_size, nb_emotions, device)
         self.store.finalize()
@@ -490,19 +491,53 @@ class SentimentNet:
         if self.frozen_bn:     # the statistics mode of this forward and backward: moving statistics, read-only
             self.image.frozen_step = True
         try:
+            self._async_head_grads(True)
             logits = self.forward(batch, dropout_mask, seed)
             ce = self.cross_entropy(logits, batch["labels"])
-            if st.n_l2 > 0:      # trainable part of the L2 loss, on the pre-update weights
-                ops.sumsq(st.theta, st.n_l2, self.l2_scratch, self.l2_buf)
+            self._enqueue_l2_term()      # trainable part of the L2 loss, on the pre-update weights
             self.reducer.begin_step()
             ce.backward()          # engines call reducer.stage_done(...): bucket 1 is all-reduced under the backward
+            self._join_head_grads()
         finally:
+            self._async_head_grads(False)
             if self.frozen_bn:
                 self.image.frozen_step = False
         grad_scale = self.reducer.finish()
         ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
                     ADAM_B1, ADAM_B2, ADAM_EPS)
         return ce
+
+    def _l2_term(self):
+        st = self.store
+        ops.sumsq(st.theta, st.n_l2, self.l2_scratch, self.l2_buf)
+
+    def _enqueue_l2_term(self):
+        """sum(w^2) over the trainable weights under the L2 regulariser, before the update.  Only total_loss_value() reads it:
+        with the grouped head chain it is handed to the engine whose backward() runs first, which runs it behind its parameter
+        gradients on the weight-gradient stream (joined before the optimiser); otherwise here, on the current stream."""
+        if self.store.n_l2 <= 0:
+            return
+        if self.mode == "joint" and self.head.grouped():
+            self.head.side_job = self._l2_term
+        elif self.mode == "image" and self.image.head_group:
+            self.image.side_job = self._l2_term
+        else:
+            self._l2_term()
+
+    def _async_head_grads(self, on):
+        """A step of this class resets every leaf's .grad first (AccumulateGrad then adopts the engines' gradient views and
+        launches nothing) and joins the weight-gradient stream before the optimiser: only there may the joint head leave its
+        parameter gradients on that stream.  Any other autograd use of the head keeps them on the stream of its backward()."""
+        if self.mode == "joint":
+            self.head.async_grads = bool(on)
+
+    def _join_head_grads(self):
+        """The joint head's parameter gradients on the image engine's weight-gradient stream are joined by the image tower's
+        backward pass, which follows the head's in every step; should none have followed, join here."""
+        im = self.image
+        if im is not None and im.head_grads_pending:
+            torch.cuda.current_stream().wait_stream(im.side_w)
+            im.head_grads_pending = False
 
     # ---- one training step of several clones ---------------------------------------------------------
     def check_clones(self, num_clones, batch_rows=None, seed=None):
@@ -603,8 +638,8 @@ class SentimentNet:
     def _step_kernels(self, batch, dropout_mask):
         """Everything train_step enqueues between the batch and Adam -- forward, CE, L2 term, backward -- with the
         engines driven directly (the autograd nodes of functions.py are thin wrappers around exactly these calls,
-        in this order, on these streams)."""
-        st = self.store
+        in this order, on these streams; with the grouped head chain the cross entropy and its gradient come out of the
+        W_softmax combine's launch instead of two ds_softmax_ce calls)."""
         main = torch.cuda.current_stream()
         side = self.text_stream if (self.image is not None and self.text is not None) else None
         im = tx = None
@@ -621,25 +656,36 @@ class SentimentNet:
                 main.wait_stream(side)
             else:
                 tx = self.text.forward(batch["texts"], batch["seq_lens"])
+        if self.dlogits is None or self.dlogits.shape[0] != batch["labels"].shape[0]:
+            raise RuntimeError("capture_step: run one eager train_step with this batch size first")
+        ce_done = False
         if self.mode == "image":
             logits = im
         elif self.mode == "text":
             logits = self.head.forward(tx)
+        elif self.head.grouped() and self.head.ce_fused():
+            # the cross entropy and its gradient from the launch that combines the W_softmax GEMM (the same bits)
+            logits = self.head.forward(im, tx, ce=(batch["labels"], self.loss_buf, self.dlogits))
+            ce_done = True
         else:
             logits = self.head.forward(im, tx)
         self.logits = logits
-        if self.dlogits is None or self.dlogits.shape != logits.shape:
+        if self.dlogits.shape != logits.shape:
             raise RuntimeError("capture_step: run one eager train_step with this batch size first")
         B, C_ = logits.shape
-        ops.softmax_ce(logits, batch["labels"], B, C_, 1.0, None, self.loss_buf, self.dlogits)
-        if st.n_l2 > 0:
-            ops.sumsq(st.theta, st.n_l2, self.l2_scratch, self.l2_buf)
+        if not ce_done:
+            ops.softmax_ce(logits, batch["labels"], B, C_, 1.0, None, self.loss_buf, self.dlogits)
+        self._enqueue_l2_term()
         if self.mode == "image":
             self.image.backward(self.dlogits)
         elif self.mode == "text":
             self.text.backward(self.head.backward(self.dlogits))
         else:
-            d_im, d_tx = self.head.backward(self.dlogits)
+            self._async_head_grads(True)      # (image.backward below joins the weight-gradient stream)
+            try:
+                d_im, d_tx = self.head.backward(self.dlogits)
+            finally:
+                self._async_head_grads(False)
             if side is not None:              # BPTT next to the Inception backward, as in the eager step
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
@@ -649,6 +695,7 @@ class SentimentNet:
             else:
                 self.text.backward(d_tx)
                 self.image.backward(d_im)
+        self._join_head_grads()
 
     def capture_step(self, batch, dropout_mask=None, num_clones=1):
         """Capture one whole training step on `batch`'s tensors (static addresses: refill them in place between

@@ -195,6 +195,69 @@ class SplitGemm:
             t.end(self)
 
 
+def slab_combine(gemm, out, ldo, flags=0, bias=None, mask=None, ldmask=0, pre=None, out2=None, ldo2=0, n_split=0):
+    """ds_slab_combine of a SplitGemm's slabs into `out` (addresses; ds_slab_epilogue's arguments).  pre: a second SplitGemm
+    whose combined slabs are the DS_EPI_ACCUM operand; out2 / ldo2 / n_split: columns [n_split, N) go to a second tensor."""
+    c = _lib.SlabCombine()
+    c.slabs, c.splits, c.slab_stride, c.lds = gemm.slabs.data_ptr(), gemm.splits, gemm.M * gemm.N, gemm.N
+    if pre is not None:
+        assert (pre.M, pre.N) == (gemm.M, gemm.N)
+        c.pre_slabs, c.pre_splits, c.pre_slab_stride, c.pre_lds = pre.slabs.data_ptr(), pre.splits, pre.M * pre.N, pre.N
+    c.M, c.N, c.flags = gemm.M, gemm.N, flags
+    c.out, c.ldo, c.out2, c.ldo2, c.n_split = out, ldo, out2, ldo2, n_split
+    c.bias, c.mask, c.ldmask = bias, mask, ldmask
+    return c
+
+
+def _addr(p):
+    return p.value if isinstance(p, C.c_void_p) else p
+
+
+class GemmGroup:
+    """SplitGemms that do not depend on each other (at most four) as ONE ds_gemm_group launch into their own slabs and ONE
+    ds_slab_epilogue_group launch of `combines` (slab_combine): the bits of the SplitGemm.run calls they replace, two launches
+    on the chain instead of two per GEMM."""
+
+    def __init__(self, gemms, combines):
+        n = len(gemms)
+        self.gemms, self.n = gemms, n
+        self._descs = (_lib._CD * n)(*[C.pointer(g.plan.d) for g in gemms])
+        self._z = (C.c_void_p * n)(*[g.slabs.data_ptr() for g in gemms])
+        self._combines = (_lib.SlabCombine * len(combines))(*combines)
+        self.alg_flops = sum(g.alg_flops for g in gemms)
+
+    def run(self, xs, ws):
+        t = CONV_TIMER
+        if t is not None:
+            t.begin()
+        lib = _lib.load()
+        n = self.n
+        if n == 1:      # (one problem: its own launch)
+            _lib.check(lib.ds_conv_igemm(C.byref(self.gemms[0].plan.d), xs[0], ws[0], _p(self.gemms[0].slabs), None, None, None,
+                                         None, _stream()), "ds_conv_igemm")
+        else:
+            x = (C.c_void_p * n)(*[_addr(p) for p in xs])
+            w = (C.c_void_p * n)(*[_addr(p) for p in ws])
+            _lib.check(lib.ds_gemm_group(self._descs, x, w, self._z, n, _stream()), "ds_gemm_group")
+        _lib.check(lib.ds_slab_epilogue_group(self._combines, len(self._combines), _stream()), "ds_slab_epilogue_group")
+        if t is not None:
+            t.end(self)
+
+
+def split_gemm_ce(gemm, x, w, logits, bias, labels, loss, dlogits):
+    """SplitGemm.run of the W_softmax GEMM with DS_EPI_BIAS and softmax_ce(logits, labels, .., 1.0, None, loss, dlogits) behind
+    it, the combine and the cross entropy as ONE single-workgroup launch (ds_slab_epilogue_ce): the same bits."""
+    t = CONV_TIMER
+    if t is not None:
+        t.begin()
+    lib = _lib.load()
+    _lib.check(lib.ds_conv_igemm(C.byref(gemm.plan.d), x, w, _p(gemm.slabs), None, None, None, None, _stream()), "ds_conv_igemm")
+    if t is not None:
+        t.end(gemm)
+    _lib.check(lib.ds_slab_epilogue_ce(_p(gemm.slabs), gemm.splits, gemm.M * gemm.N, gemm.N, gemm.M, gemm.N, _p(logits), bias,
+                                       _p(labels), 1.0, None, _p(loss), _p(dlogits), _stream()), "ds_slab_epilogue_ce")
+
+
 class WinoPlan:
     """3x3 stride-1 SAME conv through ds_conv_wino (fused Winograd F(2x2,3x3)) or, with f4, ds_conv_wino4
     (F(4x4,3x3): H, W multiples of four); `u` is the transformed filter (`u_elems` floats)."""
