@@ -1,6 +1,6 @@
 """The grouped head chain (JointHeadEngine.group / InceptionV1Engine.head_group, default on): W_fc's two halves as one
 ds_gemm_group + ds_slab_epilogue_group launch pair, both feature gradients as one GEMM through W_fc with two outputs, the cross
-entropy in the W_softmax combine (ds_slab_epilogue_ce, captured step), the parameter gradients off the chain.  Every result
+entropy in the W_softmax combine (ds_slab_epilogue_ce, eager and captured step), the parameter gradients off the chain.  Every result
 keeps the bits of the separate launches; each is also held against an fp64 NumPy evaluation of its own inputs at the kernel
 tests' bound, 2e-4 * max|ref|."""
 import ctypes as C
@@ -234,8 +234,10 @@ def _same(a, b):
 def test_joint_step_is_bit_identical(monkeypatch):
     """Two joint training steps at batch 8 with the model's own head dims, switch on and off: logits, loss, every gradient, the
     updated parameters and the BatchNorm moving statistics are BIT-identical -- and the launches really differ."""
-    on_calls, _, on = _run_steps("joint", True, monkeypatch)
-    off_calls, _, off = _run_steps("joint", False, monkeypatch)
+    on_calls, on_every, on = _run_steps("joint", True, monkeypatch)
+    off_calls, off_every, off = _run_steps("joint", False, monkeypatch)
+    # the step-level anchor of the fused cross entropy: on forms it in the W_softmax combine, off with ds_softmax_ce
+    assert "ds_slab_epilogue_ce" in on_every and "ds_softmax_ce" in off_every and "ds_slab_epilogue_ce" not in off_every
     assert on_calls.count("ds_gemm_group") == 1 and on_calls.count("ds_slab_epilogue_group") == 2
     assert "ds_gemm_group" not in off_calls and "ds_slab_epilogue_group" not in off_calls
     # the Logits layer: input gradient and the pool's gradient first, then the leaves
@@ -257,10 +259,10 @@ def test_image_step_is_bit_identical(monkeypatch):
 
 
 def test_captured_step_equals_the_eager_step(monkeypatch):
-    """Switch on: a captured joint step (the cross entropy formed in the W_softmax combine, one side stream in the capture)
-    replayed twice leaves the bits of two eager steps."""
+    """Switch on: a captured joint step (one side stream in the capture) replayed twice leaves the bits of two eager steps; both
+    form the cross entropy in the W_softmax combine (against ds_softmax_ce: test_joint_step_is_bit_identical)."""
     _, eager_all, eager = _run_steps("joint", True, monkeypatch)
     cap_calls, cap_all, cap = _run_steps("joint", True, monkeypatch, captured=True)
-    assert "ds_slab_epilogue_ce" not in eager_all and "ds_slab_epilogue_ce" in cap_all and "ds_gemm_group" in cap_all
+    assert "ds_slab_epilogue_ce" in eager_all and "ds_slab_epilogue_ce" in cap_all and "ds_gemm_group" in cap_all
     assert cap_calls == []      # (a replay launches the graph, nothing else)
     _same(eager, cap)

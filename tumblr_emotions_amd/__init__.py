@@ -1,7 +1,7 @@
 """tumblr_emotions_amd -- the Deep Sentiment training path of anthonyhu/tumblr-emotions,
 rebuilt MI355X-first: hand-written gfx950 HIP kernels behind a C ABI (include/ds_kernels.h,
 libds_kernels.so), orchestrated from Python with PyTorch-ROCm providing device memory, streams,
-autograd plumbing and torch.distributed (RCCL).
+graph capture and torch.distributed (RCCL); gradients come from the engines' own backward passes, not from torch.autograd.
 
 Front ends keep the reference's module paths and call signatures:
     tumblr_emotions_amd.image_model.im_model.train_image_model(checkpoints_dir, train_dir, num_steps)

@@ -1351,11 +1351,9 @@ class InceptionV1Engine:
         self.wgrad_side = True       # Mixed_5c's weight gradients on their own stream, off the dgrad chain
         self.side_w = None
         self.wgrad_stream = None
-        # the Logits layer's weight and bias gradient (and side_job: the L2 term) on that stream too, its input gradient first
-        # on the chain (JointHeadEngine.group is the joint head's half of this).  Bit-identical (tests).  DS_HEAD_GROUP=0: A/B
+        # the Logits layer's weight and bias gradient (and backward's side_job: the L2 term) on that stream too, its input gradient
+        # first on the chain (JointHeadEngine.group is the joint head's half of this).  Bit-identical (tests).  DS_HEAD_GROUP=0: A/B
         self.head_group = _lib.tuning_env("DS_HEAD_GROUP", "1") != "0"
-        self.head_grads_pending = False      # JointHeadEngine left its parameter gradients on side_w: backward() joins it
-        self.side_job = None                 # callable run once behind the Logits gradients of the next backward() (SentimentNet)
         self.bwd_sums = True         # BatchNorm backward sums from the producing dgrad's epilogue (DS_EPI_BNSUMS) where it can
         self.stem_direct = True      # Conv2d_1a_7x7 from the packed RGB batch (ds_conv_stem; False: generic kernel on a 4-channel copy)
         self.stem_pool = _lib.tuning_env("DS_STEM_POOL", "1") != "0"      # ... with MaxPool_2a inside that kernel (ds_conv_stem_pool; ConvStage.alloc)
@@ -1420,7 +1418,6 @@ class InceptionV1Engine:
         # forward(fused=True): the inference forward with BatchNorm + ReLU in the conv epilogues (fp32).  _fused_key: the weight
         # version the prepared (rstd, shift) vectors belong to; None after a load, a training step, a plain forward or alloc
         self.fused_infer = False
-        self.fused_request = False
         self._fused_key = None
         self._fused_targets = {}
         self._fused_jobs = None
@@ -1696,13 +1693,11 @@ class InceptionV1Engine:
         return [(l.key, self._fused_targets[id(l)]) for l in self.layers
                 if isinstance(self._fused_targets.get(id(l)), str)]
 
-    def forward(self, images, dropout_mask=None, seed=0, input_grad=False, fused=None):
+    def forward(self, images, dropout_mask=None, seed=0, input_grad=False, fused=False):
         """images: [B,224,224,3] fp32 NHWC in [-1,1] (preprocess_for_eval range).  Returns the
         internal logits buffer [B,num_classes].  input_grad: the pass input_backward() differentiates (unpooled stem).
         fused: moving-statistics forward with BatchNorm + ReLU inside the conv launches (fp32, not training)."""
         B = images.shape[0]
-        if fused is None:             # (SentimentNet.predict(fused=True) reaches this pass through the autograd function)
-            fused = self.fused_request
         if fused and (self.training or input_grad or self.dtype != "f32" or self.mul3):
             raise ValueError("the fused forward is the fp32 moving-statistics pass (is_training=False)")
         self.fused_infer = bool(fused)
@@ -1757,16 +1752,16 @@ class InceptionV1Engine:
         self.fc.run(ops._p(self.pooled), self.w_fc, ops._p(self.logits), bias=self.b_fc)
         return self.logits
 
-    def backward(self, dlogits):
-        """dlogits [B,num_classes] -> gradients of every trainable image-tower variable in store.grad."""
+    def backward(self, dlogits, side_job=None):
+        """dlogits [B,num_classes] -> gradients of every trainable image-tower variable in store.grad.
+        side_job: a callable run once behind the Logits gradients (SentimentNet: the L2 term)."""
         B, nc, F = self.B, self.num_classes, self.feat
         last = self.last
         dl = ops._p(dlogits)
         self.wgrad_stream = self.side_w if (self.wgrad_side and self.side_w is not None) else None
-        # (the joint head's parameter gradients may already run on the weight-gradient stream: the walk below joins it)
-        self.wgrad_pending = bool(self.head_grads_pending) and self.wgrad_stream is not None
-        self.head_grads_pending = False
-        job, self.side_job = self.side_job, None
+        # (the joint head's parameter gradients may already run on the weight-gradient stream: Mixed_5c's weight gradients follow
+        # them there and set wgrad_pending, so the walk below joins it)
+        self.wgrad_pending = False
         if self.head_group and self.wgrad_stream is not None:
             # the chain first; the two Logits gradients are leaves of the backward graph (only the optimiser and the all-reduce
             # read them): onto the weight-gradient stream, with its workspace
@@ -1775,21 +1770,19 @@ class InceptionV1Engine:
             self.fc_dgrad.run(dl, self.w_fc, ops._p(self.dpooled))
             ops.avgpool_dropout_bwd(self.dpooled, self.mask, B, last.H * last.W, F, self.keep, last.dout)
             self.wgrad_stream.wait_event(ev)
-            if not torch.cuda.is_current_stream_capturing():
-                dlogits.record_stream(self.wgrad_stream)      # (an autograd temporary must outlive its readers there)
             with torch.cuda.stream(self.wgrad_stream):
                 self.fc_wgrad.run(ops._p(self.pooled), dl, self.gw_fc, ops._p(self.ws_set[3]), self.ws_bytes)
                 ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_fc)
-                if job is not None:
-                    job()
+                if side_job is not None:
+                    side_job()
             self.wgrad_pending = True
         else:
             self.fc_wgrad.run(ops._p(self.pooled), dl, self.gw_fc, ops._p(self.ws), self.ws_bytes)
             ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_fc)
             self.fc_dgrad.run(dl, self.w_fc, ops._p(self.dpooled))
             ops.avgpool_dropout_bwd(self.dpooled, self.mask, B, last.H * last.W, F, self.keep, last.dout)
-            if job is not None:
-                job()
+            if side_job is not None:
+                side_job()
         n = len(self.stages)
         # below the last trainable stage only BatchNorm betas still need gradients
         stop = 0

@@ -238,12 +238,10 @@ class JointHeadEngine:
         self.reducer = None          # dp.GradientReducer, set by SentimentNet
         # The chain between the towers' forward and backward passes, grouped (ops.GemmGroup): W_fc's two halves as one launch
         # pair, the gradients of both features as one GEMM through W_fc with two outputs, and everything only the optimiser
-        # reads -- the four parameter gradients here, the L2 term (side_job) -- off the chain, on the image engine's
+        # reads -- the four parameter gradients here, the L2 term (backward's side_job) -- off the chain, on the image engine's
         # weight-gradient stream (`image`, set by SentimentNet).  Bit-identical (tests).  DS_HEAD_GROUP=0: A/B
         self.group = _lib.tuning_env("DS_HEAD_GROUP", "1") != "0"
         self.image = None            # InceptionV1Engine whose side_w carries the parameter gradients (None: the current stream)
-        self.async_grads = False     # set by SentimentNet for its own steps, which join side_w before the optimiser
-        self.side_job = None         # callable run once behind the parameter gradients of the next backward() (SentimentNet)
         self.fwd_group = None
 
     def alloc(self, B):
@@ -301,7 +299,7 @@ class JointHeadEngine:
 
     def forward(self, im_feat, tx_feat, ce=None):
         """ce: (labels, loss, dlogits) -- the cross entropy of the logits and its gradient (softmax_ce with grad_scale 1) from
-        the W_softmax combine's own launch (SentimentNet._step_kernels; the grouped chain only: see ce_fused)."""
+        the W_softmax combine's own launch (SentimentNet._step_body; the grouped chain only: see ce_fused)."""
         B = im_feat.shape[0]
         self.alloc(B)
         lds = (im_feat.stride(0), tx_feat.stride(0))
@@ -327,16 +325,14 @@ class JointHeadEngine:
 
     def _grad_stream(self):
         im = self.image
-        if not self.async_grads or im is None or not im.wgrad_side or im.side_w is None:
-            return None
-        return im.side_w
+        return im.side_w if (im is not None and im.wgrad_side) else None
 
-    def backward(self, dlogits):
+    def backward(self, dlogits, side_job=None):
+        """side_job: a callable run once behind the parameter gradients (SentimentNet: the L2 term)."""
         B, fc, nc = self.B, self.fc, self.nc
         dl, ws = ops._p(dlogits), ops._p(self.ws)
-        job, self.side_job = self.side_job, None
         if self.grouped():
-            return self._backward_grouped(dlogits, job)
+            return self._backward_grouped(dlogits, side_job)
         self.sm_wgrad.run(ops._p(self.dense), dl, self.gw_sm, ws, self.ws_bytes)
         ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_sm)
         self.sm_dgrad.run(dl, self.w_sm, ops._p(self.ddense), mask=ops._p(self.dense))      # ReluGrad fused
@@ -346,8 +342,8 @@ class JointHeadEngine:
         ops.colsum(self.ddense, B, fc, fc, self.colsum_scratch, self.gb_fc)
         self.im_dgrad.run(dd, self.w_im, ops._p(self.d_im))
         self.tx_dgrad.run(dd, self.w_tx, ops._p(self.d_tx))
-        if job is not None:
-            job()
+        if side_job is not None:
+            side_job()
         if self.reducer is not None:
             self.reducer.stage_done("head")
         return self.d_im, self.d_tx
@@ -368,8 +364,6 @@ class JointHeadEngine:
         self.bwd_group.run((dd,), (self.w_im,))
         if side is not None:
             side.wait_event(ev)
-            if not torch.cuda.is_current_stream_capturing():
-                dlogits.record_stream(side)      # (an autograd temporary must outlive its readers on the other stream)
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             self.sm_wgrad.run(ops._p(self.dense), dl, self.gw_sm, ws, self.ws_bytes)
             ops.colsum(dlogits, B, nc, nc, self.colsum_scratch, self.gb_sm)
@@ -380,8 +374,6 @@ class JointHeadEngine:
                 job()
             if self.reducer is not None:
                 self.reducer.stage_done("head")
-        if side is not None:
-            self.image.head_grads_pending = True      # InceptionV1Engine.backward joins side_w before the optimiser
         return self.d_im, self.d_tx
 
     def input_backward(self, dlogits, with_text=False):

@@ -17,8 +17,6 @@ import torch
 from . import ops
 from .engine_image import InceptionV1Engine, WEIGHT_DECAY
 from .engine_text import JointHeadEngine, TextHeadEngine, TextTowerEngine
-from .functions import (InceptionV1Function, JointHeadFunction, SoftmaxCrossEntropyFunction, TextHeadFunction,
-                        TextTowerFunction)
 from .dp import GradientReducer
 from .params import ParamStore
 
@@ -65,11 +63,6 @@ class SentimentNet:
             self.head = TextHeadEngine(self.store, rnn_size, nb_emotions, device)
         self.store.finalize()
         st = self.store
-        self.leaves = {e.name: st.view(e.name).detach().requires_grad_() for e in st.entries.values() if e.trainable}
-        if self.image is not None:
-            self.image_param_names = [n for n in self.leaves if n.startswith("InceptionV1/")]
-            self.image.param_names = self.image_param_names
-            self.image_params = [self.leaves[n] for n in self.image_param_names]
         self.step = 0
         self.frozen_l2_sumsq = 0.0
         self.loss_buf = torch.zeros(1, device=self.device)
@@ -78,6 +71,10 @@ class SentimentNet:
         self.lr_t_dev = torch.zeros(1, device=self.device)
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.dlogits = None
+        # a step of several clones (train_step(num_clones=K > 1)): allocated by the first one
+        self._clone_count = 1
+        self.grad_acc = self.clone_loss = self.clone_logits = None
+        self._predict_calls = 0
         self.pg = process_group
         from . import streams
         streams.reserve(self.device)
@@ -195,42 +192,39 @@ class SentimentNet:
             self.release_graph()
 
     # ---- forward / loss ---------------------------------------------------------------------------
-    def forward(self, batch, dropout_mask=None, seed=0):
-        """batch: dict with device tensors images [B,224,224,3] f32, texts [B,T] i64, seq_lens [B] i64."""
-        L = self.leaves
-        tx = im = None
-        # image tower first: autograd runs later-created nodes first, so the (short) text backward runs
-        # before the Inception backward and bucket 1 of the gradient is complete right after Mixed_5c
-        inputs_ready = None
-        if self.image is not None and self.text is not None and self.text_stream is not None:
+    def _towers(self, batch, dropout_mask, seed, fused=False):
+        """(im, tx): the image tower enqueued on the current stream and the text tower -- in the joint model ~130
+        launch-latency-bound kernels (LSTM steps) -- beside it on its own HIP stream, forked and joined with events."""
+        im = tx = None
+        side = self.text_stream if (self.image is not None and self.text is not None) else None
+        if side is not None:
+            main = torch.cuda.current_stream()
             inputs_ready = torch.cuda.Event()
-            inputs_ready.record(torch.cuda.current_stream())
+            inputs_ready.record(main)
         if self.image is not None:
-            im = InceptionV1Function.apply(self.image, batch["images"], dropout_mask, seed, *self.image_params)
-        if self.text is not None:
-            # The text tower is ~130 launch-latency-bound kernels (LSTM steps): in the joint model it runs
-            # on its own HIP stream, concurrently with the Inception tower; autograd replays the backward
-            # of each node on its forward stream, so the BPTT overlaps the Inception backward too.
-            side = self.text_stream if inputs_ready is not None else None
-            if side is not None:
-                main = torch.cuda.current_stream()
-                side.wait_event(inputs_ready)          # NOT wait_stream: the image tower is already enqueued on main
-                if self.image.text_gate is not None and self.image.text_gate_event is not None:
-                    side.wait_event(self.image.text_gate_event)      # (A/B: start behind a stage of the image tower)
-                with torch.cuda.stream(side):
-                    tx = TextTowerFunction.apply(self.text, batch["texts"], batch["seq_lens"], L[self.text.KERNEL],
-                                                 L[self.text.BIAS])
-                main.wait_stream(side)
-            else:
-                tx = TextTowerFunction.apply(self.text, batch["texts"], batch["seq_lens"], L[self.text.KERNEL],
-                                             L[self.text.BIAS])
+            im = self.image.forward(batch["images"], dropout_mask, seed, fused=fused)
+        if side is not None:
+            side.wait_event(inputs_ready)          # NOT wait_stream: the image tower is already enqueued on main
+            if self.image.text_gate is not None and self.image.text_gate_event is not None:
+                side.wait_event(self.image.text_gate_event)      # (A/B: start behind a stage of the image tower)
+            with torch.cuda.stream(side):
+                tx = self.text.forward(batch["texts"], batch["seq_lens"])
+            main.wait_stream(side)
+        elif self.text is not None:
+            tx = self.text.forward(batch["texts"], batch["seq_lens"])
+        return im, tx
+
+    def forward(self, batch, dropout_mask=None, seed=0, fused=False):
+        """batch: dict with device tensors images [B,224,224,3] f32, texts [B,T] i64, seq_lens [B] i64.  Returns the logits
+        buffer of the engines (nothing here is recorded by autograd: gradients come from train_step, input_gradient and
+        eval_gradients, which drive the engines' backward passes themselves)."""
+        im, tx = self._towers(batch, dropout_mask, seed, fused)
         if self.mode == "image":
             self.logits = im
         elif self.mode == "text":
-            self.logits = TextHeadFunction.apply(self.head, tx, L["W_softmax"], L["b_softmax"])
+            self.logits = self.head.forward(tx)
         else:
-            self.logits = JointHeadFunction.apply(self.head, im, tx, L["W_fc"], L["b_fc"], L["W_softmax"],
-                                                  L["b_softmax"])
+            self.logits = self.head.forward(im, tx)
         return self.logits
 
     def predict(self, batch, is_training=False, seed=None, fused=False):
@@ -247,18 +241,16 @@ class SentimentNet:
             raise NotImplementedError("predict(fused=True) is implemented for the fp32 configuration, not %r" % self.dtype)
         if self.image is not None:
             self.image.training, self.image.update_moving = is_training, False
-            self.image.fused_request = bool(fused)
         # evaluation on mode='train' keeps dropout on: every call draws a fresh mask (a fixed seed would apply
         # the identical mask to every evaluation batch)
-        self._predict_calls = getattr(self, "_predict_calls", 0) + 1
+        self._predict_calls += 1
         seed = (1 << 40) + self._predict_calls if seed is None else seed
         try:
             with torch.no_grad():
-                return self.forward(batch, None, seed=self._rank_seed(seed))
+                return self.forward(batch, None, seed=self._rank_seed(seed), fused=bool(fused))
         finally:
             if self.image is not None:
                 self.image.training, self.image.update_moving = True, True
-                self.image.fused_request = False
 
     def fused_report(self):
         """[(layer key, reason)]: the conv layers that kept conv -> BatchNorm-apply in the last predict(fused=True)."""
@@ -342,7 +334,7 @@ class SentimentNet:
         eng = self.image
         dimg = dwords = scores = None
         if eng is not None:
-            eng.training, eng.update_moving, eng.fused_request = False, False, False
+            eng.training, eng.update_moving = False, False
         try:
             with torch.no_grad():
                 im = tx = None
@@ -424,11 +416,6 @@ class SentimentNet:
         delta = f[B:] - f[:B]
         return im_attr, tok_attr, delta
 
-    def cross_entropy(self, logits, labels):
-        if self.dlogits is None or self.dlogits.shape != logits.shape:
-            self.dlogits = torch.empty(logits.shape, device=self.device)
-        return SoftmaxCrossEntropyFunction.apply(logits, labels, self.loss_buf, self.dlogits)
-
     def total_loss_value(self):
         """Host value of slim.losses.get_total_loss(): CE + sum_conv wd*||W||^2/2 (syncs).  Since this read
         synchronises anyway it also checks the persistent LSTM's error words (ds_lstm_seq_status) and raises if a
@@ -436,7 +423,7 @@ class SentimentNet:
         reg = 0.0
         if self.store.n_l2 > 0 or self.frozen_l2_sumsq:
             reg = 0.5 * WEIGHT_DECAY * (self.frozen_l2_sumsq + float(self.l2_buf.item()))
-        if getattr(self, "_clone_count", 1) > 1:      # slim's total loss of this rank's clones: the mean of their cross-entropies
+        if self._clone_count > 1:      # slim's total loss of this rank's clones: the mean of their cross-entropies
             ce = 0.0
             for x in self.clone_loss.cpu().tolist():      # summed in clone order, in double
                 ce += x
@@ -470,11 +457,7 @@ class SentimentNet:
             return self._train_step_clones(batch, lr, dropout_mask, seed, num_clones, after_clone)
         self._clone_count = 1
         st = self.store
-        self.step += 1
-        t = self.step
-        if self.image is not None:
-            self.image.invalidate_fused()      # beta and the moving statistics move: predict(fused=True) prepares them again
-        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
+        lr_t = self._begin_step(lr)
         # dropout stream: one seed per (step, rank) -- ranks must not share a mask pattern across their shards
         seed = self._rank_seed(self.step) if seed is None else seed
         if self._graph is not None:
@@ -486,58 +469,79 @@ class SentimentNet:
                 return self.loss_buf.view(())
             if self._graph_key[-2:] != self._batch_key(batch, dropout_mask)[-2:]:
                 self.release_graph()     # buffers re-allocated or weights reloaded since the capture: the graph is stale
-        for p in self.leaves.values():
-            p.grad = None
-        if self.frozen_bn:     # the statistics mode of this forward and backward: moving statistics, read-only
-            self.image.frozen_step = True
-        try:
-            self._async_head_grads(True)
-            logits = self.forward(batch, dropout_mask, seed)
-            ce = self.cross_entropy(logits, batch["labels"])
-            self._enqueue_l2_term()      # trainable part of the L2 loss, on the pre-update weights
-            self.reducer.begin_step()
-            ce.backward()          # engines call reducer.stage_done(...): bucket 1 is all-reduced under the backward
-            self._join_head_grads()
-        finally:
-            self._async_head_grads(False)
-            if self.frozen_bn:
-                self.image.frozen_step = False
+        self.reducer.begin_step()      # engines call reducer.stage_done(...): bucket 1 is all-reduced under the backward
+        self._step_body(batch, dropout_mask, seed, self.loss_buf)
         grad_scale = self.reducer.finish()
         ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
                     ADAM_B1, ADAM_B2, ADAM_EPS)
-        return ce
+        return self.loss_buf.view(())
+
+    def _begin_step(self, lr):
+        """Count the step and return its Adam step size lr_t."""
+        self.step += 1
+        if self.image is not None:
+            self.image.invalidate_fused()      # beta and the moving statistics move: predict(fused=True) prepares them again
+        return lr * math.sqrt(1.0 - ADAM_B2 ** self.step) / (1.0 - ADAM_B1 ** self.step)
 
     def _l2_term(self):
+        """sum(w^2) over the trainable weights under the L2 regulariser, before the update.  Only total_loss_value() reads it."""
         st = self.store
         ops.sumsq(st.theta, st.n_l2, self.l2_scratch, self.l2_buf)
 
-    def _enqueue_l2_term(self):
-        """sum(w^2) over the trainable weights under the L2 regulariser, before the update.  Only total_loss_value() reads it:
-        with the grouped head chain it is handed to the engine whose backward() runs first, which runs it behind its parameter
-        gradients on the weight-gradient stream (joined before the optimiser); otherwise here, on the current stream."""
-        if self.store.n_l2 <= 0:
-            return
-        if self.mode == "joint" and self.head.grouped():
-            self.head.side_job = self._l2_term
-        elif self.mode == "image" and self.image.head_group:
-            self.image.side_job = self._l2_term
-        else:
-            self._l2_term()
-
-    def _async_head_grads(self, on):
-        """A step of this class resets every leaf's .grad first (AccumulateGrad then adopts the engines' gradient views and
-        launches nothing) and joins the weight-gradient stream before the optimiser: only there may the joint head leave its
-        parameter gradients on that stream.  Any other autograd use of the head keeps them on the stream of its backward()."""
-        if self.mode == "joint":
-            self.head.async_grads = bool(on)
-
-    def _join_head_grads(self):
-        """The joint head's parameter gradients on the image engine's weight-gradient stream are joined by the image tower's
-        backward pass, which follows the head's in every step; should none have followed, join here."""
-        im = self.image
-        if im is not None and im.head_grads_pending:
-            torch.cuda.current_stream().wait_stream(im.side_w)
-            im.head_grads_pending = False
+    def _step_body(self, batch, dropout_mask, seed, loss_out, l2=True):
+        """Everything a step enqueues between the batch and the optimiser -- the towers, the head, the cross entropy (into
+        loss_out) with its gradient, the L2 term (l2=False: not this time), the backward passes -- with the engines driven
+        directly.  The eager step, every clone of a step of several and the captured step are this one sequence."""
+        labels = batch["labels"]
+        B, C_ = labels.shape[0], self.nb_emotions
+        if self.dlogits is None or self.dlogits.shape[0] != B:
+            self.dlogits = torch.empty(B, C_, device=self.device)
+        if self.frozen_bn:     # the statistics mode of this forward and backward: moving statistics, read-only
+            self.image.frozen_step = True
+        try:
+            im, tx = self._towers(batch, dropout_mask, seed)
+            ce_done = False
+            if self.mode == "image":
+                logits = im
+            elif self.mode == "text":
+                logits = self.head.forward(tx)
+            else:
+                # ce_done: the cross entropy and its gradient from the launch that combines the W_softmax GEMM (the same bits);
+                # the head is asked about the plans of THIS batch size (none yet: forward builds them, one ds_softmax_ce below)
+                self.head.alloc(B)
+                ce_done = self.head.grouped() and self.head.ce_fused()
+                logits = self.head.forward(im, tx, ce=(labels, loss_out, self.dlogits) if ce_done else None)
+            self.logits = logits
+            if not ce_done:
+                ops.softmax_ce(logits, labels, B, C_, 1.0, None, loss_out, self.dlogits)
+            # The L2 term, on the pre-update weights: with the grouped head chain the engine whose backward() runs first runs it
+            # behind its parameter gradients on the weight-gradient stream (joined before the optimiser); otherwise here
+            job = self._l2_term if (l2 and self.store.n_l2 > 0) else None
+            grouped = self.head.grouped() if self.mode == "joint" else (self.mode == "image" and self.image.head_group)
+            if job is not None and not grouped:
+                job()
+                job = None
+            if self.mode == "image":
+                self.image.backward(self.dlogits, side_job=job)
+            elif self.mode == "text":
+                self.text.backward(self.head.backward(self.dlogits))
+            else:
+                # (the head may leave its parameter gradients on the image engine's weight-gradient stream: image.backward joins it)
+                d_im, d_tx = self.head.backward(self.dlogits, side_job=job)
+                side = self.text_stream
+                if side is not None:              # BPTT next to the Inception backward; the (short) text backward first, so that
+                    main = torch.cuda.current_stream()      # bucket 1 of the gradient is complete right after Mixed_5c
+                    side.wait_stream(main)
+                    with torch.cuda.stream(side):
+                        self.text.backward(d_tx)
+                    self.image.backward(d_im)
+                    main.wait_stream(side)
+                else:
+                    self.text.backward(d_tx)
+                    self.image.backward(d_im)
+        finally:
+            if self.frozen_bn:
+                self.image.frozen_step = False
 
     # ---- one training step of several clones ---------------------------------------------------------
     def check_clones(self, num_clones, batch_rows=None, seed=None):
@@ -578,19 +582,13 @@ class SentimentNet:
         st = self.store
         b = B // K
         nc = self.nb_emotions
-        if getattr(self, "grad_acc", None) is None:
+        if self.grad_acc is None:
             self.grad_acc = torch.zeros_like(st.grad)
-        if getattr(self, "clone_loss", None) is None or self.clone_loss.shape[0] != K:
+        if self.clone_loss is None or self.clone_loss.shape[0] != K:
             self.clone_loss = torch.zeros(K, device=self.device)
-        if getattr(self, "clone_logits", None) is None or tuple(self.clone_logits.shape) != (B, nc):
+        if self.clone_logits is None or tuple(self.clone_logits.shape) != (B, nc):
             self.clone_logits = torch.empty(B, nc, device=self.device)
-        self.step += 1
-        t = self.step
-        if self.image is not None:
-            self.image.invalidate_fused()
-        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
-        if self.frozen_bn:
-            self.image.frozen_step = True
+        lr_t = self._begin_step(lr)
         try:
             self.reducer.begin_step(defer=True)      # store.grad is complete only after the last accumulation
             for c in range(K):
@@ -599,26 +597,16 @@ class SentimentNet:
                 mask = None if dropout_mask is None else self._clone_rows(dropout_mask, lo, hi)
                 # the dropout stream of virtual rank rank * K + c: the numbering of a (K * world)-rank run
                 clone_seed = int(self.step) * 4096 + self.reducer.rank * K + c
-                for p in self.leaves.values():
-                    p.grad = None
                 if self.image is not None:
                     self.image.update_moving = c == 0      # the moving averages are clone 0's (model_deploy.py:353-355)
-                logits = self.forward(sub, mask, clone_seed)
-                if self.dlogits is None or self.dlogits.shape != logits.shape:
-                    self.dlogits = torch.empty(logits.shape, device=self.device)
-                ce = SoftmaxCrossEntropyFunction.apply(logits, sub["labels"], self.clone_loss[c:c + 1], self.dlogits)
-                if c == 0 and st.n_l2 > 0:      # trainable part of the L2 loss, once, on the pre-update weights
-                    ops.sumsq(st.theta, st.n_l2, self.l2_scratch, self.l2_buf)
-                ce.backward()
-                self.clone_logits[lo:hi].copy_(logits.detach())
+                self._step_body(sub, mask, clone_seed, self.clone_loss[c:c + 1], l2=c == 0)      # (the L2 term once)
+                self.clone_logits[lo:hi].copy_(self.logits)
                 ops.grad_accumulate(self.grad_acc, st.grad, st.n_trainable_padded, 0 if c == 0 else (2 if c == K - 1 else 1))
                 if after_clone is not None:
                     after_clone(c)
         finally:
             if self.image is not None:
                 self.image.update_moving = True
-            if self.frozen_bn:
-                self.image.frozen_step = False
         self.reducer.finish()
         self.logits = self.clone_logits
         self._clone_count = K
@@ -634,68 +622,6 @@ class SentimentNet:
         wv = self.image.weights_version if self.image is not None else 0
         return tuple(sorted((k, v.data_ptr(), tuple(v.shape)) for k, v in batch.items())) + (
             None if dropout_mask is None else dropout_mask.data_ptr(), gen, wv)
-
-    def _step_kernels(self, batch, dropout_mask):
-        """Everything train_step enqueues between the batch and Adam -- forward, CE, L2 term, backward -- with the
-        engines driven directly (the autograd nodes of functions.py are thin wrappers around exactly these calls,
-        in this order, on these streams; with the grouped head chain the cross entropy and its gradient come out of the
-        W_softmax combine's launch instead of two ds_softmax_ce calls)."""
-        main = torch.cuda.current_stream()
-        side = self.text_stream if (self.image is not None and self.text is not None) else None
-        im = tx = None
-        if side is not None:
-            ready = torch.cuda.Event()
-            ready.record(main)
-        if self.image is not None:
-            im = self.image.forward(batch["images"], dropout_mask, 0)
-        if self.text is not None:
-            if side is not None:
-                side.wait_event(ready)
-                with torch.cuda.stream(side):
-                    tx = self.text.forward(batch["texts"], batch["seq_lens"])
-                main.wait_stream(side)
-            else:
-                tx = self.text.forward(batch["texts"], batch["seq_lens"])
-        if self.dlogits is None or self.dlogits.shape[0] != batch["labels"].shape[0]:
-            raise RuntimeError("capture_step: run one eager train_step with this batch size first")
-        ce_done = False
-        if self.mode == "image":
-            logits = im
-        elif self.mode == "text":
-            logits = self.head.forward(tx)
-        elif self.head.grouped() and self.head.ce_fused():
-            # the cross entropy and its gradient from the launch that combines the W_softmax GEMM (the same bits)
-            logits = self.head.forward(im, tx, ce=(batch["labels"], self.loss_buf, self.dlogits))
-            ce_done = True
-        else:
-            logits = self.head.forward(im, tx)
-        self.logits = logits
-        if self.dlogits.shape != logits.shape:
-            raise RuntimeError("capture_step: run one eager train_step with this batch size first")
-        B, C_ = logits.shape
-        if not ce_done:
-            ops.softmax_ce(logits, batch["labels"], B, C_, 1.0, None, self.loss_buf, self.dlogits)
-        self._enqueue_l2_term()
-        if self.mode == "image":
-            self.image.backward(self.dlogits)
-        elif self.mode == "text":
-            self.text.backward(self.head.backward(self.dlogits))
-        else:
-            self._async_head_grads(True)      # (image.backward below joins the weight-gradient stream)
-            try:
-                d_im, d_tx = self.head.backward(self.dlogits)
-            finally:
-                self._async_head_grads(False)
-            if side is not None:              # BPTT next to the Inception backward, as in the eager step
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    self.text.backward(d_tx)
-                self.image.backward(d_im)
-                main.wait_stream(side)
-            else:
-                self.text.backward(d_tx)
-                self.image.backward(d_im)
-        self._join_head_grads()
 
     def capture_step(self, batch, dropout_mask=None, num_clones=1):
         """Capture one whole training step on `batch`'s tensors (static addresses: refill them in place between
@@ -740,7 +666,7 @@ class SentimentNet:
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._step_kernels(batch, dropout_mask)
+            self._step_body(batch, dropout_mask, 0, self.loss_buf)      # (the seed of a replay is seed_dev's)
             ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, 1.0, 0.0,
                         ADAM_B1, ADAM_B2, ADAM_EPS, lr_t_dev=self.lr_t_dev)
         self._graph, self._graph_key = g, self._batch_key(batch, dropout_mask)
