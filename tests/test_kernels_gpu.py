@@ -2397,6 +2397,98 @@ def test_every_conv_instantiation_matches_the_oracle(tuning_lib):
         lib.ds_debug_conv_set_tile(0, 0)
 
 
+# The epilogue combinations of the shared tile / wave-row epilogues (csrc/conv_epilogue.h) that no test above pins a kernel for
+# (profiles/conv_epilogue_notes.md has the table).  One shape that reaches every guard: 1x1, M = 165 (second row tile of 128:
+# wave 0 full, wave 1 five rows, waves 2-3 none), Cin = 32, Cout = 40 (column block 1 partial), ldz = ldmask = 48.
+_EPI_SHAPE = (165, 32, 40, 48)
+_EPI_REF = {}
+
+
+def _epilogue_operands():
+    """x, w (HWIO 1x1, [K][N]), bias, previous z, mask, pivot and the fp64 product, computed once and left unchanged."""
+    if not _EPI_REF:
+        M, K, N, ld = _EPI_SHAPE
+        rng = np.random.RandomState(165)
+        r = dict(x=rng.normal(size=(M, K)), w=rng.normal(size=(K, N)) * 0.1, bias=rng.normal(size=N), prev=rng.normal(size=(M, ld)),
+                 mask=rng.normal(size=(M, ld)), pivot=rng.normal(size=N) * 0.2)
+        r["core"] = r["x"] @ r["w"]
+        _EPI_REF.update(r)
+    return _EPI_REF
+
+
+@pytest.mark.parametrize("combo", ["BIAS", "BIAS|RELU", "ACCUM", "MASK", "STATS+pivot"])
+@pytest.mark.parametrize("path", [2, 3], ids=["direct", "glds"])
+def test_tile_epilogue_combinations_of_the_pinned_direct_and_lds_dma_kernels(path, combo, tuning_lib):
+    """conv_direct_kernel (path 2) and conv_glds_kernel (path 3), pinned at the 128 x 64 tile, with the epilogue flags the
+    sweeps above run on the register-staged kernel only.  Tolerances: those of test_every_conv_instantiation_matches_the_oracle,
+    the test that pins these two kernels -- z 2e-4 of max|ref|, column sums 1e-3 of max|sum| + 1e-3 (partials summed over P in
+    fp64, about the pivot; the sum of squares against the same bound of its own reference)."""
+    ops = _ops()
+    from tumblr_emotions_amd import _lib
+    lib = _lib.load()
+    M, K, N, ld = _EPI_SHAPE
+    o = _epilogue_operands()
+    flags = {"BIAS": ops.DS_EPI_BIAS, "BIAS|RELU": ops.DS_EPI_BIAS | ops.DS_EPI_RELU, "ACCUM": ops.DS_EPI_ACCUM, "MASK": ops.DS_EPI_MASK,
+             "STATS+pivot": ops.DS_EPI_STATS}[combo]
+    want = o["core"] + (o["bias"] if flags & ops.DS_EPI_BIAS else 0.0)
+    if flags & ops.DS_EPI_ACCUM:
+        want = want + o["prev"][:, :N]
+    if flags & ops.DS_EPI_MASK:
+        want = want * (o["mask"][:, :N] > 0)
+    if flags & ops.DS_EPI_RELU:
+        want = np.maximum(want, 0.0)
+    try:
+        assert lib.ds_debug_conv_set_path(path) == 0 and lib.ds_debug_conv_set_wide(0) == 0 and lib.ds_debug_conv_set_tile(1, 2) == 0
+        plan = ops.ConvPlan(M, 1, 1, K, K, 1, 1, 1, N, ld, 0, 1, N, flags=flags, ldmask=ld, pad_t=0, pad_l=0, OH=1, OW=1)
+        z = dev(o["prev"])
+        stats = torch.zeros(2, N, max(plan.partials, 1), device="cuda")
+        xd, wd, bd, md, pd = dev(o["x"]), dev(o["w"]), dev(o["bias"]), dev(o["mask"]), dev(o["pivot"])
+        plan.run(ops._p(xd), ops._p(wd), ops._p(z), bias=ops._p(bd), mask=ops._p(md), stats=ops._p(stats), pivot=ops._p(pd))
+        torch.cuda.synchronize()
+    finally:
+        lib.ds_debug_conv_set_path(0)
+        lib.ds_debug_conv_set_wide(1)
+        lib.ds_debug_conv_set_tile(0, 0)
+    got = z.cpu().numpy().astype(np.float64)
+    assert np.abs(got[:, :N] - want).max() <= 2e-4 * np.abs(want).max()
+    assert np.array_equal(got[:, N:], o["prev"][:, N:].astype(np.float32))          # the row padding is not written
+    if flags & ops.DS_EPI_STATS:
+        u = want - o["pivot"]
+        s = stats.double().sum(2).cpu().numpy()
+        assert np.abs(s[0] - u.sum(0)).max() <= 1e-3 * np.abs(u.sum(0)).max() + 1e-3
+        assert np.abs(s[1] - (u ** 2).sum(0)).max() <= 1e-3 * np.abs((u ** 2).sum(0)).max() + 1e-3
+
+
+def test_f32x3_accumulate_with_sums_rebuilds_the_activation_from_z():
+    """conv_bf16d_kernel's mask_rstd / mask_shift path, which only ds_conv_f32x3 reaches: DS_EPI_ACCUM | DS_EPI_BNSUMS with `mask`
+    holding the consumer's z, y = relu(z * rstd + shift) per column.  Tolerances of
+    test_fp32_products_from_three_bf16_pieces_match_the_oracle: z 2e-4, the two column sums 2e-3 (partials summed over P)."""
+    ops = _ops()
+    M, K, N, ld = _EPI_SHAPE
+    o = _epilogue_operands()
+    rng = np.random.RandomState(40)
+    mr = (np.abs(rng.normal(size=N)) + 0.5).astype(np.float32).astype(np.float64)
+    ms = (rng.normal(size=N) * 0.3).astype(np.float32).astype(np.float64)
+    plan = ops.F32x3Plan(M, 1, 1, K, K, 1, 1, N, ld, flags=ops.DS_EPI_ACCUM | ops.DS_EPI_BNSUMS, pad_t=0, pad_l=0, OH=1, OW=1)
+    wb = torch.empty(ops.weights_f32x3_bytes(K, N, 1, False), dtype=torch.uint8, device="cuda")
+    wd = dev(o["w"])
+    ops.weights_to_f32x3(ops._p(wd), wb, K, N, 1, False)
+    mrd, msd = dev(mr), dev(ms)
+    plan.d.ldmask, plan.d.mask_rstd, plan.d.mask_shift = ld, mrd.data_ptr(), msd.data_ptr()
+    z, zc = dev(o["prev"]), dev(o["mask"])
+    sums = torch.full((2, N, plan.partials_for_sums), float("nan"), device="cuda")
+    xd = dev(o["x"])
+    plan.run(ops._p(xd), ops._p(wb), ops._p(z), stats=ops._p(sums), mask=ops._p(zc))
+    torch.cuda.synchronize()
+    want = o["prev"][:, :N] + o["core"]
+    close(z[:, :N], want)
+    assert np.array_equal(z[:, N:].cpu().numpy(), o["prev"][:, N:].astype(np.float32))
+    y = np.maximum(o["mask"][:, :N].astype(np.float32).astype(np.float64) * mr + ms, 0.0)
+    g = want * (y > 0)
+    close(sums.double().sum(2)[0], g.sum(0), 2e-3)
+    close(sums.double().sum(2)[1], (g * y).sum(0), 2e-3)
+
+
 def test_split_k_gemm_slabs_feed_lstm_cell():
     """LSTM step as the engine runs it: split-K recurrent GEMM -> slabs -> cell kernel adds them."""
     ops = _ops()

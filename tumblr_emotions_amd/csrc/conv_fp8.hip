@@ -15,16 +15,17 @@
 //     that IS its A fragment), weights by LDS-DMA, a wave owns 32 pixels x NB*32 columns;
 //   * epilogue: z = acc / (s_a * s_w) in fp32, BatchNorm column statistics about the pivot (DS_EPI_STATS).
 #include <stdlib.h>
-#include "ds_common.h"
+#include "conv_epilogue.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ds::f32x16;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void *lds_ptr;
 
 namespace {
 
-constexpr unsigned kOOB = 0x80000000u;
+using ds::kOOB;
+using ds::make_srd;
 constexpr float kMaxE4M3 = 448.f, kMaxE5M2 = 57344.f;
 
 struct Fp8Params {
@@ -40,10 +41,6 @@ struct Fp8Params {
     int M, row_tiles, col_tiles, ncols;
     unsigned x_bytes, w_bytes;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
 
 // 2^floor(log2(fmax / amax)): the largest power of two that keeps amax * s <= fmax (1 for an all-zero tensor)
 __host__ __device__ __forceinline__ float pow2_scale(float amax, float fmax) {
@@ -197,8 +194,9 @@ __global__ __launch_bounds__(256, 2) void conv_fp8d_kernel(const Fp8Params p) {
         __syncthreads();
     }
 
-    // ---- epilogue: unscale, store, BatchNorm column statistics (two phases as gemm_wide_kernel: reads and sums for
-    // every column block first, all stores last -- a read behind a store waits for it) ----------------------------------
+    // ---- epilogue: unscale, store, BatchNorm column statistics: ds::wave_row_epilogue (conv_epilogue.h) with acc = acc * inv +
+    // z_prev in front, in place (on the shared function the K loop's schedule moved: profiles/conv_epilogue_notes.md).
+    // Two phases: reads and sums for every column block first, all stores last -- a read behind a store waits for it.
     const int flags = d.flags;
     float *red = reinterpret_cast<float *>(smem + 2 * DJ * 4096);
     const int mrow0 = trow * 128 + wave * 32;

@@ -23,9 +23,9 @@
 //     match a scalar fp32 reference to rounding.
 #include <stdlib.h>
 #include <type_traits>
-#include "ds_common.h"
+#include "conv_epilogue.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ds::f32x16;
 typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector (HIP's float4 is a struct)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -35,7 +35,8 @@ namespace {
 
 constexpr int BK = 16;    // K-tile (floats)
 constexpr int LDK = 20;   // padded LDS row stride for [row][k] tiles: 80 B, conflict-free b128 reads
-constexpr unsigned kOOB = 0x80000000u;   // byte offset beyond any descriptor: the load returns 0
+using ds::kOOB;
+using ds::make_srd;
 
 struct ConvParams {
     ds_conv_desc d;
@@ -59,10 +60,6 @@ struct ConvParams {
     double fin_inv_count;
     const float *scale, *shift;  // DS_EPI_BN_RELU (the <.., BNR = true> instantiations): Cout floats each
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
 
 // Which tile does this workgroup own?  Two launch shapes:
 //   * col_tiles == 0: 2-D grid, blockIdx.x = first row tile (persistent stride gridDim.x), blockIdx.y = column
@@ -340,77 +337,14 @@ __device__ __forceinline__ void igemm_workgroup(const ConvParams &p, float *smem
             par ^= 1;
         }
 
-        // ---- epilogue: bias / accumulate / mask / relu, store, BatchNorm column statistics -------
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            const int col = n0 + b * 32 + li;
-            const bool colok = col < d.Cout;
-            const float bv = ((flags & DS_EPI_BIAS) && colok) ? p.bias[col] : 0.f;
-            const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;      // statistics are taken about the pivot
-            float s = 0.f, q = 0.f;
-            if constexpr (BNR) {          // scale / shift once per column, then nothing but stores
-                const float sc = colok ? p.scale[col] : 0.f, sh = colok ? p.shift[col] : 0.f;
-#pragma unroll
-                for (int a = 0; a < MT; ++a) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = m0 + wm * MT * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                        if (row < p.M && colok) zout[(int64_t)row * d.ldz + col] = fmaxf(fmaf(acc[a][b][r], sc, sh), 0.f);
-                    }
-                }
-                continue;
-            }
-#pragma unroll
-            for (int a = 0; a < MT; ++a) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + wm * MT * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                    if (row < p.M && colok) {
-                        float v = acc[a][b][r] + bv;
-                        const int64_t off = (int64_t)row * d.ldz + col;
-                        if (flags & DS_EPI_ACCUM) v += zout[off];
-                        if (flags & DS_EPI_MASK) v = p.mask[(int64_t)row * d.ldmask + col] > 0.f ? v : 0.f;
-                        if (flags & DS_EPI_RELU) v = fmaxf(v, 0.f);
-                        zout[off] = v;
-                        const float u = v - pv;
-                        s += u;
-                        q += u * u;
-                    }
-                }
-            }
-            csum[b] += s;
-            csq[b] += q;
-        }
+        // ---- epilogue (conv_epilogue.h): bias / accumulate / mask / relu, store, BatchNorm column statistics -------
+        ds::tile_store<MT, NT, BNR>(p.d, p.M, zout, p.bias, p.mask, p.pivot, p.scale, p.shift, [&](int a, int b) -> const f32x16 & { return acc[a][b]; },
+                                    m0 + wm * MT * 32 + 4 * lk, n0 + li, csum, csq);
     }
     }
 
-    if (flags & DS_EPI_STATS) {
-        // rows of a column live in lanes l and l^32, and in the 4 waves stacked along M
-        float *red = smem;   // [WM][BN][2]; safe: every wave passed the last K-loop barrier
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            const float s = csum[b] + __shfl_xor(csum[b], 32);
-            const float q = csq[b] + __shfl_xor(csq[b], 32);
-            if (lk == 0) {
-                const int c = b * 32 + li;
-                red[(wm * BN + c) * 2 + 0] = s;
-                red[(wm * BN + c) * 2 + 1] = q;
-            }
-        }
-        __syncthreads();
-        if (tid < BN && n0 + tid < d.Cout && tid0.row < p.row_tiles) {
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int w = 0; w < WM; ++w) {
-                s += red[(w * BN + tid) * 2 + 0];
-                q += red[(w * BN + tid) * 2 + 1];
-            }
-            // partials laid out [2][Cout][P] (P = workgroups per column tile) so ds_bn_finalize reads them contiguously
-            p.stats[(int64_t)(n0 + tid) * tid0.stride + tid0.row] = s;
-            p.stats[((int64_t)d.Cout + n0 + tid) * tid0.stride + tid0.row] = q;
-        }
-    }
+    if (flags & DS_EPI_STATS)      // (red = the operand tiles: every wave passed the last K-loop barrier)
+        ds::tile_stats_combine<NT>(smem, csum, csq, n0, d.Cout, tid0.row < p.row_tiles, p.stats, tid0.stride, tid0.row);
 }
 
 template <int MT, int NT, bool BNMAJOR, bool FOLD, bool VEC, bool BNR = false>
@@ -622,7 +556,8 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvParams p) {
             mma(f0);
         }
 
-        // ---- epilogue (same contract as the LDS kernel) -----------------------------------------------
+        // ---- epilogue: ds::tile_store's store phase in place (on the shared function this kernel's schedule and occupancy, hence
+        // its grid and partial count, moved: profiles/conv_epilogue_notes.md) ------------------------------------------------
 #pragma unroll
         for (int b = 0; b < NT; ++b) {
             const int col = n0 + b * 32 + li;
@@ -876,68 +811,13 @@ __global__ __launch_bounds__(256, NT == 1 ? 4 : (NT == 2 ? 3 : 2)) void conv_gld
             par ^= 1;
         }
 
-        // ---- epilogue: bias / accumulate / mask / relu, store, BatchNorm column statistics -------
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            const int col = n0 + b * 32 + li;
-            const bool colok = col < d.Cout;
-            const float bv = ((flags & DS_EPI_BIAS) && colok) ? p.bias[col] : 0.f;
-            const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;      // statistics are taken about the pivot
-            float s = 0.f, q = 0.f;
-            if constexpr (BNR) {
-                const float sc = colok ? p.scale[col] : 0.f, sh = colok ? p.shift[col] : 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                    if (row < p.M && colok) zout[(int64_t)row * d.ldz + col] = fmaxf(fmaf(acc[b][r], sc, sh), 0.f);
-                }
-                continue;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                if (row < p.M && colok) {
-                    float v = acc[b][r] + bv;
-                    const int64_t off = (int64_t)row * d.ldz + col;
-                    if (flags & DS_EPI_ACCUM) v += zout[off];
-                    if (flags & DS_EPI_MASK) v = p.mask[(int64_t)row * d.ldmask + col] > 0.f ? v : 0.f;
-                    if (flags & DS_EPI_RELU) v = fmaxf(v, 0.f);
-                    zout[off] = v;
-                    const float u = v - pv;
-                    s += u;
-                    q += u * u;
-                }
-            }
-            csum[b] += s;
-            csq[b] += q;
-        }
+        // ---- epilogue (conv_epilogue.h): bias / accumulate / mask / relu, store, BatchNorm column statistics -------
+        ds::tile_store<1, NT, BNR>(p.d, p.M, zout, p.bias, p.mask, p.pivot, p.scale, p.shift, [&](int, int b) -> const f32x16 & { return acc[b]; },
+                                   m0 + wm * 32 + 4 * lk, n0 + li, csum, csq);
     }
 
-    if (flags & DS_EPI_STATS) {
-        float *red = smem;   // [4][BN][2]; safe: every wave passed the last K-loop barrier and no DMA is in flight
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            const float s = csum[b] + __shfl_xor(csum[b], 32);
-            const float q = csq[b] + __shfl_xor(csq[b], 32);
-            if (lk == 0) {
-                const int c = b * 32 + li;
-                red[(wm * BN + c) * 2 + 0] = s;
-                red[(wm * BN + c) * 2 + 1] = q;
-            }
-        }
-        __syncthreads();
-        if (tid < BN && n0 + tid < d.Cout && tid0.row < p.row_tiles) {
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                s += red[(w * BN + tid) * 2 + 0];
-                q += red[(w * BN + tid) * 2 + 1];
-            }
-            p.stats[(int64_t)(n0 + tid) * tid0.stride + tid0.row] = s;
-            p.stats[((int64_t)d.Cout + n0 + tid) * tid0.stride + tid0.row] = q;
-        }
-    }
+    if (flags & DS_EPI_STATS)      // (red = the operand tiles: every wave passed the last K-loop barrier and no DMA is in flight)
+        ds::tile_stats_combine<NT>(smem, csum, csq, n0, d.Cout, tid0.row < p.row_tiles, p.stats, tid0.stride, tid0.row);
 }
 
 
@@ -1125,6 +1005,8 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void conv_bf16_kernel(const C
             __syncthreads();
             par ^= 1;
         }
+        // The tile epilogue (ds::tile_store, ds::tile_stats_combine) in place: on the shared functions this kernel gains occupancy,
+        // and a persistent launch sizes its grid and partial count by it (profiles/conv_epilogue_notes.md).
 #pragma unroll
         for (int b = 0; b < NT; ++b) {
             const int col = n0 + b * 32 + li;
@@ -1222,6 +1104,9 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void conv_bf16_kernel(const C
 // (today: under one).  Same MFMA sequence per output element: bit-identical to the register form.
 template <int N>
 __device__ __forceinline__ void barrier_keep_vm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory"); }
+
+template <bool BNR>
+struct WideEpi : ds::WaveRowOpt { static constexpr bool bnr = BNR, mask_rstd = true, publish = true; };
 
 template <int NB, bool BNMAJOR, bool BNB = false, bool POOL = false, int AST = 0, bool BNR = false>      // BNR: DS_EPI_BN_RELU (see conv_igemm_kernel)
 __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const ConvParams p) {
@@ -1557,130 +1442,14 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         __syncthreads();
     }
 
-    // ---- epilogue: store, BatchNorm column statistics ---------------------------------------------------------------
-    // Two phases.  (1) per column block: the accumulate / mask reads, the sums, the LDS combine -- results stay in the
-    // accumulator registers; (2) all stores.  With the stores of block b in front of the reads of block b + 1 every
-    // block cost a memory round trip (a load behind a store waits for it: one in-order counter).
+    // ---- epilogue (conv_epilogue.h): store, BatchNorm column statistics ------------------------------------------------
+    // POOL: the row bound is this wave's last real row (Mw, wave-uniform), so the rows a 28-pixel block leaves unused -- they
+    // would alias the NEXT block's pixels -- are dropped by the same range check as the rows past M; a surplus wave past the
+    // last image has no row.  fin: the partials are read back by another workgroup of THIS launch.
     const int flags = d.flags;
     float *red = smem + BST * BSZ;
-    // (outputs of 2 GiB and more stay on the LDS-tile kernels: wide_nb)
-    // POOL: the descriptors end with this wave's last real row (Mw, wave-uniform), so the rows a 28-pixel block leaves
-    // unused -- they would alias the NEXT block's pixels -- are dropped by the same range check as the rows past M
-    const bool any_row = Mw > mrow0;          // (uniform; POOL: a surplus wave past the last image has none)
-    const __amdgpu_buffer_rsrc_t srd_z = make_srd(p.z, any_row ? (unsigned)(((int64_t)(Mw - 1) * d.ldz + d.Cout) * 4) : 0u);
-    const __amdgpu_buffer_rsrc_t srd_m = make_srd((flags & DS_EPI_BNSUMS) ? p.mask : p.z,
-                                                  ((flags & DS_EPI_BNSUMS) && any_row) ? (unsigned)(((int64_t)(Mw - 1) * d.ldmask + d.Cout) * 4) : 0u);
-    const int rz = d.ldz * 4, rm = d.ldmask * 4;                 // bytes per row
-    const int rbase = mrow0 + 4 * kh;                            // this lane's first row; accumulator element r: + (r & 3) + 8 (r >> 2)
-    // z (and the accumulate / activation reads at the same rows and columns) through buffer descriptors: ONE 32-bit lane
-    // offset per column block plus the row's wave-uniform byte offset, added into the VECTOR offset (the scalar offset of a
-    // buffer instruction is not range-checked); rows past M and columns past Cout (offset kOOB = 2^31, which the row offsets
-    // cannot wrap) fall out of the descriptor's range: loads return 0, stores are dropped.  The 64-bit address per row and
-    // the per-row branches of the pointer form cost more than the accesses: fifteen 1x1 shapes, forward with statistics
-    // 1747 -> 1658 us, dgrad with accumulate + sums 2346 -> 2121 us, step 14.34 -> 14.10 ms (three interleaved pairs).
-    auto ld_row = [&](__amdgpu_buffer_rsrc_t srd, unsigned v, int r, int row_bytes) -> float {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd, v + (unsigned)(((r & 3) + 8 * (r >> 2)) * row_bytes), 0, 0));
-    };
-    auto st_row = [&](float val, unsigned v, int r) {
-        const unsigned bits = __builtin_bit_cast(unsigned, val);          // (of a COPY: bit_cast of a vector-element lvalue reads element 0)
-        __builtin_amdgcn_raw_buffer_store_b32(bits, srd_z, v + (unsigned)(((r & 3) + 8 * (r >> 2)) * rz), 0, 2 /* nt */);
-    };
-    float pss[NB], pqq[NB];                          // (threads 0..31) this workgroup's partials of column block b
-    float bsc[BNR ? NB : 1], bsh[BNR ? NB : 1];      // BNR: scale / shift of this lane's column of block b (read phase)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int col = n0 + 32 * b + li;
-        const bool colok = item && col < d.Cout;
-        if constexpr (BNR) {
-            bsc[b] = colok ? p.scale[col] : 0.f;
-            bsh[b] = colok ? p.shift[col] : 0.f;
-            pss[b] = pqq[b] = 0.f;
-            continue;
-        }
-        const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;
-        const unsigned vz = colok ? (unsigned)(rbase * d.ldz + col) * 4u : kOOB;
-        const unsigned vm = colok ? (unsigned)(rbase * d.ldmask + col) * 4u : kOOB;
-        float s = 0.f, q = 0.f;
-        if (flags & DS_EPI_ACCUM) {                  // the sixteen previous values, requested together
-            float zv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) zv[r] = ld_row(srd_z, vz, r, rz);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[b][r] += zv[r];
-        }
-        if (flags & DS_EPI_BNSUMS) {
-            // dgrad whose result dy feeds a BatchNorm + ReLU backward: column sums of g = dy (y > 0) and g * y, y = the
-            // consumer layer's forward activation (same rows / columns as dy)
-            float yv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                yv[r] = ld_row(srd_m, vm, r, rm);
-            if (d.mask_rstd && colok) {      // `mask` holds z of the consumer layers: y = relu(z * rstd + shift) per column
-                const float mr = d.mask_rstd[col], ms = d.mask_shift[col];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rbase + (r & 3) + 8 * (r >> 2);
-                    yv[r] = row < Mw ? fmaxf(fmaf(yv[r], mr, ms), 0.f) : 0.f;      // (rows past M read 0, which a shift > 0 would turn on)
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float u = yv[r] > 0.f ? acc[b][r] : 0.f;          // (out of range: y = 0)
-                s += u;
-                q += u * yv[r];
-            }
-        } else if (flags & DS_EPI_STATS) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rbase + (r & 3) + 8 * (r >> 2);
-                if (row < Mw && colok) {
-                    const float u = acc[b][r] - pv;
-                    s += u;
-                    q += u * u;
-                }
-            }
-        }
-        pss[b] = pqq[b] = 0.f;
-        if (flags & (DS_EPI_STATS | DS_EPI_BNSUMS)) {
-            s += __shfl_xor(s, 32);
-            q += __shfl_xor(q, 32);
-            __syncthreads();
-            if (kh == 0) {
-                red[(wave * 32 + li) * 2 + 0] = s;
-                red[(wave * 32 + li) * 2 + 1] = q;
-            }
-            __syncthreads();
-            if (tid < 32) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    pss[b] += red[(w * 32 + tid) * 2 + 0];
-                    pqq[b] += red[(w * 32 + tid) * 2 + 1];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int col = n0 + 32 * b + li;
-        const bool colok = item && col < d.Cout;
-        const unsigned vz = colok ? (unsigned)(rbase * d.ldz + col) * 4u : kOOB;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if constexpr (BNR) st_row(fmaxf(fmaf(acc[b][r], bsc[b], bsh[b]), 0.f), vz, r);
-            else st_row(acc[b][r], vz, r);
-        }
-        if ((flags & (DS_EPI_STATS | DS_EPI_BNSUMS)) && tid < 32 && item && n0 + 32 * b + tid < d.Cout) {
-            float *const sp = p.stats + (int64_t)(n0 + 32 * b + tid) * t0.stride + t0.row;
-            float *const qp = p.stats + ((int64_t)d.Cout + n0 + 32 * b + tid) * t0.stride + t0.row;
-            if (p.fin.ticket) {          // (uniform) read back by another workgroup of THIS launch: write-through
-                __hip_atomic_store(reinterpret_cast<unsigned *>(sp), __float_as_uint(pss[b]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(reinterpret_cast<unsigned *>(qp), __float_as_uint(pqq[b]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                *sp = pss[b];
-                *qp = pqq[b];
-            }
-        }
-    }
+    ds::wave_row_epilogue<NB, WideEpi<BNR>>(acc, d, p.z, p.mask, p.stats, p.pivot, item, n0, mrow0, Mw, Mw > mrow0, t0.row, t0.stride,
+                                            red, wave, li, kh, p.scale, p.shift, p.fin.ticket != nullptr);
     // ds_bn_finalize inside the launch (ds_conv_desc.fin): the last workgroup of a column tile to publish its partials
     // finalizes the tile's columns -- one wave per column, bn_finalize_kernel's summation tree (ds_common.h) -- so the
     // dependent ds_bn_finalize launch disappears.  Hand-off as in lstm_seq.hip: write-through payload, every storing wave
@@ -1728,6 +1497,8 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
 // weight update (ds_weights_to_f32x3: three planes per K-loop iteration), the A fragment in registers (~40 VALU per 8
 // values, shared by the NB column blocks).  Measured on the 1x1 layers of the joint step (B = 256): 1.15 - 1.5x over the
 // wide fp32 kernel on twelve of fourteen shapes, up to 163 TFLOP/s of fp32-accurate GEMM -- above the fp32 MFMA peak.
+struct Bf16dEpi : ds::WaveRowOpt { static constexpr bool half = true, mask_rstd = true; };
+
 template <int NB, int KS, bool XB, bool X3 = false>      // KS x KS taps (1 or 3); XB: x is stored as bf16 (16-bit activation storage)
 __global__ __launch_bounds__(256, 2) void conv_bf16d_kernel(const ConvParams p) {
     // iterations per step: X3 keeps three weight planes in LDS, so shorter steps (SI * NB % 4 == 0: whole DMA slots)
@@ -1885,120 +1656,9 @@ __global__ __launch_bounds__(256, 2) void conv_bf16d_kernel(const ConvParams p) 
         __syncthreads();
     }
 
-    // ---- epilogue: store, BatchNorm column statistics (two phases as gemm_wide_kernel: reads and sums, then stores) -----
-    const int flags = d.flags;
-    float *red = reinterpret_cast<float *>(smem + 2 * BSZ);
-    const int mrow0 = t0.row * 128 + wave * 32;
-    // (as gemm_wide_kernel) z / accumulate / activation accesses through buffer descriptors: 32-bit lane offset + row offset
-    // in the vector offset, hardware range check for rows past M and columns past Cout (kOOB)
-    const bool m16 = d.mask_dtype == DS_DTYPE_BF16;      // (uniform) BatchNorm-sums activation in bf16 storage
-    const bool z16 = d.z_dtype == DS_DTYPE_BF16;         // (uniform) z stored rounded to bf16 (forward, no accumulate)
-    const unsigned zeb = z16 ? 2u : 4u;
-    const __amdgpu_buffer_rsrc_t srd_z = make_srd(p.z, (unsigned)(((int64_t)(p.M - 1) * d.ldz + d.Cout) * zeb));
-    const __amdgpu_buffer_rsrc_t srd_m = make_srd((flags & DS_EPI_BNSUMS) ? p.mask : p.z,
-                                                  (flags & DS_EPI_BNSUMS) ? (unsigned)(((int64_t)(p.M - 1) * d.ldmask + d.Cout) * (m16 ? 2 : 4)) : 0u);
-    const int rz = d.ldz * (int)zeb, rm = d.ldmask * (m16 ? 2 : 4);
-    const int rbase = mrow0 + 4 * kh;
-    auto roff = [](int r, int row_bytes) -> unsigned { return (unsigned)(((r & 3) + 8 * (r >> 2)) * row_bytes); };
-    float pss[NB], pqq[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int col = n0 + 32 * b + li;
-        const bool colok = item && col < d.Cout;
-        const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;
-        const unsigned vz = colok ? (unsigned)(rbase * d.ldz + col) * zeb : kOOB;
-        const unsigned vm = colok ? (unsigned)(rbase * d.ldmask + col) * (m16 ? 2u : 4u) : kOOB;
-        float s = 0.f, q = 0.f;
-        if (flags & DS_EPI_ACCUM) {
-            float zv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                zv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd_z, vz + roff(r, rz), 0, 0));
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[b][r] += zv[r];
-        }
-        if (flags & DS_EPI_BNSUMS) {
-            // (as gemm_wide_kernel) dgrad whose result dy feeds a BatchNorm + ReLU backward: column sums of
-            // g = dy (y > 0) and g * y; `mask` holds y (fp32, or bf16 under 16-bit activation storage), or z with
-            // mask_rstd / mask_shift
-            float yv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (m16) yv[r] = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b16(srd_m, vm + roff(r, rm), 0, 0) << 16);
-                else yv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd_m, vm + roff(r, rm), 0, 0));
-            }
-            if (d.mask_rstd && colok) {
-                const float mr = d.mask_rstd[col], ms = d.mask_shift[col];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rbase + (r & 3) + 8 * (r >> 2);
-                    yv[r] = row < p.M ? fmaxf(fmaf(yv[r], mr, ms), 0.f) : 0.f;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float u = yv[r] > 0.f ? acc[b][r] : 0.f;          // (out of range: y = 0)
-                s += u;
-                q += u * yv[r];
-            }
-        } else if (flags & DS_EPI_STATS) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mrow0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                if (row < p.M && colok) {
-                    const float u = acc[b][r] - pv;
-                    s += u;
-                    q += u * u;
-                }
-            }
-        }
-        pss[b] = pqq[b] = 0.f;
-        if (flags & (DS_EPI_STATS | DS_EPI_BNSUMS)) {
-            s += __shfl_xor(s, 32);
-            q += __shfl_xor(q, 32);
-            __syncthreads();
-            if (kh == 0) {
-                red[(wave * 32 + li) * 2 + 0] = s;
-                red[(wave * 32 + li) * 2 + 1] = q;
-            }
-            __syncthreads();
-            if (tid < 32) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    pss[b] += red[(w * 32 + tid) * 2 + 0];
-                    pqq[b] += red[(w * 32 + tid) * 2 + 1];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int col = n0 + 32 * b + li;
-        const bool colok = item && col < d.Cout;
-        const unsigned vz = colok ? (unsigned)(rbase * d.ldz + col) * zeb : kOOB;
-        if (z16) {
-            // z CENTRED about the pivot before it is rounded: the BatchNorm passes use z - mean, and for a channel with
-            // |mean| >> sigma a bf16 z would carry (|mean| / sigma) 2^-9 of error into xhat; z - pivot (pivot = the previous
-            // step's mean) is of the size of sigma, its rounding error 2^-9 of xhat itself.  The consumers get mean - pivot and
-            // beta - (mean - pivot) rstd (ds_bn_finalize_centered)
-            const float pvz = (p.pivot && colok) ? p.pivot[col] : 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const __bf16 hv = (__bf16)(acc[b][r] - pvz);          // round to nearest even
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, hv), srd_z, vz + roff(r, rz), 0, 2 /* nt */);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float val = acc[b][r];          // (bit_cast of a vector-element lvalue reads element 0: copy first)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), srd_z, vz + roff(r, rz), 0, 2 /* nt */);
-            }
-        }
-        if ((flags & (DS_EPI_STATS | DS_EPI_BNSUMS)) && tid < 32 && item && n0 + 32 * b + tid < d.Cout) {
-            p.stats[(int64_t)(n0 + 32 * b + tid) * t0.stride + t0.row] = pss[b];
-            p.stats[((int64_t)d.Cout + n0 + 32 * b + tid) * t0.stride + t0.row] = pqq[b];
-        }
-    }
+    // ---- epilogue (conv_epilogue.h): store, BatchNorm column statistics; 16-bit z / activation storage per launch ---------
+    ds::wave_row_epilogue<NB, Bf16dEpi>(acc, d, p.z, p.mask, p.stats, p.pivot, item, n0, t0.row * 128 + wave * 32, p.M, true, t0.row,
+                                        t0.stride, reinterpret_cast<float *>(smem + 2 * BSZ), wave, li, kh, nullptr, nullptr, false);
 }
 
 // wb[it][column][16] bf16, it = chunk * taps + tap, from the TF HWIO filter w [taps][Cin][Cout] (fp32).

@@ -39,9 +39,9 @@
 // workgroups) and left out of the statistics.  LDS: the filter without its zero rows (37.6 KB) + the ring (43 KB) = 80.6 KB,
 // two workgroups per CU as before.
 #include <math.h>
-#include "ds_common.h"
+#include "conv_epilogue.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ds::f32x16;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x3 __attribute__((ext_vector_type(3)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -51,7 +51,7 @@ typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 
 namespace {
 
-constexpr unsigned kOOB = 0x80000000u;
+using ds::kOOB;
 constexpr int CO = 64;
 
 struct StemParams {

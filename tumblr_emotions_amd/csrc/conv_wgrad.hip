@@ -10,9 +10,9 @@
 // slabs that a second kernel sums in a fixed order (deterministic, no atomics).
 #include <stdio.h>
 #include <stdlib.h>
-#include "ds_common.h"
+#include "conv_epilogue.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ds::f32x16;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -36,14 +36,12 @@ struct WgradParams {
     int slabs;          // wgrad_direct_kernel: split-K slabs (see the id -> slab mapping there)
 };
 
-constexpr unsigned kOOB = 0x80000000u;   // byte offset beyond any descriptor: the load returns 0
+using ds::kOOB;
+using ds::make_srd;
 
 // SRD buffer loads as in conv_igemm.hip: rows past the split, padding pixels and channels past the
 // tensor get an out-of-range offset and come back as zeros, so the loader has no branches and the
 // loads of a K-tile stay in flight under the MFMAs of the previous one.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
 
 __device__ __forceinline__ f32x4 load4(__amdgpu_buffer_rsrc_t r, unsigned off, bool ok, bool vec, int valid) {
     if (vec) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, ok ? off : kOOB, 0, 0));

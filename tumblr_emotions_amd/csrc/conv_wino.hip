@@ -30,14 +30,15 @@
 // multiply), so results match the direct kernels to ~1e-6 relative, not bit for bit; reductions are ordered and
 // deterministic.
 #include <stdlib.h>
-#include "ds_common.h"
+#include "conv_epilogue.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ds::f32x16;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr unsigned kOOB = 0x80000000u;
+using ds::kOOB;
+using ds::make_srd;
 
 struct WinoParams {
     const float *x;         // [N, H, W, ldx]
@@ -54,9 +55,6 @@ struct WinoParams {
     const float *scale, *shift;      // DS_EPI_BN_RELU (conv_wino_kernel<false, true>): Cout floats each
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wsrd(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
 
 typedef __attribute__((address_space(3))) void *lds_ptr;
 
@@ -91,8 +89,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoParams p) {
     const int group = lin / p.ncol, cblk = lin - group * p.ncol;
     const int co0 = cblk * 32;
     const int tile0 = group < p.groups ? (group * 4 + wave) * 32 : p.Mt;      // surplus workgroups own no tile
-    const __amdgpu_buffer_rsrc_t srd_x = wsrd(p.x, p.x_bytes);
-    const __amdgpu_buffer_rsrc_t srd_u = wsrd(p.u, p.u_bytes);
+    const __amdgpu_buffer_rsrc_t srd_x = make_srd(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t srd_u = make_srd(p.u, p.u_bytes);
 
     // ---- this lane's tile: byte offsets of the 16 pixels of its 4x4 input patch (channel 4 kh) -------------
     const int m = tile0 + li;
@@ -210,7 +208,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoParams p) {
     const int col = co0 + li;
     const bool colok = col < p.Cout;
     const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;
-    const __amdgpu_buffer_rsrc_t srd_z = wsrd(p.z, p.z_bytes);
+    const __amdgpu_buffer_rsrc_t srd_z = make_srd(p.z, p.z_bytes);
     // byte offset of the tile's top-left output pixel (channel 0), or out of range; bit 0 / 1 = the tile has a
     // right column / a bottom row inside the image (odd H, W).  Read from the lane that owns the tile with
     // v_readlane (the row of an accumulator element is a compile-time constant plus 4 kh).
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoParams p) {
 
     } else {
         constexpr bool bns = true;
-        const __amdgpu_buffer_rsrc_t srd_y = wsrd(bns ? p.y : p.z, p.z_bytes);
+        const __amdgpu_buffer_rsrc_t srd_y = make_srd(bns ? p.y : p.z, p.z_bytes);
         // DS_EPI_BNSUMS (this launch is a dgrad whose result dy feeds a BatchNorm + ReLU backward): per column, the sums
         // of g = dy (y > 0) and g * y.  y sits at the offsets of the stores; (out-of-range
         // offsets read zeros: y = 0 drops the element from both sums).

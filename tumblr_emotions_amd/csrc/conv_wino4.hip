@@ -39,15 +39,16 @@
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
-#include "ds_common.h"
+#include "conv_epilogue.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ds::f32x16;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr unsigned kOOB = 0x80000000u;
+using ds::kOOB;
+using ds::make_srd;
 
 struct Wino4Params {
     const float *x;         // [N, H, W, ldx]
@@ -98,9 +99,6 @@ struct Wino4Params {
 #define DS_W4H_RP2 3          // AR, NB = 2: positions of weight fragments in flight
 #endif
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t w4srd(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -243,7 +241,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const Wino4Params p)
     const int lt = tid >> 3, cp = tid & 7;
     const int64_t shift = (int64_t)(p.W + 1) * p.ldx;
     const unsigned xk0 = (unsigned)k0 * 16u * EB;          // this slice's first channel (bytes); the range still ends at the tensor's end
-    const __amdgpu_buffer_rsrc_t srd_x = w4srd(reinterpret_cast<const char *>(p.x) - shift * EB + xk0, p.x_bytes + (unsigned)(shift * EB) - xk0);
+    const __amdgpu_buffer_rsrc_t srd_x = make_srd(reinterpret_cast<const char *>(p.x) - shift * EB + xk0, p.x_bytes + (unsigned)(shift * EB) - xk0);
     unsigned rowoff[6];         // patch row py: the tile's base offset, or out of range (row outside the image / no tile)
     bool cv[6];                 // patch column px inside the image
     {
@@ -277,7 +275,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const Wino4Params p)
     const int ustep = p.Cout * 32;                                 // bytes between half steps (AR: pieces) of one position
     const int upos = nhalf * ustep;                                // bytes between positions
     const unsigned uk0 = (unsigned)k0 * 2u * (unsigned)ustep;      // this slice's first half step
-    const __amdgpu_buffer_rsrc_t srd_u = w4srd(reinterpret_cast<const char *>(p.u) + uk0, p.u_bytes - uk0);
+    const __amdgpu_buffer_rsrc_t srd_u = make_srd(reinterpret_cast<const char *>(p.u) + uk0, p.u_bytes - uk0);
 
     // NB = 2: 18 accumulators but 256 accumulation registers -- left to the compiler, two accumulators share 16 of them
     // and are swapped through the vector registers around their MFMAs (192 moves and two pipeline drains per K step:
@@ -571,8 +569,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const Wino4Params p)
     const int et = tid >> 3, eq = tid & 7;
     float neg1 = -1.f;
     asm volatile("" : "+s"(neg1));          // opaque -1 (see out1d)
-    const __amdgpu_buffer_rsrc_t srd_z = w4srd(p.z + (int64_t)split * p.zslab, p.z_bytes);
-    const __amdgpu_buffer_rsrc_t srd_y = w4srd(BNS ? p.y : p.z, Y16 ? p.z_bytes / 2 : p.z_bytes);
+    const __amdgpu_buffer_rsrc_t srd_z = make_srd(p.z + (int64_t)split * p.zslab, p.z_bytes);
+    const __amdgpu_buffer_rsrc_t srd_y = make_srd(BNS ? p.y : p.z, Y16 ? p.z_bytes / 2 : p.z_bytes);
     const int orow = p.W * p.ldz * 4, opix = p.ldz * 4;
     int tbase, hrem, wrem;      // pixel index of the tile's top-left output (or -1); EDGE: rows / columns inside the image
     {
