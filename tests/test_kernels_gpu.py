@@ -2397,6 +2397,68 @@ def test_every_conv_instantiation_matches_the_oracle(tuning_lib):
         lib.ds_debug_conv_set_tile(0, 0)
 
 
+# Both sides of every threshold in ds_conv_igemm's launch choice (conv_igemm.hip: wide_nb, pick_cfg, choose), worked out by hand
+# for 256 CUs: (id, N, H, W, Cin, Cout, k, statistics partials, ds_conv_igemm_bnsums_supported = the wide 1x1 kernel is chosen)
+_CHOICE_CASES = [
+    # (a) 1x1, two column blocks per wave = one column tile: the wide kernel from 128 workgroups up
+    ("a-127-workgroups-tile", 1, 127, 128, 32, 64, 1, 127, 0),           # M = 16256: 127 row tiles, 128 x 32 tile kernel
+    ("a-128-workgroups-wide", 1, 128, 128, 32, 64, 1, 128, 1),           # M = 16384
+    # (b) 1x1, M = 16384: the wide kernel pads Cout to 64 columns -- more than 1.25 x 48, not more than 1.25 x 52
+    ("b-cout48-padding-tile", 1, 128, 128, 32, 48, 1, 128, 0),
+    ("b-cout52-wide", 1, 128, 128, 32, 52, 1, 128, 1),
+    # (c) 3x3 into 64 columns: the 64-column tile from 640 = 2.5 x 256 row tiles up.  Below, two 32-column tiles per row tile on
+    # the 1-D XCD-aware grid: 638 x 2 = 1276 tiles on 1280 workgroups, four of which find nothing to do
+    ("c-638-row-tiles-nt1", 2, 202, 202, 16, 64, 3, 638, 0),
+    ("c-644-row-tiles-nt2", 2, 203, 203, 16, 64, 3, 644, 0),
+    # (d) 3x3, two row tiles: the LDS-DMA kernel where its 32-deep K tile pads the reduction by <= 12 % (Cin 48 -> 64: no)
+    ("d-cin48-k16", 1, 13, 11, 48, 32, 3, 2, 0),
+    ("d-cin64-lds-dma", 1, 13, 11, 64, 32, 3, 2, 0),
+    # (e) one workgroup per row tile up to 2048 of them, then persistent workgroups (one resident wave, a multiple of 8)
+    ("e-2048-row-tiles", 4, 256, 256, 8, 32, 3, 2048, 0),
+    ("e-2056-row-tiles-persistent", 4, 256, 257, 8, 32, 3, None, 0),
+]
+
+
+@pytest.mark.parametrize("case", _CHOICE_CASES, ids=[c[0] for c in _CHOICE_CASES])
+def test_plan_and_launch_agree_on_both_sides_of_every_launch_choice(case):
+    """The product library, nothing pinned, fp32 with DS_EPI_STATS through ops.ConvPlan: the plan's partial count is the one
+    worked out by hand, d.partials makes the launch fail if it would write another, every planned partial is written (the
+    buffer starts as NaN) and nothing behind them (a canary follows), and z and the column sums match fp64 within the bounds of
+    test_every_conv_instantiation_matches_the_oracle: z 2e-4 max|ref|, sums 1e-3 max|sum| + 1e-3."""
+    ops = _ops()
+    from tumblr_emotions_amd import _lib
+    lib = _lib.load()
+    _, N, H, W, Ci, Co, k, partials, wide = case
+    rng = np.random.RandomState(21)
+    x = rng.normal(size=(N, H, W, Ci))
+    w = rng.normal(size=(k, k, Ci, Co)) * 0.1
+    ref = S.conv2d_same(x, w, 1).reshape(-1, Co)
+    plan = ops.ConvPlan(N, H, W, Ci, Ci, k, k, 1, Co, Co, Ci * Co, 1, Co, flags=ops.DS_EPI_STATS)
+    assert lib.ds_conv_igemm_bnsums_supported(C.byref(plan.d)) == wide
+    P = plan.partials
+    if partials is None:
+        assert P % 8 == 0 and 0 < P < 2056, P
+    else:
+        assert P == partials
+    assert plan.d.partials == P
+    xd, wd = dev(x), dev(w)
+    z = torch.full((plan.M, Co), float("nan"), device="cuda")
+    buf = torch.full((2 * Co * P + 64,), float("nan"), device="cuda")
+    buf[2 * Co * P:] = 12345.0
+    plan.run(ops._p(xd), ops._p(wd), ops._p(z), stats=ops._p(buf))
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy().astype(np.float64)
+    assert (got[2 * Co * P:] == 12345.0).all(), "the launch wrote behind its %d partials" % P
+    stats = got[:2 * Co * P].reshape(2, Co, P)
+    assert not np.isnan(stats).any(), "%d of %d planned partials were not written" % (np.isnan(stats).sum(), stats.size)
+    zerr, zmax = np.abs(z.cpu().numpy() - ref).max(), np.abs(ref).max()
+    sums = ref.sum(0)
+    serr, smax = np.abs(stats[0].sum(1) - sums).max(), np.abs(sums).max()
+    print("%s: partials %d  z err %.3e (bound %.3e)  sum err %.3e (bound %.3e)" % (case[0], P, zerr, 2e-4 * zmax, serr, 1e-3 * smax + 1e-3))
+    assert zerr <= 2e-4 * zmax
+    assert serr <= 1e-3 * smax + 1e-3
+
+
 # The epilogue combinations of the shared tile / wave-row epilogues (csrc/conv_epilogue.h) that no test above pins a kernel for
 # (profiles/conv_epilogue_notes.md has the table).  One shape that reaches every guard: 1x1, M = 165 (second row tile of 128:
 # wave 0 full, wave 1 five rows, waves 2-3 none), Cin = 32, Cout = 40 (column block 1 partial), ldz = ldmask = 48.

@@ -14,7 +14,7 @@
 //     stay in flight under the MFMAs of the current tile and are waited for only at the LDS store.
 //   * 4 waves per workgroup stacked along M; each wave owns (MT*32) rows x all BN = NT*32 columns,
 //     so the tile width is chosen per layer from NT = 1..6 to fit Cout with little padding.
-//   * launch geometry (grid_for): one workgroup per row tile up to 2048 row tiles; above that the
+//   * launch geometry (choose): one workgroup per row tile up to 2048 row tiles; above that the
 //     workgroups are persistent over row tiles (grid.x a multiple of 8 so that all column tiles of
 //     a row tile, which share the A rows, land on the same XCD/L2) with the K-loop pipeline running
 //     across tiles.  BatchNorm column statistics are accumulated in registers and emitted once per
@@ -22,7 +22,9 @@
 //   * fp32 MFMA is an exact k-ordered fmaf chain (cdna_hip_programming.md section 3), so results
 //     match a scalar fp32 reference to rounding.
 #include <stdlib.h>
+#include <mutex>
 #include <type_traits>
+#include <unordered_map>
 #include "conv_epilogue.h"
 
 using ds::f32x16;
@@ -1715,6 +1717,54 @@ __global__ __launch_bounds__(256) void weights_to_f32x3_kernel(const float *w, _
 }
 
 // ---- host-side dispatch -----------------------------------------------------------------------
+typedef void (*KernelFn)(const ConvParams);
+
+int64_t conv_M(const ds_conv_desc *d) { return (int64_t)d->N * d->OH * d->OW; }
+
+// f(std::integral_constant<int, n>) with n = the runtime i in LO .. HI (values beyond an end take that end): turns a tile or
+// block count into the template argument of a kernel
+template <int LO, int HI, class F>
+KernelFn with_const(int i, F &&f) {
+    if constexpr (LO < HI)
+        if (i > LO) return with_const<LO + 1, HI>(i, f);
+    return f(std::integral_constant<int, LO>{});
+}
+
+// The tuning state of the selection rules.  The DS_* knobs are read once through ds::tune_env (the product build reads no
+// environment, so every knob keeps its default there); the ds_debug_conv_* switches of the tuning build write into it.
+struct Tuning {
+    int wide = 1;             // DS_CONV_WIDE / ds_debug_conv_set_wide, A/B aid: 0 = never, 1 = automatic, 2 = wherever the shape allows
+    int wide_cost = 0;        // DS_WIDE_COST: the A fetch in wide_nb's cost, in halves of a block
+    int wide_nb = 0;          // DS_WIDE_NB pins the wide kernel's column blocks per wave
+    int wide_min_wgs = 128;   // DS_WIDE_MINWGS (see wide_nb)
+    int wide_ring = 0;        // DS_WIDE_RING = 3 / 4: the LDS-DMA ring instantiations (see kernel_of)
+    int mt = 0, nt = 0;       // DS_CONV_CFG="mt,nt" / ds_debug_conv_set_tile pin the tile
+    int path = 0;             // DS_CONV_PATH=lds|direct|glds / ds_debug_conv_set_path pin the kernel family: 1 / 2 / 3
+    int prio = 0;             // DS_CONV_PRIO; opt-in: measured neutral-to-negative (profiles/r01_notes.md)
+    int xcd_remap = 1;        // DS_CONV_XCD_REMAP, A/B aid; default on
+    int bf16d_max_nb = 8;     // ds_debug_conv_bf16_set_max_nb
+};
+
+Tuning &tuning() {
+    static Tuning tune = [] {
+        Tuning t;
+        const auto knob = [](const char *name, int *v) {
+            if (const char *e = ds::tune_env(name)) *v = atoi(e);
+        };
+        knob("DS_CONV_WIDE", &t.wide);
+        knob("DS_WIDE_COST", &t.wide_cost);
+        knob("DS_WIDE_NB", &t.wide_nb);
+        knob("DS_WIDE_MINWGS", &t.wide_min_wgs);
+        knob("DS_WIDE_RING", &t.wide_ring);
+        knob("DS_CONV_PRIO", &t.prio);
+        knob("DS_CONV_XCD_REMAP", &t.xcd_remap);
+        if (const char *e = ds::tune_env("DS_CONV_CFG")) sscanf(e, "%d,%d", &t.mt, &t.nt);
+        if (const char *e = ds::tune_env("DS_CONV_PATH")) t.path = e[0] == 'l' ? 1 : (e[0] == 'd' ? 2 : (e[0] == 'g' ? 3 : 0));
+        return t;
+    }();
+    return tune;
+}
+
 struct TileCfg {
     int mt, nt;
     bool direct;     // register-direct kernel (tile = per-WAVE 32*mt x 32*nt) instead of the LDS kernel
@@ -1723,12 +1773,24 @@ struct TileCfg {
     int wide;        // > 0: wide 1x1 kernel, 128 rows x 32*wide columns per workgroup
 };
 
-typedef void (*KernelFn)(const ConvParams);
-
-int64_t conv_M(const ds_conv_desc *d) { return (int64_t)d->N * d->OH * d->OW; }
-
 struct Variant {
     bool bnmajor, fold, vec;
+};
+
+// A plan-time question may be put before the operand it is about is attached to the descriptor
+enum Ask { kAsIs, kBeforeBnb, kBeforePool };
+
+// Everything ds_conv_igemm's launch of a descriptor is: made by choose(), consumed by igemm_launch, ds_gemm_group and the
+// plan-time questions
+struct Launch {
+    Variant v;
+    TileCfg c;
+    bool bnr, pool, bnb;      // DS_EPI_BN_RELU / pool_argmax / bnb instantiation
+    int row_tiles, gx, gy;    // row tiles, workgroups along the rows, column tiles
+    bool one;                 // one workgroup per tile
+    dim3 grid;                // the launch's grid (z = split-K slices) ...
+    int col_tiles;            // ... and ConvParams.col_tiles: > 0 for the 1-D XCD-aware shape (TileId)
+    int partials;             // statistics partials per channel the launch writes
 };
 
 // vector (16-byte) loads are legal when every stride is a multiple of 4 floats; pointer alignment is
@@ -1741,167 +1803,73 @@ bool dims_vec(const ds_conv_desc *d) {
     return a_vec && b_vec;
 }
 
-Variant variant_of(const ds_conv_desc *d, const float *x, const float *w) {
-    Variant v;
-    v.bnmajor = d->w_n_stride == 1 && d->w_k_stride != 1;
-    v.fold = d->fold_cin > 0;
-    v.vec = dims_vec(d) && ((((uintptr_t)x | (uintptr_t)w) & 15) == 0);
-    return v;
-}
+bool aligned16(const void *x, const void *w) { return (((uintptr_t)x | (uintptr_t)w) & 15) == 0; }
 
-template <int MT, int NT>
-KernelFn lds_kernel_mn(Variant v) {
-    if (v.bnmajor) {
-        if (v.fold) return conv_igemm_kernel<MT, NT, true, true, true>;
-        return v.vec ? conv_igemm_kernel<MT, NT, true, false, true> : conv_igemm_kernel<MT, NT, true, false, false>;
-    }
-    return v.vec ? conv_igemm_kernel<MT, NT, false, false, true> : conv_igemm_kernel<MT, NT, false, false, false>;
-}
-
-template <int MT>
-KernelFn lds_kernel_m(int nt, Variant v) {
-    switch (nt) {
-        case 1: return lds_kernel_mn<MT, 1>(v);
-        case 2: return lds_kernel_mn<MT, 2>(v);
-        case 3: return lds_kernel_mn<MT, 3>(v);
-        case 4: return lds_kernel_mn<MT, 4>(v);
-        case 5: return lds_kernel_mn<MT, 5>(v);
-        default: return lds_kernel_mn<MT, 6>(v);
-    }
-}
-
-template <int MT, int NT>
-KernelFn direct_kernel_mn(Variant v) {
-    if (v.bnmajor) return v.fold ? conv_direct_kernel<MT, NT, true, true> : conv_direct_kernel<MT, NT, true, false>;
-    return conv_direct_kernel<MT, NT, false, false>;
-}
-
-template <int MT>
-KernelFn direct_kernel_m(int nt, Variant v) {
-    switch (nt) {
-        case 1: return direct_kernel_mn<MT, 1>(v);
-        case 2: return direct_kernel_mn<MT, 2>(v);
-        case 3: return direct_kernel_mn<MT, 3>(v);
-        default: return direct_kernel_mn<MT, 4>(v);
-    }
-}
-
-// DS_EPI_BN_RELU instantiations: forward (n-contiguous weights), 16-byte loads, 128-row tiles
-KernelFn bnr_kernel(TileCfg c) {
-    if (c.glds) {
-        switch (c.nt) {
-            case 1: return conv_glds_kernel<1, true, true>;
-            case 2: return conv_glds_kernel<2, true, true>;
-            default: return conv_glds_kernel<3, true, true>;
+// The kernel of a launch choice: every instantiation of the library's conv kernels is named here, in ds_conv_bf16 or in
+// ds_conv_f32x3.
+KernelFn kernel_of(const Launch &L) {
+    const TileCfg &c = L.c;
+    const Variant &v = L.v;
+    if (c.wide) {
+        if (L.bnr) {          // (bnr_ok: forward, no bnb)
+            if (L.pool)
+                return with_const<1, 4>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, true, false, true, 0, true>; });
+            return with_const<1, 8>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, true, false, false, 0, true>; });
         }
-    }
-    switch (c.nt) {
-        case 1: return conv_igemm_kernel<1, 1, true, false, true, true>;
-        case 2: return conv_igemm_kernel<1, 2, true, false, true, true>;
-        case 3: return conv_igemm_kernel<1, 3, true, false, true, true>;
-        case 4: return conv_igemm_kernel<1, 4, true, false, true, true>;
-        case 5: return conv_igemm_kernel<1, 5, true, false, true, true>;
-        default: return conv_igemm_kernel<1, 6, true, false, true, true>;
-    }
-}
-
-KernelFn glds_kernel(int nt, Variant v) {
-    switch (nt) {
-        case 1: return v.bnmajor ? conv_glds_kernel<1, true> : conv_glds_kernel<1, false>;
-        case 2: return v.bnmajor ? conv_glds_kernel<2, true> : conv_glds_kernel<2, false>;
-        default: return v.bnmajor ? conv_glds_kernel<3, true> : conv_glds_kernel<3, false>;
-    }
-}
-
-KernelFn bf16_kernel(int nt, Variant v) {
-    if (v.fold) {
-        switch (nt) {
-            case 1: return conv_bf16_kernel<1, true, true>;
-            case 2: return conv_bf16_kernel<2, true, true>;
-            case 3: return conv_bf16_kernel<3, true, true>;
-            default: return conv_bf16_kernel<4, true, true>;
-        }
-    }
-    switch (nt) {
-        case 1: return v.bnmajor ? conv_bf16_kernel<1, true, false> : conv_bf16_kernel<1, false, false>;
-        case 2: return v.bnmajor ? conv_bf16_kernel<2, true, false> : conv_bf16_kernel<2, false, false>;
-        case 3: return v.bnmajor ? conv_bf16_kernel<3, true, false> : conv_bf16_kernel<3, false, false>;
-        default: return v.bnmajor ? conv_bf16_kernel<4, true, false> : conv_bf16_kernel<4, false, false>;
-    }
-}
-
-void launch_wide(int nb, bool bnmajor, bool bnb, dim3 grid, hipStream_t st, const ConvParams &p) {
-    if (p.d.flags & DS_EPI_BN_RELU) {          // (bnr_supported: forward, no bnb)
-#define DS_WIDE_BNR(NBV, POOLV) \
-    case NBV: hipLaunchKernelGGL((gemm_wide_kernel<NBV, true, false, POOLV, 0, true>), grid, dim3(256), 0, st, p); break;
-        if (p.d.pool_argmax) {
-            switch (nb) { DS_WIDE_BNR(1, true) DS_WIDE_BNR(2, true) DS_WIDE_BNR(3, true) default: DS_WIDE_BNR(4, true) }
-        } else {
-            switch (nb) {
-                DS_WIDE_BNR(1, false) DS_WIDE_BNR(2, false) DS_WIDE_BNR(3, false) DS_WIDE_BNR(4, false)
-                DS_WIDE_BNR(5, false) DS_WIDE_BNR(6, false) DS_WIDE_BNR(7, false) default: DS_WIDE_BNR(8, false)
-            }
-        }
-#undef DS_WIDE_BNR
-        return;
-    }
-    if (p.d.pool_argmax) {          // (pool3_nb: forward, one column tile of at most four blocks)
-        switch (nb) {
-            case 1: hipLaunchKernelGGL((gemm_wide_kernel<1, true, false, true>), grid, dim3(256), 0, st, p); break;
-            case 2: hipLaunchKernelGGL((gemm_wide_kernel<2, true, false, true>), grid, dim3(256), 0, st, p); break;
-            case 3: hipLaunchKernelGGL((gemm_wide_kernel<3, true, false, true>), grid, dim3(256), 0, st, p); break;
-            default: hipLaunchKernelGGL((gemm_wide_kernel<4, true, false, true>), grid, dim3(256), 0, st, p); break;
-        }
-        return;
-    }
-    if (bnb) {          // (wide_nb: at most two column blocks per wave with ds_conv_desc.bnb)
-        if (nb == 1) hipLaunchKernelGGL((gemm_wide_kernel<1, false, true>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_wide_kernel<2, false, true>), grid, dim3(256), 0, st, p);
-        return;
-    }
-    // round-6 experiment (tuning build only: DS_WIDE_RING = 3 / 4): the A operand through an LDS-DMA ring, NB = 2 .. 4.
-    // Bit-identical and SLOWER on the sixteen 1x1 shapes of the step (profiles/r06_wide_ring.txt: forward with statistics
-    // 1705 -> 1804 us at three stages / 1957 at four, dgrad with accumulate + sums 2138 -> 2172 / 2482): the ring's LDS caps
-    // the kernel at three (two) workgroups per CU where the register form runs seven waves per SIMD -- it lives on occupancy
+        if (L.pool)          // (pool3_nb: forward, one column tile of at most four blocks)
+            return with_const<1, 4>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, true, false, true>; });
+        if (L.bnb)          // (wide_nb: at most two column blocks per wave with ds_conv_desc.bnb)
+            return with_const<1, 2>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, false, true>; });
+        // round-6 experiment (tuning build only: DS_WIDE_RING = 3 / 4): the A operand through an LDS-DMA ring, NB = 2 .. 4.
+        // Bit-identical and SLOWER on the sixteen 1x1 shapes of the step (profiles/r06_wide_ring.txt: forward with statistics
+        // 1705 -> 1804 us at three stages / 1957 at four, dgrad with accumulate + sums 2138 -> 2172 / 2482): the ring's LDS caps
+        // the kernel at three (two) workgroups per CU where the register form runs seven waves per SIMD -- it lives on occupancy
 #ifdef DS_TUNING
-    static int ring = -1;
-    if (ring < 0) {
-        const char *e = ds::tune_env("DS_WIDE_RING");
-        ring = e ? atoi(e) : 0;
-    }
-    if ((ring == 3 || ring == 4) && nb >= 2 && nb <= 4) {
-#define DS_RING(NBV, ASTV)                                                                                                   \
-        if (nb == NBV && ring == ASTV) {                                                                                     \
-            if (bnmajor) hipLaunchKernelGGL((gemm_wide_kernel<NBV, true, false, false, ASTV>), grid, dim3(256), 0, st, p);   \
-            else hipLaunchKernelGGL((gemm_wide_kernel<NBV, false, false, false, ASTV>), grid, dim3(256), 0, st, p);          \
-            return;                                                                                                          \
-        }
-        DS_RING(2, 3) DS_RING(3, 3) DS_RING(4, 3) DS_RING(2, 4) DS_RING(3, 4) DS_RING(4, 4)
-#undef DS_RING
-    }
+        const int ring = tuning().wide_ring;
+        if ((ring == 3 || ring == 4) && c.wide >= 2 && c.wide <= 4)
+            return with_const<2, 4>(c.wide, [&](auto nb) {
+                return with_const<3, 4>(ring, [&](auto ast) {
+                    return v.bnmajor ? gemm_wide_kernel<decltype(nb)::value, true, false, false, decltype(ast)::value>
+                                     : gemm_wide_kernel<decltype(nb)::value, false, false, false, decltype(ast)::value>;
+                });
+            });
 #endif
-#define DS_WIDE(NBV)                                                                                      \
-    case NBV:                                                                                             \
-        if (bnmajor) hipLaunchKernelGGL((gemm_wide_kernel<NBV, true>), grid, dim3(256), 0, st, p);        \
-        else hipLaunchKernelGGL((gemm_wide_kernel<NBV, false>), grid, dim3(256), 0, st, p);               \
-        break;
-    switch (nb) {
-        DS_WIDE(1)
-        DS_WIDE(2)
-        DS_WIDE(3)
-        DS_WIDE(4)
-        DS_WIDE(5)
-        DS_WIDE(6)
-        DS_WIDE(7)
-        default:
-        DS_WIDE(8)
+        return with_const<1, 8>(c.wide, [&](auto nb) {
+            return v.bnmajor ? gemm_wide_kernel<decltype(nb)::value, true> : gemm_wide_kernel<decltype(nb)::value, false>;
+        });
     }
-#undef DS_WIDE
+    if (L.bnr) {          // DS_EPI_BN_RELU instantiations: forward (n-contiguous weights), 16-byte loads, 128-row tiles
+        if (c.glds) return with_const<1, 3>(c.nt, [](auto nt) { return conv_glds_kernel<decltype(nt)::value, true, true>; });
+        return with_const<1, 6>(c.nt, [](auto nt) { return conv_igemm_kernel<1, decltype(nt)::value, true, false, true, true>; });
+    }
+    if (c.bf16)
+        return with_const<1, 4>(c.nt, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if (v.fold) return conv_bf16_kernel<NT, true, true>;
+            return v.bnmajor ? conv_bf16_kernel<NT, true, false> : conv_bf16_kernel<NT, false, false>;
+        });
+    if (c.glds)
+        return with_const<1, 3>(c.nt, [&](auto nt) {
+            return v.bnmajor ? conv_glds_kernel<decltype(nt)::value, true> : conv_glds_kernel<decltype(nt)::value, false>;
+        });
+    return with_const<1, 2>(c.mt == 2 ? 2 : 1, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        if (c.direct)
+            return with_const<1, 4>(c.nt, [&](auto nt) {
+                constexpr int NT = decltype(nt)::value;
+                if (v.bnmajor) return v.fold ? conv_direct_kernel<MT, NT, true, true> : conv_direct_kernel<MT, NT, true, false>;
+                return conv_direct_kernel<MT, NT, false, false>;
+            });
+        return with_const<1, 6>(c.nt, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if (v.bnmajor) {
+                if (v.fold) return conv_igemm_kernel<MT, NT, true, true, true>;
+                return v.vec ? conv_igemm_kernel<MT, NT, true, false, true> : conv_igemm_kernel<MT, NT, true, false, false>;
+            }
+            return v.vec ? conv_igemm_kernel<MT, NT, false, false, true> : conv_igemm_kernel<MT, NT, false, false, false>;
+        });
+    });
 }
-
-// Column blocks per wave of the wide 1x1 kernel for `d`, or 0 when the layer stays on the LDS-tile kernels:
-// plain 1x1 stride-1 GEMM shape, flags within {STATS}, vector-aligned, no split-K, enough workgroups to fill the chip.
-int force_wide = -1;
 
 // MaxPool 3x3/1 on load (ds_conv_desc.pool_argmax): forward 1x1 conv with n-contiguous weights on a map at most 32 wide
 // (a wave's 32-row block holds whole image rows), whole 16-channel K steps, ONE column tile of at most four blocks (the
@@ -1923,13 +1891,12 @@ void pool3_blocks(const ds_conv_desc *d, int *rpb, int *bpi) {
     *bpi = (d->H + *rpb - 1) / *rpb;
 }
 
-int wide_nb(const ds_conv_desc *d, bool vec, bool bnb_cap = false) {
-    if (d->pool_argmax) return pool3_nb(d, vec);
-    if (force_wide < 0) {
-        const char *e = ds::tune_env("DS_CONV_WIDE");          // A/B aid: 0 = never
-        force_wide = e ? atoi(e) : 1;
-    }
-    if (!force_wide || !vec || d->dtype != DS_DTYPE_F32) return 0;
+// Column blocks per wave of the wide 1x1 kernel for `d`, or 0 when the layer stays on the LDS-tile kernels:
+// plain 1x1 stride-1 GEMM shape, flags within {STATS}, vector-aligned, no split-K, enough workgroups to fill the chip.
+int wide_nb(const ds_conv_desc *d, bool vec, Ask ask) {
+    if (d->pool_argmax || ask == kBeforePool) return pool3_nb(d, vec);
+    const Tuning &t = tuning();
+    if (!t.wide || !vec || d->dtype != DS_DTYPE_F32) return 0;
     if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->fold_cin || d->splits > 1) return 0;
     if (d->flags & ~(DS_EPI_STATS | DS_EPI_ACCUM | DS_EPI_BNSUMS | DS_EPI_BN_RELU)) return 0;
     if (d->Cin % 8 != 0 || d->Cin < 32) return 0;
@@ -1943,82 +1910,50 @@ int wide_nb(const ds_conv_desc *d, bool vec, bool bnb_cap = false) {
     // for the A fetch it does not share.  Pick the NB with the least of that (ties to the wider tile).
     int best = 0, best_pad = 0;
     int64_t best_cost = (int64_t)1 << 60;
-    static int cA = -1;
-    if (cA < 0) {
-        const char *e = ds::tune_env("DS_WIDE_COST");
-        cA = e ? atoi(e) : 0;                                    // in halves of a block
-    }
     const int64_t row_tiles = (M + 127) / 128;
     // (BatchNorm backward on load is kept for narrow dgrads only -- it wins on Conv2d_2b and nowhere else,
     // profiles/r04_bnb_layers.txt -- so its loader is instantiated for one and two column blocks per wave)
-    const int nb_max = (d->bnb || bnb_cap) ? 2 : 8;      // (bnb_cap: ds_conv_igemm_bnb_supported asks before bnb is attached)
+    const int nb_max = (d->bnb || ask == kBeforeBnb) ? 2 : 8;
     for (int nb = nb_max; nb >= (N <= 32 ? 1 : 2); --nb) {      // one block per wave only where two would be half padding
         const int tiles = (N + 32 * nb - 1) / (32 * nb);
         const int64_t rounds = (row_tiles * tiles + ds::kCUs - 1) / ds::kCUs;
-        const int64_t cost = rounds * (2 * nb + cA);
+        const int64_t cost = rounds * (2 * nb + t.wide_cost);
         if (cost < best_cost) { best_cost = cost; best = nb; best_pad = tiles * 32 * nb; }
     }
-    static int pin_nb = -1;                                      // tuning aid: DS_WIDE_NB pins the column blocks per wave
-    if (pin_nb < 0) {
-        const char *e = ds::tune_env("DS_WIDE_NB");
-        pin_nb = e ? atoi(e) : 0;
-    }
-    if (pin_nb >= 1 && pin_nb <= nb_max) {
-        best = pin_nb;
+    if (t.wide_nb >= 1 && t.wide_nb <= nb_max) {
+        best = t.wide_nb;
         best_pad = (N + 32 * best - 1) / (32 * best) * 32 * best;
     }
-    const int64_t wgs = (M + 127) / 128 * ((N + 32 * best - 1) / (32 * best));
+    const int64_t wgs = row_tiles * ((N + 32 * best - 1) / (32 * best));
     // measured per shape (profiles/r02_wide_layers.txt): wins 1.1-1.4x except with one mostly padded column tile or too
     // few workgroups to cover the CUs (7x7 maps with N <= 128)
-    static int min_wgs = -1;
-    if (min_wgs < 0) {
-        const char *e = ds::tune_env("DS_WIDE_MINWGS");
-        min_wgs = e ? atoi(e) : 128;
-    }
-    if (force_wide < 2 && (wgs < min_wgs || best_pad * 100 > N * 125)) return 0;
+    if (t.wide < 2 && (wgs < t.wide_min_wgs || best_pad * 100 > N * 125)) return 0;
     return best;
-}
-
-KernelFn kernel_for(TileCfg c, Variant v) {
-    if (c.bf16) return bf16_kernel(c.nt, v);
-    if (c.glds) return glds_kernel(c.nt, v);
-    if (c.direct) return c.mt == 2 ? direct_kernel_m<2>(c.nt, v) : direct_kernel_m<1>(c.nt, v);
-    return c.mt == 2 ? lds_kernel_m<2>(c.nt, v) : lds_kernel_m<1>(c.nt, v);
 }
 
 // Resident workgroups per CU of one instantiation (register/LDS limited), queried once and cached.
 // The persistent grid is sized to exactly one resident wave of workgroups so no CU idles while a
 // partial second wave runs; correctness never depends on it (no inter-workgroup communication).
-int resident_per_cu(TileCfg c, Variant v) {
-    static int cache[4][2][8][2][2][2];
-    int &slot = cache[c.bf16 ? 3 : (c.glds ? 2 : (int)c.direct)][c.mt - 1][c.nt - 1][v.bnmajor][v.fold][v.vec];
+int resident_per_cu(KernelFn kernel) {
+    static std::unordered_map<const void *, int> cache;
+    static std::mutex guard;          // (plans are made from one thread per device)
+    const std::lock_guard<std::mutex> lock(guard);
+    int &slot = cache[(const void *)kernel];
     if (slot == 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kernel_for(c, v), 256, 0) != hipSuccess || n < 1)
-            n = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kernel, 256, 0) != hipSuccess || n < 1) n = 1;
         slot = n > 8 ? 8 : n;
     }
     return slot;
 }
 
-// tuning aids: ds_debug_conv_set_tile() / DS_CONV_CFG="mt,nt" pin the tile; ds_debug_conv_set_path() /
-// DS_CONV_PATH=lds|direct pins the kernel family
-int force_mt = -1, force_nt = -1, force_path = -1;
-
-TileCfg pick_cfg(const ds_conv_desc *d, bool vec) {
-    if (force_mt < 0) {
-        force_mt = force_nt = 0;
-        if (const char *e = ds::tune_env("DS_CONV_CFG")) sscanf(e, "%d,%d", &force_mt, &force_nt);
-    }
-    if (force_path < 0) {
-        force_path = 0;
-        if (const char *e = ds::tune_env("DS_CONV_PATH")) force_path = e[0] == 'l' ? 1 : (e[0] == 'd' ? 2 : (e[0] == 'g' ? 3 : 0));
-    }
+TileCfg pick_cfg(const ds_conv_desc *d, bool vec, Ask ask) {
+    const Tuning &t = tuning();
     const int64_t M = conv_M(d);
     const int N = d->Cout;
     const int pad32 = (N + 31) / 32 * 32, pad64 = (N + 63) / 64 * 64;
     TileCfg c = {1, 1, false, false, false, 0};
-    if (int nb = wide_nb(d, vec)) {
+    if (int nb = wide_nb(d, vec, ask)) {
         c.wide = nb;
         c.nt = nb;
         return c;
@@ -2033,13 +1968,13 @@ TileCfg pick_cfg(const ds_conv_desc *d, bool vec) {
         }
         c.nt = N <= 32 ? 1 : best;
         if (d->tile_nt > 0) c.nt = d->tile_nt > 4 ? 4 : d->tile_nt;
-        if (force_nt > 0) c.nt = force_nt > 4 ? 4 : force_nt;
+        if (t.nt > 0) c.nt = t.nt > 4 ? 4 : t.nt;
         return c;
     }
     // Measured (profiles/r01_lds_vs_direct_sweep.txt): the LDS-staged kernel wins on every shape of this
     // model -- fragment-shaped global loads touch 32 cache lines per wave instruction and are TA-bound --
     // so the register-direct family is opt-in only.
-    c.direct = vec && force_path == 2;
+    c.direct = vec && t.path == 2;
     if (c.direct) {
         // per-WAVE tile 32*mt x 32*nt
         const int64_t row_tiles = (M + 31) / 32;
@@ -2051,16 +1986,16 @@ TileCfg pick_cfg(const ds_conv_desc *d, bool vec) {
         if (pad64 * 100 <= pad32 * 112 && row_tiles * (pad64 / 64) >= 5 * ds::kCUs / 2) c.nt = 2;
     }
     if (d->tile_nt > 0 && !c.direct) c.nt = d->tile_nt > 6 ? 6 : d->tile_nt;     // per-layer choice (tuning table)
-    if (force_mt > 0) c.mt = force_mt;
-    if (force_nt > 0) c.nt = force_nt;
+    if (t.mt > 0) c.mt = t.mt;
+    if (t.nt > 0) c.nt = t.nt;
     if (c.direct && c.nt > 4) c.nt = 4;
     // LDS-DMA kernel (K-tile 32): needs 16-byte aligned operands and no folded stem.  Automatic for the
     // multi-tap convs whose reduction the 32-deep K-tile pads by no more than ~12 % over the 16-deep one:
     // measured 3-10 % faster there (long K loops), 5-10 % slower on the 1x1 layers whose 9-26 K-tiles
     // leave the prologue/epilogue exposed (profiles/r01_glds_sweep.txt).
-    if (!c.direct && vec && d->fold_cin == 0 && force_path != 1) {
+    if (!c.direct && vec && d->fold_cin == 0 && t.path != 1) {
         const int k16 = (d->Cin + 15) / 16 * 16, k32 = (d->Cin + 31) / 32 * 32;
-        if (force_path == 3 || (d->KH * d->KW >= 4 && k32 * 100 <= k16 * 112)) {
+        if (t.path == 3 || (d->KH * d->KW >= 4 && k32 * 100 <= k16 * 112)) {
             c.glds = true;
             c.mt = 1;
             if (c.nt > 3) c.nt = 3;
@@ -2079,45 +2014,153 @@ TileCfg pick_cfg(const ds_conv_desc *d, bool vec) {
 //     hundred partials per channel instead of one per row tile.
 constexpr int kOneTilePerWg = 2048;
 
-void grid_for(const ds_conv_desc *d, TileCfg c, Variant v, int *gx, int *gy, int *row_tiles, bool *one_per_tile = nullptr) {
-    const int64_t M = conv_M(d);
+// The launch ds_conv_igemm makes of `d` with operand pointers that are (`aligned`) or are not 16-byte aligned
+Launch choose(const ds_conv_desc *d, bool aligned, Ask ask = kAsIs) {
+    Launch L;
+    L.v = {d->w_n_stride == 1 && d->w_k_stride != 1, d->fold_cin > 0, dims_vec(d) && aligned};
+    const TileCfg c = L.c = pick_cfg(d, L.v.vec, ask);
+    L.bnr = false;          // (a DS_EPI_BN_RELU launch keeps the grid the descriptor gets without the flag)
+    L.pool = d->pool_argmax || ask == kBeforePool;
+    L.bnb = d->bnb != nullptr;
     const int bm = (c.direct ? 32 : 128) * (c.glds ? 1 : c.mt), bn = 32 * c.nt;
-    *row_tiles = (int)((M + bm - 1) / bm);
-    if (c.wide && d->pool_argmax) {          // 32-row blocks of whole image rows, four per workgroup
+    L.row_tiles = (int)((conv_M(d) + bm - 1) / bm);
+    if (c.wide && L.pool) {          // 32-row blocks of whole image rows, four per workgroup
         int rpb, bpi;
         pool3_blocks(d, &rpb, &bpi);
-        *row_tiles = (int)(((int64_t)d->N * bpi + 3) / 4);
+        L.row_tiles = (int)(((int64_t)d->N * bpi + 3) / 4);
     }
-    *gy = (d->Cout + bn - 1) / bn;
-    const int wg_tiles = c.direct ? (*row_tiles + 3) / 4 : *row_tiles;     // row tiles in units of workgroups
-    int x;
-    bool one = false;
-    if (c.wide) {                       // wide 1x1 kernel: always one workgroup per (row group, column tile)
-        x = wg_tiles;
-        one = true;
-    } else if (wg_tiles <= kOneTilePerWg && !c.direct) {
-        x = wg_tiles;
-        one = true;
-    } else {
-        int target = (resident_per_cu(c, v) * ds::kCUs) / *gy;             // one resident wave of workgroups
+    L.gy = (d->Cout + bn - 1) / bn;
+    const int wg_tiles = c.direct ? (L.row_tiles + 3) / 4 : L.row_tiles;     // row tiles in units of workgroups
+    L.gx = wg_tiles;
+    L.one = true;
+    // (the wide 1x1 kernel: always one workgroup per (row group, column tile))
+    if (!c.wide && (wg_tiles > kOneTilePerWg || c.direct)) {
+        int target = (resident_per_cu(kernel_of(L)) * ds::kCUs) / L.gy;             // one resident wave of workgroups
         if (target < 8) target = 8;
-        x = wg_tiles < target ? wg_tiles : target;
-        if (x >= 8) x &= ~7;                  // multiple of 8: column tiles of a row tile share an XCD
+        L.gx = wg_tiles < target ? wg_tiles : target;
+        if (L.gx >= 8) L.gx &= ~7;                  // multiple of 8: column tiles of a row tile share an XCD
+        L.one = false;
     }
     if (d->grid_x > 0 && !c.direct) {       // per-layer override
-        x = d->grid_x < wg_tiles ? d->grid_x : wg_tiles;
-        one = x == wg_tiles;
+        L.gx = d->grid_x < wg_tiles ? d->grid_x : wg_tiles;
+        L.one = L.gx == wg_tiles;
     }
-    *gx = x;
-    if (one_per_tile) *one_per_tile = one;
+    L.bnr = (d->flags & DS_EPI_BN_RELU) != 0;
+    L.grid = dim3(L.gx, L.gy, d->splits > 1 ? d->splits : 1);
+    L.col_tiles = 0;
+    if (L.one && (c.wide || (tuning().xcd_remap && L.gy > 1)) && !c.direct) {    // one workgroup per tile: 1-D XCD-aware launch (TileId)
+        L.col_tiles = L.gy;
+        L.grid = dim3((L.row_tiles * L.gy + 7) / 8 * 8, 1, L.grid.z);
+    }
+    L.partials = c.direct ? L.gx * 4 : L.gx;
+    return L;
 }
 
 // Would the launch picked for `d` carry DS_EPI_BN_RELU?  The forward fp32 instantiations: n-contiguous weights, 16-byte loads
 // (pointer alignment is checked at launch), 128-row tiles of the LDS / LDS-DMA kernels or the wide 1x1 kernel.
-bool bnr_supported(const ds_conv_desc *d, TileCfg c, Variant v) {
-    if (d->dtype != DS_DTYPE_F32 || !v.bnmajor || !v.vec || v.fold || d->splits > 1 || d->bnb || d->fin) return false;
-    if (c.bf16 || c.direct || c.mt != 1) return false;
-    return true;
+bool bnr_ok(const ds_conv_desc *d, const Launch &L) {
+    if (d->dtype != DS_DTYPE_F32 || !L.v.bnmajor || !L.v.vec || L.v.fold || d->splits > 1 || d->bnb || d->fin) return false;
+    return !L.c.bf16 && !L.c.direct && L.c.mt == 1;
+}
+
+// What the four launchers of this file fill alike: the operands, M, the taps and the extents of the two buffer descriptors
+// (bytes from the operand pointer to the last element read; `prepared_w_bytes` < 0: the strided filter `d` describes)
+int fill_params(ConvParams &p, const char *who, const char *hint, const ds_conv_desc *d, const void *x, const void *w, float *z,
+                const void *mask, float *stats, const float *pivot, int64_t prepared_w_bytes = -1) {
+    p = ConvParams{};
+    p.d = *d;
+    if (d->splits <= 1) p.d.z_split_stride = 0;
+    p.x = (const float *)x; p.w = (const float *)w; p.z = z; p.mask = (const float *)mask; p.stats = stats;
+    p.pivot = (d->flags & DS_EPI_STATS) ? pivot : nullptr;
+    p.M = (int)conv_M(d);
+    p.taps = d->KH * d->KW;
+    const int64_t x_elems = ((int64_t)d->N * d->H * d->W - 1) * d->ldx + (d->fold_cin > 0 ? d->fold_cin : d->Cin);
+    const int64_t w_elems = (int64_t)(p.taps - 1) * d->w_tap_stride + (int64_t)(d->Cout - 1) * d->w_n_stride +
+                            (int64_t)(d->Cin - 1) * d->w_k_stride + 1;
+    const int64_t w_bytes = prepared_w_bytes < 0 ? w_elems * 4 : prepared_w_bytes;
+    DS_REQUIRE(x_elems * 4 < (1ll << 31) && w_bytes < (1ll << 31), "%s: operand larger than 2 GiB%s", who, hint);
+    p.x_bytes = (unsigned)(x_elems * 4);
+    p.w_bytes = (unsigned)w_bytes;
+    return DS_OK;
+}
+
+int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *bias, const float *mask,
+                 float *stats, const float *pivot, const float *scale, const float *shift, void *stream) {
+    DS_REQUIRE(d && x && w && z, "ds_conv_igemm: null argument");
+    DS_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->N > 0 && d->OH > 0 && d->OW > 0, "ds_conv_igemm: bad dims");
+    DS_REQUIRE(d->w_n_stride == 1 || d->w_k_stride == 1, "ds_conv_igemm: one weight stride must be 1");
+    DS_REQUIRE(!(d->flags & DS_EPI_BIAS) || bias, "ds_conv_igemm: DS_EPI_BIAS without bias");
+    DS_REQUIRE(!(d->flags & DS_EPI_MASK) || mask, "ds_conv_igemm: DS_EPI_MASK without mask");
+    DS_REQUIRE(!(d->flags & DS_EPI_STATS) || stats, "ds_conv_igemm: DS_EPI_STATS without stats buffer");
+    DS_REQUIRE(!(d->flags & DS_EPI_BNSUMS) || (stats && mask && !(d->flags & (DS_EPI_STATS | DS_EPI_MASK)) && d->ldmask >= d->Cout),
+               "ds_conv_igemm: DS_EPI_BNSUMS needs the partials buffer (stats), y (mask, ldmask) and excludes STATS / MASK");
+    DS_REQUIRE(conv_M(d) < (1ll << 31), "ds_conv_igemm: M too large");
+    DS_REQUIRE(d->dtype == DS_DTYPE_F32 || d->dtype == DS_DTYPE_BF16, "ds_conv_igemm: dtype must be DS_DTYPE_F32 or DS_DTYPE_BF16");
+    const Launch L = choose(d, aligned16(x, w));
+    const Variant &v = L.v;
+    const TileCfg &c = L.c;
+    DS_REQUIRE(!(d->flags & DS_EPI_STATS) || v.vec == dims_vec(d),
+               "ds_conv_igemm: DS_EPI_STATS needs 16-byte aligned operand pointers");
+
+    ConvParams p;
+    if (int rc = fill_params(p, "ds_conv_igemm", " (split the batch)", d, x, w, z, mask, stats, pivot)) return rc;
+    p.bias = bias;
+    p.prio_mode = tuning().prio;
+    DS_REQUIRE(!v.fold || (v.bnmajor && v.vec && d->KW == 1 && d->fold_cin % 4 == 0 && d->ldx == d->fold_cin),
+               "ds_conv_igemm: fold_cin needs KW=1, n-contiguous 16-byte-aligned weights, ldx==fold_cin");
+
+    DS_REQUIRE(d->dtype != DS_DTYPE_BF16 || (v.vec && d->splits <= 1),
+               "ds_conv_igemm: DS_DTYPE_BF16 needs 16-byte aligned operands with channel counts / strides divisible by 4, no split-K");
+    DS_REQUIRE(d->splits <= 1 || (d->flags == 0 && d->z_split_stride >= (int64_t)(conv_M(d) - 1) * d->ldz + d->Cout),
+               "ds_conv_igemm: split-K needs flags == 0 and non-overlapping output slabs");
+    DS_REQUIRE(!L.bnr || (d->flags == DS_EPI_BN_RELU && scale && shift && bnr_ok(d, L)),
+               "ds_conv_igemm: DS_EPI_BN_RELU excludes every other epilogue flag, needs scale / shift and a forward fp32 launch "
+               "with 16-byte aligned operands (ds_conv_plan_enable_bn_relu)");
+    p.scale = scale; p.shift = shift;
+    DS_REQUIRE((!d->norm_rstd && !d->norm_shift) || (c.wide && d->norm_rstd && d->norm_shift && d->Cin <= 1024),
+               "ds_conv_igemm: norm_rstd / norm_shift are implemented by the wide 1x1 kernel only (ds_conv_igemm_norm_supported)");
+    DS_REQUIRE((!d->mask_rstd && !d->mask_shift) || ((d->flags & DS_EPI_BNSUMS) && d->mask_rstd && d->mask_shift),
+               "ds_conv_igemm: mask_rstd / mask_shift go with DS_EPI_BNSUMS");
+    DS_REQUIRE(!(d->flags & DS_EPI_BNSUMS) || c.wide,
+               "ds_conv_igemm: DS_EPI_BNSUMS is implemented by the wide 1x1 kernel only (ds_conv_igemm_bnsums_supported)");
+    // the statistics partial count the caller planned with (ds_conv_igemm_partials at plan time) must be the one this
+    // launch writes: the tile choice depends on debug switches / environment caches that may have changed since
+    DS_REQUIRE(!(d->flags & (DS_EPI_STATS | DS_EPI_BNSUMS)) || d->partials <= 0 || d->partials == L.partials,
+               "ds_conv_igemm: the launch would write %d statistics partials but the plan was made for %d "
+               "(a ds_debug_conv_set_* switch changed after planning?)", L.partials, d->partials);
+    p.row_tiles = L.row_tiles;
+    p.col_tiles = L.col_tiles;
+    if (d->bnb) {
+        const ds_bn_bwd_on_load &b = *d->bnb;
+        DS_REQUIRE(c.wide && !v.bnmajor && d->Cin <= 1024 && !d->norm_rstd,
+                   "ds_conv_igemm: ds_conv_desc.bnb is implemented by the wide 1x1 kernel for k-contiguous weights only "
+                   "(ds_conv_igemm_bnb_supported)");
+        DS_REQUIRE(b.mean && b.rstd && b.shift && b.coef && b.nseg >= 1 && b.nseg <= 3 && b.c_end[b.nseg - 1] == d->Cin,
+                   "ds_conv_igemm: bnb needs mean / rstd / shift / coef and 1..3 channel ranges that end at Cin");
+        for (int i = 0; i < b.nseg; ++i) {
+            const int cb = i ? b.c_end[i - 1] : 0;
+            DS_REQUIRE(b.dy[i] && (((uintptr_t)b.dy[i]) & 15) == 0 && b.ld[i] % 4 == 0 && b.c_end[i] > cb && cb % 16 == 0 &&
+                           b.ld[i] >= b.c_end[i] - cb && ((int64_t)(p.M - 1) * b.ld[i] + (b.c_end[i] - cb)) * 4 < (1ll << 31),
+                       "ds_conv_igemm: bnb channel range %d (16-byte aligned dy, ld %% 4 == 0, boundaries %% 16 == 0)", i);
+        }
+        p.bnb = b;
+    }
+    if (d->fin) {
+        DS_REQUIRE(c.wide && (d->flags & DS_EPI_STATS) && L.row_tiles <= 256 && d->fin->ticket && d->fin->beta && d->fin->mean &&
+                       d->fin->rstd && d->fin->shift && d->fin->count > 0,
+                   "ds_conv_igemm: ds_conv_desc.fin needs a DS_EPI_STATS launch of the wide 1x1 kernel with at most 256 partials "
+                   "(ds_conv_igemm_finalize_tickets) and beta / mean / rstd / shift / ticket / count");
+        p.fin = *d->fin;
+        p.fin_inv_count = 1.0 / (double)d->fin->count;
+    }
+    if (d->pool_argmax) {
+        DS_REQUIRE(c.wide && v.bnmajor && !d->bnb,
+                   "ds_conv_igemm: ds_conv_desc.pool_argmax is implemented by the wide 1x1 kernel's forward instantiation only "
+                   "(ds_conv_igemm_pool3_supported)");
+        pool3_blocks(d, &p.pool_rpb, &p.pool_bpi);
+    }
+    hipLaunchKernelGGL(kernel_of(L), L.grid, dim3(256), 0, (hipStream_t)stream, p);
+    return ds::check_launch("ds_conv_igemm");
 }
 
 }  // namespace
@@ -2125,60 +2168,53 @@ bool bnr_supported(const ds_conv_desc *d, TileCfg c, Variant v) {
 #ifdef DS_TUNING
 extern "C" int ds_debug_conv_set_tile(int mt, int nt) {
     DS_REQUIRE((mt == 0 && nt == 0) || ((mt == 1 || mt == 2) && nt >= 1 && nt <= 6), "ds_debug_conv_set_tile: mt in {1,2}, nt in 1..6, or 0,0 = automatic");
-    force_mt = mt;
-    force_nt = nt;
+    tuning().mt = mt;
+    tuning().nt = nt;
     return DS_OK;
 }
-#endif
 
-#ifdef DS_TUNING
 extern "C" int ds_debug_conv_set_wide(int mode) {
     DS_REQUIRE(mode >= 0 && mode <= 2, "ds_debug_conv_set_wide: 0 = never, 1 = automatic, 2 = wherever the shape allows");
-    force_wide = mode;
+    tuning().wide = mode;
     return DS_OK;
 }
-#endif
 
-#ifdef DS_TUNING
 extern "C" int ds_debug_conv_set_path(int path) {
     DS_REQUIRE(path >= 0 && path <= 3, "ds_debug_conv_set_path: 0 = automatic, 1 = register-staged LDS kernel, 2 = register-direct kernel, 3 = LDS-DMA kernel");
-    force_path = path;
+    tuning().path = path;
     return DS_OK;
+}
+
+extern "C" int ds_debug_conv_bf16_set_max_nb(int nb) {
+    DS_REQUIRE(nb >= 1 && nb <= 8, "ds_debug_conv_bf16_set_max_nb: 1 .. 8 column blocks per wave");
+    tuning().bf16d_max_nb = nb;
+    return 0;
 }
 #endif
 
-extern "C" int ds_conv_igemm_partials(const ds_conv_desc *d) {
-    // BatchNorm convs are always 16-byte aligned in this model; ds_conv_igemm refuses DS_EPI_STATS
-    // when the operands turn out not to be, so the count returned here is the one the launch uses.
-    Variant v;
-    v.bnmajor = d->w_n_stride == 1 && d->w_k_stride != 1;
-    v.fold = d->fold_cin > 0;
-    v.vec = dims_vec(d);
-    const TileCfg c = pick_cfg(d, v.vec);
-    int gx, gy, rt;
-    grid_for(d, c, v, &gx, &gy, &rt);
-    return c.direct ? gx * 4 : gx;
-}
+// ---- plan-time questions: each is asked of the launch choose() makes, with 16-byte aligned operands assumed (BatchNorm convs
+// are always aligned in this model; ds_conv_igemm refuses DS_EPI_STATS when the operands turn out not to be, so the count
+// returned here is the one the launch uses)
+extern "C" int ds_conv_igemm_partials(const ds_conv_desc *d) { return choose(d, true).partials; }
 
 extern "C" int ds_conv_igemm_bnsums_supported(const ds_conv_desc *d) {
-    // DS_EPI_BNSUMS lives in the wide 1x1 kernel's epilogue: supported where that kernel is the one chosen (16-byte
-    // aligned operands assumed, as for ds_conv_igemm_partials)
+    // DS_EPI_BNSUMS lives in the wide 1x1 kernel's epilogue: supported where that kernel is the one chosen
     if (!d) return 0;
     ds_conv_desc t = *d;
     t.flags = (t.flags & DS_EPI_ACCUM) | DS_EPI_BNSUMS;
-    return wide_nb(&t, dims_vec(&t)) > 0 ? 1 : 0;
+    return choose(&t, true).c.wide > 0 ? 1 : 0;
 }
 
 extern "C" int ds_conv_igemm_norm_supported(const ds_conv_desc *d) {
     // BatchNorm + ReLU on load lives in the wide 1x1 kernel's loader (Cin <= 1024: the per-channel values sit in LDS)
     if (!d || d->Cin > 1024) return 0;
-    return wide_nb(d, dims_vec(d)) > 0 ? 1 : 0;
+    return choose(d, true).c.wide > 0 ? 1 : 0;
 }
 
 extern "C" int ds_conv_igemm_pool3_supported(const ds_conv_desc *d) {
     // the 3x3 / 1 max pool on load lives in the wide 1x1 kernel's loader (forward instantiation)
     if (!d) return 0;
-    return pool3_nb(d, dims_vec(d)) > 0 ? 1 : 0;
+    return choose(d, true, kBeforePool).c.wide > 0 ? 1 : 0;
 }
 
 extern "C" int ds_conv_igemm_finalize_tickets(const ds_conv_desc *d) {
@@ -2188,12 +2224,8 @@ extern "C" int ds_conv_igemm_finalize_tickets(const ds_conv_desc *d) {
     ds_conv_desc t = *d;
     t.partials = 0;
     t.fin = nullptr;
-    const Variant v = {t.w_n_stride == 1 && t.w_k_stride != 1, t.fold_cin > 0, dims_vec(&t)};
-    const TileCfg c = pick_cfg(&t, v.vec);
-    if (!c.wide) return 0;
-    int gx, gy, rt;
-    grid_for(&t, c, v, &gx, &gy, &rt);
-    return rt <= 256 ? gy : 0;
+    const Launch L = choose(&t, true);
+    return L.c.wide && L.row_tiles <= 256 ? L.gy : 0;
 }
 
 // ds_conv_plan_enable_bn_relu's question for this family: would the launch picked for `d` carry DS_EPI_BN_RELU?  (forward
@@ -2204,20 +2236,14 @@ int conv_igemm_bn_relu_supported(const ds_conv_desc *d) {
     if (!d || (d->flags & ~DS_EPI_BN_RELU)) return 0;
     ds_conv_desc t = *d;
     t.flags = DS_EPI_BN_RELU;
-    const Variant v = {t.w_n_stride == 1 && t.w_k_stride != 1, t.fold_cin > 0, dims_vec(&t)};
-    return bnr_supported(&t, pick_cfg(&t, v.vec), v) ? 1 : 0;
+    return bnr_ok(&t, choose(&t, true)) ? 1 : 0;
 }
 }  // namespace ds
 
 extern "C" int ds_conv_igemm_bnb_supported(const ds_conv_desc *d) {
     // BatchNorm backward on load lives in the wide 1x1 kernel's loader, k-contiguous-weights (dgrad) instantiation
     if (!d || d->Cin > 1024 || (d->w_n_stride == 1 && d->w_k_stride != 1) || d->norm_rstd) return 0;
-    return wide_nb(d, dims_vec(d), true) > 0 ? 1 : 0;      // with the launch's own cap of two column blocks per wave
-}
-
-namespace {
-int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *bias, const float *mask,
-                 float *stats, const float *pivot, const float *scale, const float *shift, void *stream);
+    return choose(d, true, kBeforeBnb).c.wide > 0 ? 1 : 0;      // with the launch's own cap of two column blocks per wave
 }
 
 extern "C" int ds_conv_igemm(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *bias,
@@ -2235,131 +2261,10 @@ int conv_igemm_bn_relu(const ds_conv_desc *d, const float *x, const float *w, fl
 }
 }  // namespace ds
 
-namespace {
-int xcd_remap_on() {
-    static int xcd_remap = -1;
-    if (xcd_remap < 0) {
-        const char *e = ds::tune_env("DS_CONV_XCD_REMAP");      // A/B aid; default on
-        xcd_remap = e ? atoi(e) : 1;
-    }
-    return xcd_remap;
-}
-
-int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z, const float *bias, const float *mask,
-                 float *stats, const float *pivot, const float *scale, const float *shift, void *stream) {
-    DS_REQUIRE(d && x && w && z, "ds_conv_igemm: null argument");
-    DS_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->N > 0 && d->OH > 0 && d->OW > 0, "ds_conv_igemm: bad dims");
-    DS_REQUIRE(d->w_n_stride == 1 || d->w_k_stride == 1, "ds_conv_igemm: one weight stride must be 1");
-    DS_REQUIRE(!(d->flags & DS_EPI_BIAS) || bias, "ds_conv_igemm: DS_EPI_BIAS without bias");
-    DS_REQUIRE(!(d->flags & DS_EPI_MASK) || mask, "ds_conv_igemm: DS_EPI_MASK without mask");
-    DS_REQUIRE(!(d->flags & DS_EPI_STATS) || stats, "ds_conv_igemm: DS_EPI_STATS without stats buffer");
-    DS_REQUIRE(!(d->flags & DS_EPI_BNSUMS) || (stats && mask && !(d->flags & (DS_EPI_STATS | DS_EPI_MASK)) && d->ldmask >= d->Cout),
-               "ds_conv_igemm: DS_EPI_BNSUMS needs the partials buffer (stats), y (mask, ldmask) and excludes STATS / MASK");
-    DS_REQUIRE(conv_M(d) < (1ll << 31), "ds_conv_igemm: M too large");
-    DS_REQUIRE(d->dtype == DS_DTYPE_F32 || d->dtype == DS_DTYPE_BF16, "ds_conv_igemm: dtype must be DS_DTYPE_F32 or DS_DTYPE_BF16");
-    const Variant v = variant_of(d, x, w);
-    DS_REQUIRE(!(d->flags & DS_EPI_STATS) || v.vec == dims_vec(d),
-               "ds_conv_igemm: DS_EPI_STATS needs 16-byte aligned operand pointers");
-
-    ConvParams p;
-    p.d = *d;
-    p.x = x; p.w = w; p.z = z; p.bias = bias; p.mask = mask; p.stats = stats;
-    p.pivot = (d->flags & DS_EPI_STATS) ? pivot : nullptr;
-    p.M = (int)conv_M(d);
-    p.taps = d->KH * d->KW;
-    static int prio_mode = -1;
-    if (prio_mode < 0) {
-        const char *e = ds::tune_env("DS_CONV_PRIO");
-        prio_mode = e ? atoi(e) : 0;   // opt-in: measured neutral-to-negative (profiles/r01_notes.md)
-    }
-    p.prio_mode = prio_mode;
-    // extents of the two buffer descriptors (bytes from the operand pointer to the last float read)
-    const int64_t x_elems = ((int64_t)d->N * d->H * d->W - 1) * d->ldx + (v.fold ? d->fold_cin : d->Cin);
-    const int64_t w_elems = (int64_t)(p.taps - 1) * d->w_tap_stride + (int64_t)(d->Cout - 1) * d->w_n_stride +
-                            (int64_t)(d->Cin - 1) * d->w_k_stride + 1;
-    DS_REQUIRE(x_elems * 4 < (1ll << 31) && w_elems * 4 < (1ll << 31),
-               "ds_conv_igemm: operand larger than 2 GiB (split the batch)");
-    p.x_bytes = (unsigned)(x_elems * 4);
-    p.w_bytes = (unsigned)(w_elems * 4);
-    DS_REQUIRE(!v.fold || (v.bnmajor && v.vec && d->KW == 1 && d->fold_cin % 4 == 0 && d->ldx == d->fold_cin),
-               "ds_conv_igemm: fold_cin needs KW=1, n-contiguous 16-byte-aligned weights, ldx==fold_cin");
-
-    DS_REQUIRE(d->dtype != DS_DTYPE_BF16 || (v.vec && d->splits <= 1),
-               "ds_conv_igemm: DS_DTYPE_BF16 needs 16-byte aligned operands with channel counts / strides divisible by 4, no split-K");
-    const int splits = d->splits > 1 ? d->splits : 1;
-    DS_REQUIRE(splits == 1 || (d->flags == 0 && d->z_split_stride >= (int64_t)(conv_M(d) - 1) * d->ldz + d->Cout),
-               "ds_conv_igemm: split-K needs flags == 0 and non-overlapping output slabs");
-    if (splits == 1) p.d.z_split_stride = 0;
-    const TileCfg c = pick_cfg(d, v.vec);
-    const bool bnr = (d->flags & DS_EPI_BN_RELU) != 0;
-    DS_REQUIRE(!bnr || (d->flags == DS_EPI_BN_RELU && scale && shift && bnr_supported(d, c, v)),
-               "ds_conv_igemm: DS_EPI_BN_RELU excludes every other epilogue flag, needs scale / shift and a forward fp32 launch "
-               "with 16-byte aligned operands (ds_conv_plan_enable_bn_relu)");
-    p.scale = scale; p.shift = shift;
-    int gx, gy, rt;
-    bool one;
-    grid_for(d, c, v, &gx, &gy, &rt, &one);
-    // the statistics partial count the caller planned with (ds_conv_igemm_partials at plan time) must be the one this
-    // launch writes: the tile choice depends on debug switches / environment caches that may have changed since
-    DS_REQUIRE((!d->norm_rstd && !d->norm_shift) || (c.wide && d->norm_rstd && d->norm_shift && d->Cin <= 1024),
-               "ds_conv_igemm: norm_rstd / norm_shift are implemented by the wide 1x1 kernel only (ds_conv_igemm_norm_supported)");
-    DS_REQUIRE((!d->mask_rstd && !d->mask_shift) || ((d->flags & DS_EPI_BNSUMS) && d->mask_rstd && d->mask_shift),
-               "ds_conv_igemm: mask_rstd / mask_shift go with DS_EPI_BNSUMS");
-    DS_REQUIRE(!(d->flags & DS_EPI_BNSUMS) || c.wide,
-               "ds_conv_igemm: DS_EPI_BNSUMS is implemented by the wide 1x1 kernel only (ds_conv_igemm_bnsums_supported)");
-    DS_REQUIRE(!(d->flags & (DS_EPI_STATS | DS_EPI_BNSUMS)) || d->partials <= 0 || d->partials == (c.direct ? gx * 4 : gx),
-               "ds_conv_igemm: the launch would write %d statistics partials but the plan was made for %d "
-               "(a ds_debug_conv_set_* switch changed after planning?)", c.direct ? gx * 4 : gx, d->partials);
-    p.row_tiles = rt;
-    const int xcd_remap = xcd_remap_on();
-    dim3 grid(gx, gy, splits);
-    p.col_tiles = 0;
-    if (one && (c.wide || (xcd_remap && gy > 1)) && !c.direct) {    // one workgroup per tile: 1-D XCD-aware launch (TileId)
-        p.col_tiles = gy;
-        grid = dim3((rt * gy + 7) / 8 * 8, 1, splits);
-    }
-    if (d->bnb) {
-        const ds_bn_bwd_on_load &b = *d->bnb;
-        DS_REQUIRE(c.wide && !v.bnmajor && d->Cin <= 1024 && !d->norm_rstd,
-                   "ds_conv_igemm: ds_conv_desc.bnb is implemented by the wide 1x1 kernel for k-contiguous weights only "
-                   "(ds_conv_igemm_bnb_supported)");
-        DS_REQUIRE(b.mean && b.rstd && b.shift && b.coef && b.nseg >= 1 && b.nseg <= 3 && b.c_end[b.nseg - 1] == d->Cin,
-                   "ds_conv_igemm: bnb needs mean / rstd / shift / coef and 1..3 channel ranges that end at Cin");
-        for (int i = 0; i < b.nseg; ++i) {
-            const int cb = i ? b.c_end[i - 1] : 0;
-            DS_REQUIRE(b.dy[i] && (((uintptr_t)b.dy[i]) & 15) == 0 && b.ld[i] % 4 == 0 && b.c_end[i] > cb && cb % 16 == 0 &&
-                           b.ld[i] >= b.c_end[i] - cb && ((int64_t)(p.M - 1) * b.ld[i] + (b.c_end[i] - cb)) * 4 < (1ll << 31),
-                       "ds_conv_igemm: bnb channel range %d (16-byte aligned dy, ld %% 4 == 0, boundaries %% 16 == 0)", i);
-        }
-        p.bnb = b;
-    }
-    p.fin = ds_bn_finalize_in_launch{};
-    p.fin_inv_count = 0.0;
-    if (d->fin) {
-        DS_REQUIRE(c.wide && (d->flags & DS_EPI_STATS) && rt <= 256 && d->fin->ticket && d->fin->beta && d->fin->mean &&
-                       d->fin->rstd && d->fin->shift && d->fin->count > 0,
-                   "ds_conv_igemm: ds_conv_desc.fin needs a DS_EPI_STATS launch of the wide 1x1 kernel with at most 256 partials "
-                   "(ds_conv_igemm_finalize_tickets) and beta / mean / rstd / shift / ticket / count");
-        p.fin = *d->fin;
-        p.fin_inv_count = 1.0 / (double)d->fin->count;
-    }
-    p.pool_rpb = p.pool_bpi = 0;
-    if (d->pool_argmax) {
-        DS_REQUIRE(c.wide && v.bnmajor && pool3_nb(d, v.vec) == c.wide && !d->bnb,
-                   "ds_conv_igemm: ds_conv_desc.pool_argmax is implemented by the wide 1x1 kernel's forward instantiation only "
-                   "(ds_conv_igemm_pool3_supported)");
-        pool3_blocks(d, &p.pool_rpb, &p.pool_bpi);
-    }
-    if (c.wide) launch_wide(c.wide, v.bnmajor, d->bnb != nullptr, grid, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(bnr ? bnr_kernel(c) : kernel_for(c, v), grid, dim3(256), 0, (hipStream_t)stream, p);
-    return ds::check_launch("ds_conv_igemm");
-}
-}  // namespace
-
 // One launch for `count` (1..4) independent GEMMs, each described as for ds_conv_igemm (split-K descriptors write their slabs
 // at z[i] + s * z_split_stride).  Problem i's tiles receive exactly what ds_conv_igemm(descs[i], x[i], w[i], z[i]) writes: the
-// grid of that launch is laid into this one and the workgroups run the same code.  Plain 1x1 fp32 problems without epilogue
-// whose own launch is the 128 x 32 LDS-staged tile (the batch x features GEMMs of the heads); anything else is DS_ERR_ARG.
+// grid of that launch (choose) is laid into this one and the workgroups run the same code.  Plain 1x1 fp32 problems without
+// epilogue whose own launch is the 128 x 32 LDS-staged tile (the batch x features GEMMs of the heads); anything else is DS_ERR_ARG.
 extern "C" int ds_gemm_group(const ds_conv_desc *const *descs, const float *const *x, const float *const *w, float *const *z,
                              int32_t count, void *stream) {
     DS_REQUIRE(descs && x && w && z && count >= 1 && count <= kGemmGroupMax, "ds_gemm_group: 1..%d problems", kGemmGroupMax);
@@ -2377,37 +2282,21 @@ extern "C" int ds_gemm_group(const ds_conv_desc *const *descs, const float *cons
                    "ds_gemm_group: problem %d: fp32 without epilogue flags or on-load operands (combine with ds_slab_epilogue_group)", i);
         DS_REQUIRE(d->w_n_stride == 1 || d->w_k_stride == 1, "ds_gemm_group: one weight stride must be 1");
         DS_REQUIRE(d->ldx >= d->Cin && d->ldz >= d->Cout, "ds_gemm_group: problem %d: row strides below the row lengths", i);
-        const int splits = d->splits > 1 ? d->splits : 1;
-        DS_REQUIRE(splits == 1 || d->z_split_stride >= (int64_t)(d->N - 1) * d->ldz + d->Cout,
+        DS_REQUIRE(d->splits <= 1 || d->z_split_stride >= (int64_t)(d->N - 1) * d->ldz + d->Cout,
                    "ds_gemm_group: problem %d: overlapping output slabs", i);
-        const Variant v = variant_of(d, x[i], w[i]);
-        const TileCfg c = pick_cfg(d, v.vec);
+        const Launch L = choose(d, aligned16(x[i], w[i]));
+        const TileCfg &c = L.c;
         DS_REQUIRE(c.mt == 1 && c.nt == 1 && !c.direct && !c.glds && !c.bf16 && !c.wide,
                    "ds_gemm_group: problem %d's own launch is not the 128 x 32 tile (run it through ds_conv_igemm)", i);
         ConvParams &p = g.p[i];
-        p.d = *d;
-        if (splits == 1) p.d.z_split_stride = 0;
-        p.x = x[i]; p.w = w[i]; p.z = z[i];
-        p.M = d->N;
-        p.taps = 1;
-        const int64_t x_elems = (int64_t)(d->N - 1) * d->ldx + d->Cin;
-        const int64_t w_elems = (int64_t)(d->Cout - 1) * d->w_n_stride + (int64_t)(d->Cin - 1) * d->w_k_stride + 1;
-        DS_REQUIRE(x_elems * 4 < (1ll << 31) && w_elems * 4 < (1ll << 31), "ds_gemm_group: operand larger than 2 GiB");
-        p.x_bytes = (unsigned)(x_elems * 4);
-        p.w_bytes = (unsigned)(w_elems * 4);
-        int gx, gy, rt;
-        bool one;
-        grid_for(d, c, v, &gx, &gy, &rt, &one);
-        p.row_tiles = rt;
-        if (one && xcd_remap_on() && gy > 1) {      // the 1-D XCD-aware shape of ds_conv_igemm's launch (TileId)
-            p.col_tiles = gy;
-            gx = (rt * gy + 7) / 8 * 8;
-            gy = 1;
-        }
-        g.gx[i] = gx; g.gy[i] = gy; g.splits[i] = splits;
-        g.variant[i] = (v.bnmajor ? 1 : 0) | (v.vec ? 2 : 0);
-        DS_REQUIRE((int64_t)wgs + (int64_t)gx * gy * splits < (1 << 20), "ds_gemm_group: too many workgroups");
-        wgs += gx * gy * splits;
+        if (int rc = fill_params(p, "ds_gemm_group", "", d, x[i], w[i], z[i], nullptr, nullptr, nullptr)) return rc;
+        p.row_tiles = L.row_tiles;
+        p.col_tiles = L.col_tiles;
+        g.gx[i] = L.grid.x; g.gy[i] = L.grid.y; g.splits[i] = L.grid.z;
+        g.variant[i] = (L.v.bnmajor ? 1 : 0) | (L.v.vec ? 2 : 0);
+        const int64_t own = (int64_t)L.grid.x * L.grid.y * L.grid.z;
+        DS_REQUIRE(wgs + own < (1 << 20), "ds_gemm_group: too many workgroups");
+        wgs += (int)own;
         g.wg_end[i] = wgs;
     }
     hipLaunchKernelGGL(gemm_group_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, g);
@@ -2416,13 +2305,13 @@ extern "C" int ds_gemm_group(const ds_conv_desc *const *descs, const float *cons
 
 // ---- bf16 register-direct path -------------------------------------------------------------------------------------
 namespace {
-int g_bf16d_max_nb = 8;       // ds_debug_conv_bf16_set_max_nb (tuning)
 int bf16d_nb(int Cout, bool x16_1x1) {
     // a workgroup's cost per K step ~ (A fetch + NB MFMAs); minimise column tiles x (c + NB), c ~ 4, ties to wider.
     // 1x1 launches from 16-bit activation storage are pure streaming (8 passes per 16 channels): at most four column blocks
     // per wave, i.e. 3-4 waves per SIMD instead of 2 -- twelve 1x1 shapes of the tower, forward with statistics:
     // 479 -> 434 us (scripts/bf16_wide_sweep.py); the input gradients (fp32 dz) keep eight (492 against 521)
-    const int top = x16_1x1 && g_bf16d_max_nb > 4 ? 4 : g_bf16d_max_nb;
+    const int max_nb = tuning().bf16d_max_nb;
+    const int top = x16_1x1 && max_nb > 4 ? 4 : max_nb;
     int best = top, best_cost = 1 << 30;
     for (int nb = top; nb >= 1; --nb) {
         const int tiles = (Cout + 32 * nb - 1) / (32 * nb);
@@ -2438,6 +2327,22 @@ bool bf16d_ok(const ds_conv_desc *d) {
            // the epilogue addresses z (and the BatchNorm-sums activation) through 32-bit buffer offsets
            ((conv_M(d) - 1) * d->ldz + d->Cout) * 4 < (1ll << 31) &&
            (!(d->flags & DS_EPI_BNSUMS) || ((conv_M(d) - 1) * d->ldmask + d->Cout) * 4 < (1ll << 31));
+}
+
+// The launch ds_conv_bf16 and ds_conv_f32x3 share: conv_bf16d_kernel<NB = nb, ..> on the prepared weights (`planes` bf16 planes),
+// 128 rows x 32 * nb columns per workgroup, on the 1-D XCD-aware grid (TileId)
+int bf16d_launch(const char *who, const ds_conv_desc *d, const void *x, const void *wb, int planes, float *z, const void *mask,
+                 float *stats, const float *pivot, int nb, KernelFn kernel, void *stream) {
+    ConvParams p;
+    const int64_t wb_bytes = planes * (int64_t)((d->Cin + 15) / 16) * (d->KH * d->KW) * ((d->Cout + 31) / 32 * 32) * 32;
+    if (int rc = fill_params(p, who, "", d, x, wb, z, mask, stats, pivot, wb_bytes)) return rc;
+    if (d->x_dtype == DS_DTYPE_BF16) p.x_bytes /= 2;
+    p.col_total = (d->Cout + 31) / 32 * 32;
+    p.row_tiles = (int)((conv_M(d) + 127) / 128);
+    p.col_tiles = (d->Cout + 32 * nb - 1) / (32 * nb);
+    const dim3 grid((unsigned)(((int64_t)p.row_tiles * p.col_tiles + 7) / 8 * 8));
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return ds::check_launch(who);
 }
 }  // namespace
 
@@ -2457,14 +2362,6 @@ extern "C" int ds_weights_to_bf16(const float *w, void *wb, int32_t Cin, int32_t
 
 extern "C" int ds_conv_bf16_supported(const ds_conv_desc *d) { return d && bf16d_ok(d) ? 1 : 0; }
 
-#ifdef DS_TUNING
-extern "C" int ds_debug_conv_bf16_set_max_nb(int nb) {
-    DS_REQUIRE(nb >= 1 && nb <= 8, "ds_debug_conv_bf16_set_max_nb: 1 .. 8 column blocks per wave");
-    g_bf16d_max_nb = nb;
-    return 0;
-}
-#endif
-
 extern "C" int ds_conv_bf16_partials(const ds_conv_desc *d) { return (int)((conv_M(d) + 127) / 128); }
 
 extern "C" int ds_conv_bf16(const ds_conv_desc *d, const void *x, const void *wb, float *z, const void *mask, float *stats,
@@ -2479,50 +2376,17 @@ extern "C" int ds_conv_bf16(const ds_conv_desc *d, const void *x, const void *wb
     const bool xb = d->x_dtype == DS_DTYPE_BF16;
     DS_REQUIRE(bf16d_ok(d), "ds_conv_bf16: needs a 1x1 or 3x3 conv, Cin %% 8 == 0, ldx %% 4 == 0, flags within DS_EPI_STATS, or "
                             "DS_EPI_ACCUM | DS_EPI_BNSUMS for a dgrad");
-    DS_REQUIRE(((((uintptr_t)x | (uintptr_t)wb) & 15) == 0) && conv_M(d) < (1ll << 31), "ds_conv_bf16: operands must be 16-byte aligned");
+    DS_REQUIRE(aligned16(x, wb) && conv_M(d) < (1ll << 31), "ds_conv_bf16: operands must be 16-byte aligned");
     DS_REQUIRE(!(d->flags & DS_EPI_STATS) || stats, "ds_conv_bf16: DS_EPI_STATS without stats buffer");
     DS_REQUIRE(d->z_dtype == DS_DTYPE_F32 || (d->z_dtype == DS_DTYPE_BF16 && !(d->flags & (DS_EPI_ACCUM | DS_EPI_BNSUMS))),
                "ds_conv_bf16: the output in bf16 storage excludes the accumulate / BatchNorm-sums epilogues");
-    ConvParams p = {};
-    p.d = *d;
-    p.x = (const float *)x; p.w = (const float *)wb; p.z = z; p.stats = stats; p.mask = (const float *)mask;
-    p.pivot = (d->flags & DS_EPI_STATS) ? pivot : nullptr;
-    p.M = (int)conv_M(d);
-    p.taps = d->KH * d->KW;
-    const int64_t x_elems = ((int64_t)d->N * d->H * d->W - 1) * d->ldx + d->Cin;
-    const int64_t wb_bytes = (int64_t)((d->Cin + 15) / 16) * p.taps * ((d->Cout + 31) / 32 * 32) * 32;
-    DS_REQUIRE(x_elems * 4 < (1ll << 31) && wb_bytes < (1ll << 31), "ds_conv_bf16: operand larger than 2 GiB");
-    p.x_bytes = (unsigned)(x_elems * (xb ? 2 : 4));
-    p.w_bytes = (unsigned)wb_bytes;
-    p.col_total = (d->Cout + 31) / 32 * 32;
     const int nb = bf16d_nb(d->Cout, xb && d->KH == 1);
-    p.row_tiles = (int)((conv_M(d) + 127) / 128);
-    p.col_tiles = (d->Cout + 32 * nb - 1) / (32 * nb);
-    const dim3 grid((unsigned)(((int64_t)p.row_tiles * p.col_tiles + 7) / 8 * 8));
-    hipStream_t st = (hipStream_t)stream;
-#define DS_B16(NBV)                                                                                        \
-    case NBV:                                                                                              \
-        if (xb) {                                                                                          \
-            if (d->KH == 1) hipLaunchKernelGGL((conv_bf16d_kernel<NBV, 1, true>), grid, dim3(256), 0, st, p);  \
-            else hipLaunchKernelGGL((conv_bf16d_kernel<NBV, 3, true>), grid, dim3(256), 0, st, p);             \
-        } else {                                                                                           \
-            if (d->KH == 1) hipLaunchKernelGGL((conv_bf16d_kernel<NBV, 1, false>), grid, dim3(256), 0, st, p); \
-            else hipLaunchKernelGGL((conv_bf16d_kernel<NBV, 3, false>), grid, dim3(256), 0, st, p);            \
-        }                                                                                                  \
-        break;
-    switch (nb) {
-        DS_B16(1)
-        DS_B16(2)
-        DS_B16(3)
-        DS_B16(4)
-        DS_B16(5)
-        DS_B16(6)
-        DS_B16(7)
-        default:
-        DS_B16(8)
-    }
-#undef DS_B16
-    return ds::check_launch("ds_conv_bf16");
+    const KernelFn kernel = with_const<1, 8>(nb, [&](auto n) {
+        constexpr int NB = decltype(n)::value;
+        if (xb) return d->KH == 1 ? conv_bf16d_kernel<NB, 1, true> : conv_bf16d_kernel<NB, 3, true>;
+        return d->KH == 1 ? conv_bf16d_kernel<NB, 1, false> : conv_bf16d_kernel<NB, 3, false>;
+    });
+    return bf16d_launch("ds_conv_bf16", d, x, wb, 1, z, mask, stats, pivot, nb, kernel, stream);
 }
 
 // ---- fp32 products on the bf16 matrix cores (see conv_bf16d_kernel<.., X3>) ----------------------------------------
@@ -2560,33 +2424,14 @@ extern "C" int ds_conv_f32x3(const ds_conv_desc *d, const float *x, const void *
                "ds_conv_f32x3: norm_rstd / norm_shift and mask_rstd / mask_shift come in pairs (the latter with DS_EPI_BNSUMS)");
     DS_REQUIRE(!(d->flags & DS_EPI_BNSUMS) || (mask && stats && d->ldmask >= d->Cout),
                "ds_conv_f32x3: DS_EPI_BNSUMS needs mask (row stride ldmask) and a partials buffer");
-    DS_REQUIRE(((((uintptr_t)x | (uintptr_t)wb) & 15) == 0) && conv_M(d) < (1ll << 31), "ds_conv_f32x3: operands must be 16-byte aligned");
+    DS_REQUIRE(aligned16(x, wb) && conv_M(d) < (1ll << 31), "ds_conv_f32x3: operands must be 16-byte aligned");
     DS_REQUIRE(!(d->flags & DS_EPI_STATS) || stats, "ds_conv_f32x3: DS_EPI_STATS without stats buffer");
-    ConvParams p = {};
-    p.d = *d;
-    p.x = x; p.w = (const float *)wb; p.z = z; p.stats = stats; p.mask = mask;
-    p.pivot = (d->flags & DS_EPI_STATS) ? pivot : nullptr;
-    p.M = (int)conv_M(d);
-    p.taps = d->KH * d->KW;
-    const int64_t x_elems = ((int64_t)d->N * d->H * d->W - 1) * d->ldx + d->Cin;
-    const int64_t wb_bytes = 3 * (int64_t)((d->Cin + 15) / 16) * p.taps * ((d->Cout + 31) / 32 * 32) * 32;
-    DS_REQUIRE(x_elems * 4 < (1ll << 31) && wb_bytes < (1ll << 31), "ds_conv_f32x3: operand larger than 2 GiB");
-    p.x_bytes = (unsigned)(x_elems * 4);
-    p.w_bytes = (unsigned)wb_bytes;
-    p.col_total = (d->Cout + 31) / 32 * 32;
     // two column blocks per wave (one where Cout <= 32): measured best on all fourteen 1x1 layer shapes (NB = 4: the
     // split is better amortised but two waves per SIMD no longer fit; profiles/r03_f32x3_layers.txt)
     const int nb = d->Cout <= 32 ? 1 : 2;
-    p.row_tiles = (int)((conv_M(d) + 127) / 128);
-    p.col_tiles = (d->Cout + 32 * nb - 1) / (32 * nb);
-    const dim3 grid((unsigned)(((int64_t)p.row_tiles * p.col_tiles + 7) / 8 * 8));
-    hipStream_t st = (hipStream_t)stream;
-    if (nb == 1) {
-        if (d->KH == 1) hipLaunchKernelGGL((conv_bf16d_kernel<1, 1, false, true>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((conv_bf16d_kernel<1, 3, false, true>), grid, dim3(256), 0, st, p);
-    } else {
-        if (d->KH == 1) hipLaunchKernelGGL((conv_bf16d_kernel<2, 1, false, true>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((conv_bf16d_kernel<2, 3, false, true>), grid, dim3(256), 0, st, p);
-    }
-    return ds::check_launch("ds_conv_f32x3");
+    const KernelFn kernel = with_const<1, 2>(nb, [&](auto n) {
+        return d->KH == 1 ? conv_bf16d_kernel<decltype(n)::value, 1, false, true> : conv_bf16d_kernel<decltype(n)::value, 3, false, true>;
+    });
+    return bf16d_launch("ds_conv_f32x3", d, x, wb, 3, z, mask, stats, pivot, nb, kernel, stream);
 }
+

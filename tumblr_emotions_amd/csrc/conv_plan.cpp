@@ -45,6 +45,13 @@ inline void same_pad(int n, int k, int s, int *out, int *before) {
 
 inline bool is_wino(const ds_conv_layer_plan *p) { return p->family == DS_FAM_WINO2 || p->family == DS_FAM_WINO4 || p->family == DS_FAM_WINO4H; }
 
+// the plan's descriptor as the ds_conv_igemm_* questions want it: without the partial count planned so far
+ds_conv_desc igemm_desc(const ds_conv_layer_plan *p) {
+    ds_conv_desc t = p->d;
+    t.partials = 0;
+    return t;
+}
+
 // partial count of the statistics epilogue of the chosen launch
 int plan_partials(const ds_conv_layer_plan *p) {
     const ds_conv_desc &d = p->d;
@@ -61,11 +68,19 @@ int plan_partials(const ds_conv_layer_plan *p) {
     case DS_FAM_FP8D: return ds_conv_fp8_partials(&d);
     case DS_FAM_F32X3: return ds_conv_f32x3_partials(&d);
     default: {
-        ds_conv_desc t = d;
-        t.partials = 0;
+        const ds_conv_desc t = igemm_desc(p);
         return ds_conv_igemm_partials(&t);
     }
     }
+}
+
+// after a plan's flags or on-load operands changed: count its partials again (the implicit GEMM's descriptor carries the count
+// to the launch, which refuses to write another one)
+int recount_partials(ds_conv_layer_plan *p) {
+    p->d.partials = 0;
+    p->partials = plan_partials(p);
+    if (p->family == DS_FAM_IGEMM) p->d.partials = p->partials;
+    return p->partials;
 }
 
 }  // namespace
@@ -216,18 +231,14 @@ extern "C" int ds_conv_plan(ds_conv_layer_plan *out, int32_t role, int32_t arith
     }
     PLAN_REQUIRE(!(flags & DS_EPI_BN_RELU), "ds_conv_plan: DS_EPI_BN_RELU is added by ds_conv_plan_enable_bn_relu");
     if (is_wino(out)) PLAN_REQUIRE(!(flags & ~(DS_EPI_STATS | DS_EPI_BNSUMS)), "ds_conv_plan: Winograd epilogues are STATS / BNSUMS");
-    out->partials = plan_partials(out);
-    if (fam == DS_FAM_IGEMM) d.partials = out->partials;
+    recount_partials(out);
     return DS_OK;
 }
 
 extern "C" int ds_conv_plan_set_flags(ds_conv_layer_plan *p, int32_t flags) {
     PLAN_REQUIRE(p != nullptr, "ds_conv_plan_set_flags: null plan");
     p->d.flags = flags;
-    p->d.partials = 0;
-    p->partials = plan_partials(p);
-    if (p->family == DS_FAM_IGEMM) p->d.partials = p->partials;
-    return p->partials;
+    return recount_partials(p);
 }
 
 extern "C" int ds_conv_plan_enable_bnsums(ds_conv_layer_plan *p, int32_t ldy) {
@@ -235,8 +246,7 @@ extern "C" int ds_conv_plan_enable_bnsums(ds_conv_layer_plan *p, int32_t ldy) {
     if (is_wino(p)) {
         p->d.flags = (p->d.flags & ~DS_EPI_STATS) | DS_EPI_BNSUMS;      // (the two sum epilogues exclude each other)
     } else if (p->family == DS_FAM_IGEMM && p->k == 1 && p->d.dtype == DS_DTYPE_F32) {
-        ds_conv_desc t = p->d;
-        t.partials = 0;
+        const ds_conv_desc t = igemm_desc(p);
         if (!ds_conv_igemm_bnsums_supported(&t)) return 0;
         p->d.flags |= DS_EPI_BNSUMS;
         p->d.ldmask = ldy;
@@ -246,17 +256,13 @@ extern "C" int ds_conv_plan_enable_bnsums(ds_conv_layer_plan *p, int32_t ldy) {
     } else {
         return 0;      // implicit-GEMM fallbacks of other shapes (LDS-staged kernels): the separate reduce pass stays
     }
-    p->d.partials = 0;
-    p->partials = plan_partials(p);
-    if (p->family == DS_FAM_IGEMM) p->d.partials = p->partials;
-    return p->partials;
+    return recount_partials(p);
 }
 
 extern "C" int ds_conv_plan_norm_supported(const ds_conv_layer_plan *p) {
     if (p == nullptr) return 0;
     if (p->family == DS_FAM_IGEMM) {
-        ds_conv_desc t = p->d;
-        t.partials = 0;
+        const ds_conv_desc t = igemm_desc(p);
         return ds_conv_igemm_norm_supported(&t);
     }
     return p->family == DS_FAM_F32X3 && p->k == 1 && p->d.Cin <= 1024 ? 1 : 0;
@@ -264,20 +270,16 @@ extern "C" int ds_conv_plan_norm_supported(const ds_conv_layer_plan *p) {
 
 extern "C" int ds_conv_plan_bnb_supported(const ds_conv_layer_plan *p) {
     if (p == nullptr || p->role != DS_CONV_DGRAD || p->family != DS_FAM_IGEMM || p->k != 1) return 0;
-    ds_conv_desc t = p->d;
-    t.partials = 0;
+    const ds_conv_desc t = igemm_desc(p);
     return ds_conv_igemm_bnb_supported(&t);
 }
 
 extern "C" int ds_conv_plan_enable_pool3(ds_conv_layer_plan *p, uint8_t *argmax) {
     if (p == nullptr || argmax == nullptr || p->role != DS_CONV_FWD || p->family != DS_FAM_IGEMM || p->k != 1) return 0;
-    ds_conv_desc t = p->d;
-    t.partials = 0;
+    const ds_conv_desc t = igemm_desc(p);
     if (!ds_conv_igemm_pool3_supported(&t)) return 0;
     p->d.pool_argmax = argmax;
-    p->d.partials = 0;
-    p->partials = plan_partials(p);
-    p->d.partials = p->partials;
+    recount_partials(p);
     return 1;
 }
 
@@ -286,8 +288,7 @@ extern "C" int ds_conv_plan_enable_bn_relu(ds_conv_layer_plan *p) {
     // one the plan already has, so the accumulators are those of the plain launch
     if (p == nullptr || p->role != DS_CONV_FWD || p->d.dtype != DS_DTYPE_F32 || p->d.flags != 0) return 0;
     if (p->family == DS_FAM_IGEMM) {
-        ds_conv_desc t = p->d;
-        t.partials = 0;
+        const ds_conv_desc t = igemm_desc(p);
         if (!ds::conv_igemm_bn_relu_supported(&t)) return 0;
     } else if (p->family == DS_FAM_WINO4) {
         if (p->d.ldz % 4 != 0 || p->d.ldz < p->d.Cout) return 0;
@@ -302,7 +303,7 @@ extern "C" int ds_conv_plan_enable_bn_relu(ds_conv_layer_plan *p) {
 
 extern "C" int ds_conv_plan_finalize_tickets(const ds_conv_layer_plan *p) {
     if (p == nullptr || p->role != DS_CONV_FWD || p->family != DS_FAM_IGEMM) return 0;
-    ds_conv_desc t = p->d;
+    ds_conv_desc t = igemm_desc(p);
     t.flags |= DS_EPI_STATS;
     return ds_conv_igemm_finalize_tickets(&t);
 }
