@@ -177,6 +177,18 @@ int ds_debug_conv_wino_allow_ablation(int on);
 int ds_debug_conv_wino4_set_nb(int nb);
 /* tuning: the most column blocks (of 32) a wave of ds_conv_bf16 may own (1 .. 8; default 8) */
 int ds_debug_conv_bf16_set_max_nb(int nb);
+/* ds_conv_wgrad's register-direct kernel: pin the tile shape (ai, bj in {1, 2, 4}) and / or the split-K slab count (1, 2, 4 or
+ * a multiple of 8 up to 64); 0 in a field = the cycle model's choice, (0, 0, 0) = the default.  Anything else is DS_ERR_ARG.
+ * A pinned ai (bj) wider than the vector width the call's operands allow (wx, wz below) is ignored for that call.  The
+ * caller sizes the workspace for a pinned slab count: slabs * KH * KW * Cin * Cout floats.                                */
+int ds_debug_conv_wgrad_force(int ai, int bj, int slabs);
+/* What ds_conv_wgrad would launch for these arguments (the same host decision; nothing is launched, the pointers are only
+ * looked at for their alignment): out = {direct, ai, bj, slabs, wx, wz}.  direct = 1: wgrad_direct_kernel<ai, bj>; 0: the LDS
+ * kernel (ai = bj = 0).  wx (wz) = the widest of 4, 2, 1 floats that divides Cin and ldx (Cout and lddz) with x (dz, and for
+ * the direct kernel dw and ws, which it stores bj floats at a time) aligned to that many floats; the LDS kernel loads 16
+ * bytes at width 4 and single floats below.                                                                            */
+int ds_debug_conv_wgrad_plan(const ds_conv_desc *d, const float *x, const float *dz, int32_t lddz, const float *dw,
+                             const void *ws, int out[6]);
 #endif /* DS_TUNING */
 /* Number of row-tile blocks (P) the launch for `d` will use = number of stats partials.   */
 int ds_conv_igemm_partials(const ds_conv_desc *d);

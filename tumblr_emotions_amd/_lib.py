@@ -326,6 +326,8 @@ DEBUG_SIGNATURES = {
     "ds_debug_conv_wino_allow_ablation": (C.c_int, [C.c_int]),
     "ds_debug_conv_wino4_set_nb": (C.c_int, [C.c_int]),
     "ds_debug_conv_bf16_set_max_nb": (C.c_int, [C.c_int]),
+    "ds_debug_conv_wgrad_force": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "ds_debug_conv_wgrad_plan": (C.c_int, [_CD, _P, _P, _i32, _P, _P, C.POINTER(C.c_int)]),
     "ds_debug_lstm_seq_set_profile": (C.c_int, [_P]),
     "ds_debug_lstm_seq_set_profile_bwd": (C.c_int, [_P]),
 }

@@ -295,10 +295,16 @@ __global__ __launch_bounds__(256, (AI * BJ > 8) ? 1 : 2) void wgrad_direct_kerne
         const int h = v < 0 ? -1 : v / stride;
         return h > oext - 1 ? oext - 1 : h;
     };
-    const int lo_h = lo_of(d.pad_t, dh, d.stride), lo_w = lo_of(d.pad_l, dw, d.stride);
-    const unsigned span_h = (unsigned)(hi_of(d.pad_t, dh, d.stride, d.H, d.OH) - lo_h);
-    const unsigned span_w = (unsigned)(hi_of(d.pad_l, dw, d.stride, d.W, d.OW) - lo_w);
     const int OWc = d.OW, OHc = d.OH;
+    int lo_h = lo_of(d.pad_t, dh, d.stride), lo_w = lo_of(d.pad_l, dw, d.stride);
+    const int hi_h = hi_of(d.pad_t, dh, d.stride, d.H, d.OH), hi_w = hi_of(d.pad_l, dw, d.stride, d.W, d.OW);
+    // a tap with no valid output coordinate on an axis (hi < lo: a 3-tap filter over an extent of 1, the far taps of a
+    // stride-2 filter wider than the image) reads padding at every pixel: lo = the output extent, which oh / ow never reach
+    // (hi - lo itself would wrap to 0xffffffff and pass everything)
+    if (hi_h < lo_h) lo_h = OHc;
+    if (hi_w < lo_w) lo_w = OWc;
+    const unsigned span_h = hi_h < lo_h ? 0u : (unsigned)(hi_h - lo_h);
+    const unsigned span_w = hi_w < lo_w ? 0u : (unsigned)(hi_w - lo_w);
     auto offsets = [&](unsigned &ox, unsigned &oz) {
         const bool mv = m < we;
         const bool in = (unsigned)(oh - lo_h) <= span_h && (unsigned)(ow - lo_w) <= span_w;
@@ -444,7 +450,19 @@ struct WgradPlan {
     int direct;      // 1: wgrad_direct_kernel<ai, bj>
     int ai, bj;
     int splits;
+    int wx, wz;      // widest vector (floats) the x side and the dz / dw / ws side allow (max_width)
 };
+
+// split-K slab counts of the direct kernel: 1, 2, 4 or a multiple of 8 (XCD-aligned, see the kernel)
+constexpr int kSlabs[] = {1, 2, 4, 8, 16, 24, 32, 40, 48, 56, 64};
+
+#ifdef DS_TUNING
+struct WgradForce { int ai, bj, slabs; };      // ds_debug_conv_wgrad_force: 0 = the model's choice
+WgradForce &wgrad_force() {
+    static WgradForce f = {0, 0, 0};
+    return f;
+}
+#endif
 
 int max_width(int C, int ld, uintptr_t ptr) {
     for (int w = 4; w > 1; w >>= 1)
@@ -467,7 +485,6 @@ bool direct_ok(const ds_conv_desc *d, int64_t M) {
 WgradPlan plan_direct(const ds_conv_desc *d, int64_t M, int wx, int wz, int only_ai = 0, int only_bj = 0) {
     WgradPlan best = {};
     double best_cost = 1e30;
-    static const int kSlabs[] = {1, 2, 4, 8, 16, 24, 32, 40, 48, 56, 64};
     const double wbytes = (double)d->KH * d->KW * d->Cin * d->Cout * 4.0;
     for (int ai = 1; ai <= wx; ai *= 2)
         for (int bj = 1; bj <= wz; bj *= 2) {
@@ -509,20 +526,31 @@ WgradPlan plan_wgrad(const ds_conv_desc *d, int64_t M, const float *x, const flo
         const uintptr_t zalign = (uintptr_t)dz | (uintptr_t)dw | (uintptr_t)ws;
         const int wx = max_width(d->Cin, d->ldx, (uintptr_t)x), wz = max_width(d->Cout, lddz, zalign);
         WgradPlan pl = plan_direct(d, M, wx, wz);
-        if (const char *e = ds::tune_env("DS_WGRAD_FORCE")) {          // "ai,bj,slabs" (tuning aid; the caller sizes the workspace)
-            int a = 0, b = 0, sl = 0;
-            if (sscanf(e, "%d,%d,%d", &a, &b, &sl) == 3) {
-                if ((a && a <= wx) || (b && b <= wz)) {          // the slab count the model gives THAT tile shape
-                    const WgradPlan f = plan_direct(d, M, wx, wz, a <= wx ? a : 0, b <= wz ? b : 0);
-                    if (f.direct) pl = f;
-                }
-                if (sl) pl.splits = sl;
-            }
+#ifdef DS_TUNING
+        // a pinned plan (tuning aid; the caller sizes the workspace): ds_debug_conv_wgrad_force, or DS_WGRAD_FORCE = "ai,bj,slabs"
+        // where the setter leaves a field to the model
+        int a = 0, b = 0, sl = 0;
+        if (const char *e = ds::tune_env("DS_WGRAD_FORCE"))
+            if (sscanf(e, "%d,%d,%d", &a, &b, &sl) != 3) a = b = sl = 0;
+        const WgradForce &f = wgrad_force();
+        a = f.ai ? f.ai : a;
+        b = f.bj ? f.bj : b;
+        sl = f.slabs ? f.slabs : sl;
+        if ((a && a <= wx) || (b && b <= wz)) {          // the slab count the model gives THAT tile shape
+            const WgradPlan t = plan_direct(d, M, wx, wz, a <= wx ? a : 0, b <= wz ? b : 0);
+            if (t.direct) pl = t;
         }
+        if (sl) pl.splits = sl;
+#endif
+        pl.wx = wx;
+        pl.wz = wz;
         return pl;
     }
+    // the LDS kernel: 16-byte loads where the operand allows them, single floats otherwise; its stores are scalar
     WgradPlan pl = {};
     pl.splits = pick_splits(d, M);
+    pl.wx = max_width(d->Cin, d->ldx, (uintptr_t)x);
+    pl.wz = max_width(d->Cout, lddz, (uintptr_t)dz);
     return pl;
 }
 
@@ -573,8 +601,8 @@ extern "C" int ds_conv_wgrad(const ds_conv_desc *d, const float *x, const float 
     p.z_bytes = (unsigned)(z_elems * 4);
     p.inv_ohw = 1.0f / (float)(d->OH * d->OW);
     p.inv_ow = 1.0f / (float)d->OW;
-    p.x_vec = (d->ldx % 4 == 0) && (d->Cin % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    p.z_vec = (lddz % 4 == 0) && (d->Cout % 4 == 0) && (((uintptr_t)dz & 15) == 0);
+    p.x_vec = !pl.direct && pl.wx == 4;      // the LDS kernel's 16-byte loads (the direct kernel's widths are ai and bj)
+    p.z_vec = !pl.direct && pl.wz == 4;
     hipStream_t s = (hipStream_t)stream;
     int pps = (int)((M + splits - 1) / splits);
     if (pl.direct) {
@@ -601,3 +629,23 @@ extern "C" int ds_conv_wgrad(const ds_conv_desc *d, const float *x, const float 
     }
     return ds::check_launch("ds_conv_wgrad");
 }
+
+#ifdef DS_TUNING
+extern "C" int ds_debug_conv_wgrad_force(int ai, int bj, int slabs) {
+    auto tile = [](int v) { return v == 0 || v == 1 || v == 2 || v == 4; };
+    bool slab_ok = slabs == 0;
+    for (int s : kSlabs) slab_ok = slab_ok || s == slabs;
+    DS_REQUIRE(tile(ai) && tile(bj) && slab_ok,
+               "ds_debug_conv_wgrad_force: ai, bj in {1,2,4}, slabs in {1,2,4,8,16,...,64}, 0 = the model's choice");
+    wgrad_force() = {ai, bj, slabs};
+    return DS_OK;
+}
+
+extern "C" int ds_debug_conv_wgrad_plan(const ds_conv_desc *d, const float *x, const float *dz, int32_t lddz, const float *dw,
+                                        const void *ws, int out[6]) {
+    DS_REQUIRE(d && out, "ds_debug_conv_wgrad_plan: null argument");
+    const WgradPlan pl = plan_wgrad(d, (int64_t)d->N * d->OH * d->OW, x, dz, lddz, dw, ws);
+    out[0] = pl.direct; out[1] = pl.ai; out[2] = pl.bj; out[3] = pl.splits; out[4] = pl.wx; out[5] = pl.wz;
+    return DS_OK;
+}
+#endif
