@@ -1092,9 +1092,13 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void conv_bf16_kernel(const C
 // POOL (ds_conv_desc.pool_argmax: an Inception block's Branch_3, MaxPool 3x3/1 SAME -> Conv2d_0b_1x1, as ONE launch): the A
 // fragment of pixel (h, w) becomes the maximum of x over its 3x3 neighbourhood as it is loaded.  A wave's 32-row block holds
 // WHOLE image rows (28 of 32 lanes on the 28 / 14 / 7-wide maps), so that a pixel's left and right neighbours are the
-// neighbouring lanes: lane (pixel, kh) loads its own column -- rows h-1, h, h+1, the same 2 x 4 channels -- takes the column
+// neighbouring lanes: lane (pixel, kh) takes its own column -- rows h-1, h, h+1, the same 2 x 4 channels -- forms the column
 // maximum and the first row that holds it, gets its neighbours' column maxima by two DPP wave shifts and keeps the
-// row-major-first winner (kh * 3 + kw: what maxpool3_fwd_rolling records), 3 loads per output instead of 9 and no LDS.
+// row-major-first winner (kh * 3 + kw: what maxpool3_fwd_rolling records).  The three rows come from an LDS tile of the
+// workgroup's centre rows (its four blocks are consecutive row groups), which the waves fill with one 64-byte sector per lane
+// quad; only the row above wave 0's block and the one below wave 3's are read from memory a second time.  The fragment
+// layout took all three rows from memory, four rows per lane quad: 454 L1 tag lookups per wave and K step, 1.96 cycles
+// each, was the whole launch time on the 28 x 28 maps (profiles/pool_on_load_notes.md).
 // With norm_rstd / norm_shift the maximum is taken over the raw z and relu(max * rstd + shift) applied once (rstd > 0), as
 // ds_maxpool_bn_relu_fwd does.  The winners' bytes are the only thing besides z that is written: the pooled tensor
 // (4 B per element out of the pool kernel and 4 B back into this one) never exists.
@@ -1117,7 +1121,8 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
     constexpr int BSZ = DJ * 1024;                             // floats per B buffer (odd NB: the last DMA is half used)
     constexpr int BST = AST > 0 ? AST - 1 : 2;                 // B buffers
     static_assert(AST == 0 || (AST >= 3 && !BNB && !POOL), "the A ring is built for the plain and the normalising loader");
-    __shared__ __attribute__((aligned(128))) float smem[BST * BSZ + 256 + AST * 2048];
+    constexpr int PT = 2048;                                   // POOL: floats per centre-row tile (128 pixels x 16 channels)
+    __shared__ __attribute__((aligned(128))) float smem[BST * BSZ + 256 + AST * 2048 + (POOL ? 2 * PT : 0)];
     // BatchNorm + ReLU on load (ds_conv_desc.norm_rstd / norm_shift): rstd and shift of all Cin reduction channels;
     // BNB: rstd, shift, mean, coef[0], coef[1]
     __shared__ __attribute__((aligned(16))) float nrm[BNB ? 5 : 2][1024 + WK];
@@ -1135,6 +1140,12 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
     int mrow0 = t0.row * 128 + wave * 32, Mw = p.M;
     bool hasU = false, hasD = false, hasL = false, hasR = false;      // POOL: which neighbours of the lane's pixel exist
     int prow = 0;                                                     // POOL: bytes between image rows of x
+    // POOL: where the pixel above / below comes from.  The workgroup's four blocks are consecutive row groups, so it is a
+    // pixel of this wave's block, of the neighbouring wave's block -- both in the centre-row tile in LDS (pu / pd: its pixel
+    // slot, the lane's own where there is no neighbour or it comes from memory) -- or, for the first row of wave 0 and the
+    // last row of wave 3, a halo row read from memory (upM / dnM)
+    bool upM = false, dnM = false;
+    int pu = 0, pd = 0;
     if constexpr (POOL) {
         const int blk = t0.row * 4 + wave;                           // (uniform)
         const int n = blk / p.pool_bpi, rb = blk - n * p.pool_bpi;
@@ -1150,6 +1161,14 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         hasL = ok && ow > 0;
         hasR = ok && ow + 1 < d.W;
         prow = d.W * d.ldx * 4;
+        const bool top = dr == 0, bot = dr + 1 == rows;              // the block's first / last image row
+        upM = hasU && top && wave == 0;
+        dnM = hasD && bot && wave == 3;
+        pu = pd = wave * 32 + li;
+        if (hasU && !top) pu -= d.W;
+        if (hasU && top && wave > 0) pu = (wave - 1) * 32 + (p.pool_rpb - 1) * d.W + ow;      // (a block above is a full one)
+        if (hasD && !bot) pd += d.W;
+        if (hasD && bot && wave < 3) pd = (wave + 1) * 32 + ow;
     }
     const int m = mrow0 + li;
     const unsigned voff = (item && m < Mw) ? ((unsigned)m * (unsigned)d.ldx + 4u * kh) * 4u : kOOB;
@@ -1190,16 +1209,43 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         for (int e = 0; e < 16; ++e) acc[b][e] = 0.f;
 
     // POOL: the rows above and below (out-of-range where they do not exist), the winners' bytes, the neighbour exchange
-    const unsigned vup = (POOL && hasU) ? voff - (unsigned)prow : kOOB, vdn = (POOL && hasD) ? voff + (unsigned)prow : kOOB;
+    const unsigned vup = (POOL && upM) ? voff - (unsigned)prow : kOOB, vdn = (POOL && dnM) ? voff + (unsigned)prow : kOOB;
     const __amdgpu_buffer_rsrc_t srd_am = make_srd(POOL ? (const void *)d.pool_argmax : (const void *)p.x,
                                                    POOL ? (unsigned)((int64_t)p.M * K) : 0u);
-    const unsigned vam = (POOL && item && m < Mw && t0.col == 0) ? (unsigned)m * (unsigned)K + 4u * kh : kOOB;
-    f32x4 ru0, ru1, rd0, rd1;                      // POOL: the same channels of the pixel above / below
-    auto load_ud = [&](int c0) {
-        ru0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, vup, c0 * 4, 0));
-        ru1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, vup, c0 * 4 + 32, 0));
-        rd0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, vdn, c0 * 4, 0));
-        rd1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, vdn, c0 * 4 + 32, 0));
+    const unsigned vam = (POOL && item && m < Mw && t0.col == 0) ? (unsigned)m * (unsigned)K + 8u * kh : kOOB;
+    // POOL: the halo row of this wave -- the image row above wave 0's block or below wave 3's; waves 1 and 2 have none
+    const bool halo = POOL && (wave == 0 || wave == 3);          // (uniform)
+    const unsigned vhalo = wave == 0 ? vup : vdn;
+    f32x4 rh0 = {0.f, 0.f, 0.f, 0.f}, rh1 = {0.f, 0.f, 0.f, 0.f};
+    auto load_halo = [&](int c0) {
+        if (halo) {
+            rh0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, vhalo, c0 * 4, 0));
+            rh1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, vhalo, c0 * 4 + 32, 0));
+        }
+    };
+    // POOL: the centre rows of a K step, raw, as an LDS tile [2 stages][128 pixels][16 channels].  A wave fetches its block
+    // with FOUR lanes per pixel (lane -> pixel 16 j + lane / 4, 16-byte chunk lane % 4: one 64-byte sector per quad, where the
+    // fragment layout touches four rows per quad and the L1 spends a tag lookup on each), puts it into the tile, and every
+    // wave reads its own fragments AND the pixels above and below from there: an input row is fetched once per workgroup.
+    // The four chunks of a pixel are XOR-swizzled by (pixel >> 1) & 3 (conflict-free fragment reads, as in the A ring).
+    float *const ptile = smem + BST * BSZ + 256;
+    const int pown = wave * 32 + li, sown = (li >> 1) & 3, sup = (pu >> 1) & 3, sdn = (pd >> 1) & 3;
+    unsigned vco[2] = {kOOB, kOOB};
+    int tco[2] = {0, 0};
+    if constexpr (POOL) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int row = 16 * j + (lane >> 2), chunk = lane & 3;
+            vco[j] = (item && mrow0 + row < Mw) ? ((unsigned)(mrow0 + row) * (unsigned)d.ldx + 4u * chunk) * 4u : kOOB;
+            tco[j] = (wave * 32 + row) * 16 + ((chunk ^ ((row >> 1) & 3)) * 4);
+        }
+    }
+    auto tile_put = [&](int st, const f32x4 &c0v, const f32x4 &c1v) {
+        *reinterpret_cast<f32x4 *>(ptile + st * PT + tco[0]) = c0v;
+        *reinterpret_cast<f32x4 *>(ptile + st * PT + tco[1]) = c1v;
+    };
+    auto tile_get = [&](int st, int px, int sw, int half) -> f32x4 {
+        return *reinterpret_cast<const f32x4 *>(ptile + st * PT + px * 16 + (((2 * half + kh) ^ sw) * 4));
     };
     // lane i <- lane i - 1 / lane i + 1 of the wave (DPP wave shifts: one VALU move each, no LDS).  The block starts and ends
     // at image-row boundaries, so the lanes the shift wraps into (0, 31 | 32, 63) never use what they get.
@@ -1232,11 +1278,14 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         return bytes;
     };
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+    // the A loads of a K step: the lane's fragments, POOL: its two chunks of the tile
+    const unsigned va0 = POOL ? vco[0] : voff, va1 = POOL ? vco[1] : voff;
+    constexpr int kA1 = POOL ? 0 : 32;
     if constexpr (AST == 0) {
-        a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, voff, 0, 0));
-        a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, voff, 32, 0));
+        a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, va0, 0, 0));
+        a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, va1, kA1, 0));
     }
-    if constexpr (POOL) load_ud(0);
+    if constexpr (POOL) load_halo(0);
     // BNB: the gradient dy of the layer's activation, per channel range its own descriptor and row offset
     const ds_bn_bwd_on_load &bb = p.bnb;
     __amdgpu_buffer_rsrc_t srd_dy[3];
@@ -1298,13 +1347,42 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
 #pragma unroll
         for (int j = 0; j < 4; ++j) a[j] = ds::bn_bwd_dz(a[j], dy[j], r[j], sh[j], mu[j], k1[j], k2[j]);
     };
+    if constexpr (POOL) tile_put(0, a0, a1);
     __syncthreads();
-    auto pool_step = [&](int c0) {          // a0 / a1 hold the centre row of channels c0 ...: pool them, record the winners
-        const unsigned w0 = pool4(a0, ru0, rd0), w1 = pool4(a1, ru1, rd1);
-        __builtin_amdgcn_raw_buffer_store_b32(w0, srd_am, vam, c0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(w1, srd_am, vam, c0 + 8, 0);
+    // stage st of the tile holds every wave's centre rows of channels c0 ...: a0 / a1 <- the lane's fragments pooled, and
+    // the winners recorded
+    // The operands of the step after it (channels cnext ..., none: cnext < 0) are requested from here, behind the barrier
+    // that made the tile visible and ahead of the pooling arithmetic: they have that and the step's MFMAs to arrive.
+    f32x4 pn0 = {0.f, 0.f, 0.f, 0.f}, pn1 = {0.f, 0.f, 0.f, 0.f};
+    auto pool_step = [&](int c0, int st, int cnext) {
+        if (cnext >= 0) {
+            pn0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, va0, cnext * 4, 0));
+            pn1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, va1, cnext * 4, 0));
+        }
+        a0 = tile_get(st, pown, sown, 0);
+        a1 = tile_get(st, pown, sown, 1);
+        f32x4 u0 = tile_get(st, pu, sup, 0), u1 = tile_get(st, pu, sup, 1);
+        f32x4 e0 = tile_get(st, pd, sdn, 0), e1 = tile_get(st, pd, sdn, 1);
+        if (halo) {
+            if (wave == 0) {
+                u0 = upM ? rh0 : u0;
+                u1 = upM ? rh1 : u1;
+            } else {
+                e0 = dnM ? rh0 : e0;
+                e1 = dnM ? rh1 : e1;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (cnext >= 0) load_halo(cnext);          // (this step's halo is in u / e now)
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned w0 = pool4(a0, u0, e0), w1 = pool4(a1, u1, e1);
+        // the lanes (pixel, 0) and (pixel, 1) trade a word: 8 consecutive winners per lane, one store per K step
+        const auto sw = __builtin_amdgcn_permlane32_swap(w0, w1, false, false);
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 pr = {sw[0], sw[1]};
+        __builtin_amdgcn_raw_buffer_store_b64(pr, srd_am, vam, c0, 0);
     };
-    if constexpr (POOL) pool_step(0);
+    if constexpr (POOL) pool_step(0, 0, ksteps > 1 ? WK : -1);
     if (norm && AST == 0) {
         apply_norm(a0, 4 * kh);
         apply_norm(a1, 8 + 4 * kh);
@@ -1406,14 +1484,13 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
                 for (int j = 0; j < 4; ++j) { bf[j] = lo[j]; bf[4 + j] = hi[j]; }
             }
             if (more) {                                    // next K step's operands, spread over the column blocks
-                if (b == 0) {
+                if (b == 0 && !POOL) {                     // (POOL: requested by the pool step, see there)
                     n0v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, voff, cn * 4, 0));
                     if (BNB) d0 = load_dy(cn, 0);
                 }
-                if (b == ((NB > 1 && !DS_WIDE_A_B2B) ? 1 : 0)) {
+                if (b == ((NB > 1 && !DS_WIDE_A_B2B) ? 1 : 0) && !POOL) {
                     n1v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, voff, cn * 4 + 32, 0));
                     if (BNB) d1 = load_dy(cn, 1);
-                    if constexpr (POOL) load_ud(cn);      // (the previous step's rows were consumed before this K step began)
                 }
                 if (b < DJ) dma_b((ks + 1) & 1, cn, b);
             }
@@ -1428,10 +1505,15 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
 #pragma unroll
             for (int i = NB; i < DJ; ++i) dma_b((ks + 1) & 1, cn, i);
         }
-        a0 = n0v;
-        a1 = n1v;
         if constexpr (POOL) {
-            if (more) pool_step(cn);
+            // the K step's barrier stands between the waves' puts and their reads of the tile, whose other stage the slower
+            // waves may still be reading
+            if (more) tile_put((ks + 1) & 1, pn0, pn1);
+            __syncthreads();
+            if (more) pool_step(cn, (ks + 1) & 1, ks + 2 < ksteps ? cn + WK : -1);
+        } else {
+            a0 = n0v;
+            a1 = n1v;
         }
         if (norm && more) {
             apply_norm(a0, cn + 4 * kh);
@@ -1441,7 +1523,7 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
             apply_bnb(a0, d0, cn + 4 * kh);
             apply_bnb(a1, d1, cn + 8 + 4 * kh);
         }
-        __syncthreads();
+        if constexpr (!POOL) __syncthreads();
     }
 
     // ---- epilogue (conv_epilogue.h): store, BatchNorm column statistics ------------------------------------------------
@@ -1879,7 +1961,7 @@ int pool3_nb(const ds_conv_desc *d, bool vec) {
     if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->fold_cin || d->splits > 1 || d->bnb) return 0;
     if (d->flags & ~(DS_EPI_STATS | DS_EPI_BN_RELU)) return 0;
     if (!(d->w_n_stride == 1 && d->w_k_stride != 1)) return 0;
-    if (d->W > 32 || d->Cin % 16 != 0 || d->Cin < 32 || d->Cin > 1024 || d->Cout > 128) return 0;
+    if (d->W > 32 || d->Cin % 16 != 0 || d->Cin < 16 || d->Cin > 1024 || d->Cout > 128) return 0;
     const int64_t M = conv_M(d);
     if (((M - 1) * d->ldz + d->Cout) * 4 >= (1ll << 31) || M * d->Cin >= (1ll << 31)) return 0;
     return (d->Cout + 31) / 32;
