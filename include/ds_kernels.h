@@ -823,6 +823,43 @@ int ds_adam_tf(float *theta, const float *g, float *m, float *v, int64_t n, int6
                float grad_scale, float lr_t, const float *lr_t_dev, float beta1, float beta2, float eps,
                void *stream);
 
+/* Gradient norms, clipping factors and the non-finite guard of slim.learning.create_train_op(clip_gradient_norm=...)
+ * (im_text_rnn_model.py:135 leaves it at 0).  TensorFlow is not in the reference tree; restated from TF 1.x:
+ *   tf.clip_by_norm(t, c)                 t * c / max(||t||_2, c)                      (slim clip_gradient_norms, per variable)
+ *   tf.clip_by_global_norm(ts, c)         every t * c / max(sqrt(sum_t ||t||_2^2), c); a non-finite norm makes every entry NaN
+ * The clipped quantity is what compute_gradients(total_loss) returns, the g_eff of ds_adam_tf (L2 term included).
+ *
+ * Tables of int64 words on the device, built once per parameter layout:
+ *   segments[nseg][8]  one TF variable each: {offset, rows, ld, c0, ncols, chunk0, nchunks, 0}; element k < rows * ncols is
+ *                      flat element offset + (k / ncols) * ld + c0 + k % ncols (plain variable: rows 1, ld = ncols, c0 0; a
+ *                      column range of a horizontally fused tensor otherwise); its chunks are chunk0 .. chunk0 + nchunks - 1
+ *   chunks[nchunks][4] {seg, k0, count, 0}: elements k0 .. k0 + count - 1 of segment seg, never more than one segment;
+ *                      seg = -1: `count` pad elements from flat element k0 on, which belong to no variable
+ * The kernels check every chunk's flat range against n: a chunk that points outside the buffers is left out, never followed.
+ *
+ * ds_grad_norms, two launches, no atomics, bitwise reproducible and independent of the launch shape:
+ *   partials[c]   (nchunks doubles, workspace; every one is written) the sum of g_eff^2 over chunk c: g_eff in fp32 exactly as
+ *                 ds_adam_tf forms it, squares and sums in double -- per thread in index order, then a fixed tree
+ *   sumsq[s]      (nseg + 1 doubles) the partials of segment s added in chunk order; sumsq[nseg]: those added in segment order
+ *   factors[s]    (nseg + 1 floats) what ds_adam_tf_clipped multiplies segment s by; factors[nseg]: the global factor
+ *                 mode 0: all 1.  mode 1: (float)(clip / max(sqrt(sumsq[s]), clip)), factors[nseg] = 1.
+ *                 mode 2: (float)(clip / max(sqrt(sumsq[nseg]), clip)) everywhere.  Exactly 1.0f when nothing clips; NaN where
+ *                 the sum it is made from is NaN or Inf (set explicitly: a max() would drop the NaN).
+ *   flags[0]      1 if any sum is NaN or Inf, else 0;   flags[1] = flags[0] && skip_nonfinite: the step is to be skipped
+ *   flags[2]      is not written here (ds_adam_tf_clipped counts the skipped steps in it); flags holds 4 int32.
+ * clip: finite and > 0 unless mode is 0.
+ *
+ * ds_adam_tf_clipped: ds_adam_tf with g_eff * factors[seg] in place of g_eff (pad elements: factor 1) -- with every factor
+ * 1.0f the bits of ds_adam_tf, both kernels share one per-element update.  flags[1] != 0: theta, m and v are left untouched
+ * bit for bit and flags[2] goes up by one.  Plain vector stores only. */
+int ds_grad_norms(const float *theta, const float *g, int64_t n, int64_t n_wd, float wd, float grad_scale,
+                  const int64_t *segments, int32_t nseg, const int64_t *chunks, int32_t nchunks, int32_t mode, double clip,
+                  int32_t skip_nonfinite, double *partials, double *sumsq, float *factors, int32_t *flags, void *stream);
+int ds_adam_tf_clipped(float *theta, const float *g, float *m, float *v, int64_t n, int64_t n_wd, float wd,
+                       float grad_scale, float lr_t, const float *lr_t_dev, float beta1, float beta2, float eps,
+                       const int64_t *segments, int32_t nseg, const int64_t *chunks, int32_t nchunks, const float *factors,
+                       int32_t *flags, void *stream);
+
 /* Clone-gradient accumulation over the flat gradient buffer (slim/deployment/model_deploy.py:414-444, _sum_clones_gradients).
  * mode 0: acc[i] = g[i]            (first clone)
  * mode 1: acc[i] = acc[i] + g[i]   (middle clones)

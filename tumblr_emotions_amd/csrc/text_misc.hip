@@ -267,19 +267,195 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float *logits, co
 }
 
 // ---- TF Adam over a flat buffer ------------------------------------------------------------------
+// What compute_gradients(total_loss) returns for element i (w = theta[i]): the (all-reduced, clone-summed) gradient times
+// grad_scale plus the L2 regulariser's term on the first n_wd entries.  ONE definition: ds_adam_tf, ds_adam_tf_clipped and the
+// norm pass of ds_grad_norms evaluate it.  No contraction into fused multiply-adds, here and in adam_tf_update: the
+// compiler forms them in one caller's loop and not in another's (it did, in an unrolled norm loop), and the three kernels
+// must round alike -- products and sums, each rounded once, which is what adam_tf_kernel has always compiled to.
+__device__ __forceinline__ float adam_g_eff(const float *g, int64_t i, float w, int64_t n_wd, float wd, float grad_scale) {
+#pragma clang fp contract(off)
+    float gi = g[i] * grad_scale;
+    if (i < n_wd) gi += wd * w;                       // d/dw of wd * sum(w^2)/2
+    return gi;
+}
+
+// The update of element i from its effective gradient gi, shared by both Adam kernels.
+__device__ __forceinline__ void adam_tf_update(float *theta, float *m, float *v, int64_t i, float w, float gi, float lr_t,
+                                               float b1, float b2, float eps) {
+#pragma clang fp contract(off)
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    theta[i] = w - lr_t * mi / (sqrtf(vi) + eps);     // epsilon outside the bias correction (A10)
+}
+
 __global__ __launch_bounds__(256) void adam_tf_kernel(float *theta, const float *g, float *m, float *v, int64_t n,
                                                       int64_t n_wd, float wd, float grad_scale, float lr_t,
                                                       const float *lr_t_dev, float b1, float b2, float eps) {
     if (lr_t_dev) lr_t = lr_t_dev[0];         // step size kept on device (hipGraph replay safe)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float w = theta[i];
-        float gi = g[i] * grad_scale;
-        if (i < n_wd) gi += wd * w;                       // d/dw of wd * sum(w^2)/2
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        theta[i] = w - lr_t * mi / (sqrtf(vi) + eps);     // epsilon outside the bias correction (A10)
+        adam_tf_update(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale), lr_t, b1, b2, eps);
+    }
+}
+
+// ---- gradient norms, clipping factors and the non-finite guard (ds_grad_norms, ds_adam_tf_clipped) -------------------------
+// Tables (int64, built by the host once per parameter layout):
+//   segment s = one TF variable: {offset, rows, ld, c0, ncols, chunk0, nchunks, 0} -- element k of it (k < rows * ncols) is
+//               flat element offset + (k / ncols) * ld + c0 + k % ncols (a plain variable: rows = 1, ld = ncols, c0 = 0; a
+//               column range of a horizontally fused tensor otherwise); its chunks are chunk0 .. chunk0 + nchunks - 1
+//   chunk c   = {seg, k0, count, 0}: elements k0 .. k0 + count - 1 of segment seg; seg = -1: `count` pad elements from flat
+//               element k0 on (they belong to no variable; the optimiser visits them with factor 1)
+// A chunk never straddles a segment, so a workgroup's sum belongs to one variable and the optimiser reads ONE factor per
+// workgroup.  Every chunk's flat range is checked against n before it is walked (a chunk that fails is left out as a whole): a
+// broken table cannot make a kernel leave the buffers.
+constexpr int kSegWords = 8, kChunkWords = 4;
+enum { kFlagNonfinite = 0, kFlagSkip = 1, kFlagSkipped = 2 };
+
+struct ClipChunk {
+    int64_t seg, k0, count, offset, ld, c0, ncols;
+    bool plain, ok;
+};
+
+__device__ __forceinline__ ClipChunk clip_chunk(const int64_t *segments, int nseg, const int64_t *chunks, int c, int64_t n) {
+    ClipChunk q;
+    q.seg = chunks[(int64_t)c * kChunkWords];
+    q.k0 = chunks[(int64_t)c * kChunkWords + 1];
+    q.count = chunks[(int64_t)c * kChunkWords + 2];
+    q.ok = q.seg >= -1 && q.seg < nseg && q.k0 >= 0 && q.count >= 0 && q.count <= n;
+    if (q.seg < 0 || !q.ok) {          // pad elements: flat from k0
+        q.offset = 0; q.ld = 1; q.c0 = 0; q.ncols = 1; q.plain = true;
+        q.ok = q.ok && q.k0 <= n - q.count;
+        return q;
+    }
+    const int64_t *s = segments + q.seg * kSegWords;
+    const int64_t rows = s[1];
+    q.offset = s[0]; q.ld = s[2]; q.c0 = s[3]; q.ncols = s[4];
+    q.plain = q.ld == q.ncols;
+    // the segment lies inside [0, n) (its last element is offset + (rows - 1) ld + c0 + ncols - 1) and the chunk inside the segment
+    q.ok = q.offset >= 0 && q.offset < n && rows > 0 && rows <= n && q.ncols > 0 && q.ld >= q.ncols && q.ld <= n && q.c0 >= 0 &&
+           q.c0 + q.ncols <= q.ld && q.c0 + q.ncols <= n - q.offset && rows - 1 <= (n - q.offset - q.c0 - q.ncols) / q.ld &&
+           q.k0 <= rows * q.ncols - q.count;
+    return q;
+}
+
+// flat index of element j (j < count) of a chunk that clip_chunk found inside the buffers
+__device__ __forceinline__ int64_t clip_flat(const ClipChunk &q, int64_t j) {
+    const int64_t k = q.k0 + j;
+    if (q.plain) return q.offset + q.c0 + k;
+    const int64_t r = (k | q.ncols) >> 32 ? k / q.ncols : (int64_t)((uint32_t)k / (uint32_t)q.ncols);
+    return q.offset + r * q.ld + q.c0 + (k - r * q.ncols);
+}
+
+// sum over the workgroup, in double, in a fixed order: thread t's own terms in index order, then the tree below
+__device__ __forceinline__ double block_sum_f64(double acc, double *red) {
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// Stage 1: partials[c] = sum of g_eff^2 over chunk c (0 for a pad chunk).  g_eff in fp32 as the optimiser forms it, the
+// squares and the sums in double.  The chunks are walked grid-stride, so the result does not depend on the grid.
+__global__ __launch_bounds__(256) void grad_norms_stage1(const float *theta, const float *g, int64_t n, int64_t n_wd, float wd,
+                                                         float grad_scale, const int64_t *segments, int nseg,
+                                                         const int64_t *chunks, int nchunks, double *partials) {
+    __shared__ double red[256];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const ClipChunk q = clip_chunk(segments, nseg, chunks, c, n);
+        double acc = 0.0;
+        if (q.ok && q.seg >= 0) {
+#pragma unroll 4
+            for (int64_t j = threadIdx.x; j < q.count; j += 256) {
+                const int64_t i = clip_flat(q, j);
+                const double ge = (double)adam_g_eff(g, i, theta[i], n_wd, wd, grad_scale);
+                acc += ge * ge;
+            }
+        }
+        const double s = block_sum_f64(acc, red);
+        if (threadIdx.x == 0) partials[c] = s;
+    }
+}
+
+__device__ __forceinline__ float clip_factor(double sumsq, double clip) {
+    if (!(fabs(sumsq) <= 1.7976931348623157e308)) return __builtin_nanf("");      // NaN or Inf norm: fmax would drop the NaN
+    const double nrm = sqrt(sumsq);
+    return (float)(clip / (nrm > clip ? nrm : clip));                             // exactly 1.0f when nothing clips
+}
+
+// Stage 2, one workgroup: sumsq[s] = the partials of segment s added in chunk order, sumsq[nseg] = the segment sums added in
+// segment order; flags[0] = some sum is NaN / Inf, flags[1] = the step is to be skipped (that, under the guard);
+// factors[s] = what the optimiser multiplies segment s by, factors[nseg] = the global factor (1 unless mode 2).
+// mode 0: no clipping, 1: tf.clip_by_norm per variable, 2: tf.clip_by_global_norm.
+__global__ __launch_bounds__(256) void grad_norms_stage2(const int64_t *segments, int nseg, int nchunks, const double *partials,
+                                                         int mode, double clip, int guard, double *sumsq, float *factors,
+                                                         int *flags) {
+    __shared__ int bad;
+    __shared__ float gfac;
+    if (threadIdx.x == 0) bad = 0;
+    __syncthreads();
+    for (int s = threadIdx.x; s < nseg; s += 256) {
+        int64_t c0 = segments[(int64_t)s * kSegWords + 5], c1 = c0 + segments[(int64_t)s * kSegWords + 6];
+        if (c0 < 0) c0 = 0;
+        if (c1 > nchunks) c1 = nchunks;
+        double acc = 0.0;
+        int64_t c = c0;
+        for (; c + 8 <= c1; c += 8) {          // eight loads in flight, added in chunk order
+            double p[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) p[j] = partials[c + j];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc += p[j];
+        }
+        for (; c < c1; ++c) acc += partials[c];
+        sumsq[s] = acc;
+        if (!(fabs(acc) <= 1.7976931348623157e308)) bad = 1;      // (every writer stores the same value)
+        if (mode != 2) factors[s] = mode == 1 ? clip_factor(acc, clip) : 1.f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int s = 0; s < nseg; ++s) tot += sumsq[s];
+        sumsq[nseg] = tot;
+        if (!(fabs(tot) <= 1.7976931348623157e308)) bad = 1;
+        gfac = mode == 2 ? clip_factor(tot, clip) : 1.f;
+        factors[nseg] = gfac;
+        flags[kFlagNonfinite] = bad;
+        flags[kFlagSkip] = bad && guard ? 1 : 0;
+    }
+    __syncthreads();
+    if (mode == 2)
+        for (int s = threadIdx.x; s < nseg; s += 256) factors[s] = gfac;
+}
+
+// The optimiser launch behind ds_grad_norms: chunk by chunk, g_eff * factors[seg] into adam_tf_update.  flags[1] set: nothing
+// is written but flags[2], the count of skipped steps, which workgroup 0 raises by one.
+__global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float *theta, const float *g, float *m, float *v, int64_t n,
+                                                              int64_t n_wd, float wd, float grad_scale, float lr_t,
+                                                              const float *lr_t_dev, float b1, float b2, float eps,
+                                                              const int64_t *segments, int nseg, const int64_t *chunks,
+                                                              int nchunks, const float *factors, int *flags) {
+    if (flags[kFlagSkip]) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) flags[kFlagSkipped] = flags[kFlagSkipped] + 1;
+        return;
+    }
+    if (lr_t_dev) lr_t = lr_t_dev[0];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const ClipChunk q = clip_chunk(segments, nseg, chunks, c, n);
+        if (!q.ok) continue;
+        const float f = q.seg >= 0 ? factors[q.seg] : 1.f;
+#pragma unroll 4
+        for (int64_t j = threadIdx.x; j < q.count; j += 256) {
+            const int64_t i = clip_flat(q, j);
+            const float w = theta[i];
+            adam_tf_update(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale) * f, lr_t, b1, b2, eps);
+        }
     }
 }
 
@@ -540,6 +716,36 @@ extern "C" int ds_adam_tf(float *theta, const float *g, float *m, float *v, int6
     hipLaunchKernelGGL(adam_tf_kernel, dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
                        n, n_wd, wd, grad_scale, lr_t, lr_t_dev, beta1, beta2, eps);
     return ds::check_launch("ds_adam_tf");
+}
+
+extern "C" int ds_grad_norms(const float *theta, const float *g, int64_t n, int64_t n_wd, float wd, float grad_scale,
+                             const int64_t *segments, int32_t nseg, const int64_t *chunks, int32_t nchunks, int32_t mode,
+                             double clip, int32_t skip_nonfinite, double *partials, double *sumsq, float *factors,
+                             int32_t *flags, void *stream) {
+    DS_REQUIRE(theta && g && n > 0 && n_wd >= 0 && n_wd <= n, "ds_grad_norms: bad argument");
+    DS_REQUIRE(segments && chunks && nseg > 0 && nchunks > 0, "ds_grad_norms: empty segment or chunk table");
+    DS_REQUIRE(partials && sumsq && factors && flags, "ds_grad_norms: null output");
+    DS_REQUIRE(mode >= 0 && mode <= 2, "ds_grad_norms: mode must be 0 (none), 1 (per variable) or 2 (global), not %d", (int)mode);
+    DS_REQUIRE(mode == 0 || (clip > 0.0 && clip <= 1.7976931348623157e308),
+               "ds_grad_norms: the clipping threshold must be a finite number > 0 (got %g)", clip);
+    hipLaunchKernelGGL(grad_norms_stage1, dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream, theta, g, n,
+                       n_wd, wd, grad_scale, segments, nseg, chunks, nchunks, partials);
+    hipLaunchKernelGGL(grad_norms_stage2, dim3(1), dim3(256), 0, (hipStream_t)stream, segments, nseg, nchunks, partials, mode,
+                       clip, skip_nonfinite ? 1 : 0, sumsq, factors, flags);
+    return ds::check_launch("ds_grad_norms");
+}
+
+extern "C" int ds_adam_tf_clipped(float *theta, const float *g, float *m, float *v, int64_t n, int64_t n_wd, float wd,
+                                  float grad_scale, float lr_t, const float *lr_t_dev, float beta1, float beta2, float eps,
+                                  const int64_t *segments, int32_t nseg, const int64_t *chunks, int32_t nchunks,
+                                  const float *factors, int32_t *flags, void *stream) {
+    DS_REQUIRE(theta && g && m && v && n > 0 && n_wd >= 0 && n_wd <= n, "ds_adam_tf_clipped: bad argument");
+    DS_REQUIRE(segments && chunks && nseg > 0 && nchunks > 0, "ds_adam_tf_clipped: empty segment or chunk table");
+    DS_REQUIRE(factors && flags, "ds_adam_tf_clipped: null factors or flags");
+    hipLaunchKernelGGL(adam_tf_clipped_kernel, dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream, theta, g,
+                       m, v, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, beta1, beta2, eps, segments, nseg, chunks, nchunks,
+                       factors, flags);
+    return ds::check_launch("ds_adam_tf_clipped");
 }
 
 extern "C" int ds_grad_accumulate(float *acc, float *g, int64_t n, int32_t mode, void *stream) {

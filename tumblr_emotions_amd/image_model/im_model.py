@@ -4,7 +4,7 @@ import os
 import numpy as np
 
 from ..net import SentimentNet
-from ..training import SyntheticInput, check_clones_config, run_training
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, run_training
 
 _RANDOM_SEED = 0
 _CONFIG = {'mode': 'train',
@@ -62,6 +62,8 @@ class ImageModel(SyntheticInput):
                 net_kw.setdefault(key, bool(config[key]))
         if "dtype" in config:
             net_kw.setdefault("dtype", config["dtype"])
+        for key, value in clip_net_kwargs(config).items():      # gradient clipping / the non-finite guard (training.py)
+            net_kw.setdefault(key, value)
         self.net = SentimentNet(mode="image", nb_emotions=self.nb_emotions, device=device, **net_kw)
         self.net.initialize(seed=config.get('seed', 1))
         self.logits = None

@@ -7,7 +7,7 @@ from .. import ops
 from ..image_model.im_model import get_init_fn
 from ..net import SentimentNet
 from ..text_model.text_preprocessing import resolve_embedding
-from ..training import SyntheticInput, check_clones_config, run_training
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, run_training
 
 _POST_SIZE = 50
 _CONFIG = {'mode': 'train',
@@ -40,6 +40,8 @@ class DeepSentiment(SyntheticInput):
                 net_kw.setdefault(key, bool(config[key]))
         if "dtype" in config:
             net_kw.setdefault("dtype", config["dtype"])
+        for key, value in clip_net_kwargs(config).items():      # gradient clipping / the non-finite guard (training.py)
+            net_kw.setdefault(key, value)
         self.net = SentimentNet(mode="joint", nb_emotions=self.nb_emotions,
                                 im_features_size=config['im_features_size'], rnn_size=config['rnn_size'],
                                 fc_size=config['fc_size'], vocab_size=vocab, embedding_dim=dim, post_size=post,

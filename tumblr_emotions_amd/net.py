@@ -23,14 +23,36 @@ from .params import ParamStore
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8      # tf.train.AdamOptimizer defaults (:134)
 
 
+def check_clip_config(clip_gradient_norm=None, clip_global_norm=None):
+    """(mode, threshold) of the two clipping arguments; needs no device.  clip_gradient_norm = c: slim's clip_gradient_norms,
+    tf.clip_by_norm per variable; clip_global_norm = c: tf.clip_by_global_norm.  ValueError if both are given or c is not a
+    finite number > 0 (a bool is not a number)."""
+    if clip_gradient_norm is not None and clip_global_norm is not None:
+        raise ValueError("clip_gradient_norm and clip_global_norm are mutually exclusive")
+    for key, c, mode in (("clip_gradient_norm", clip_gradient_norm, ops.CLIP_PER_VARIABLE),
+                         ("clip_global_norm", clip_global_norm, ops.CLIP_GLOBAL)):
+        if c is None:
+            continue
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, float, np.integer, np.floating)) \
+                or not math.isfinite(c) or not c > 0:
+            raise ValueError("%s must be a finite number > 0, not %r" % (key, c))
+        return mode, float(c)
+    return ops.CLIP_NONE, 0.0
+
+
 class SentimentNet:
     def __init__(self, mode="joint", nb_emotions=15, im_features_size=256, rnn_size=512, fc_size=512,
                  vocab_size=10000, embedding_dim=300, post_size=32, image_size=224, dropout_keep_prob=0.8,
                  trainable_bn_beta=True, device="cuda", process_group=None, overlap_comm=True,
                  concurrent_towers=True, train_all=False, trainable_embedding=False, dtype="f32",
-                 force_dp_buckets=False, sync_bn=False, frozen_bn=False):
+                 force_dp_buckets=False, sync_bn=False, frozen_bn=False, clip_gradient_norm=None, clip_global_norm=None,
+                 skip_nonfinite_steps=False):
         assert mode in ("joint", "image", "text")
         self.dtype = dtype
+        # gradient clipping and the non-finite guard (opt-in, DESIGN.md 7.13); refused before anything touches the device
+        self.clip_mode, self.clip_norm = check_clip_config(clip_gradient_norm, clip_global_norm)
+        self.skip_nonfinite_steps = bool(skip_nonfinite_steps)
+        self.clip_active = self.clip_mode != ops.CLIP_NONE or self.skip_nonfinite_steps
         # frozen_bn (opt-in): train_step normalises with the MOVING statistics -- slim.arg_scope([slim.batch_norm],
         # is_training=False) around a tower that otherwise trains (dropout on, the same trainable set, beta's gradient is the
         # plain column sum) -- and never writes them; everything but train_step is that of any other net (DESIGN.md 7.9)
@@ -105,6 +127,17 @@ class SentimentNet:
                 raise ValueError("sync_bn is implemented for the fp32 configuration")
             self.image.sync_bn, self.image.sync_world, self.image.sync_group = True, self.world, process_group
         self.logits = None
+        self.clip_state = None
+        if self.clip_active:
+            if st.clip_segments.shape[0] == 0:
+                raise ValueError("gradient clipping: the model has no trainable variable")
+            seg, chunks = st.clip_tables()
+            nseg = seg.shape[0]
+            # partials (workspace), sumsq [nseg + 1], factors [nseg + 1], flags (non-finite, skip, skipped steps, -)
+            self.clip_state = (torch.zeros(chunks.shape[0], dtype=torch.float64, device=self.device),
+                               torch.zeros(nseg + 1, dtype=torch.float64, device=self.device),
+                               torch.ones(nseg + 1, dtype=torch.float32, device=self.device),
+                               torch.zeros(4, dtype=torch.int32, device=self.device))
         self._graph = None           # captured training step (capture_step)
         self._graph_key = None
 
@@ -472,9 +505,53 @@ class SentimentNet:
         self.reducer.begin_step()      # engines call reducer.stage_done(...): bucket 1 is all-reduced under the backward
         self._step_body(batch, dropout_mask, seed, self.loss_buf)
         grad_scale = self.reducer.finish()
-        ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
-                    ADAM_B1, ADAM_B2, ADAM_EPS)
+        self._optimise(grad_scale, lr_t)
         return self.loss_buf.view(())
+
+    def _optimise(self, grad_scale, lr_t, lr_t_dev=None):
+        """The optimiser behind a step's gradients (all-reduced and clone-summed in store.grad): one ds_adam_tf launch -- or,
+        with clip_gradient_norm / clip_global_norm / skip_nonfinite_steps, the norm launches (ds_grad_norms) and the Adam launch
+        that reads their factors and skip flag from device memory (ds_adam_tf_clipped).  Nothing synchronises; store.grad is
+        only read.  Under data parallelism every rank reduces the same summed buffer with the same kernels, so the ranks
+        clip and skip alike."""
+        st = self.store
+        if not self.clip_active:
+            ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
+                        ADAM_B1, ADAM_B2, ADAM_EPS, lr_t_dev=lr_t_dev)
+            return
+        seg, chunks = st.clip_tables()
+        partials, sumsq, factors, flags = self.clip_state
+        ops.grad_norms(st.theta, st.grad, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, seg, chunks, self.clip_mode,
+                       self.clip_norm, self.skip_nonfinite_steps, partials, sumsq, factors, flags)
+        ops.adam_tf_clipped(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
+                            ADAM_B1, ADAM_B2, ADAM_EPS, seg, chunks, factors, flags, lr_t_dev=lr_t_dev)
+
+    def grad_norms(self):
+        """Gradient norms of the last step, one synchronising read of what ds_grad_norms left on the device: {tf_name: the
+        variable's ||g_eff||_2 BEFORE clipping} (g_eff = what compute_gradients(total_loss) returns: summed over ranks and
+        clones, scaled by 1 / (world * clones), L2 term included; the three block-input 1x1 convs of a fused tensor each
+        under their own name) plus 'global_norm', 'factor' (clip_global_norm: the one factor applied) or 'factors'
+        ({tf_name: factor}; all 1.0 under skip_nonfinite_steps alone), 'nonfinite' (some norm of that step was NaN / Inf) and
+        'skipped_steps' (steps the guard has skipped so far).  Needs one of clip_gradient_norm, clip_global_norm,
+        skip_nonfinite_steps: a net without them runs no norm launch (skip_nonfinite_steps=True is the one that changes no
+        finite step)."""
+        if not self.clip_active:
+            raise RuntimeError("grad_norms() needs clip_gradient_norm, clip_global_norm or skip_nonfinite_steps: this net "
+                               "runs no gradient-norm launch")
+        torch.cuda.synchronize(self.device)
+        _, sumsq, factors, flags = self.clip_state
+        sumsq, factors, flags = sumsq.cpu().numpy(), factors.cpu().numpy(), flags.cpu().numpy()
+        names = self.store.clip_names
+        out = {n: float(math.sqrt(x)) if x >= 0 else float("nan") for n, x in zip(names, sumsq[:-1])}
+        tot = float(sumsq[-1])
+        out["global_norm"] = math.sqrt(tot) if tot >= 0 else float("nan")
+        if self.clip_mode == ops.CLIP_GLOBAL:
+            out["factor"] = float(factors[-1])
+        else:
+            out["factors"] = {n: float(f) for n, f in zip(names, factors[:-1])}
+        out["nonfinite"] = bool(flags[0])
+        out["skipped_steps"] = int(flags[2])
+        return out
 
     def _begin_step(self, lr):
         """Count the step and return its Adam step size lr_t."""
@@ -610,8 +687,7 @@ class SentimentNet:
         self.reducer.finish()
         self.logits = self.clone_logits
         self._clone_count = K
-        ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, 1.0 / (self.world * K), lr_t,
-                    ADAM_B1, ADAM_B2, ADAM_EPS)
+        self._optimise(1.0 / (self.world * K), lr_t)
         return self.clone_loss
 
     # ---- the same step as one hipGraph ---------------------------------------------------------------
@@ -640,7 +716,8 @@ class SentimentNet:
         st = self.store
         # eager warm-up (allocates every buffer, builds every plan) on a snapshot of the optimiser state, so that
         # capturing has no side effect on the variables, the Adam slots or the BatchNorm moving statistics
-        keep = [b.clone() for b in (st.theta, st.m, st.v, st.frozen)]
+        state = (st.theta, st.m, st.v, st.frozen) + (() if self.clip_state is None else (self.clip_state[3],))
+        keep = [b.clone() for b in state]      # (the guard's count of skipped steps is state too)
         if self.image is not None and self.image.B != batch["images"].shape[0]:
             self.image.alloc(batch["images"].shape[0])
         if self.image is not None:
@@ -657,7 +734,7 @@ class SentimentNet:
         keep_pivots = [m.clone() for m in pivots]
         self.train_step(batch, 0.0, dropout_mask)
         self.step -= 1
-        for b, k in zip((st.theta, st.m, st.v, st.frozen), keep):
+        for b, k in zip(state, keep):
             b.copy_(k)
         for m, k in zip(pivots, keep_pivots):
             m.copy_(k)
@@ -667,8 +744,7 @@ class SentimentNet:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._step_body(batch, dropout_mask, 0, self.loss_buf)      # (the seed of a replay is seed_dev's)
-            ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, 1.0, 0.0,
-                        ADAM_B1, ADAM_B2, ADAM_EPS, lr_t_dev=self.lr_t_dev)
+            self._optimise(1.0, 0.0, lr_t_dev=self.lr_t_dev)
         self._graph, self._graph_key = g, self._batch_key(batch, dropout_mask)
         return True
 

@@ -1046,6 +1046,36 @@ def adam_tf(theta, g, m, v, n, n_wd, wd, grad_scale, lr_t, b1, b2, eps, lr_t_dev
                                       b1, b2, eps, _stream()), "ds_adam_tf")
 
 
+CLIP_NONE, CLIP_PER_VARIABLE, CLIP_GLOBAL = 0, 1, 2
+
+
+def grad_norms(theta, g, n, n_wd, wd, grad_scale, segments, chunks, mode, clip, skip_nonfinite, partials, sumsq, factors,
+               flags):
+    """Per-variable and global sums of squares of the effective gradient, the clipping factors and the skip flag
+    (ds_grad_norms): segments int64 [nseg, 8], chunks int64 [nchunks, 4] (ParamStore.clip_tables), partials float64 [nchunks],
+    sumsq float64 [nseg + 1], factors float32 [nseg + 1], flags int32 [4].  Two launches, nothing is read back."""
+    nseg, nchunks = segments.shape[0], chunks.shape[0]
+    assert partials.dtype == torch.float64 and partials.numel() >= nchunks
+    assert sumsq.dtype == torch.float64 and sumsq.numel() >= nseg + 1
+    assert factors.dtype == torch.float32 and factors.numel() >= nseg + 1
+    assert flags.dtype == torch.int32 and flags.numel() >= 4
+    assert segments.dtype == torch.int64 and chunks.dtype == torch.int64 and segments.shape[1] == 8 and chunks.shape[1] == 4
+    _lib.check(_lib.load().ds_grad_norms(_p(theta), _p(g), n, n_wd, wd, grad_scale, _p(segments), nseg, _p(chunks), nchunks,
+                                         mode, float(clip), int(bool(skip_nonfinite)), _p(partials), _p(sumsq), _p(factors),
+                                         _p(flags), _stream()), "ds_grad_norms")
+
+
+def adam_tf_clipped(theta, g, m, v, n, n_wd, wd, grad_scale, lr_t, b1, b2, eps, segments, chunks, factors, flags,
+                    lr_t_dev=None):
+    """ds_adam_tf on g_eff * factors[segment], skipped as a whole when flags[1] is set (ds_adam_tf_clipped)."""
+    nseg, nchunks = segments.shape[0], chunks.shape[0]
+    assert factors.dtype == torch.float32 and factors.numel() >= nseg + 1 and flags.dtype == torch.int32 and flags.numel() >= 4
+    assert segments.dtype == torch.int64 and chunks.dtype == torch.int64 and segments.shape[1] == 8 and chunks.shape[1] == 4
+    _lib.check(_lib.load().ds_adam_tf_clipped(_p(theta), _p(g), _p(m), _p(v), n, n_wd, wd, grad_scale, lr_t, _p(lr_t_dev),
+                                              b1, b2, eps, _p(segments), nseg, _p(chunks), nchunks, _p(factors), _p(flags),
+                                              _stream()), "ds_adam_tf_clipped")
+
+
 def grad_accumulate(acc, g, n, mode):
     """Clone-gradient accumulation over the first n floats of two flat buffers: mode 0 acc = g, 1 acc = acc + g,
     2 g = acc + g (the running sum is the left operand; n % 4 == 0, 16-byte aligned)."""

@@ -29,6 +29,46 @@ class Entry:
         self.offset = -1
 
 
+CLIP_CHUNK = 4096      # elements of a variable that one workgroup of the gradient-norm / clipped-Adam kernels walks
+
+
+def build_clip_tables(entries, n, chunk=CLIP_CHUNK):
+    """The tables of ds_grad_norms / ds_adam_tf_clipped (include/ds_kernels.h) for trainable `entries` laid out (offsets set,
+    ascending) in a flat buffer of `n` elements.  Returns (names, segments int64 [nseg, 8], chunks int64 [nchunks, 4]).
+      segment = one TF variable: (offset, rows, ld, c0, ncols, chunk0, nchunks, 0) -- a plain variable is one row of numel
+                columns; every (tf_name, c0, c1) of a fused tensor's `columns` is the column range [c0, c1) of its
+                [numel / ld, ld] matrix, ld = shape[-1], with a norm and a clipping factor of its own;
+      chunk   = (segment, k0, count, 0): at most `chunk` consecutive elements of ONE segment, in the segment's own element
+                order; (-1, flat start, count, 0): the pad elements between two tensors (and behind the last), which belong
+                to no variable but are still visited by the optimiser.
+    Every flat element of [0, n) is in exactly one chunk."""
+    names, segs, chunks = [], [], []
+
+    def segment(name, offset, rows, ld, c0, ncols):
+        total, first = rows * ncols, len(chunks)
+        for k0 in range(0, total, chunk):
+            chunks.append((len(segs), k0, min(chunk, total - k0), 0))
+        names.append(name)
+        segs.append((offset, rows, ld, c0, ncols, first, len(chunks) - first, 0))
+
+    end = 0
+    for e in entries:
+        assert e.offset >= end, e.name
+        if e.offset > end:
+            chunks.append((-1, end, e.offset - end, 0))
+        if e.columns:
+            ld = e.shape[-1]
+            assert e.numel % ld == 0 and sorted(c for (_, c0, c1) in e.columns for c in range(c0, c1)) == list(range(ld)), e.name
+            for (name, c0, c1) in e.columns:
+                segment(name, e.offset, e.numel // ld, ld, c0, c1 - c0)
+        else:
+            segment(e.name, e.offset, 1, e.numel, 0, e.numel)
+        end = e.offset + e.numel
+    if n > end:
+        chunks.append((-1, end, n - end, 0))
+    return (names, np.asarray(segs, dtype=np.int64).reshape(-1, 8), np.asarray(chunks, dtype=np.int64).reshape(-1, 4))
+
+
 class ParamStore:
     def __init__(self, device="cuda"):
         self.device = torch.device(device)
@@ -69,7 +109,16 @@ class ParamStore:
         self.v = torch.zeros_like(self.theta)
         self.grad = torch.zeros_like(self.theta)
         self.frozen = torch.zeros(max(off, 4), dtype=torch.float32, device=self.device)
+        self.clip_names, self.clip_segments, self.clip_chunks = build_clip_tables(tr, n_tr)
+        self._clip_dev = None
         self.finalized = True
+
+    def clip_tables(self):
+        """(segments, chunks) of the gradient-norm kernels as int64 tensors on the store's device (copied there once)."""
+        if self._clip_dev is None:
+            self._clip_dev = (torch.from_numpy(self.clip_segments).to(self.device),
+                              torch.from_numpy(self.clip_chunks).to(self.device))
+        return self._clip_dev
 
     # -- views ------------------------------------------------------------------------------------
     def _buf(self, e):

@@ -4,7 +4,7 @@ import torch
 
 from ..net import SentimentNet
 from .text_preprocessing import resolve_embedding
-from ..training import SyntheticInput, check_clones_config, run_training
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, run_training
 
 _RANDOM_SEED = 0
 _CONFIG = {'mode': 'train',
@@ -35,6 +35,8 @@ class TextModel(SyntheticInput):
                 net_kw.setdefault(key, bool(config[key]))
         if "dtype" in config:
             net_kw.setdefault("dtype", config["dtype"])
+        for key, value in clip_net_kwargs(config).items():      # gradient clipping / the non-finite guard (training.py)
+            net_kw.setdefault(key, value)
         self.net = SentimentNet(mode="text", nb_emotions=self.nb_emotions, rnn_size=config['rnn_size'],
                                 vocab_size=vocab, embedding_dim=dim, post_size=post, device=device, **net_kw)
         self.net.initialize(seed=config.get('seed', 1))

@@ -42,6 +42,41 @@ def check_clones_config(config):
     return K
 
 
+def clip_net_kwargs(config):
+    """The gradient-clipping keys of a front-end config as SentimentNet arguments; needs no device.
+    config['clip_gradient_norm'] = c: slim's create_train_op(clip_gradient_norm=c), tf.clip_by_norm per variable;
+    config['clip_global_norm'] = c: tf.clip_by_global_norm; config['skip_nonfinite_steps'] = True: a step whose gradient
+    has a NaN / Inf norm leaves the variables and the Adam slots alone.  config['log_gradient_norms'] = True: run_training
+    appends net.grad_norms() to <train_dir>/gradients.jsonl on its logging steps -- a ValueError without one of the other
+    three keys, which are what makes the step compute norms (skip_nonfinite_steps is the one that changes no finite step).
+    ValueError for both thresholds at once, a threshold that is not a finite number > 0, or a flag that is not a bool."""
+    from .net import check_clip_config
+    kw = {k: config[k] for k in ("clip_gradient_norm", "clip_global_norm") if config.get(k) is not None}
+    check_clip_config(**kw)
+    for k in ("skip_nonfinite_steps", "log_gradient_norms"):
+        if not isinstance(config.get(k, False), (bool, np.bool_)):
+            raise ValueError("config[%r] must be a bool, not %r" % (k, config[k]))
+    if config.get("skip_nonfinite_steps", False):
+        kw["skip_nonfinite_steps"] = True
+    if config.get("log_gradient_norms", False) and not kw:
+        raise ValueError("config['log_gradient_norms'] needs config['clip_gradient_norm'], config['clip_global_norm'] or "
+                         "config['skip_nonfinite_steps']: without them the step computes no gradient norm")
+    return kw
+
+
+def _log_gradient_norms(net, train_dir, step):
+    """One line of <train_dir>/gradients.jsonl: the step, the global norm, the factor(s), the skipped count, the norms."""
+    gn = net.grad_norms()
+    line = {"global_step": step, "global_norm": gn.pop("global_norm"), "nonfinite": gn.pop("nonfinite"),
+            "skipped_steps": gn.pop("skipped_steps")}
+    for k in ("factor", "factors"):
+        if k in gn:
+            line[k] = gn.pop(k)
+    line["norms"] = gn
+    with open(os.path.join(train_dir, "gradients.jsonl"), "a") as f:
+        f.write(json.dumps(line) + "\n")
+
+
 def _rank_world():
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         return torch.distributed.get_rank(), torch.distributed.get_world_size()
@@ -132,6 +167,7 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
     cfg = model.config
     batch_size, initial_lr, decay = cfg["batch_size"], cfg["initial_lr"], cfg["decay_factor"]
     num_clones = check_clones_config(cfg)      # batch_size is the batch of ONE clone, as in slim
+    log_norms = bool(cfg.get("log_gradient_norms", False)) and bool(clip_net_kwargs(cfg))
     # python-2 integer division, :140; under data parallelism one step consumes batch_size * num_clones * world samples
     nb_batches = max(1, model.dataset.num_samples // (batch_size * num_clones * world))
     net = model.net
@@ -157,6 +193,8 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
         if (step + 1) % log_every == 0 or step + 1 == num_steps:
             loss_val = net.total_loss_value()                        # syncs: only on logging steps
             dt = (time.time() - t0) / (log_every if (step + 1) % log_every == 0 else max(1, (step + 1) % log_every))
+            if rank == 0 and log_norms:                              # (this step has synchronised already)
+                _log_gradient_norms(net, train_dir, step + 1)
             t0 = time.time()
             if rank == 0 and not quiet:
                 print("global step %d: loss = %.4f (%.3f sec/step)" % (step + 1, loss_val, dt))
@@ -252,7 +290,9 @@ class SyntheticInput:
     streaming metrics in evaluate_* and validation during train_* (metrics.check_metrics_config lists what each takes;
     a bad value or a key that would do nothing is a ValueError).
     config['num_clones'] = K (default 1): train_* run K clones per rank and step with config['batch_size'] rows each
-    (check_clones_config; the trainers call use_clones() before the first batch); evaluate_* and the analyses ignore it."""
+    (check_clones_config; the trainers call use_clones() before the first batch); evaluate_* and the analyses ignore it.
+    config['clip_gradient_norm'], config['clip_global_norm'], config['skip_nonfinite_steps'], config['log_gradient_norms']:
+    gradient clipping, the non-finite step guard and gradients.jsonl (clip_net_kwargs)."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
