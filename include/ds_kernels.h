@@ -1169,6 +1169,29 @@ int ds_ragged_gather(const uint8_t *arena, int64_t narena, const uint8_t *spill,
 int ds_ragged_gather_host(const uint8_t *arena, int64_t narena, const uint8_t *spill, int64_t nspill,
                           const ds_gather_desc *desc, int32_t batch, uint8_t *out, int64_t nout);
 
+/* The Mixed_5b feature cache: one launch assembles a training batch from tables that are resident on the device and share
+ * a row count -- the features [nrows, 40768] fp32 and the batch's small tensors (texts, seq_lens, labels, post_ids, days). */
+typedef struct ds_rows_table {
+    const void *src;           /* the resident table: nrows rows of row_bytes bytes, contiguous                         */
+    void *dst;                 /* the batch buffer: n rows of row_bytes bytes, contiguous                               */
+    int64_t row_bytes;         /* a positive multiple of 4                                                              */
+} ds_rows_table;
+/* For every table t < ntables (1..8) and every i < n: dst_t[i * row_bytes_t .. +row_bytes_t) = src_t[index[i] * row_bytes_t
+ * .. +row_bytes_t), offsets in 64-bit arithmetic.  index: n int64 values; source rows may repeat.  An index[i] outside
+ * [0, nrows) leaves row i of EVERY table without a single store and the other rows are copied (the caller validates the
+ * permutation it generates); no byte outside the n destination rows is written.  `tables` is a HOST array in both functions:
+ * the launch carries it by value, nothing is uploaded.  One definition of the address arithmetic (csrc/rows_gather_common.h)
+ * serves both functions.
+ * ds_rows_gather: src / dst / index are DEVICE pointers, src and dst 4-byte and index 8-byte aligned; a table whose row_bytes,
+ * src and dst are multiples of 16 moves in 16-byte loads and stores, any other in 4-byte ones; one launch on `stream`, plain
+ * vector loads and stores, no atomics.
+ * ds_rows_gather_host: the CPU statement, plain C++ on HOST pointers of any alignment.
+ * Both return DS_ERR_ARG (text in ds_last_error) before anything is written or launched: a null tables / index / src / dst,
+ * ntables outside 1..8, n < 1, nrows < 1, a row_bytes that is not a positive multiple of 4, n * row_bytes / 4 > 2^31; the
+ * device entry also for a misaligned pointer. */
+int ds_rows_gather(const ds_rows_table *tables, int32_t ntables, const int64_t *index, int64_t n, int64_t nrows, void *stream);
+int ds_rows_gather_host(const ds_rows_table *tables, int32_t ntables, const int64_t *index, int64_t n, int64_t nrows);
+
 /* ---- streaming evaluation metrics (csrc/metrics.hip) ----------------------------------------------------------------------
  * ds_eval_metrics_update adds one batch to two accumulators that stay on the device; the caller zeroes them once and reads
  * them back when the evaluation is over.  logits: fp32 [B, C], row stride ldl >= C floats; labels: int64 [B].

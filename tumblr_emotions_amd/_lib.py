@@ -156,6 +156,11 @@ class GatherDesc(C.Structure):
                 ("y0", C.c_int32), ("x0", C.c_int32), ("height", C.c_int32), ("width", C.c_int32)]
 
 
+class RowsTable(C.Structure):
+    """ds_rows_table"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64)]
+
+
 class ExampleFields(C.Structure):
     """ds_example_fields"""
     _fields_ = [("image_offset", C.c_int64), ("image_length", C.c_int64), ("seq_len", C.c_int64), ("label", C.c_int64),
@@ -314,6 +319,8 @@ SIGNATURES = {
     "ds_jpeg_entropy_decode_device": (C.c_int, [_P, _i64, _P, _i32, _P, _i64, _P, _i64, _P, _P]),
     "ds_ragged_gather": (C.c_int, [_P, _i64, _P, _i64, _P, _i32, _P, _i64, _P]),
     "ds_ragged_gather_host": (C.c_int, [_P, _i64, _P, _i64, _P, _i32, _P, _i64]),
+    "ds_rows_gather": (C.c_int, [C.POINTER(RowsTable), _i32, _P, _i64, _i64, _P]),
+    "ds_rows_gather_host": (C.c_int, [C.POINTER(RowsTable), _i32, _P, _i64, _i64]),
     "ds_eval_metrics_workspace": (C.c_int, [_i32, _i32]),
     "ds_eval_metrics_update": (C.c_int, [_P, _i32, _P, _i32, _i32, _P, _P, _P, _P]),
 }

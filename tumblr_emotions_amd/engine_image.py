@@ -48,6 +48,7 @@ TOPOLOGY = [
 ]
 ENDPOINTS = [t[1] for t in TOPOLOGY]
 AMAX_RECORDS = 160     # fp8: max|.| records handed out by InceptionV1Engine.new_amax (about 91 in use)
+FEATURE_ENDPOINT = "Mixed_5b"           # the feature cache keeps this end point's output: everything up to it is frozen
 TRAINABLE_ENDPOINTS = ("Mixed_5c",)      # inception_v1.py:229-231; earlier scopes are trainable=False (:57-59)
 
 
@@ -1693,22 +1694,15 @@ class InceptionV1Engine:
         return [(l.key, self._fused_targets[id(l)]) for l in self.layers
                 if isinstance(self._fused_targets.get(id(l)), str)]
 
-    def forward(self, images, dropout_mask=None, seed=0, input_grad=False, fused=False):
+    def forward(self, images, dropout_mask=None, seed=0, input_grad=False, fused=False, stop=None):
         """images: [B,224,224,3] fp32 NHWC in [-1,1] (preprocess_for_eval range).  Returns the
         internal logits buffer [B,num_classes].  input_grad: the pass input_backward() differentiates (unpooled stem).
-        fused: moving-statistics forward with BatchNorm + ReLU inside the conv launches (fp32, not training)."""
+        fused: moving-statistics forward with BatchNorm + ReLU inside the conv launches (fp32, not training).
+        stop: run the first `stop` stages only and return None (forward_features)."""
         B = images.shape[0]
         if fused and (self.training or input_grad or self.dtype != "f32" or self.mul3):
             raise ValueError("the fused forward is the fp32 moving-statistics pass (is_training=False)")
-        self.fused_infer = bool(fused)
-        self._set_input_grad(input_grad)
-        self.alloc(B)
-        if self._restore_pivots is not None:
-            pB, pivots = self._restore_pivots
-            self._restore_pivots = None
-            if pB == B:
-                for l, m in zip(self.layers, pivots):
-                    l.mean.copy_(m)
+        self._enter_pass(B, input_grad, fused)
         if input_grad:
             self._input_grad_training = bool(self.training)
         if input_grad and self.training:      # every input-gradient pass from the same pivots: a function of the state and its arguments only
@@ -1731,26 +1725,104 @@ class InceptionV1Engine:
             # the generic stem kernel and the stem's wgrad (train_all) read a zero-padded 4-channel copy
             ops.pad_channels(images, 3, self.input.out, 4, B * self.input.H * self.input.W)
         if self.frozen_step:
-            if not self.training or input_grad or fused:
+            if input_grad or fused:
                 raise ValueError("a frozen-BatchNorm step is a plain training pass")
-            if self.dtype != "f32" or self.train_all or self.sync_bn:
-                raise NotImplementedError("frozen-BatchNorm training is the fp32 configuration without train_all / sync_bn")
-            self._frozen_prepare()
+            self._enter_frozen()
         if self.fused_infer:
             self._fused_prepare()
         else:
             self._fused_key = None      # (this pass leaves its own rstd / shift in the vectors the fused pass prepared)
         gate = self.text_gate
-        for i, s in enumerate(self.stages):
+        for i, s in enumerate(self.stages[:stop]):
             s.forward()
             if gate is not None and i == gate:      # the text tower's stream may start here (SentimentNet.forward)
                 self.text_gate_event = torch.cuda.Event()
                 self.text_gate_event.record(torch.cuda.current_stream())
+        if stop is not None:
+            return None
+        return self._head_forward(dropout_mask, seed)
+
+    def _enter_pass(self, B, input_grad=False, fused=False):
+        """What every forward pass settles before its first launch: the layout (fused or not, input gradients or not), the
+        buffers of this batch size, and the statistics pivots a left input-gradient layout kept."""
+        self.fused_infer = bool(fused)
+        self._set_input_grad(input_grad)
+        self.alloc(B)
+        if self._restore_pivots is not None:
+            pB, pivots = self._restore_pivots
+            self._restore_pivots = None
+            if pB == B:
+                for l, m in zip(self.layers, pivots):
+                    l.mean.copy_(m)
+
+    def _enter_frozen(self):
+        """The checks and the one prepare launch of a frozen-BatchNorm training pass (frozen_step is set)."""
+        if not self.training:
+            raise ValueError("a frozen-BatchNorm step is a plain training pass")
+        if self.dtype != "f32" or self.train_all or self.sync_bn:
+            raise NotImplementedError("frozen-BatchNorm training is the fp32 configuration without train_all / sync_bn")
+        self._frozen_prepare()
+
+    def _head_forward(self, dropout_mask, seed):
+        """AvgPool_0a_7x7 + dropout + Logits behind the last stage's output."""
+        B = self.B
         last = self.last
         ops.avgpool_dropout_fwd(last.out, B, last.H * last.W, self.feat, self.keep if self.training else 1.0, seed,
                                 dropout_mask, self.mask, self.pooled, seed_dev=self.seed_dev)
         self.fc.run(ops._p(self.pooled), self.w_fc, ops._p(self.logits), bias=self.b_fc)
         return self.logits
+
+    # ---- the Mixed_5b feature cache (DESIGN.md 7.14) ----------------------------------------------------------------------
+    def _feature_stage(self):
+        return next(s for s in self.stages if s.name == FEATURE_ENDPOINT)
+
+    def check_features(self):
+        """The feature passes need what makes Mixed_5b's output a function of the image and of variables no step writes."""
+        if self.dtype != "f32":
+            raise NotImplementedError("the feature passes are implemented for the fp32 configuration, not %r" % self.dtype)
+        if self.train_all:
+            raise ValueError("features with train_all: every step would move the layers below %s" % FEATURE_ENDPOINT)
+        if self.trainable_bn_beta:
+            raise ValueError("features need trainable_bn_beta=False: a trainable beta below %s changes them every step"
+                             % FEATURE_ENDPOINT)
+        if self.sync_bn:
+            raise ValueError("features with sync_bn: the frozen statistics leave nothing to synchronise")
+
+    def forward_features(self, images):
+        """Mixed_5b's output [B, 7, 7, 832] (a view of the stage buffer: copy it before the next pass) of the frozen-statistics
+        TRAINING forward -- the plans, the one prepare launch and the stage loop of forward() under frozen_step, stopped behind
+        Mixed_5b: the bits a frozen train_step on these images leaves there."""
+        self.check_features()
+        frozen, training = self.frozen_step, self.training
+        self.frozen_step, self.training = True, True
+        try:
+            self.forward(images, stop=self.stages.index(self._feature_stage()) + 1)
+        finally:
+            self.frozen_step, self.training = frozen, training
+        return self._feature_stage().out
+
+    def feature_buffer(self, B):
+        """Mixed_5b's output buffer of batch size B, [B, 7, 7, 832] fp32: where forward_from_features(B) reads its input.  Ask
+        at every step and keep nothing: alloc() for another batch size (a predict() in between) re-allocates the stage buffers."""
+        self.check_features()
+        self._enter_pass(B)
+        return self._feature_stage().out
+
+    def forward_from_features(self, B, dropout_mask=None, seed=0):
+        """The frozen-statistics training forward from Mixed_5b's output on: the caller has filled feature_buffer(B); one
+        prepare launch, the Mixed_5c stage and the avg-pool / dropout / Logits tail.  No stem padding copy, no lower stage.
+        Returns the logits buffer; backward() follows as after forward()."""
+        self.check_features()
+        if not self.frozen_step:
+            raise ValueError("the feature forward is a frozen-BatchNorm training pass (frozen_step)")
+        self._enter_pass(B)
+        self._enter_frozen()
+        self._fused_key = None
+        self.text_gate_event = None      # (no lower stage: the text tower starts with the inputs)
+        first = self.stages.index(self._feature_stage()) + 1
+        for s in self.stages[first:]:
+            s.forward()
+        return self._head_forward(dropout_mask, seed)
 
     def backward(self, dlogits, side_job=None):
         """dlogits [B,num_classes] -> gradients of every trainable image-tower variable in store.grad.

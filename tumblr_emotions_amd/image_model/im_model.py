@@ -4,6 +4,7 @@ import os
 import numpy as np
 
 from ..net import SentimentNet
+from ..feature_cache import check_feature_cache_config
 from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, run_training
 
 _RANDOM_SEED = 0
@@ -57,7 +58,7 @@ class ImageModel(SyntheticInput):
         self.learning_rate = config['initial_lr']
         self._init_input(config, config.get('post_size', 50), config.get('vocab_size', 400000), nb_emotions, True, device)
         self.nb_emotions = self.dataset.num_classes
-        for key in ("train_all", "trainable_embedding", "frozen_bn", "sync_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
+        for key in ("train_all", "trainable_embedding", "frozen_bn", "trainable_bn_beta", "sync_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
             if key in config:
                 net_kw.setdefault(key, bool(config[key]))
         if "dtype" in config:
@@ -73,9 +74,11 @@ def train_image_model(checkpoints_dir, train_dir, num_steps, *, config=None, qui
     """Fine tune the Image model, retraining Mixed_5c (im_model.py:166-225)."""
     config = dict(_CONFIG, **(config or {}))
     check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
+    check_feature_cache_config(config)
     model = ImageModel(config)
     model.use_clones()
     model.use_augmentation()
+    model.use_feature_cache()        # config['feature_cache']: built at the first batch, behind the warm start
     init_fn = get_init_fn(checkpoints_dir)
     if init_fn is not None:
         init_fn(model.net)

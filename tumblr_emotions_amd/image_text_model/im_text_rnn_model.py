@@ -7,6 +7,7 @@ from .. import ops
 from ..image_model.im_model import get_init_fn
 from ..net import SentimentNet
 from ..text_model.text_preprocessing import resolve_embedding
+from ..feature_cache import check_feature_cache_config
 from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, run_training
 
 _POST_SIZE = 50
@@ -35,7 +36,7 @@ class DeepSentiment(SyntheticInput):
         embedding, vocab, dim, self.word_to_id = resolve_embedding(config, embedding)
         self._init_input(config, post, vocab, nb_emotions, True, device)
         self.nb_emotions = self.dataset.num_classes
-        for key in ("train_all", "trainable_embedding", "frozen_bn", "sync_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
+        for key in ("train_all", "trainable_embedding", "frozen_bn", "trainable_bn_beta", "sync_bn"):      # optional fine-tuning switches (not in the reference _CONFIG)
             if key in config:
                 net_kw.setdefault(key, bool(config[key]))
         if "dtype" in config:
@@ -67,9 +68,11 @@ def train_deep_sentiment(checkpoints_dir, train_dir, num_steps, *, config=None, 
     """Fine tune the inception model, retraining the last layer (im_text_rnn_model.py:107-169)."""
     config = dict(_CONFIG, **(config or {}))
     check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
+    check_feature_cache_config(config)
     model = DeepSentiment(config)
     model.use_clones()
     model.use_augmentation()
+    model.use_feature_cache()        # config['feature_cache']: built at the first batch, behind the warm start
     init_fn = get_init_fn(checkpoints_dir)
     if init_fn is not None:
         init_fn(model.net)

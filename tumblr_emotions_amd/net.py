@@ -234,7 +234,13 @@ class SentimentNet:
             main = torch.cuda.current_stream()
             inputs_ready = torch.cuda.Event()
             inputs_ready.record(main)
-        if self.image is not None:
+        if self.image is not None and "features" in batch:      # Mixed_5b's output instead of images (check_feature_batch)
+            B = batch["features"].shape[0]
+            buf = self.image.feature_buffer(B)
+            if batch["features"].data_ptr() != buf.data_ptr():      # (the feature cache gathers straight into the buffer)
+                buf.copy_(batch["features"])
+            im = self.image.forward_from_features(B, dropout_mask, seed)
+        elif self.image is not None:
             im = self.image.forward(batch["images"], dropout_mask, seed, fused=fused)
         if side is not None:
             side.wait_event(inputs_ready)          # NOT wait_stream: the image tower is already enqueued on main
@@ -476,6 +482,46 @@ class SentimentNet:
     def _rank_seed(self, seed):
         return int(seed) * 4096 + self.reducer.rank
 
+    # ---- Mixed_5b features in place of images ---------------------------------------
+    def check_features(self):
+        """What the feature passes need of the net; raises before anything is enqueued or counted."""
+        if self.image is None:
+            raise ValueError("features need the image tower (mode 'image' or 'joint'), not mode %r" % self.mode)
+        if self.dtype != "f32":
+            raise NotImplementedError("features are implemented for the fp32 configuration, not %r" % self.dtype)
+        if self.image.train_all:
+            raise ValueError("features with train_all: every step would move the layers the features come from")
+        if not self.frozen_bn:
+            raise ValueError("features need frozen_bn=True: batch statistics tie a sample's features to its batch")
+        self.image.check_features()
+
+    def check_feature_batch(self, batch):
+        """A train_step batch that carries 'features' ([B, 7, 7, 832] fp32, contiguous, on the device) in place of 'images'."""
+        self.check_features()
+        if "images" in batch:
+            raise ValueError("a batch carries either 'images' or 'features', not both")
+        f = batch["features"]
+        st = self.image._feature_stage()
+        if not torch.is_tensor(f) or f.dtype != torch.float32 or f.dim() != 4 or tuple(f.shape[1:]) != (st.H, st.W, st.C) \
+                or f.shape[0] != batch["labels"].shape[0] or not f.is_contiguous() or not f.is_cuda:
+            raise ValueError("features must be a contiguous float32 device tensor [B, %d, %d, %d] with one row per label"
+                             % (st.H, st.W, st.C))
+
+    def image_features(self, images):
+        """Mixed_5b's output [B, 7, 7, 832] fp32 for `images` ([B, 224, 224, 3] as for train_step): the frozen-statistics
+        training forward stopped behind Mixed_5b -- the bits a frozen train_step on the same images leaves there, whatever
+        the other images of the batch are.  A view of the engine's stage buffer: copy it before the next pass.  Variables,
+        moving statistics, Adam slots and `step` are not touched."""
+        self.check_features()
+        with torch.no_grad():
+            return self.image.forward_features(images)
+
+    def feature_buffer(self, B):
+        """The buffer a feature batch of B rows is read from (Mixed_5b's output of the image engine): a batch whose
+        'features' IS this tensor is used in place, any other is copied into it.  Ask at every step, keep nothing."""
+        self.check_features()
+        return self.image.feature_buffer(B)
+
     # ---- one training step -----------------------------------------------------------------------
     def train_step(self, batch, lr, dropout_mask=None, seed=None, num_clones=1, after_clone=None):
         """One optimiser step on `batch`.  num_clones = K > 1: the step of K of slim's in-graph clones on this device, run back
@@ -485,7 +531,12 @@ class SentimentNet:
         counted once, the moving statistics are clone 0's, `step` advances once.  `logits` then holds all B rows in order and
         total_loss_value() the mean of the K cross-entropies + the L2 term.  after_clone(c), a test and diagnostic hook, is
         called once clone c's backward pass and accumulation are enqueued, before clone c + 1 starts.  num_clones = 1 is the
-        plain step, launch for launch."""
+        plain step, launch for launch.
+        A batch may carry 'features' ([B, 7, 7, 832] fp32: Mixed_5b's output, image_features()) in place of 'images' on a
+        frozen_bn net with trainable_bn_beta=False: the image tower then runs from Mixed_5c on (check_feature_batch lists what
+        is refused, before anything is enqueued or counted); the step is the image step's, bit for bit."""
+        if "features" in batch:
+            self.check_feature_batch(batch)
         if type(num_clones) is not int or num_clones != 1:
             return self._train_step_clones(batch, lr, dropout_mask, seed, num_clones, after_clone)
         self._clone_count = 1

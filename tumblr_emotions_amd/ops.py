@@ -1675,3 +1675,66 @@ def ragged_gather(arena, spill, desc, out, desc_dev=None):
     _lib.check(_lib.load().ds_ragged_gather(_p(arena), arena.numel(), _p(spill), 0 if spill is None else spill.numel(),
                                             _p(desc_dev), B, _p(out), out.numel(), _stream()), "ds_ragged_gather")
     return out
+
+
+# ---- the Mixed_5b feature cache: batch assembly from resident tables (ds_rows_gather) ------------------------------------------
+class RowsGather:
+    """One ds_rows_gather launch shape: the ds_rows_table array (host side; it travels by value in the launch) of up to 8
+    (src, dst) pairs whose rows are gathered by one index vector.  src [nrows, ...] and dst [n, ...] are contiguous device
+    tensors of one dtype with equal row shapes; the addresses are read at construction, so build it anew when a buffer is
+    re-allocated."""
+
+    def __init__(self, pairs):
+        pairs = list(pairs)
+        if not 1 <= len(pairs) <= 8:
+            raise ValueError("rows_gather: 1 to 8 tables")
+        nrows, n = pairs[0][0].shape[0], pairs[0][1].shape[0]
+        self.tables = (_lib.RowsTable * len(pairs))()
+        for t, (src, dst) in zip(self.tables, pairs):
+            for x in (src, dst):
+                if not x.is_cuda:
+                    raise RuntimeError("tumblr_emotions_amd kernels need CUDA/HIP tensors; there is no CPU fallback")
+            if src.dtype != dst.dtype or src.shape[1:] != dst.shape[1:] or not src.is_contiguous() or not dst.is_contiguous() \
+                    or src.dim() < 1 or src.shape[0] != nrows or dst.shape[0] != n:
+                raise ValueError("rows_gather: a table and its destination are contiguous, of one dtype and row shape, and "
+                                 "all tables share their row counts")
+            row_bytes = src[0].numel() * src.element_size() if nrows else 0
+            if row_bytes < 4 or row_bytes % 4:
+                raise ValueError("rows_gather: row_bytes must be a positive multiple of 4, not %d" % row_bytes)
+            t.src, t.dst, t.row_bytes = src.data_ptr(), dst.data_ptr(), row_bytes
+        self.nrows, self.n, self.keep = int(nrows), int(n), pairs
+
+    def run(self, index):
+        """dst_t[i] = src_t[index[i]] for every table: index is a contiguous int64 device vector of n entries inside
+        [0, nrows) (validated by whoever generated it: a row whose index is outside is left without a store)."""
+        if not index.is_cuda or index.dtype != torch.int64 or index.dim() != 1 or index.shape[0] != self.n or not index.is_contiguous():
+            raise ValueError("rows_gather: index must be a contiguous int64 device vector of %d entries" % self.n)
+        _lib.check(_lib.load().ds_rows_gather(self.tables, len(self.tables), _p(index), self.n, self.nrows, _stream()),
+                   "ds_rows_gather")
+
+
+def rows_gather(pairs, index):
+    """ds_rows_gather once: pairs = [(src, dst), ...] (see RowsGather), index int64 [n] on the device."""
+    RowsGather(pairs).run(index)
+
+
+def rows_gather_host(pairs, index, nrows=None):
+    """ds_rows_gather_host on NumPy arrays: pairs = [(src, dst), ...] with dst written in place, index int64 [n].  The arrays
+    need no alignment (views at odd byte offsets are fine) but must be C-contiguous; nrows defaults to the tables' rows."""
+    import numpy as np
+    pairs = list(pairs)
+    if not 1 <= len(pairs) <= 8:
+        raise ValueError("rows_gather_host: 1 to 8 tables")
+    index = np.asarray(index)
+    if index.dtype != np.int64 or index.ndim != 1 or not index.flags.c_contiguous:
+        raise ValueError("rows_gather_host: index must be a contiguous int64 vector")
+    tables = (_lib.RowsTable * len(pairs))()
+    for t, (src, dst) in zip(tables, pairs):
+        if not src.flags.c_contiguous or not dst.flags.c_contiguous or src.dtype != dst.dtype or src.shape[1:] != dst.shape[1:] \
+                or dst.shape[0] != index.shape[0] or src.shape[0] != pairs[0][0].shape[0]:
+            raise ValueError("rows_gather_host: a table and its destination are contiguous, of one dtype and row shape")
+        t.src, t.dst, t.row_bytes = src.ctypes.data, dst.ctypes.data, src[0].nbytes
+    rc = _lib.load().ds_rows_gather_host(tables, len(pairs), index.ctypes.data, index.shape[0],
+                                         pairs[0][0].shape[0] if nrows is None else nrows)
+    if rc != 0:
+        raise ValueError("ds_rows_gather_host: %s (%d)" % (_lib.load().ds_last_error().decode(), rc))

@@ -18,6 +18,7 @@ import time
 import numpy as np
 import torch
 
+from .feature_cache import check_feature_cache_config
 from .metrics import check_metrics_config
 from .synthetic import synthetic_batch_numpy, to_device
 
@@ -289,6 +290,9 @@ class SyntheticInput:
     config['eval_metrics'], config['validate_every'], config['validate_batches'], config['keep_best'], config['metrics_top_k']:
     streaming metrics in evaluate_* and validation during train_* (metrics.check_metrics_config lists what each takes;
     a bad value or a key that would do nothing is a ValueError).
+    config['feature_cache']: 'none' (default) or 'device' with config['feature_cache_gb'] (a positive number of GB, no
+    default): train_image_model / train_deep_sentiment run the frozen tower once per record and then train from Mixed_5b's
+    output kept in device memory (feature_cache.py; check_feature_cache_config lists what the key needs and refuses).
     config['num_clones'] = K (default 1): train_* run K clones per rank and step with config['batch_size'] rows each
     (check_clones_config; the trainers call use_clones() before the first batch); evaluate_* and the analyses ignore it.
     config['clip_gradient_norm'], config['clip_global_norm'], config['skip_nonfinite_steps'], config['log_gradient_norms']:
@@ -326,6 +330,8 @@ class SyntheticInput:
             if isinstance(gb, bool) or not isinstance(gb, (int, float)) or not gb > 0:
                 raise ValueError("config['input_cache'] = 'device' needs config['input_cache_gb'], a positive number of GB: "
                                  "there is no default")
+        self._feature_cache = None
+        check_feature_cache_config(config, with_images)
         ddir = config.get("dataset_dir")
         split = os.path.join(ddir or "", "photos", "train_valid_split.txt")
         if config.get("synthetic", False):
@@ -349,6 +355,18 @@ class SyntheticInput:
         if self._records is not None:
             raise RuntimeError("use_augmentation() must precede the first batch")
         self._augment = bool(self.config.get("augment", False))
+
+    def use_feature_cache(self, rank=None, world=None):
+        """Called by the trainers of the models that read images, before the first batch: config['feature_cache'] = 'device'
+        takes effect -- next_batch() then serves Mixed_5b features from feature_cache.FeatureCache (built at the first batch,
+        i.e. behind the warm start) instead of images.  rank / world: this process's shard (default: the process group's).
+        Returns the cache, or None when the key is off."""
+        if self._records is not None or self._feature_cache is not None:
+            raise RuntimeError("use_feature_cache() must precede the first batch")
+        if check_feature_cache_config(self.config, self._in[3]) is not None:
+            from .feature_cache import FeatureCache
+            self._feature_cache = FeatureCache(self, rank, world)
+        return self._feature_cache
 
     def validation_batches(self, count):
         """The held-out batches of config['validate_every']: the same `count` batches of config['batch_size'] at every call,
@@ -391,7 +409,9 @@ class SyntheticInput:
         post_size, vocab, nb, with_images, device = self._in
         rank, world = _rank_world()
         rows = self.config["batch_size"] * getattr(self, "_train_clones", 1)
-        if hasattr(self.dataset, "data_sources"):            # real TFRecords
+        if self._feature_cache is not None:                  # config['feature_cache']: features instead of images
+            b = self._feature_cache.next_batch()
+        elif hasattr(self.dataset, "data_sources"):          # real TFRecords
             if self._records is None:
                 from .image_model.im_model import load_batch_with_text
                 self._records = load_batch_with_text(self.dataset, rows, height=224, width=224,
