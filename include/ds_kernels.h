@@ -503,15 +503,6 @@ typedef struct ds_bn_finalize_job {
 } ds_bn_finalize_job;
 int ds_bn_finalize_multi(const ds_bn_finalize_job *jobs, int32_t njobs, float eps, float decay, void *stream);
 
-/* ds_bn_finalize and the ds_bn_apply_relu pass that reads its result as ONE launch: the first C workgroups finalize a channel
- * each and publish, the others wait for all C (device-side ticket) and stream.  Saves the dependent-launch boundary between
- * the two (~4 us of idle GPU per layer).  ticket: two zero-initialised uint32 owned by the caller, one pair per layer that
- * may be in flight at a time (the launch leaves them zero).  Results bit-identical to the two launches.                   */
-int ds_bn_finalize_apply_relu(const float *stats, int32_t P, int64_t count, int32_t C, const float *beta, const float *pivot,
-                              float eps, float decay, float *mean, float *rstd, float *shift, float *moving_mean,
-                              float *moving_var, const float *z, int64_t M, const struct ds_segments *dst, uint32_t *ticket,
-                              void *stream);
-
 /* y = relu(z*rstd + shift) scattered to up to 4 channel segments (branch outputs written
  * straight into the concat buffer: replaces tf.concat, inception_v1.py:96 ... :248).       */
 typedef struct ds_segments {
@@ -526,11 +517,6 @@ typedef struct ds_segments {
     float *amax[4];           /* ds_bn_apply_relu only, nullable: device word that receives max(y) of the segment by  */
                               /* atomic max (the caller zeroes it once per step): the per-tensor scale of the fp8     */
                               /* conv that reads the segment, without a separate ds_absmax pass                     */
-    const float *ptr2[4];     /* ds_bn_bwd_apply / _bf16 only, nullable: a SECOND addend of the segment's gradient with */
-                              /* the same layout (dy = *ptr + *ptr2).  An Inception block's input gradient is the sum of */
-                              /* the fused 1x1 dgrad's output and Branch_3's pool gradient: where the dgrad cannot        */
-                              /* accumulate (16-bit configurations) the two stay separate tensors, written concurrently   */
-                              /* on two streams, and the one consumer adds them as it reads                              */
 } ds_segments;
 int ds_bn_apply_relu(const float *z, int64_t M, int32_t C, const float *rstd, const float *shift,
                      const ds_segments *dst, void *stream);
@@ -572,9 +558,6 @@ typedef struct ds_bn_sum_segments {
     int32_t kind[4];
     const float *s[4];
     const float *q[4];
-    int32_t P2[4];            /* > 0: a SECOND source of the same kind for the segment (the sums are linear in the gradient: */
-    const float *s2[4];       /* with dy = a + b in two tensors, each producer emits the sums of its own addend), P2[i]    */
-    const float *q2[4];       /* partials per channel at s2[i] / q2[i]; added behind the first source's                     */
 } ds_bn_sum_segments;
 int ds_bn_bwd_finalize_segs(const ds_bn_sum_segments *sg, int64_t M, int32_t C, const float *beta, float *dbeta,
                             float *coef, void *stream);
@@ -583,13 +566,6 @@ int ds_bn_bwd_finalize_segs(const ds_bn_sum_segments *sg, int64_t M, int32_t C, 
  * first channel; coef is float[2][C] over the concatenated columns -- what ONE ds_bn_bwd_apply over those columns reads.  */
 int ds_bn_bwd_finalize_multi(const ds_bn_sum_segments *sg, int64_t M, int32_t C, const float *const *beta,
                              float *const *dbeta, float *coef, void *stream);
-/* ds_bn_bwd_finalize_segs / _multi and the ds_bn_bwd_apply (dz_dtype DS_DTYPE_F32: dz [M, ldz]) / ds_bn_bwd_apply_bf16
- * (DS_DTYPE_BF16: dz [M, lddz]) pass behind it as ONE launch (see ds_bn_finalize_apply_relu; ticket as there).  beta / dbeta:
- * one vector for all columns, or -- beta_v non-null -- the segments' own (ds_bn_bwd_finalize_multi).  Bit-identical.     */
-int ds_bn_bwd_finalize_apply(const ds_bn_sum_segments *sg, const float *beta, float *dbeta, const float *const *beta_v,
-                             float *const *dbeta_v, float *coef, const float *z, int32_t ldz, const ds_segments *dy, int64_t M,
-                             int32_t C, const float *mean, const float *rstd, const float *shift, void *dz, int32_t dz_dtype,
-                             int32_t lddz, float *amax, uint32_t *ticket, void *stream);
 /* amax (nullable): device word that receives max|dz| by atomic max (zeroed by the caller): the scale of an fp8 dgrad */
 /* ldz: row stride of z AND dz in floats (>= C, % 4 == 0): a layer whose conv writes straight into its slice of the   */
 /* Inception concat buffer is differentiated in place there                                                          */
@@ -597,7 +573,7 @@ int ds_bn_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t 
                     const float *rstd, const float *shift, const float *coef, float *dz, float *amax, void *stream);
 /* ds_bn_bwd_apply over a COLUMN RANGE of a layer: z / dz / mean / rstd / shift point at the range's first column, dy's
  * segments count from it, and the two coefficient vectors come separately -- coef_g = coef + c0, coef_gx = coef + C + c0 of the
- * layer's float[2][C] -- because the second no longer follows the first at + ncols.  fp32, no second addend, no amax.  The
+ * layer's float[2][C] -- because the second no longer follows the first at + ncols.  fp32, no amax.  The
  * fused 1x1 layer of a Mixed block in front of a stride-2 pool: its reduce columns here, its Branch_0 columns through
  * ds_bn_pool_bwd_apply_cols.  The same kernel and per-element arithmetic as ds_bn_bwd_apply: bit-identical.              */
 int ds_bn_bwd_apply_cols(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t ncols, const float *mean,
@@ -605,7 +581,7 @@ int ds_bn_bwd_apply_cols(const float *z, int32_t ldz, const ds_segments *dy, int
                          void *stream);
 /* The moving-statistics twin (is_training=False: BatchNorm is a fixed per-channel affine map, its backward pointwise):
  * dz = rstd * dy * [z*rstd + shift > 0], the predicate evaluated as ds_bn_apply_relu evaluates it.  No mean, no coef, no
- * sums.  dy as for ds_bn_bwd_apply (up to four segments, ptr2 second addends honoured); ldz: row stride of z AND dz; dz may
+ * sums.  dy as for ds_bn_bwd_apply (up to four segments); ldz: row stride of z AND dz; dz may
  * alias z.  fp32 only.                                                                                                      */
 int ds_bn_infer_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *rstd,
                           const float *shift, float *dz, void *stream);

@@ -80,7 +80,7 @@ class ConvIO(C.Structure):
 class Segments(C.Structure):
     _fields_ = [("nseg", C.c_int32), ("c_begin", C.c_int32 * 4), ("c_end", C.c_int32 * 4),
                 ("ld", C.c_int32 * 4), ("ptr", C.c_void_p * 4), ("dtype", C.c_int32 * 4),
-                ("amax", C.c_void_p * 4), ("ptr2", C.c_void_p * 4)]
+                ("amax", C.c_void_p * 4)]
 
 
 class BnFinalizeJob(C.Structure):
@@ -103,8 +103,7 @@ class BnSumJob(C.Structure):
 
 class SumSegments(C.Structure):
     _fields_ = [("nseg", C.c_int32), ("c_begin", C.c_int32 * 4), ("c_end", C.c_int32 * 4), ("P", C.c_int32 * 4),
-                ("kind", C.c_int32 * 4), ("s", C.c_void_p * 4), ("q", C.c_void_p * 4), ("P2", C.c_int32 * 4),
-                ("s2", C.c_void_p * 4), ("q2", C.c_void_p * 4)]
+                ("kind", C.c_int32 * 4), ("s", C.c_void_p * 4), ("q", C.c_void_p * 4)]
 
 
 class SlabCombine(C.Structure):
@@ -252,8 +251,6 @@ SIGNATURES = {
     "ds_bn_bwd_finalize": (C.c_int, [_P, _i32, _i64, _i32, _P, _P, _P]),
     "ds_bn_bwd_finalize_multi": (C.c_int, [_SS, _i64, _i32, _P, _P, _P, _P]),
     "ds_bn_finalize_multi": (C.c_int, [_P, _i32, _f32, _f32, _P]),
-    "ds_bn_finalize_apply_relu": (C.c_int, [_P, _i32, _i64, _i32, _P, _P, _f32, _f32, _P, _P, _P, _P, _P, _P, _i64, _SG, _P, _P]),
-    "ds_bn_bwd_finalize_apply": (C.c_int, [_SS, _P, _P, _P, _P, _P, _P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _i32, _i32, _P, _P, _P]),
     "ds_bn_bwd_apply": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _P, _P]),
     "ds_bn_bwd_apply_cols": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P, _P, _P, _P]),
     "ds_bn_infer_bwd_apply": (C.c_int, [_P, _i32, _SG, _i64, _i32, _P, _P, _P, _P]),

@@ -19,7 +19,6 @@ struct SegDev {
     float *ptr[4];
     int dtype[4];
     float *amax[4];
-    const float *ptr2[4];      // bn_bwd_apply: second addend of the segment (ds_segments.ptr2)
 };
 
 SegDev to_dev(const ds_segments *s) {
@@ -32,7 +31,6 @@ SegDev to_dev(const ds_segments *s) {
         o.ptr[i] = (float *)s->ptr[i];
         o.dtype[i] = s->dtype[i];
         o.amax[i] = s->amax[i];
-        o.ptr2[i] = s->ptr2[i];
     }
     return o;
 }
@@ -64,34 +62,10 @@ using ds::wave_sum_f64;
 #define DS_BN_ROWS 2          // rows per pass of the fixed-column streaming kernels (tuning builds: -DDS_BN_ROWS=4)
 #endif
 
-// Hand-off INSIDE a launch (the finalize + apply kernels below): the producer's few per-channel results go out as agent-scope
-// relaxed atomic stores (write-through: visible at the device's coherence point once vmcnt drains), the consumers read them
-// with agent-scope relaxed atomic loads (never a stale line of their XCD's L2).  No release / acquire fences: at agent scope
-// those write back / invalidate a whole L2 per workgroup (measured: +80 us per launch).
-template <bool COH>
-__device__ __forceinline__ void st_res(float *p, float v) {
-    if constexpr (COH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-template <bool COH>
-__device__ __forceinline__ float4 ld_res4(const float *p) {
-    if constexpr (COH) {
-        float4 v;
-        v.x = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v.y = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v.z = __hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v.w = __hip_atomic_load(p + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return v;
-    } else {
-        return *reinterpret_cast<const float4 *>(p);
-    }
-}
-
 // ---- forward ------------------------------------------------------------------------------------
 // one workgroup per channel; partials are laid out [2][C][P] so the threads read contiguous floats
 // (P is a few hundred for the persistent conv launches, one per row tile -- up to 2048 -- otherwise);
 // combined in double in a fixed order: strided per thread, butterfly per wave, waves 0..3 (deterministic)
-template <bool COH = false>
 __device__ __forceinline__ void finalize_channel(const float *stats, int P, double inv_count, int C, int c, const float *beta,
                                                  const float *pivot, float eps, float decay, float *mean, float *rstd,
                                                  float *shift, float *mm, float *mv, float *mean_c = nullptr,
@@ -121,8 +95,8 @@ __device__ __forceinline__ void finalize_channel(const float *stats, int P, doub
         if (var < 0.0) var = 0.0;
         const float r = (float)(1.0 / sqrt(var + (double)eps));
         mean[c] = (float)mu;
-        st_res<COH>(rstd + c, r);
-        st_res<COH>(shift + c, beta[c] - (float)mu * r);
+        rstd[c] = r;
+        shift[c] = beta[c] - (float)mu * r;
         if (mean_c) {                 // z stored centred about the pivot (ds_bn_finalize_centered)
             mean_c[c] = (float)du;
             shift_c[c] = beta[c] - (float)du * r;
@@ -163,13 +137,13 @@ __global__ __launch_bounds__(256) void bn_finalize_multi_kernel(FinJobsDev jb, f
 // segment lookup happen once, the loop has no division, and consecutive threads still read consecutive addresses.  Tensors
 // that are read once come in with the non-temporal hint (scripts/microbench/stream_bw.hip: 5.3 -> 6.4 TB/s for "two in,
 // one out"); two rows per pass with both rows' loads before either store (a load behind a store waits for it).
-template <bool COH = false, bool Z16 = false>
+template <bool Z16 = false>
 __device__ __forceinline__ void apply_relu_body(int bid, const float *z, int64_t M, int C, const float *rstd,
                                                 const float *shift, const SegDev &dst, int drow) {
     const int C4 = C >> 2;
     const int t0 = bid * 256 + threadIdx.x;
     const int row0 = t0 / C4, c = (t0 - row0 * C4) * 4;
-    const float4 r = ld_res4<COH>(rstd + c), s = ld_res4<COH>(shift + c);
+    const float4 r = *reinterpret_cast<const float4 *>(rstd + c), s = *reinterpret_cast<const float4 *>(shift + c);
     int sgi = 0;                                 // this column group's destination segment
 #pragma unroll
     for (int i = 1; i < 4; ++i)
@@ -226,65 +200,7 @@ __device__ __forceinline__ void apply_relu_body(int bid, const float *z, int64_t
 template <bool Z16 = false>
 __global__ __launch_bounds__(256) void bn_apply_relu_kernel(const float *z, int64_t M, int C, const float *rstd,
                                                             const float *shift, SegDev dst, int drow) {
-    apply_relu_body<false, Z16>((int)blockIdx.x, z, M, C, rstd, shift, dst, drow);
-}
-
-// ---- finalize + apply as ONE launch --------------------------------------------------------------------------------------
-// A finalize is one workgroup per channel and ~1 us of work; the apply pass that reads its result used to be the next launch
-// on the same stream, i.e. a dependent-launch boundary (~4 us of idle GPU + the launch's own ramp) for every BatchNorm layer
-// and direction -- at 32 samples per GPU a tenth of the step.  Here the first C workgroups of the launch finalize their
-// channel and publish (release increment of ticket[0]); the others are the apply pass: thread 0 spins on ticket[0] == C
-// (acquire), then the workgroup reads the per-channel vectors and streams as before.  No deadlock: a grid's workgroups are
-// dispatched in id order, so whenever an apply workgroup occupies a slot every finalize workgroup has been placed already
-// and runs to completion.  The last apply workgroup to pass its end (ticket[1]) zeroes both words for the next launch.
-// Arithmetic and summation order are the separate launches': bit-identical.
-__device__ __forceinline__ void fa_publish(unsigned *ticket) {
-    if (threadIdx.x == 0) {          // (thread 0 wrote the channel's results: st_res<true>)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-__device__ __forceinline__ void fa_wait(unsigned *ticket, unsigned need) {
-    if (threadIdx.x == 0) {
-        unsigned n = 0;
-        // (a thousand workgroups polling one word every few hundred ns queue up at its memory channel in front of the very
-        // increments they wait for: first poll after ~3 us, then every ~1.5 us)
-        __builtin_amdgcn_s_sleep(127);
-        while (__hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-            __builtin_amdgcn_s_sleep(60);
-            if (++n > (1u << 21)) __builtin_trap();          // (seconds: cannot happen, see above -- fail loudly, never hang)
-        }
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void fa_leave(unsigned *ticket, unsigned napply) {
-    if (threadIdx.x == 0) {
-        const unsigned old = __hip_atomic_fetch_add(ticket + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == napply - 1) {
-            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ticket + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-struct FinApplyArgs {
-    const float *stats; int P; double inv_count; int C;
-    const float *beta, *pivot; float eps, decay;
-    float *mean, *rstd, *shift, *mm, *mv;
-    const float *z; int64_t M; SegDev dst; int drow;
-    unsigned *ticket;
-};
-
-__global__ __launch_bounds__(256) void bn_finalize_apply_relu_kernel(const FinApplyArgs a) {
-    if ((int)blockIdx.x < a.C) {
-        finalize_channel<true>(a.stats, a.P, a.inv_count, a.C, (int)blockIdx.x, a.beta, a.pivot, a.eps, a.decay, a.mean, a.rstd,
-                               a.shift, a.mm, a.mv);
-        fa_publish(a.ticket);
-        return;
-    }
-    fa_wait(a.ticket, (unsigned)a.C);
-    apply_relu_body<true>((int)blockIdx.x - a.C, a.z, a.M, a.C, a.rstd, a.shift, a.dst, a.drow);
-    fa_leave(a.ticket, gridDim.x - (unsigned)a.C);
+    apply_relu_body<Z16>((int)blockIdx.x, z, M, C, rstd, shift, dst, drow);
 }
 
 // ---- backward -----------------------------------------------------------------------------------
@@ -418,18 +334,15 @@ struct SumSegDev {
     int nseg;
     int c_begin[4], c_end[4], P[4], kind[4];
     const float *s[4], *q[4];
-    int P2[4];                 // second source of the segment (ds_bn_sum_segments.P2 / s2 / q2), 0: none
-    const float *s2[4], *q2[4];
     const float *beta[4];      // the segment's beta / dbeta, indexed from its first channel (ds_bn_bwd_finalize_segs: one
     float *dbeta[4];           // vector offset per segment; ds_bn_bwd_finalize_multi: the layers' own vectors); nullable
 };
 
-template <bool COH = false>
 __device__ __forceinline__ void bwd_finalize_segs_channel(const SumSegDev &sg, double inv_count, int C, float *coef, int c) {
     __shared__ double red[2][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int P = 0, kind = 0, P2 = 0;
-    const float *sp = nullptr, *qp = nullptr, *beta = nullptr, *sp2 = nullptr, *qp2 = nullptr;
+    int P = 0, kind = 0;
+    const float *sp = nullptr, *qp = nullptr, *beta = nullptr;
     float *dbeta = nullptr;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -438,11 +351,6 @@ __device__ __forceinline__ void bwd_finalize_segs_channel(const SumSegDev &sg, d
             kind = sg.kind[i];
             sp = sg.s[i] + (int64_t)(c - sg.c_begin[i]) * P;
             qp = sg.q[i] + (int64_t)(c - sg.c_begin[i]) * P;
-            P2 = sg.P2[i];
-            if (P2 > 0) {
-                sp2 = sg.s2[i] + (int64_t)(c - sg.c_begin[i]) * P2;
-                qp2 = sg.q2[i] + (int64_t)(c - sg.c_begin[i]) * P2;
-            }
             beta = sg.beta[i] ? sg.beta[i] + (c - sg.c_begin[i]) : nullptr;
             dbeta = sg.dbeta[i] ? sg.dbeta[i] + (c - sg.c_begin[i]) : nullptr;
         }
@@ -450,10 +358,6 @@ __device__ __forceinline__ void bwd_finalize_segs_channel(const SumSegDev &sg, d
     for (int p = threadIdx.x; p < P; p += 256) {
         s += (double)sp[p];
         q += (double)qp[p];
-    }
-    for (int p = threadIdx.x; p < P2; p += 256) {          // (second source: the other addend's sums)
-        s += (double)sp2[p];
-        q += (double)qp2[p];
     }
     s = wave_sum_f64(s);
     q = wave_sum_f64(q);
@@ -467,8 +371,8 @@ __device__ __forceinline__ void bwd_finalize_segs_channel(const SumSegDev &sg, d
         q = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
         if (kind == 1) q -= (double)*beta * s;
         if (dbeta) *dbeta = (float)s;
-        st_res<COH>(coef + c, (float)(s * inv_count));
-        st_res<COH>(coef + C + c, (float)(q * inv_count));
+        coef[c] = (float)(s * inv_count);
+        coef[C + c] = (float)(q * inv_count);
     }
 }
 
@@ -479,9 +383,8 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_segs_kernel(SumSegDev sg,
 // THE row walk of the BatchNorm-backward passes over z [M, ldz] and the gradient of the layer's activation in up to four
 // column segments.  Thread = one float4 column group c, rows row0, row0 + drow, ... (see bn_apply_relu_kernel): f.channel(c)
 // once, then f.element(z[4], dy[4], c, row, offset of the z element) per row.  DS_BN_ROWS rows per pass, every load of the pass
-// before any of its stores.  ADD2: the gradient is the sum of two tensors of the same layout (ds_segments.ptr2); a segment
-// without one adds nothing.  Z16: z is stored as bf16.
-template <bool ADD2, bool Z16, class F>
+// before any of its stores.  Z16: z is stored as bf16.
+template <bool Z16, class F>
 __device__ __forceinline__ void bn_row_walk(int bid, const float *z, int ldz, const SegDev &dy, int64_t M, int C, int drow, F &f) {
     const int C4 = C >> 2;
     const int t0 = bid * 256 + threadIdx.x;
@@ -493,7 +396,6 @@ __device__ __forceinline__ void bn_row_walk(int bid, const float *z, int ldz, co
         if (i < dy.nseg && c >= dy.c_begin[i] && c < dy.c_end[i]) sgi = i;
     const float *const dyp = dy.ptr[sgi] + (c - dy.c_begin[sgi]);
     const int64_t dyld = dy.ld[sgi];
-    const float *const dyp2 = (ADD2 && dy.ptr2[sgi]) ? dy.ptr2[sgi] + (c - dy.c_begin[sgi]) : nullptr;
     constexpr int NR = DS_BN_ROWS;
     for (int64_t row = row0; row < M; row += NR * (int64_t)drow) {
         int64_t rws[NR], zo[NR];
@@ -511,13 +413,6 @@ __device__ __forceinline__ void bn_row_walk(int bid, const float *z, int ldz, co
             else zv[u] = ds::ld_stream4(z + zo[u]);
             dv[u] = ds::ld_stream4(dyp + rws[u] * dyld);
         }
-        if (ADD2 && dyp2) {
-#pragma unroll
-            for (int u = 0; u < NR; ++u) {
-                const float4 e = ds::ld_stream4(dyp2 + rws[u] * dyld);
-                dv[u].x += e.x; dv[u].y += e.y; dv[u].z += e.z; dv[u].w += e.w;
-            }
-        }
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
             if (u > 0 && !ok[u]) break;
@@ -532,7 +427,7 @@ __device__ __forceinline__ void bn_row_walk(int bid, const float *z, int ldz, co
 // gradients read it with one 16-byte load per eight channels (conv_bf16d_kernel<.., XB = true>); the values are the ones that
 // kernel would have rounded on load (RNE), so the dgrad's result has the same bits
 // coef_gx: the second coefficient vector where it does not follow the first at + C (ds_bn_bwd_apply_cols)
-template <bool OUT16, bool COH>
+template <bool OUT16>
 struct BwdApply {
     const float *mean, *rstd, *shift, *coef_g, *coef_gx;
     float *dz;
@@ -542,7 +437,7 @@ struct BwdApply {
         ds::ld_vec4(rr, rstd + c);
         ds::ld_vec4(ss, shift + c);
         ds::ld_vec4(mm, mean + c);
-        const float4 k14 = ld_res4<COH>(coef_g + c), k24 = ld_res4<COH>(coef_gx + c);
+        const float4 k14 = *reinterpret_cast<const float4 *>(coef_g + c), k24 = *reinterpret_cast<const float4 *>(coef_gx + c);
         a1[0] = k14.x; a1[1] = k14.y; a1[2] = k14.z; a1[3] = k14.w;
         a2[0] = k24.x; a2[1] = k24.y; a2[2] = k24.z; a2[3] = k24.w;
         am = 0.f;
@@ -561,13 +456,13 @@ struct BwdApply {
     }
 };
 
-template <bool OUT16, bool COH = false, bool ADD2 = false, bool Z16 = false>
+template <bool OUT16, bool Z16 = false>
 __device__ __forceinline__ void bwd_apply_body(int bid, const float *z, int ldz, const SegDev &dy, int64_t M, int C,
                                                const float *mean, const float *rstd, const float *shift,
                                                const float *coef, float *dz, float *amax, int drow, int lddz,
                                                const float *coef_gx = nullptr) {
-    BwdApply<OUT16, COH> f{mean, rstd, shift, coef, coef_gx ? coef_gx : coef + C, dz, lddz};
-    bn_row_walk<ADD2, Z16>(bid, z, ldz, dy, M, C, drow, f);
+    BwdApply<OUT16> f{mean, rstd, shift, coef, coef_gx ? coef_gx : coef + C, dz, lddz};
+    bn_row_walk<Z16>(bid, z, ldz, dy, M, C, drow, f);
     if (amax) {
         float am = f.am;
 #pragma unroll
@@ -576,12 +471,12 @@ __device__ __forceinline__ void bwd_apply_body(int bid, const float *z, int ldz,
     }
 }
 
-template <bool OUT16, bool ADD2 = false, bool Z16 = false>
+template <bool OUT16, bool Z16 = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *z, int ldz, SegDev dy, int64_t M, int C,
                                                            const float *mean, const float *rstd, const float *shift,
                                                            const float *coef, float *dz, float *amax, int drow, int lddz,
                                                            const float *coef_gx = nullptr) {
-    bwd_apply_body<OUT16, false, ADD2, Z16>((int)blockIdx.x, z, ldz, dy, M, C, mean, rstd, shift, coef, dz, amax, drow, lddz, coef_gx);
+    bwd_apply_body<OUT16, Z16>((int)blockIdx.x, z, ldz, dy, M, C, mean, rstd, shift, coef, dz, amax, drow, lddz, coef_gx);
 }
 
 // ---- moving-statistics (is_training=False) backward ------------------------------------------------------------------------
@@ -595,11 +490,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *z, int l
 // partials[c][blockIdx.x] -- float[C][P], P = gridDim.x, the layout of the other sum producers without the second (g*xhat)
 // plane.  No atomics: ds_bn_dbeta_reduce_multi adds the P partials in a fixed order.
 // WRITE = false: dz is not wanted (a frozen layer with nothing below it: the stem), the pass only sums.
-template <bool ADD2, bool WRITE, bool SUMS>
+template <bool WRITE, bool SUMS>
 __global__ __launch_bounds__(256) void bn_infer_bwd_kernel(const float *z, int ldz, SegDev dy, int64_t M, int C, const float *rstd,
                                                            const float *shift, float *dz, int drow, float *partials) {
     ds::InferBwd<WRITE, SUMS> f{rstd, shift, dz};
-    bn_row_walk<ADD2, false>((int)blockIdx.x, z, ldz, dy, M, C, drow, f);
+    bn_row_walk<false>((int)blockIdx.x, z, ldz, dy, M, C, drow, f);
     if constexpr (SUMS) {
         __shared__ float sh[256][4];
         ds::combine_column_groups<1>(sh, f.sum, C >> 2, C, partials);
@@ -634,29 +529,6 @@ __global__ __launch_bounds__(256) void bn_dbeta_reduce_multi_kernel(const SumJob
     if (threadIdx.x == 0) jb.dbeta[j][c] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
 }
 
-// ds_bn_bwd_finalize_apply: the backward finalize (segments, per-segment beta / dbeta) and the apply pass as one launch
-// (see bn_finalize_apply_relu_kernel)
-struct BwdFinApplyArgs {
-    SumSegDev sg; double inv_count; int C; float *coef;
-    const float *z; int ldz; SegDev dy; int64_t M;
-    const float *mean, *rstd, *shift;
-    float *dz, *amax; int drow, lddz;
-    unsigned *ticket;
-};
-
-template <bool OUT16>
-__global__ __launch_bounds__(256) void bn_bwd_finalize_apply_kernel(const BwdFinApplyArgs a) {
-    if ((int)blockIdx.x < a.C) {
-        bwd_finalize_segs_channel<true>(a.sg, a.inv_count, a.C, a.coef, (int)blockIdx.x);
-        fa_publish(a.ticket);
-        return;
-    }
-    fa_wait(a.ticket, (unsigned)a.C);
-    bwd_apply_body<OUT16, true>((int)blockIdx.x - a.C, a.z, a.ldz, a.dy, a.M, a.C, a.mean, a.rstd, a.shift, a.coef, a.dz, a.amax, a.drow,
-                          a.lddz);
-    fa_leave(a.ticket, gridDim.x - (unsigned)a.C);
-}
-
 // Launch shape of the fixed-column streaming kernels: gridDim.x * 256 threads = drow rows of C4 column groups each, i.e. the
 // grid is a multiple of C4 / gcd(C4, 256); about 16 workgroups per CU (DS_STREAM_BPC; 4 until round 6: 13.28 -> 13.17 ms, bf16 9.60 -> 9.47), fewer for small tensors
 // (two rows per thread and pass).
@@ -678,12 +550,6 @@ int column_grid(int64_t M, int C4, int *drow) {
     return (int)grid;
 }
 
-bool has_second_addend(const ds_segments *s) {
-    for (int i = 0; i < s->nseg && i < 4; ++i)
-        if (s->ptr2[i]) return true;
-    return false;
-}
-
 int check_segments(const ds_segments *s, int C, const char *who, bool allow_bf16 = false) {
     DS_REQUIRE(s && s->nseg >= 1 && s->nseg <= 4, "%s: 1..4 segments required", who);
     int covered = 0;
@@ -693,7 +559,6 @@ int check_segments(const ds_segments *s, int C, const char *who, bool allow_bf16
         DS_REQUIRE(s->c_begin[i] % 4 == 0 && s->c_end[i] % 4 == 0 && s->ld[i] % 4 == 0 && s->ptr[i] &&
                        (((uintptr_t)s->ptr[i]) & (s->dtype[i] == DS_DTYPE_BF16 ? 7 : 15)) == 0,
                    "%s: segment %d not 4-channel aligned", who, i);
-        DS_REQUIRE((((uintptr_t)s->ptr2[i]) & 15) == 0, "%s: segment %d's second addend is not 16-byte aligned", who, i);
         covered += s->c_end[i] - s->c_begin[i];
     }
     DS_REQUIRE(covered == C, "%s: segments cover %d of %d channels", who, covered, C);
@@ -812,24 +677,6 @@ extern "C" int ds_bn_apply_relu(const float *z, int64_t M, int32_t C, const floa
     return ds::check_launch("ds_bn_apply_relu");
 }
 
-extern "C" int ds_bn_finalize_apply_relu(const float *stats, int32_t P, int64_t count, int32_t C, const float *beta,
-                                         const float *pivot, float eps, float decay, float *mean, float *rstd, float *shift,
-                                         float *moving_mean, float *moving_var, const float *z, int64_t M,
-                                         const ds_segments *dst, uint32_t *ticket, void *stream) {
-    DS_REQUIRE(stats && beta && mean && rstd && shift && P > 0 && count > 0 && C > 0 && C % 4 == 0 && z && M > 0 && ticket,
-               "ds_bn_finalize_apply_relu: bad argument (C %% 4 != 0?)");
-    if (int e = check_segments(dst, C, "ds_bn_finalize_apply_relu", true)) return e;
-    FinApplyArgs a;
-    a.stats = stats; a.P = P; a.inv_count = 1.0 / (double)count; a.C = C;
-    a.beta = beta; a.pivot = pivot; a.eps = eps; a.decay = decay;
-    a.mean = mean; a.rstd = rstd; a.shift = shift; a.mm = moving_mean; a.mv = moving_var;
-    a.z = z; a.M = M; a.dst = to_dev(dst);
-    a.ticket = ticket;
-    const int grid = column_grid(M, C / 4, &a.drow);
-    hipLaunchKernelGGL(bn_finalize_apply_relu_kernel, dim3(C + grid), dim3(256), 0, (hipStream_t)stream, a);
-    return ds::check_launch("ds_bn_finalize_apply_relu");
-}
-
 extern "C" int ds_bn_apply_relu_z16(const void *z16, int64_t M, int32_t C, const float *rstd, const float *shift,
                                     const ds_segments *dst, void *stream) {
     DS_REQUIRE(z16 && rstd && shift && M > 0 && C > 0 && C % 4 == 0 && (((uintptr_t)z16) & 7) == 0,
@@ -857,7 +704,6 @@ extern "C" int ds_bn_bwd_reduce(const void *z, int32_t ldz, int32_t z_dtype, con
                    (((uintptr_t)z) & (z_dtype == DS_DTYPE_BF16 ? 7 : 15)) == 0,
                "ds_bn_bwd_reduce: bad argument (need C %% 4 == 0, C <= 1024, ldz %% 4 == 0, aligned pointers, z_dtype f32 / bf16)");
     if (int e = check_segments(dy, C, "ds_bn_bwd_reduce")) return e;
-    DS_REQUIRE(!has_second_addend(dy), "ds_bn_bwd_reduce: a gradient in two addends takes its sums from the producers (ds_bn_sum_segments.P2)");
     const int C4 = C / 4;
     const int RG = 256 / C4 > 0 ? 256 / C4 : 1;
     const size_t shmem = (size_t)RG * C4 * 8 * sizeof(float);
@@ -888,9 +734,7 @@ int build_sum_segs(const char *who, const ds_bn_sum_segments *sg, int64_t M, int
         d.c_begin[i] = sg->c_begin[i]; d.c_end[i] = sg->c_end[i]; d.P[i] = sg->P[i]; d.kind[i] = sg->kind[i];
         d.s[i] = sg->s[i]; d.q[i] = sg->q[i];
         d.beta[i] = nullptr; d.dbeta[i] = nullptr;
-        d.P2[i] = i < sg->nseg ? sg->P2[i] : 0; d.s2[i] = sg->s2[i]; d.q2[i] = sg->q2[i];
         if (i < sg->nseg) {
-            DS_REQUIRE(sg->P2[i] >= 0 && (sg->P2[i] == 0 || (sg->s2[i] && sg->q2[i])), "%s: segment %d has a malformed second source", who, i);
             DS_REQUIRE(sg->s[i] && sg->q[i] && sg->P[i] > 0 && sg->c_end[i] > sg->c_begin[i] && (sg->kind[i] == 0 || sg->kind[i] == 1),
                        "%s: segment %d is malformed", who, i);
             d.beta[i] = beta_v ? beta_v[i] : (beta ? beta + sg->c_begin[i] : nullptr);
@@ -923,30 +767,6 @@ extern "C" int ds_bn_bwd_finalize_multi(const ds_bn_sum_segments *sg, int64_t M,
     return launch_finalize_segs("ds_bn_bwd_finalize_multi", sg, M, C, nullptr, nullptr, beta, dbeta, coef, stream);
 }
 
-extern "C" int ds_bn_bwd_finalize_apply(const ds_bn_sum_segments *sg, const float *beta, float *dbeta, const float *const *beta_v,
-                                        float *const *dbeta_v, float *coef, const float *z, int32_t ldz, const ds_segments *dy,
-                                        int64_t M, int32_t C, const float *mean, const float *rstd, const float *shift, void *dz,
-                                        int32_t dz_dtype, int32_t lddz, float *amax, uint32_t *ticket, void *stream) {
-    const bool out16 = dz_dtype == DS_DTYPE_BF16;
-    DS_REQUIRE(z && mean && rstd && shift && coef && dz && ticket && M > 0 && C > 0 && C % 4 == 0 && ldz >= C && ldz % 4 == 0 &&
-                   (((uintptr_t)z) & 15) == 0 && (dz_dtype == DS_DTYPE_F32 || out16) &&
-                   (((uintptr_t)dz) & (out16 ? 7 : 15)) == 0 && (!out16 || (lddz >= C && lddz % 4 == 0)),
-               "ds_bn_bwd_finalize_apply: bad argument (see ds_bn_bwd_apply / ds_bn_bwd_apply_bf16)");
-    if (int e = check_segments(dy, C, "ds_bn_bwd_finalize_apply")) return e;
-    DS_REQUIRE(!has_second_addend(dy), "ds_bn_bwd_finalize_apply: no second addend (use ds_bn_bwd_finalize_segs + ds_bn_bwd_apply)");
-    BwdFinApplyArgs a;
-    if (int e = build_sum_segs("ds_bn_bwd_finalize_apply", sg, M, C, beta, dbeta, beta_v, dbeta_v, coef, a.sg)) return e;
-    a.inv_count = 1.0 / (double)M; a.C = C; a.coef = coef;
-    a.z = z; a.ldz = ldz; a.dy = to_dev(dy); a.M = M;
-    a.mean = mean; a.rstd = rstd; a.shift = shift;
-    a.dz = reinterpret_cast<float *>(dz); a.amax = amax; a.lddz = out16 ? lddz : ldz;
-    a.ticket = ticket;
-    const int grid = column_grid(M, C / 4, &a.drow);
-    if (out16) hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<true>, dim3(C + grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<false>, dim3(C + grid), dim3(256), 0, (hipStream_t)stream, a);
-    return ds::check_launch("ds_bn_bwd_finalize_apply");
-}
-
 extern "C" int ds_bn_bwd_apply(const float *z, int32_t ldz, const ds_segments *dy, int64_t M, int32_t C, const float *mean,
                                const float *rstd, const float *shift, const float *coef, float *dz, float *amax,
                                void *stream) {
@@ -956,12 +776,8 @@ extern "C" int ds_bn_bwd_apply(const float *z, int32_t ldz, const ds_segments *d
     if (int e = check_segments(dy, C, "ds_bn_bwd_apply")) return e;
     int drow;
     const int grid = column_grid(M, C / 4, &drow);
-    if (has_second_addend(dy))
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, mean,
-                           rstd, shift, coef, dz, amax, drow, ldz);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, mean, rstd,
-                           shift, coef, dz, amax, drow, ldz);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, mean, rstd,
+                       shift, coef, dz, amax, drow, ldz);
     return ds::check_launch("ds_bn_bwd_apply");
 }
 
@@ -972,7 +788,6 @@ extern "C" int ds_bn_bwd_apply_cols(const float *z, int32_t ldz, const ds_segmen
                    ldz % 4 == 0 && ((((uintptr_t)z) | ((uintptr_t)dz) | ((uintptr_t)coef_g) | ((uintptr_t)coef_gx)) & 15) == 0,
                "ds_bn_bwd_apply_cols: bad argument (need ncols %% 4 == 0, ldz >= ncols, ldz %% 4 == 0, 16-byte aligned z / dz / coef)");
     if (int e = check_segments(dy, ncols, "ds_bn_bwd_apply_cols")) return e;
-    DS_REQUIRE(!has_second_addend(dy), "ds_bn_bwd_apply_cols: no second addend");
     int drow;
     const int grid = column_grid(M, ncols / 4, &drow);
     hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, ncols, mean, rstd,
@@ -990,12 +805,8 @@ extern "C" int ds_bn_bwd_apply_z16(const void *z16, int32_t ldz, const ds_segmen
     int drow;
     const int grid = column_grid(M, C / 4, &drow);
     const float *zf = reinterpret_cast<const float *>(z16);
-    if (has_second_addend(dy))
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, zf, ldz, to_dev(dy), M, C,
-                           mean, rstd, shift, coef, reinterpret_cast<float *>(dz16), amax, drow, lddz);
-    else
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<true, false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, zf, ldz, to_dev(dy), M, C,
-                           mean, rstd, shift, coef, reinterpret_cast<float *>(dz16), amax, drow, lddz);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, zf, ldz, to_dev(dy), M, C,
+                       mean, rstd, shift, coef, reinterpret_cast<float *>(dz16), amax, drow, lddz);
     return ds::check_launch("ds_bn_bwd_apply_z16");
 }
 
@@ -1008,12 +819,8 @@ extern "C" int ds_bn_bwd_apply_bf16(const float *z, int32_t ldz, const ds_segmen
     if (int e = check_segments(dy, C, "ds_bn_bwd_apply_bf16")) return e;
     int drow;
     const int grid = column_grid(M, C / 4, &drow);
-    if (has_second_addend(dy))
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, mean,
-                           rstd, shift, coef, reinterpret_cast<float *>(dz16), amax, drow, lddz);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, mean,
-                           rstd, shift, coef, reinterpret_cast<float *>(dz16), amax, drow, lddz);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C, mean,
+                       rstd, shift, coef, reinterpret_cast<float *>(dz16), amax, drow, lddz);
     return ds::check_launch("ds_bn_bwd_apply_bf16");
 }
 
@@ -1025,12 +832,8 @@ extern "C" int ds_bn_infer_bwd_apply(const float *z, int32_t ldz, const ds_segme
     if (int e = check_segments(dy, C, "ds_bn_infer_bwd_apply")) return e;
     int drow;
     const int grid = column_grid(M, C / 4, &drow);
-    if (has_second_addend(dy))
-        hipLaunchKernelGGL((bn_infer_bwd_kernel<true, true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C,
-                           rstd, shift, dz, drow, (float *)nullptr);
-    else
-        hipLaunchKernelGGL((bn_infer_bwd_kernel<false, true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C,
-                           rstd, shift, dz, drow, (float *)nullptr);
+    hipLaunchKernelGGL((bn_infer_bwd_kernel<true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, z, ldz, to_dev(dy), M, C,
+                       rstd, shift, dz, drow, (float *)nullptr);
     return ds::check_launch("ds_bn_infer_bwd_apply");
 }
 
@@ -1050,19 +853,12 @@ extern "C" int ds_bn_infer_bwd_apply_sums(const float *z, int32_t ldz, const ds_
     if (int e = check_segments(dy, C, "ds_bn_infer_bwd_apply_sums")) return e;
     int drow;
     const int grid = column_grid(M, C / 4, &drow);
-    const bool add2 = has_second_addend(dy);
     hipStream_t st = (hipStream_t)stream;
-    if (add2 && dz)
-        hipLaunchKernelGGL((bn_infer_bwd_kernel<true, true, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
-                           dz, drow, partials);
-    else if (add2)
-        hipLaunchKernelGGL((bn_infer_bwd_kernel<true, false, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
-                           dz, drow, partials);
-    else if (dz)
-        hipLaunchKernelGGL((bn_infer_bwd_kernel<false, true, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+    if (dz)
+        hipLaunchKernelGGL((bn_infer_bwd_kernel<true, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
                            dz, drow, partials);
     else
-        hipLaunchKernelGGL((bn_infer_bwd_kernel<false, false, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
+        hipLaunchKernelGGL((bn_infer_bwd_kernel<false, true>), dim3(grid), dim3(256), 0, st, z, ldz, to_dev(dy), M, C, rstd, shift,
                            dz, drow, partials);
     return ds::check_launch("ds_bn_infer_bwd_apply_sums");
 }

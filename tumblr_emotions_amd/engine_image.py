@@ -111,8 +111,6 @@ class ConvBN:
         self.rstd = torch.empty(cout, device=dev)
         self.shift = torch.empty(cout, device=dev)
         self.coef = torch.empty(2, cout, device=dev)
-        self.fa_ticket = torch.zeros(4, dtype=torch.int32, device=dev)      # finalize + apply as one launch: [0:2] forward, [2:4] backward
-        self._plain_segs = None
         # The library plans the launch (ds_conv_plan): kernel family per shape and arithmetic -- implicit GEMM / wide 1x1,
         # fused Winograd F(2x2) / F(4x4) by its launch-time model, the packed-RGB stem kernel, the register-direct bf16 /
         # fp8 / f32x3 kernels -- the BatchNorm partial count and the prepared filter form.  The engine only says what the
@@ -223,15 +221,13 @@ class ConvBN:
         self.dy_segs = make_segments(parts)
         self.part_segs = [make_segments([(0, c1 - c0, ptr, ld)]) for (c0, c1, ptr, ld) in parts]
         self.part_sums = [None] * len(parts)
-        self.part_sums2 = [None] * len(parts)    # a second source of the same form: the part's gradient lives in TWO tensors (dy2)
-        self.dy2 = False                         # some part has a second addend (dy_segs.ptr2): see MixedStage.alloc, split_dout
         self.part_pool = [None] * len(parts)     # (pool stage, first column): the part feeds nothing but that max pool
         self._sum_segs = None
         self._rest_segs = None                   # parts 1.. counted from part 0's end (_bwd_apply_pooled)
 
-    def sums_from(self, part, src, src2=None):
-        """Part `part` takes its sums from the dgrad epilogue that writes its gradient (src2: its second addend's, dy2)."""
-        self.part_sums[part], self.part_sums2[part] = src, src2
+    def sums_from(self, part, src):
+        """Part `part` takes its sums from the dgrad epilogue that writes its gradient."""
+        self.part_sums[part] = src
         self._sum_segs = None
 
     def sums_from_pool(self, part, pool, off):
@@ -270,11 +266,6 @@ class ConvBN:
                     sg.P[i], sg.kind[i] = src.P, 1
                     sg.s[i], sg.q[i] = src.ptrs()
                     self._sync_views += src.views(c1 - c0)
-                    src2 = self.part_sums2[i]
-                    if src2 is not None:          # the other addend's sums, added by the finalize
-                        sg.P2[i] = src2.P
-                        sg.s2[i], sg.q2[i] = src2.ptrs()
-                        self._sync_views += src2.views(c1 - c0)
                     continue
                 n, dst = c1 - c0, _vp(scratch)          # nobody emitted them: one ds_bn_bwd_reduce into this layer's scratch
                 if self.part_pool[i] is None:
@@ -472,12 +463,6 @@ class ConvBN:
                 count = self.M * eng.sync_world
             if fin is None and not defer_finalize:
                 mm, mv = (self.mm, self.mv) if eng.update_moving else (None, None)
-                if eng.fuse_fin_apply and not eng.sync_bn and segs is not None and not self.skip_apply and not self.z16:
-                    # ds_bn_finalize and the apply pass that reads its result as ONE launch (no dependent-launch boundary)
-                    ops.bn_finalize_apply_relu(self.stats_buf, plan.partials, count, self.cout, self.beta, BN_EPS, BN_DECAY,
-                                               self.mean, self.rstd, self.shift, mm, mv, self.mean, self.z, self.M, segs,
-                                               self.fa_ticket[0:2])
-                    return
                 if self.z16:
                     ops.bn_finalize_centered(self.stats_buf, plan.partials, count, self.cout, self.beta, BN_EPS, BN_DECAY, self.mean,
                                              self.rstd, self.shift, mm, mv, self.mean, self.mean_c, self.shift_c)
@@ -646,40 +631,22 @@ class ConvBN:
         from_parts = any(ps is not None for ps in self.part_sums) or any(pp is not None for pp in self.part_pool)
         track = self.dgrad is not None and self.dgrad.family == ops.DS_FAM_FP8D
         dz = self.z if self.dz16 is None else self.dz16          # dz over z, or into its own bf16 tensor
-        if eng.fuse_fin_apply and not eng.sync_bn and (need_dx or self.trainable) and not self.bnb and not self.dy2 and not self.z16:
-            # the finalize and the apply pass behind it as ONE launch (ds_bn_bwd_finalize_apply)
-            assert pool is None
-            if from_parts:
-                sg = self._sum_plan()
-                self._run_reduce_jobs()
-            else:
-                ops.bn_bwd_reduce(self.z, dy_segs, M, Cc, self.zmean, self.rstd, self.zshift, self.bwdp_buf, ldz=self.ldz)
-                if self._plain_segs is None:
-                    sg = ops.SumSegments()
-                    sg.nseg = 1
-                    sg.c_begin[0], sg.c_end[0], sg.P[0], sg.kind[0] = 0, Cc, self.bwd_P, 0
-                    sg.s[0], sg.q[0] = self.bwdp_buf.data_ptr(), self.bwdp_buf.data_ptr() + 4 * Cc * self.bwd_P
-                    self._plain_segs = sg
-                sg = self._plain_segs
-            ops.bn_bwd_finalize_apply(sg, M, Cc, self.beta, self.gbeta, self.coef, self.z, dy_segs, self.mean, self.rstd,
-                                      self.shift, dz, self.fa_ticket[2:4], amax=self.dz_amax if track else None, ldz=self.ldz)
+        if from_parts:
+            self._bn_bwd_sums()
         else:
-            if from_parts:
-                self._bn_bwd_sums()
-            else:
-                ops.bn_bwd_reduce(self.z, dy_segs, M, Cc, self.zmean, self.rstd, self.zshift, self.bwdp_buf, ldz=self.ldz)
-                self._finalize_plain(self.bwd_P)
-            if not (need_dx or self.trainable):
-                return
-            if self.bnb:              # z stays as it is: the dgrad's loader forms dz
-                self._run_dgrad(dx_ptr)
-                return
-            if pool is not None:
-                assert from_parts and not self.bnb and not track and dz is self.z and self.ldz == Cc
-                self._bwd_apply_pooled(pool)
-            else:
-                ops.bn_bwd_apply(self.z, dy_segs, M, Cc, self.zmean, self.rstd, self.zshift, self.coef, dz,
-                                 amax=self.dz_amax if track else None, ldz=self.ldz)
+            ops.bn_bwd_reduce(self.z, dy_segs, M, Cc, self.zmean, self.rstd, self.zshift, self.bwdp_buf, ldz=self.ldz)
+            self._finalize_plain(self.bwd_P)
+        if not (need_dx or self.trainable):
+            return
+        if self.bnb:              # z stays as it is: the dgrad's loader forms dz
+            self._run_dgrad(dx_ptr)
+            return
+        if pool is not None:
+            assert from_parts and not self.bnb and not track and dz is self.z and self.ldz == Cc
+            self._bwd_apply_pooled(pool)
+        else:
+            ops.bn_bwd_apply(self.z, dy_segs, M, Cc, self.zmean, self.rstd, self.zshift, self.coef, dz,
+                             amax=self.dz_amax if track else None, ldz=self.ldz)
         self._dz_amax_live = track
         if self.trainable:
             self._run_wgrad(x_ptr, ldx)
@@ -844,11 +811,11 @@ class PoolStage(Stage):
         # ... and such a block (Mixed_3c, Mixed_4f) also APPLIES its BatchNorm backward from the pooled tensors
         # (ds_bn_pool_bwd_apply_cols): this stage launches no MaxPoolGrad and the block's full-resolution `dout` is neither
         # written nor read.  fp32 zcat blocks with the block-batched backward; MixedStage.backward keeps the former path for the
-        # passes that cannot take it (moving statistics, sync_bn, DS_FIN_APPLY).  `dout` stays allocated for those.
+        # passes that cannot take it (moving statistics, sync_bn).  `dout` stays allocated for those.
         eng = self.eng
         p.pooled_bwd = bool(eng.pool_apply and isinstance(p, MixedStage) and targets and self.stride == 2 and self.k in (2, 3)
                             and eng.dtype == "f32" and not eng.act16 and p.fused.dgrad.family != ops.DS_FAM_FP8D
-                            and p.zcat and (p.batch_bn & 2) and not eng.split_dout and not p.fused.bnb and p.fused.dz16 is None
+                            and p.zcat and (p.batch_bn & 2) and not p.fused.bnb and p.fused.dz16 is None
                             and not p.fused.z16 and p.b[0] % 4 == 0)
 
     @property
@@ -992,7 +959,6 @@ class MixedStage(Stage):
             self.batch_bn = (3 if B <= 128 else 2) if eng.batch_bn is None else int(eng.batch_bn)
             self._fin_jobs = {}
             self._close_plan = None
-            self.fa_ticket = torch.zeros(2, dtype=torch.int32, device=dev)
         if self.prev.zcat:    # this block reads a zcat concat
             self.fused.fwd.d.norm_rstd = self.prev.rs_cat[0].data_ptr()
             self.fused.fwd.d.norm_shift = self.prev.rs_cat[1].data_ptr()
@@ -1003,12 +969,6 @@ class MixedStage(Stage):
         self.c1.make_dgrad(b1a, allow_z16=True)
         self.c2.make_dgrad(b2a, allow_z16=True)
         self.c3.make_dgrad(cin, allow_z16=True)
-        # 16-bit labels: Branch_3's Conv2DBackpropInput output lives between that launch and the pool gradient only -- in bf16
-        # storage (ds_conv_desc.z_dtype on the dgrad, ds_maxpool3_bwd_dy16): 2 B written and 2 B read per element instead of 4
-        self.dpooled16 = bool(eng.dpooled16 and eng.act16 and self.c3.dgrad.family == ops.DS_FAM_BF16D)
-        if self.dpooled16:
-            self.dpooled = torch.empty(M, cin, device=dev, dtype=torch.bfloat16)
-            self.c3.dgrad.d.z_dtype = ops.DS_DTYPE_BF16
         # BatchNorm backward sums from the epilogue of the dgrad that produces the gradient (DS_EPI_BNSUMS) instead of
         # a separate pass over z and dy:
         #  * the Branch_1 / Branch_2 3x3 dgrads write dr1 / dr2, the gradients of the fused 1x1 layer's reduce outputs;
@@ -1021,10 +981,7 @@ class MixedStage(Stage):
         p = self.prev
         # (the register-direct bf16 / fp8 dgrads have the accumulate epilogue too, but at their two workgroups per CU its
         # dependent read-add-store chain costs more than the pass it saves: bf16 step 12.5 -> 14.0 ms, profiles/r04_notes.md)
-        # DS_POOL_FIRST_16=1 (A/B): also for the register-direct bf16 / fp8 dgrads -- 12.98 -> 13.45 ms at bf16 even with the
-        # accumulate reads requested up front (14.0 before that): two waves per SIMD cannot hide a read-modify-write epilogue
-        fams = (ops.DS_FAM_IGEMM, ops.DS_FAM_BF16D, ops.DS_FAM_FP8D) if _lib.tuning_env("DS_POOL_FIRST_16") == "1" else (ops.DS_FAM_IGEMM,)
-        self.pool_first = bool(eng.pool_first and self.fused.dgrad.family in fams)
+        self.pool_first = bool(eng.pool_first and self.fused.dgrad.family == ops.DS_FAM_IGEMM)
         if isinstance(p, MixedStage) and self.pool_first:
             src = self.fused.emit_dx_sums(p.out)
             if src is not None and p.zcat:      # the epilogue rebuilds y from the concat's z
@@ -1036,38 +993,13 @@ class MixedStage(Stage):
         #  * where the fused dgrad cannot accumulate (the 16-bit configurations' register-direct kernels) the order is the
         #    reverse: the dgrad writes, Branch_3's pool gradient is added LAST -- and that launch, which then holds the complete
         #    gradient of the previous block's output, emits the sums instead (ds_maxpool3_bwd_sums)
-        #    split_dout: ... and then that launch need not wait for the dgrad at all -- the two addends stay TWO tensors
-        #    (p.dout from the fused dgrad on the main chain, p.dout2 from the pool gradient inside the Branch_3 chain on its side
-        #    stream), each producer emits the BatchNorm sums of its own addend (the sums are linear in the gradient:
-        #    ds_bn_sum_segments.P2) and the one consumer, the previous block's ds_bn_bwd_apply, adds them as it reads
-        #    (ds_segments.ptr2).  The pool gradient (a sixth of the 16-bit step's critical chain) leaves the main stream.
         self.pool_sums = None
-        self.split_dout = False
         if isinstance(p, MixedStage) and not self.pool_first and eng.bwd_sums and eng.pool_sums and cin <= 1024 \
                 and not p.zcat:          # (a zcat concat holds z, not y: the dgrad epilogue's business)
             P = ops.maxpool3_bwd_sums_partials(B, p.W, cin)
             self.pool_sums = torch.empty(2 * cin * P, device=dev)
-            # (the dgrad addend's sums: NOT from the register-direct kernels' DS_EPI_BNSUMS epilogue -- measured, it costs the
-            # fused dgrads 51 -> 75 us each, bf16 step 9.75 -> 10.13 ms -- but from one ds_bn_bwd_reduce over (y, dout) behind the
-            # dgrad: 6 B/element on the main chain where the accumulating pool gradient was 15; with mean = 0, rstd = 1,
-            # shift = 0 its sums are sum g and sum g*y over y > 0, the DS_EPI_BNSUMS form)
-            src, delta = None, 0
-            if eng.split_dout and cin % 4 == 0:
-                P1 = ops.bn_bwd_partials(M, cin)
-                self.dgrad_sums = torch.empty(2 * cin * P1, device=dev)
-                self._dgrad_sum_segs = make_segments([(0, cin, p.dout.data_ptr(), cin)])
-                src = SumSource(self.dgrad_sums, P1, 0, cin)
-                self.split_dout = True
-                p.dout2 = torch.empty_like(p.dout)
-                delta = p.dout2.data_ptr() - p.dout.data_ptr()
             for layer, off in p.concat_layers():
-                pool_src = SumSource(self.pool_sums, P, off, cin)
-                if self.split_dout:
-                    layer.sums_from(0, src._replace(off=off), pool_src)
-                    layer.dy_segs.ptr2[0] = layer.dy_segs.ptr[0] + delta          # (part 0 of each layer lives in p.dout)
-                    layer.dy2 = True
-                else:
-                    layer.sums_from(0, pool_src)
+                layer.sums_from(0, SumSource(self.pool_sums, P, off, cin))
 
     # The three chains behind the block input -- [fused 1x1 -> Branch_1 3x3], [... -> Branch_2 3x3] and
     # [3x3/1 pool -> Branch_3 1x1] -- are independent: Branch_3 and then Branch_2 are issued on a side stream (fork /
@@ -1191,18 +1123,13 @@ class MixedStage(Stage):
         sg, dy, z = self._close_plan
         for l in layers:
             l._run_reduce_jobs()
-        if self.eng.fuse_fin_apply:      # ... and those two as one (ds_bn_bwd_finalize_apply)
-            ops.bn_bwd_finalize_apply(sg, M, Cb, None, None, self.coef_cat, z, dy, self.mean_cat[b0:], self.rs_cat[0, b0:],
-                                      self.rs_cat[1, b0:], z, self.fa_ticket, ldz=Ct, betas=[l.beta for l in layers],
-                                      dbetas=[l.gbeta for l in layers])
+        ops.bn_bwd_finalize_multi(sg, M, Cb, [l.beta for l in layers], [l.gbeta for l in layers], self.coef_cat)
+        if from_pool:
+            nx = self.next
+            ops.bn_pool_bwd_apply_cols(z, Ct, z, Ct, nx.dout, nx.argmax, Ct, b0, self.B, self.H, self.W, Cb, self.mean_cat[b0:],
+                                       self.rs_cat[0, b0:], self.rs_cat[1, b0:], self.coef_cat[0], self.coef_cat[1], nx.k)
         else:
-            ops.bn_bwd_finalize_multi(sg, M, Cb, [l.beta for l in layers], [l.gbeta for l in layers], self.coef_cat)
-            if from_pool:
-                nx = self.next
-                ops.bn_pool_bwd_apply_cols(z, Ct, z, Ct, nx.dout, nx.argmax, Ct, b0, self.B, self.H, self.W, Cb, self.mean_cat[b0:],
-                                           self.rs_cat[0, b0:], self.rs_cat[1, b0:], self.coef_cat[0], self.coef_cat[1], nx.k)
-            else:
-                ops.bn_bwd_apply(z, dy, M, Cb, self.mean_cat[b0:], self.rs_cat[0, b0:], self.rs_cat[1, b0:], self.coef_cat, z, ldz=Ct)
+            ops.bn_bwd_apply(z, dy, M, Cb, self.mean_cat[b0:], self.rs_cat[0, b0:], self.rs_cat[1, b0:], self.coef_cat, z, ldz=Ct)
         for l in layers:
             l._dz_amax_live = False
 
@@ -1240,7 +1167,7 @@ class MixedStage(Stage):
         batched = self._batch_backward(need_dx) and not infer
         # pooled_bwd (Mixed_3c / 4f): the gradient of this block's output exists only pooled, behind the stride-2 pool -- both
         # apply passes that would read self.dout rebuild it from there.  A pass that cannot has the pool gradient written first
-        from_pool = self.pooled_bwd and batched and not eng.fuse_fin_apply
+        from_pool = self.pooled_bwd and batched
         if self.pooled_bwd and not from_pool:
             nx = self.next
             ops.maxpool_bwd(nx.dout, nx.argmax, self.dout, False, self.B, self.H, self.W, self.C, nx.k, nx.stride, "SAME")
@@ -1276,27 +1203,18 @@ class MixedStage(Stage):
             closing(self.c3, None if self.fuse_b3 else ops._p(self.pooled), p.C, ops._p(self.dpooled), need_dx)      # (x: weight gradient only)
             if pool_first:
                 ops.maxpool_bwd(self.dpooled, self.argmax, p.dout, False, self.B, p.H, p.W, p.C, 3, 1, "SAME")
-            elif need_dx and self.split_dout and infer:
-                ops.maxpool_bwd(self.dpooled, self.argmax, p.dout2, False, self.B, p.H, p.W, p.C, 3, 1, "SAME")
-            elif need_dx and self.split_dout:       # the pool gradient into its OWN tensor, with its own sums: inside this chain
-                ops.maxpool3_bwd_sums(self.dpooled, self.argmax, p.dout2, False, p.out, self.B, p.H, p.W, p.C, self.pool_sums)
 
         # (the fused layer runs last, behind the join: nothing in the three chains waits for more than the block's gradient)
         self._fork_join(None, lambda: closing(self.c1, ops._p(self.r1), b1a, ops._p(self.dr1), True),
                         lambda: closing(self.c2, ops._p(self.r2), b2a, ops._p(self.dr2), True), branch3)
+        # (need_dx: always set in input_backward's walk; a frozen-BatchNorm step with trainable_bn_beta=False ends at
+        # Mixed_5c, whose input gradient nobody reads)
         if infer:
             self.fused.backward_pointwise(x, p.C, ops._p(p.dout) if need_dx else None, need_dx)
-            # (need_dx: always set in input_backward's walk; a frozen-BatchNorm step with trainable_bn_beta=False ends at
-            # Mixed_5c, whose input gradient nobody reads)
-            if need_dx and not pool_first and not self.split_dout:
-                ops.maxpool_bwd(self.dpooled, self.argmax, p.dout, True, self.B, p.H, p.W, p.C, 3, 1, "SAME")
-            return
-        self.fused.backward(x, p.C, ops._p(p.dout) if need_dx else None, need_dx, pool=self.next if from_pool else None)
-        if need_dx and self.split_dout:             # the sums of the dgrad's addend (the pool gradient's came with it: branch3)
-            ops.bn_bwd_reduce(p.out, self._dgrad_sum_segs, self.B * p.H * p.W, p.C, eng.zeros, eng.ones, eng.zeros, self.dgrad_sums,
-                              ldz=p.C)
-        if need_dx and not pool_first and not self.split_dout:
-            if self.pool_sums is not None:          # ... and the previous block's BatchNorm-backward sums (alloc)
+        else:
+            self.fused.backward(x, p.C, ops._p(p.dout) if need_dx else None, need_dx, pool=self.next if from_pool else None)
+        if need_dx and not pool_first:
+            if self.pool_sums is not None and not infer:      # ... and the previous block's BatchNorm-backward sums (alloc)
                 ops.maxpool3_bwd_sums(self.dpooled, self.argmax, p.dout, True, p.out, self.B, p.H, p.W, p.C, self.pool_sums)
             else:
                 ops.maxpool_bwd(self.dpooled, self.argmax, p.dout, True, self.B, p.H, p.W, p.C, 3, 1, "SAME")
@@ -1380,29 +1298,15 @@ class InceptionV1Engine:
         # (profiles/r06_notes.md).  DS_FUSE_FIN=1 switches it on (A/B)
         self.fuse_finalize = _lib.tuning_env("DS_FUSE_FIN", "0") == "1"
         # zcat blocks: the BatchNorm launches of the three block-closing layers once per block (MixedStage.alloc); DS_BATCH_BN=0: A/B
-        # a BatchNorm finalize and the apply pass that reads its result as ONE launch, both directions (ds_bn_finalize_apply_relu,
-        # ds_bn_bwd_finalize_apply: device-side ticket instead of a dependent-launch boundary).  Built, bit-identical (tests),
-        # measured, OFF: a cross-XCD hand-off (write-through results, ticket, poll, coherent reads) costs ~15 us where the launch
-        # boundary costs ~9 -- B = 256 13.23 -> 13.61 ms, B = 32 3.81 -> 4.11 (with release / acquire fences, which write back and
-        # invalidate a whole L2 per workgroup: 17.4 / 6.6; profiles/r06_notes.md).  DS_FIN_APPLY=1 switches it on (A/B)
-        self.fuse_fin_apply = _lib.tuning_env("DS_FIN_APPLY", "0") == "1"
         # bit 0: the forward finalizes, bit 1: the backward finalize + apply; None = by batch size (MixedStage.alloc)
         e = _lib.tuning_env("DS_BATCH_BN")
         self.batch_bn = int(e) if e else None
         self.pool_sums = _lib.tuning_env("DS_POOL_SUMS", "1") != "0"      # ... or from the Branch_3 pool gradient where that is the last addend (MixedStage.alloc)
-        # ... which then stays a second tensor the consumer adds on load (MixedStage.alloc).  Built, tested, measured, OFF: the pool
-        # gradient leaves the main chain, but the Branch_3 chain it joins becomes the longest of the block and the step moves
-        # 6 B/element more -- bf16 9.74 -> 10.01 ms (10.13 with the sums from the register-direct dgrads' epilogue), every side
-        # stream arrangement (profiles/r06_notes.md).  DS_SPLIT_DOUT=1 switches it on (A/B)
-        self.split_dout = _lib.tuning_env("DS_SPLIT_DOUT", "0") == "1"
         # 16-bit configurations: z of the frozen Mixed-block layers in bf16 storage, centred about the statistics pivot
         # (ConvBN.make_dgrad; ds_conv_desc.z_dtype, ds_bn_finalize_centered): conv write, apply read and backward read move 2 B per
         # element of z instead of 4 -- bf16 step 9.58 -> 9.38 ms.  Like the 16-bit activation storage it is a rounding the fp64
         # reference emulation of the tests does not model; the labels' gates hold with it (profiles/r06_notes.md).  DS_Z16=0: A/B
         self.z16 = _lib.tuning_env("DS_Z16", "1") != "0"
-        # ... and Branch_3's dgrad output (MixedStage.alloc).  Built, measured, OFF: -0.66 GB/step but no time (bf16 9.35 -> 9.37 ms:
-        # the 2-byte stores of the register-direct epilogue and the 8-byte loads of the pool gradient are instruction-rate bound)
-        self.dpooled16 = _lib.tuning_env("DS_DPOOLED16", "0") == "1"
         self.stem_sums_from_dgrad = _lib.tuning_env("DS_STEM_SUMS", "1") != "0"      # pooled stem: its BatchNorm sums from Conv2d_2b's dgrad epilogue
         self.dz16 = int(_lib.tuning_env("DS_DZ16", "2"))      # 16-bit configurations: bf16 dz for the frozen 1x1 (1) and 3x3 (2) layers (ConvBN.make_dgrad)
         self.fuse_branch3 = _lib.tuning_env("DS_FUSE_B3", "1") != "0"      # Branch_3's 3x3/1 max pool formed on load by its 1x1 conv (MixedStage.alloc)
