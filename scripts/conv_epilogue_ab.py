@@ -11,7 +11,6 @@ has 5 rows, waves 2-3 none, and column block 1 is partial), one 3x3 case per ker
 shapes of scripts/wide_epi_bench.py for the timing.  `compare`: equal digests, and the second build's median per timed case
 inside the range of the first build's window medians."""
 import ast
-import ctypes as C
 import hashlib
 import json
 import os
@@ -142,34 +141,17 @@ def main():
         def build():
             pin(0, 2, 0, 0)
             x = rnd(M, K)
-            if combo in ("BNR", "fin"):
+            if combo == "BNR":
                 w = rnd(K, Nc, scale=0.1)
-                plan = E.LayerPlan(E.DS_CONV_FWD, E.DS_ARITH_F32, 0, 1, M, 1, K, Nc, 1, 1, K, ld, E.DS_EPI_STATS if combo == "fin" else 0)
+                plan = E.LayerPlan(E.DS_CONV_FWD, E.DS_ARITH_F32, 0, 1, M, 1, K, Nc, 1, 1, K, ld, 0)
                 if plan.family != E.DS_FAM_IGEMM:
                     return None
                 z = torch.empty(M, ld, device=dev)
-                if combo == "BNR":
-                    q = plan.bn_relu_variant(ld)
-                    if q is None:
-                        return None
-                    sc, sh = torch.rand(Nc, device=dev) + 0.1, rnd(Nc)
-                    return (lambda: q.run_bn_relu(E._p(x), E._p(w), E._p(z), sc.data_ptr(), sh.data_ptr())), (lambda: z.fill_(-7.0)), [("z", z)], None
-                nt = plan.finalize_tickets()
-                if nt <= 0 or plan.partials > 256:
+                q = plan.bn_relu_variant(ld)
+                if q is None:
                     return None
-                stats = torch.zeros(2 * Nc * plan.partials + 16, device=dev)
-                beta, mean0 = rnd(Nc, scale=0.1), rnd(Nc, scale=0.05)
-                mean, rstd, shift = mean0.clone(), torch.zeros(Nc, device=dev), torch.zeros(Nc, device=dev)
-                mm, mv = torch.zeros(Nc, device=dev), torch.ones(Nc, device=dev)
-                tickets = torch.zeros(nt, dtype=torch.int32, device=dev)
-                f = _lib.BnFinalizeInLaunch()
-                f.beta, f.mean, f.rstd, f.shift = beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(), shift.data_ptr()
-                f.moving_mean, f.moving_var, f.ticket, f.count, f.eps, f.decay = mm.data_ptr(), mv.data_ptr(), tickets.data_ptr(), M, 1e-3, 0.9997
-
-                def reset():
-                    z.fill_(-7.0); mean.copy_(mean0); mm.zero_(); mv.fill_(1.0)
-                run = lambda: plan.run(E._p(x), E._p(w), E._p(z), stats=E._p(stats), pivot=E._p(mean), fin=C.addressof(f))
-                return run, reset, [("z", z), ("stats", stats), ("mean", mean), ("rstd", rstd), ("shift", shift), ("mm", mm), ("mv", mv), ("tickets", tickets)], beta
+                sc, sh = torch.rand(Nc, device=dev) + 0.1, rnd(Nc)
+                return (lambda: q.run_bn_relu(E._p(x), E._p(w), E._p(z), sc.data_ptr(), sh.data_ptr())), (lambda: z.fill_(-7.0)), [("z", z)], None
             if combo in ("0", "STATS+pivot"):          # forward: n-contiguous weights
                 flags = E.DS_EPI_STATS if combo != "0" else 0
                 w = rnd(K, Nc, scale=0.1)
@@ -252,7 +234,7 @@ def main():
             return run, (lambda: z.copy_(prev)), [("z", z), ("stats", stats)], (mr, ms)
         return build
 
-    WIDE = ["0", "STATS+pivot", "ACCUM", "ACCUM|BNSUMS", "ACCUM|BNSUMS+mask_rstd", "BNR", "fin"]
+    WIDE = ["0", "STATS+pivot", "ACCUM", "ACCUM|BNSUMS", "ACCUM|BNSUMS+mask_rstd", "BNR"]
     ROWD = {"bf16d": ["0", "STATS+pivot", "ACCUM", "ACCUM|BNSUMS", "m16", "z16"],
             "x3": ["0", "STATS+pivot", "ACCUM|BNSUMS", "ACCUM|BNSUMS+mask_rstd"],
             "fp8d": ["0", "STATS+pivot", "ACCUM", "ACCUM|BNSUMS", "m16", "z16"]}

@@ -5,7 +5,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import _tuning  # noqa: F401,E402  (the -DDS_TUNING library: DS_WIDE_RING and the other knobs are honoured)
+import _tuning  # noqa: F401,E402  (the -DDS_TUNING library: the DS_* knobs are honoured)
 import torch
 from tumblr_emotions_amd import _lib, ops
 

@@ -13,8 +13,8 @@ batch, plain and with the split-K slices ops.head_gemm_plan gives them).  Every 
 depends on the occupancy query, which fails without a device (asserted per row).
 
 Per row, through ds_conv_plan for f32 / bf16 / fp8 / f32x3: the return code, family, partials, splitk, ws_bytes, w_bytes, x16_ok
-and what ds_conv_plan_enable_bnsums / _enable_pool3 / _enable_bn_relu / _norm_supported / _bnb_supported / _finalize_tickets
-answer (with the partial counts they leave in the plan); through a raw ds_conv_desc: the six ds_conv_igemm_* answers without
+and what ds_conv_plan_enable_bnsums / _enable_pool3 / _enable_bn_relu / _norm_supported / _bnb_supported answer (with the
+partial counts they leave in the plan); through a raw ds_conv_desc: the five ds_conv_igemm_* answers without
 flags and with DS_EPI_STATS.  Of the product library the raw answers and the f32 plan are stored in full and the bf16 / fp8 /
 f32x3 plans as one sha256 prefix each.  The tuning library answers the same under ds_debug_conv_set_wide 0 / 1 / 2, set_path
 1 / 3 and set_tile (1,1) .. (2,6) -- not path 2, whose grid always comes from the occupancy query; of those, one sha256 prefix
@@ -112,7 +112,7 @@ def answers(lib, row):
         d.flags = flags
         out += [lib.ds_conv_igemm_partials(C.byref(d)), lib.ds_conv_igemm_bnsums_supported(C.byref(d)),
                 lib.ds_conv_igemm_norm_supported(C.byref(d)), lib.ds_conv_igemm_pool3_supported(C.byref(d)),
-                lib.ds_conv_igemm_finalize_tickets(C.byref(d)), lib.ds_conv_igemm_bnb_supported(C.byref(d))]
+                lib.ds_conv_igemm_bnb_supported(C.byref(d))]
     dgrad = role == L.DS_CONV_DGRAD
     ldx, ldz = (w_cout, w_cin) if dgrad else (w_cin, w_cout)
     if options & L.DS_PLAN_PACKED_RGB:
@@ -133,13 +133,12 @@ def answers(lib, row):
         if rc != 0:
             continue
         out += [p.family, p.partials, p.d.partials, p.splitk, p.ws_bytes, p.w_bytes, p.x16_ok,
-                lib.ds_conv_plan_norm_supported(C.byref(p)), lib.ds_conv_plan_bnb_supported(C.byref(p)),
-                lib.ds_conv_plan_finalize_tickets(C.byref(p))]
+                lib.ds_conv_plan_norm_supported(C.byref(p)), lib.ds_conv_plan_bnb_supported(C.byref(p))]
         q = L.LayerPlanStruct.from_buffer_copy(p)
         out += [lib.ds_conv_plan_enable_bnsums(C.byref(q), ldz), q.d.flags, q.partials, q.d.partials]
         q = L.LayerPlanStruct.from_buffer_copy(p)
         out += [lib.ds_conv_plan_enable_pool3(C.byref(q), C.c_void_p(4096)), q.partials, q.d.partials]
-        out += [lib.ds_conv_plan_norm_supported(C.byref(q)), lib.ds_conv_plan_finalize_tickets(C.byref(q))]
+        out += [lib.ds_conv_plan_norm_supported(C.byref(q))]
         out += [lib.ds_conv_plan_set_flags(C.byref(q), 0), lib.ds_conv_plan_enable_bn_relu(C.byref(q)), q.d.flags]
         rc, q = plan(arith, 0)
         out += [lib.ds_conv_plan_enable_bn_relu(C.byref(q)), q.d.flags, q.partials, q.d.partials]

@@ -4,7 +4,7 @@ The kernel tests call the families' own entry points at N <= 5 on small maps; th
 end behind loose 16-bit gates.  Here the plans come from SentimentNet(mode="image") itself after one step -- family,
 geometry, split-K slices and workspace, ldx / ldz concat strides, x_dtype / z_dtype storage, the STATS / BNSUMS / ACCUM
 epilogues as the engine left them -- so what runs is exactly the launch the product makes, on buffers the test owns.  The
-on-load fusions (norm-on-load, bnb, pool3, mask_rstd / mask_shift, in-launch finalize) point at engine buffers and have their
+on-load fusions (norm-on-load, bnb, pool3, mask_rstd / mask_shift) point at engine buffers and have their
 own bit-identity tests: they are cleared, and the partial count is re-planned for the plain launch.
 
 Configurations (each reaches launches the others do not):
@@ -62,7 +62,7 @@ def _copy_plan(src):
     C.memmove(C.addressof(q), C.addressof(src), C.sizeof(q))
     d = q.d
     d.norm_rstd = d.norm_shift = d.mask_rstd = d.mask_shift = None
-    d.bnb = d.pool_argmax = d.fin = None
+    d.bnb = d.pool_argmax = None
     _lib.load().ds_conv_plan_set_flags(C.byref(q), d.flags)
     return q
 

@@ -48,7 +48,7 @@ def _copy(src, keep_pool):
     C.memmove(C.addressof(q), C.addressof(src), C.sizeof(q))
     d = q.d
     d.norm_rstd = d.norm_shift = d.mask_rstd = d.mask_shift = None
-    d.bnb = d.fin = None
+    d.bnb = None
     if not keep_pool:
         d.pool_argmax = None
     _lib.load().ds_conv_plan_set_flags(C.byref(q), 0)

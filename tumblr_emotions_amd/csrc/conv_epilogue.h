@@ -122,7 +122,6 @@ struct WaveRowOpt {        // a kernel's options type derives from this and rede
     static constexpr bool bnr = false;         // DS_EPI_BN_RELU: scale / shift read in phase 1, relu(fma) at the store, nothing else (wide)
     static constexpr bool half = false;        // 16-bit storage exists: d.mask_dtype / d.z_dtype are honoured (bf16d)
     static constexpr bool mask_rstd = false;   // d.mask_rstd / mask_shift are honoured (wide, bf16d)
-    static constexpr bool publish = false;     // the `publish` argument is honoured (wide)
 };
 
 // Arguments that differ between callers:
@@ -132,8 +131,7 @@ struct WaveRowOpt {        // a kernel's options type derives from this and rede
 //   trow, P       the workgroup's row tile and the partial count: stats[2][Cout][P];
 //   red           [4][32][2] floats of LDS nothing else uses any more;
 //   wave, li, kh  the kernel's own: wave of the workgroup (uniform), lane & 31, lane >> 5;
-//   scale, shift  bnr;  publish: the partials are read back by another workgroup of THIS launch, so they go out
-//                 write-through (relaxed agent-scope atomic stores).
+//   scale, shift  bnr.
 // Two phases.  (1) per column block: the accumulate / activation reads -- the sixteen of a block requested together -- the
 // sums, the LDS combine (two barriers, with statistics only); results stay in the accumulator registers.  (2) all stores,
 // then the partials.  With the stores of block b in front of the reads of block b + 1 every block cost a memory round trip
@@ -146,7 +144,7 @@ template <int NB, class O>
 __device__ __forceinline__ void wave_row_epilogue(f32x16 (&acc)[NB], const ds_conv_desc &d, float *z, const float *mask, float *stats,
                                                   const float *pivot, bool item, int n0, int mrow0, int Mrow, bool any_row, int trow,
                                                   int P, float *red, int wave, int li, int kh, const float *scale,
-                                                  const float *shift, bool publish) {
+                                                  const float *shift) {
     const int tid = threadIdx.x;
     const int flags = d.flags;
     const bool m16 = O::half && d.mask_dtype == DS_DTYPE_BF16;      // (uniform) BatchNorm-sums activation in bf16 storage
@@ -264,13 +262,8 @@ __device__ __forceinline__ void wave_row_epilogue(f32x16 (&acc)[NB], const ds_co
         if ((flags & (DS_EPI_STATS | DS_EPI_BNSUMS)) && tid < 32 && item && n0 + 32 * b + tid < d.Cout) {
             float *const sp = stats + (int64_t)(n0 + 32 * b + tid) * P + trow;
             float *const qp = stats + ((int64_t)d.Cout + n0 + 32 * b + tid) * P + trow;
-            if (O::publish && publish) {          // (uniform)
-                __hip_atomic_store(reinterpret_cast<unsigned *>(sp), __float_as_uint(pss[b]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(reinterpret_cast<unsigned *>(qp), __float_as_uint(pqq[b]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                *sp = pss[b];
-                *qp = pqq[b];
-            }
+            *sp = pss[b];
+            *qp = pqq[b];
         }
     }
 }

@@ -58,8 +58,6 @@ struct ConvParams {
     int col_total;               // conv_bf16d_kernel: columns of the converted weight tensor (Cout rounded up to 32)
     ds_bn_bwd_on_load bnb;       // gemm_wide_kernel<.., BNB = true>: copy of *d.bnb (the descriptor's pointer is a host pointer)
     int pool_rpb, pool_bpi;      // gemm_wide_kernel<.., POOL = true>: image rows per 32-pixel block, blocks per image
-    ds_bn_finalize_in_launch fin;      // gemm_wide_kernel: copy of *d.fin (fin.ticket == nullptr: the caller finalizes)
-    double fin_inv_count;
     const float *scale, *shift;  // DS_EPI_BN_RELU (the <.., BNR = true> instantiations): Cout floats each
 };
 
@@ -1102,27 +1100,17 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void conv_bf16_kernel(const C
 // With norm_rstd / norm_shift the maximum is taken over the raw z and relu(max * rstd + shift) applied once (rstd > 0), as
 // ds_maxpool_bn_relu_fwd does.  The winners' bytes are the only thing besides z that is written: the pooled tensor
 // (4 B per element out of the pool kernel and 4 B back into this one) never exists.
-// AST > 0 (round 6 experiment): the A operand through an AST-stage LDS-DMA ring instead of registers.  A wave
-// DMAs its own 32 rows x 16 channels of K step ks + AST - 1 (two 1 KB instructions, 16-byte chunks XOR-swizzled on the source
-// side so the fragment reads are conflict-free) while K step ks runs; B is DMA'd AST - 2 steps ahead into AST - 1 buffers.  One
-// in-order memory counter: a step issues its B DMAs first and its A DMAs last, and the step's barrier waits with
-// vmcnt(2 (AST - 2) + DJ (AST - 3)) -- everything but the youngest requests -- so an A tile has AST - 1 K steps to arrive
-// (today: under one).  Same MFMA sequence per output element: bit-identical to the register form.
-template <int N>
-__device__ __forceinline__ void barrier_keep_vm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory"); }
-
 template <bool BNR>
-struct WideEpi : ds::WaveRowOpt { static constexpr bool bnr = BNR, mask_rstd = true, publish = true; };
+struct WideEpi : ds::WaveRowOpt { static constexpr bool bnr = BNR, mask_rstd = true; };
 
-template <int NB, bool BNMAJOR, bool BNB = false, bool POOL = false, int AST = 0, bool BNR = false>      // BNR: DS_EPI_BN_RELU (see conv_igemm_kernel)
+template <int NB, bool BNMAJOR, bool BNB = false, bool POOL = false, bool BNR = false>      // BNR: DS_EPI_BN_RELU (see conv_igemm_kernel)
 __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const ConvParams p) {
     constexpr int BN = NB * 32, WK = 16;                       // K step: 16 channels = two float4 per lane
     constexpr int DJ = (WK * BN / 4 + 255) / 256;              // 16-byte DMA slots per thread per K step: ceil(NB / 2)
     constexpr int BSZ = DJ * 1024;                             // floats per B buffer (odd NB: the last DMA is half used)
-    constexpr int BST = AST > 0 ? AST - 1 : 2;                 // B buffers
-    static_assert(AST == 0 || (AST >= 3 && !BNB && !POOL), "the A ring is built for the plain and the normalising loader");
+    constexpr int BST = 2;                                     // B buffers
     constexpr int PT = 2048;                                   // POOL: floats per centre-row tile (128 pixels x 16 channels)
-    __shared__ __attribute__((aligned(128))) float smem[BST * BSZ + 256 + AST * 2048 + (POOL ? 2 * PT : 0)];
+    __shared__ __attribute__((aligned(128))) float smem[BST * BSZ + 256 + (POOL ? 2 * PT : 0)];
     // BatchNorm + ReLU on load (ds_conv_desc.norm_rstd / norm_shift): rstd and shift of all Cin reduction channels;
     // BNB: rstd, shift, mean, coef[0], coef[1]
     __shared__ __attribute__((aligned(16))) float nrm[BNB ? 5 : 2][1024 + WK];
@@ -1227,7 +1215,7 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
     // with FOUR lanes per pixel (lane -> pixel 16 j + lane / 4, 16-byte chunk lane % 4: one 64-byte sector per quad, where the
     // fragment layout touches four rows per quad and the L1 spends a tag lookup on each), puts it into the tile, and every
     // wave reads its own fragments AND the pixels above and below from there: an input row is fetched once per workgroup.
-    // The four chunks of a pixel are XOR-swizzled by (pixel >> 1) & 3 (conflict-free fragment reads, as in the A ring).
+    // The four chunks of a pixel are XOR-swizzled by (pixel >> 1) & 3 (conflict-free fragment reads).
     float *const ptile = smem + BST * BSZ + 256;
     const int pown = wave * 32 + li, sown = (li >> 1) & 3, sup = (pu >> 1) & 3, sdn = (pd >> 1) & 3;
     unsigned vco[2] = {kOOB, kOOB};
@@ -1281,10 +1269,8 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
     // the A loads of a K step: the lane's fragments, POOL: its two chunks of the tile
     const unsigned va0 = POOL ? vco[0] : voff, va1 = POOL ? vco[1] : voff;
     constexpr int kA1 = POOL ? 0 : 32;
-    if constexpr (AST == 0) {
-        a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, va0, 0, 0));
-        a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, va1, kA1, 0));
-    }
+    a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, va0, 0, 0));
+    a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, va1, kA1, 0));
     if constexpr (POOL) load_halo(0);
     // BNB: the gradient dy of the layer's activation, per channel range its own descriptor and row offset
     const ds_bn_bwd_on_load &bb = p.bnb;
@@ -1312,10 +1298,8 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         d0 = load_dy(0, 0);
         d1 = load_dy(0, 1);
     }
-    if constexpr (AST == 0) {
 #pragma unroll
-        for (int i = 0; i < DJ; ++i) dma_b(0, 0, i);
-    }
+    for (int i = 0; i < DJ; ++i) dma_b(0, 0, i);
     const int ksteps = (K + WK - 1) / WK;
     // x holds pre-BatchNorm conv outputs: the A fragment becomes relu(x * rstd[k] + shift[k]) as it is loaded (two
     // packed multiply-adds and two packed max per float4, against 4 NB MFMAs); channels past Cin get (0, 0) -> 0
@@ -1383,7 +1367,7 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         __builtin_amdgcn_raw_buffer_store_b64(pr, srd_am, vam, c0, 0);
     };
     if constexpr (POOL) pool_step(0, 0, ksteps > 1 ? WK : -1);
-    if (norm && AST == 0) {
+    if (norm) {
         apply_norm(a0, 4 * kh);
         apply_norm(a1, 8 + 4 * kh);
     }
@@ -1391,77 +1375,7 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
         apply_bnb(a0, d0, 4 * kh);
         apply_bnb(a1, d1, 8 + 4 * kh);
     }
-    if constexpr (AST > 0) {
-        // ---- the A ring (see the template's comment) ---------------------------------------------------------------------
-        float *const ring = smem + BST * BSZ + 256;
-        unsigned aoff[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int row = 16 * j + (lane >> 2), chunk = (lane & 3) ^ ((row >> 1) & 3);
-            const int mr = mrow0 + row;
-            aoff[j] = (item && mr < Mw) ? ((unsigned)mr * (unsigned)d.ldx + 4u * chunk) * 4u : kOOB;
-        }
-        auto dma_a = [&](int stage, int c0) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_x, (lds_ptr)(ring + (stage * 4 + wave) * 512 + j * 256), 16, aoff[j], c0 * 4, 0, 0);
-        };
-        auto dma_b_all = [&](int buf, int c0) {
-#pragma unroll
-            for (int i = 0; i < DJ; ++i) dma_b(buf, c0, i);
-        };
-        // requests in the order of the steady state: ..., B(j + AST - 2), A(j + AST - 1), ...
-#pragma unroll
-        for (int j = -(AST - 1); j < 0; ++j) {
-            if (j + AST - 2 >= 0 && j + AST - 2 < ksteps) dma_b_all((j + AST - 2) % BST, (j + AST - 2) * WK);
-            if (j + AST - 1 < ksteps) dma_a((j + AST - 1) % AST, (j + AST - 1) * WK);
-        }
-        constexpr int KEEP = 2 * (AST - 2) + DJ * (AST - 3);
-        if (ksteps > AST - 1) barrier_keep_vm<KEEP>(); else barrier_keep_vm<0>();
-        int bst = 0, ast = 0;
-        const int swz = (li >> 1) & 3;
-        for (int ks = 0; ks < ksteps; ++ks) {
-            const float *ra = ring + (ast * 4 + wave) * 512 + li * 16;
-            a0 = *reinterpret_cast<const f32x4 *>(ra + ((kh ^ swz) * 4));
-            a1 = *reinterpret_cast<const f32x4 *>(ra + (((2 + kh) ^ swz) * 4));
-            if (norm) {
-                apply_norm(a0, ks * WK + 4 * kh);
-                apply_norm(a1, ks * WK + 8 + 4 * kh);
-            }
-            const float *b_s = smem + bst * BSZ;
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                float bf[8];
-                if (BNMAJOR) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        bf[j] = b_s[(4 * kh + j) * BN + 32 * b + li];
-                        bf[4 + j] = b_s[(8 + 4 * kh + j) * BN + 32 * b + li];
-                    }
-                } else {
-                    const int nl = 32 * b + li, sw = (nl >> 2) & 3;
-                    const f32x4 lo = *reinterpret_cast<const f32x4 *>(b_s + nl * 16 + ((kh ^ sw) * 4));
-                    const f32x4 hi = *reinterpret_cast<const f32x4 *>(b_s + nl * 16 + (((2 + kh) ^ sw) * 4));
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { bf[j] = lo[j]; bf[4 + j] = hi[j]; }
-                }
-                if (b == 0) {
-                    if (ks + AST - 2 < ksteps) dma_b_all((bst + AST - 2) % BST, (ks + AST - 2) * WK);
-                    if (ks + AST - 1 < ksteps) dma_a((ast + AST - 1) % AST, (ks + AST - 1) * WK);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], bf[j], acc[b], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], bf[4 + j], acc[b], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (ks + AST - 1 < ksteps) barrier_keep_vm<KEEP>(); else barrier_keep_vm<0>();
-            bst = bst + 1 == BST ? 0 : bst + 1;
-            ast = ast + 1 == AST ? 0 : ast + 1;
-        }
-    }
-    for (int ks = 0; AST == 0 && ks < ksteps; ++ks) {
+    for (int ks = 0; ks < ksteps; ++ks) {
         const bool more = ks + 1 < ksteps;
         const int cn = (ks + 1) * WK;
         const float *b_s = smem + (ks & 1) * BSZ;
@@ -1529,30 +1443,10 @@ __global__ __launch_bounds__(256, NB <= 4 ? 3 : 2) void gemm_wide_kernel(const C
     // ---- epilogue (conv_epilogue.h): store, BatchNorm column statistics ------------------------------------------------
     // POOL: the row bound is this wave's last real row (Mw, wave-uniform), so the rows a 28-pixel block leaves unused -- they
     // would alias the NEXT block's pixels -- are dropped by the same range check as the rows past M; a surplus wave past the
-    // last image has no row.  fin: the partials are read back by another workgroup of THIS launch.
-    const int flags = d.flags;
+    // last image has no row.
     float *red = smem + BST * BSZ;
     ds::wave_row_epilogue<NB, WideEpi<BNR>>(acc, d, p.z, p.mask, p.stats, p.pivot, item, n0, mrow0, Mw, Mw > mrow0, t0.row, t0.stride,
-                                            red, wave, li, kh, p.scale, p.shift, p.fin.ticket != nullptr);
-    // ds_bn_finalize inside the launch (ds_conv_desc.fin): the last workgroup of a column tile to publish its partials
-    // finalizes the tile's columns -- one wave per column, bn_finalize_kernel's summation tree (ds_common.h) -- so the
-    // dependent ds_bn_finalize launch disappears.  Hand-off as in lstm_seq.hip: write-through payload, every storing wave
-    // drained, ONE relaxed agent-scope increment; no fence (a fence would write back the XCD's whole L2, z included).
-    if (p.fin.ticket && item && (flags & DS_EPI_STATS)) {
-        __builtin_amdgcn_s_waitcnt(0);          // this wave's partial stores are acknowledged
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned old = __hip_atomic_fetch_add(p.fin.ticket + t0.col, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            red[0] = old + 1 == (unsigned)p.row_tiles ? 1.f : 0.f;
-        }
-        __syncthreads();
-        if (red[0] != 0.f) {                     // (uniform)
-            const int cend = min(n0 + BN, d.Cout);
-            for (int c = n0 + wave; c < cend; c += 4)
-                ds::bn_finalize_channel_by_wave(p.stats, t0.stride, d.Cout, c, p.fin_inv_count, p.fin, p.pivot);
-            if (tid == 0) __hip_atomic_store(p.fin.ticket + t0.col, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+                                            red, wave, li, kh, p.scale, p.shift);
 }
 
 
@@ -1742,7 +1636,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16d_kernel(const ConvParams p) 
 
     // ---- epilogue (conv_epilogue.h): store, BatchNorm column statistics; 16-bit z / activation storage per launch ---------
     ds::wave_row_epilogue<NB, Bf16dEpi>(acc, d, p.z, p.mask, p.stats, p.pivot, item, n0, t0.row * 128 + wave * 32, p.M, true, t0.row,
-                                        t0.stride, reinterpret_cast<float *>(smem + 2 * BSZ), wave, li, kh, nullptr, nullptr, false);
+                                        t0.stride, reinterpret_cast<float *>(smem + 2 * BSZ), wave, li, kh, nullptr, nullptr);
 }
 
 // wb[it][column][16] bf16, it = chunk * taps + tap, from the TF HWIO filter w [taps][Cin][Cout] (fp32).
@@ -1819,7 +1713,6 @@ struct Tuning {
     int wide_cost = 0;        // DS_WIDE_COST: the A fetch in wide_nb's cost, in halves of a block
     int wide_nb = 0;          // DS_WIDE_NB pins the wide kernel's column blocks per wave
     int wide_min_wgs = 128;   // DS_WIDE_MINWGS (see wide_nb)
-    int wide_ring = 0;        // DS_WIDE_RING = 3 / 4: the LDS-DMA ring instantiations (see kernel_of)
     int mt = 0, nt = 0;       // DS_CONV_CFG="mt,nt" / ds_debug_conv_set_tile pin the tile
     int path = 0;             // DS_CONV_PATH=lds|direct|glds / ds_debug_conv_set_path pin the kernel family: 1 / 2 / 3
     int prio = 0;             // DS_CONV_PRIO; opt-in: measured neutral-to-negative (profiles/r01_notes.md)
@@ -1837,7 +1730,6 @@ Tuning &tuning() {
         knob("DS_WIDE_COST", &t.wide_cost);
         knob("DS_WIDE_NB", &t.wide_nb);
         knob("DS_WIDE_MINWGS", &t.wide_min_wgs);
-        knob("DS_WIDE_RING", &t.wide_ring);
         knob("DS_CONV_PRIO", &t.prio);
         knob("DS_CONV_XCD_REMAP", &t.xcd_remap);
         if (const char *e = ds::tune_env("DS_CONV_CFG")) sscanf(e, "%d,%d", &t.mt, &t.nt);
@@ -1895,27 +1787,13 @@ KernelFn kernel_of(const Launch &L) {
     if (c.wide) {
         if (L.bnr) {          // (bnr_ok: forward, no bnb)
             if (L.pool)
-                return with_const<1, 4>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, true, false, true, 0, true>; });
-            return with_const<1, 8>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, true, false, false, 0, true>; });
+                return with_const<1, 4>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, true, false, true, true>; });
+            return with_const<1, 8>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, true, false, false, true>; });
         }
         if (L.pool)          // (pool3_nb: forward, one column tile of at most four blocks)
             return with_const<1, 4>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, true, false, true>; });
         if (L.bnb)          // (wide_nb: at most two column blocks per wave with ds_conv_desc.bnb)
             return with_const<1, 2>(c.wide, [](auto nb) { return gemm_wide_kernel<decltype(nb)::value, false, true>; });
-        // round-6 experiment (tuning build only: DS_WIDE_RING = 3 / 4): the A operand through an LDS-DMA ring, NB = 2 .. 4.
-        // Bit-identical and SLOWER on the sixteen 1x1 shapes of the step (profiles/r06_wide_ring.txt: forward with statistics
-        // 1705 -> 1804 us at three stages / 1957 at four, dgrad with accumulate + sums 2138 -> 2172 / 2482): the ring's LDS caps
-        // the kernel at three (two) workgroups per CU where the register form runs seven waves per SIMD -- it lives on occupancy
-#ifdef DS_TUNING
-        const int ring = tuning().wide_ring;
-        if ((ring == 3 || ring == 4) && c.wide >= 2 && c.wide <= 4)
-            return with_const<2, 4>(c.wide, [&](auto nb) {
-                return with_const<3, 4>(ring, [&](auto ast) {
-                    return v.bnmajor ? gemm_wide_kernel<decltype(nb)::value, true, false, false, decltype(ast)::value>
-                                     : gemm_wide_kernel<decltype(nb)::value, false, false, false, decltype(ast)::value>;
-                });
-            });
-#endif
         return with_const<1, 8>(c.wide, [&](auto nb) {
             return v.bnmajor ? gemm_wide_kernel<decltype(nb)::value, true> : gemm_wide_kernel<decltype(nb)::value, false>;
         });
@@ -2141,7 +2019,7 @@ Launch choose(const ds_conv_desc *d, bool aligned, Ask ask = kAsIs) {
 // Would the launch picked for `d` carry DS_EPI_BN_RELU?  The forward fp32 instantiations: n-contiguous weights, 16-byte loads
 // (pointer alignment is checked at launch), 128-row tiles of the LDS / LDS-DMA kernels or the wide 1x1 kernel.
 bool bnr_ok(const ds_conv_desc *d, const Launch &L) {
-    if (d->dtype != DS_DTYPE_F32 || !L.v.bnmajor || !L.v.vec || L.v.fold || d->splits > 1 || d->bnb || d->fin) return false;
+    if (d->dtype != DS_DTYPE_F32 || !L.v.bnmajor || !L.v.vec || L.v.fold || d->splits > 1 || d->bnb) return false;
     return !L.c.bf16 && !L.c.direct && L.c.mt == 1;
 }
 
@@ -2227,14 +2105,6 @@ int igemm_launch(const ds_conv_desc *d, const float *x, const float *w, float *z
         }
         p.bnb = b;
     }
-    if (d->fin) {
-        DS_REQUIRE(c.wide && (d->flags & DS_EPI_STATS) && L.row_tiles <= 256 && d->fin->ticket && d->fin->beta && d->fin->mean &&
-                       d->fin->rstd && d->fin->shift && d->fin->count > 0,
-                   "ds_conv_igemm: ds_conv_desc.fin needs a DS_EPI_STATS launch of the wide 1x1 kernel with at most 256 partials "
-                   "(ds_conv_igemm_finalize_tickets) and beta / mean / rstd / shift / ticket / count");
-        p.fin = *d->fin;
-        p.fin_inv_count = 1.0 / (double)d->fin->count;
-    }
     if (d->pool_argmax) {
         DS_REQUIRE(c.wide && v.bnmajor && !d->bnb,
                    "ds_conv_igemm: ds_conv_desc.pool_argmax is implemented by the wide 1x1 kernel's forward instantiation only "
@@ -2299,17 +2169,6 @@ extern "C" int ds_conv_igemm_pool3_supported(const ds_conv_desc *d) {
     return choose(d, true, kBeforePool).c.wide > 0 ? 1 : 0;
 }
 
-extern "C" int ds_conv_igemm_finalize_tickets(const ds_conv_desc *d) {
-    // ds_bn_finalize inside the launch lives in the wide 1x1 kernel's epilogue: DS_EPI_STATS launches with at most 256
-    // partials per channel (one wave re-reads a column's partials with four loads per lane)
-    if (!d || !(d->flags & DS_EPI_STATS)) return 0;
-    ds_conv_desc t = *d;
-    t.partials = 0;
-    t.fin = nullptr;
-    const Launch L = choose(&t, true);
-    return L.c.wide && L.row_tiles <= 256 ? L.gy : 0;
-}
-
 // ds_conv_plan_enable_bn_relu's question for this family: would the launch picked for `d` carry DS_EPI_BN_RELU?  (forward
 // fp32: n-contiguous weights, strides and channel counts divisible by 4, LDS-tile / LDS-DMA / wide 1x1 kernel, with or
 // without pool_argmax; the kernel and tile are the ones the same descriptor gets without the flag)
@@ -2359,7 +2218,7 @@ extern "C" int ds_gemm_group(const ds_conv_desc *const *descs, const float *cons
         DS_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->N > 0 && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->H == 1 && d->W == 1 &&
                        d->OH == 1 && d->OW == 1 && d->pad_t == 0 && d->pad_l == 0 && d->fold_cin == 0 && d->flip == 0,
                    "ds_gemm_group: problem %d is not a plain GEMM", i);
-        DS_REQUIRE(d->dtype == DS_DTYPE_F32 && d->flags == 0 && !d->bnb && !d->fin && !d->norm_rstd && !d->norm_shift &&
+        DS_REQUIRE(d->dtype == DS_DTYPE_F32 && d->flags == 0 && !d->bnb && !d->norm_rstd && !d->norm_shift &&
                        !d->mask_rstd && !d->mask_shift && !d->pool_argmax,
                    "ds_gemm_group: problem %d: fp32 without epilogue flags or on-load operands (combine with ds_slab_epilogue_group)", i);
         DS_REQUIRE(d->w_n_stride == 1 || d->w_k_stride == 1, "ds_gemm_group: one weight stride must be 1");

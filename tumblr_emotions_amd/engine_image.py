@@ -181,19 +181,6 @@ class ConvBN:
     def zshift(self):
         return self.shift_c if self.z16 else self.shift
 
-    def plan_finalize(self):
-        """ds_bn_finalize inside the forward conv launch where the library can (wide 1x1 kernel, at most 256 partials: the
-        small per-GPU batches, where a dependent launch costs more than its work).  Called once the plan is final
-        (MixedStage.alloc may still switch Branch_3's conv to the pooling loader)."""
-        eng = self.eng
-        self.fin = None
-        n = self.fwd.finalize_tickets() if eng.fuse_finalize else 0
-        if n > 0:
-            self.fin_tickets = torch.zeros(n, dtype=torch.int32, device=eng.device)
-            f = _lib.BnFinalizeInLaunch()
-            f.ticket, f.eps, f.decay = self.fin_tickets.data_ptr(), BN_EPS, BN_DECAY
-            self.fin = f
-
     def bind(self):
         st = self.eng.store
         self.w_ptr = _vp(st.ptr(self.key + "/weights"))
@@ -206,10 +193,6 @@ class ConvBN:
         for plan in (self.fwd, self.dgrad):          # split-K Winograd launches: the slices' partial outputs
             if plan is not None and plan.ws_bytes:
                 plan.set_workspace(eng.cws_set[self.slot])
-        self.plan_finalize()
-        if self.fin is not None:
-            f = self.fin
-            f.beta, f.mean, f.rstd, f.shift = self.beta.data_ptr(), self.mean.data_ptr(), self.rstd.data_ptr(), self.shift.data_ptr()
         self.gw_ptr = _vp(st.grad_ptr(self.key + "/weights")) if self.trainable else None
         self.gbeta = st.grad_view(self.key + "/BatchNorm/beta") if self.eng.trainable_bn_beta else None
 
@@ -449,19 +432,12 @@ class ConvBN:
             # the column sums are taken about a pivot near the mean -- the previous step's batch mean, the
             # moving mean before the first step (bind) -- so channels with |mean| >> std keep their variance
             plan.d.flags = DS_EPI_STATS
-            fin = None
-            if self.fin is not None and not eng.sync_bn:      # ds_bn_finalize runs inside the conv launch (plan_finalize)
-                f = self.fin
-                f.count = self.M
-                f.moving_mean = self.mm.data_ptr() if eng.update_moving else None
-                f.moving_var = self.mv.data_ptr() if eng.update_moving else None
-                fin = C.addressof(f)
-            plan.run(x_ptr, self.w_ptr, ops._p(self.z), stats=ops._p(self.stats_buf), pivot=ops._p(self.mean), x_amax=amax_p, fin=fin)
+            plan.run(x_ptr, self.w_ptr, ops._p(self.z), stats=ops._p(self.stats_buf), pivot=ops._p(self.mean), x_amax=amax_p)
             count = self.M
             if eng.sync_bn:       # statistics of the GLOBAL batch: every rank's partials are about the same pivot, so they add
                 eng.all_reduce(self.stats_buf[:2 * self.cout * plan.partials])
                 count = self.M * eng.sync_world
-            if fin is None and not defer_finalize:
+            if not defer_finalize:
                 mm, mv = (self.mm, self.mv) if eng.update_moving else (None, None)
                 if self.z16:
                     ops.bn_finalize_centered(self.stats_buf, plan.partials, count, self.cout, self.beta, BN_EPS, BN_DECAY, self.mean,
@@ -1079,10 +1055,9 @@ class MixedStage(Stage):
             ops.maxpool_fwd(p.out, self.pooled, self.argmax, self.B, p.H, p.W, p.C, 3, 1, "SAME")
 
     def _batch_forward(self):
-        """One ds_bn_finalize_multi for the block-closing layers?  (training with per-rank statistics, no in-launch finalize)"""
+        """One ds_bn_finalize_multi for the block-closing layers?  (training with per-rank statistics)"""
         eng = self.eng
-        return bool((self.batch_bn & 1) and eng.batch_stats and not eng.sync_bn
-                    and all(l.fin is None for l in (self.c1, self.c2, self.c3)))
+        return bool((self.batch_bn & 1) and eng.batch_stats and not eng.sync_bn)
 
     def _finalize_closing(self):
         eng = self.eng
@@ -1292,11 +1267,6 @@ class InceptionV1Engine:
         # shapes, the two MaxPoolGrad launches (0.18 ms alone on the chip, profiles/r06h_timeline.txt) off the chain.  The step-time
         # effect is NOT measured yet (profiles/pool_apply_notes.md says what is and what is not).  DS_POOL_APPLY=0: A/B
         self.pool_apply = _lib.tuning_env("DS_POOL_APPLY", "1") != "0"
-        # ds_bn_finalize inside the conv launch where the library can (ConvBN.plan_finalize; ds_conv_desc.fin).  Built, bit-identical
-        # (tests), measured, OFF: the last arriver of a column tile re-reads up to 256 columns x 196 partials alone while the
-        # separate launch spreads them over one workgroup per channel -- B = 32: 3.89 -> 4.36 ms, B = 64: 5.29 -> 5.59
-        # (profiles/r06_notes.md).  DS_FUSE_FIN=1 switches it on (A/B)
-        self.fuse_finalize = _lib.tuning_env("DS_FUSE_FIN", "0") == "1"
         # zcat blocks: the BatchNorm launches of the three block-closing layers once per block (MixedStage.alloc); DS_BATCH_BN=0: A/B
         # bit 0: the forward finalizes, bit 1: the backward finalize + apply; None = by batch size (MixedStage.alloc)
         e = _lib.tuning_env("DS_BATCH_BN")
