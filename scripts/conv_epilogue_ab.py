@@ -4,11 +4,11 @@
     DS_LIB=<a libds_kernels_tuning.so> python scripts/conv_epilogue_ab.py run OUT.json [--no-digest] [--no-time] [--small] [--only=SUBSTRING]
     python scripts/conv_epilogue_ab.py compare OUT.json PARENT.json TREE.json [PARENT2.json TREE2.json ...]
 
-`run` walks a fixed, seeded case list -- each of the seven kernels with every epilogue its entry point accepts -- and writes,
+`run` walks a fixed, seeded case list -- each of the six kernels with every epilogue its entry point accepts -- and writes,
 per case, a SHA-256 of every output buffer and an event-timed median.  Each combination runs at the smallest shape that
 reaches every guard (1x1, M = 165, Cin = 32, Cout = 40, ldz = ldmask = 48: in the second row tile wave 0 is full, wave 1
 has 5 rows, waves 2-3 none, and column block 1 is partial), one 3x3 case per kernel that takes 3x3, and the B = 256 1x1
-shapes of scripts/wide_epi_bench.py for the timing.  `compare`: equal digests, and the second build's median per timed case
+shapes of scripts/wide_epi_bench.py for the timing.  `compare`: equal digests on the cases both builds have, and the second build's median per timed case
 inside the range of the first build's window medians."""
 import ast
 import hashlib
@@ -28,10 +28,13 @@ SMALL = (165, 32, 40, 48)          # M, K, N, ldz = ldmask
 def compare(out, files):
     runs = [json.load(open(f)) for f in files]
     a, b = runs[0::2], runs[1::2]
-    res = {"digest_mismatch": [], "slower": [], "timed_cases": 0, "cases": len(a[0]["cases"])}
+    res = {"digest_mismatch": [], "only_in_first": [], "slower": [], "timed_cases": 0, "cases": len(a[0]["cases"])}
     for name, ca in a[0]["cases"].items():
         cb = b[0]["cases"].get(name)
-        if cb is None or ca.get("sha256") != cb.get("sha256") or ca.get("skipped") != cb.get("skipped"):
+        if cb is None:          # a case of a kernel the second build no longer has
+            res["only_in_first"].append(name)
+            continue
+        if ca.get("sha256") != cb.get("sha256") or ca.get("skipped") != cb.get("skipped"):
             res["digest_mismatch"].append(name)
         if not ca.get("timed") or ca.get("skipped") or "us" not in ca:
             continue
@@ -41,7 +44,8 @@ def compare(out, files):
         med = tb[len(tb) // 2] if len(tb) % 2 else 0.5 * (tb[len(tb) // 2 - 1] + tb[len(tb) // 2])
         if med > max(ta):
             res["slower"].append({"case": name, "first": ta, "second": tb})
-    tot = lambda rs: [round(sum(c["us"] for c in r["cases"].values() if c.get("timed") and "us" in c), 1) for r in rs]
+    both = set(a[0]["cases"]) & set(b[0]["cases"])
+    tot = lambda rs: [round(sum(c["us"] for n, c in r["cases"].items() if n in both and c.get("timed") and "us" in c), 1) for r in rs]
     res["total_us_first"], res["total_us_second"] = tot(a), tot(b)
     res["libs"] = [r["lib"] for r in runs]
     json.dump(res, open(out, "w"), indent=1)
@@ -106,14 +110,14 @@ def main():
             r["us"] = round(sorted(samples)[3], 2)
         results[name] = r
 
-    # ---- the four tile kernels, through ds_conv_igemm ------------------------------------------------------------------------
+    # ---- the three tile kernels, through ds_conv_igemm ------------------------------------------------------------------------
     TILE = {"0": 0, "BIAS": E.DS_EPI_BIAS, "BIAS|RELU": E.DS_EPI_BIAS | E.DS_EPI_RELU, "ACCUM": E.DS_EPI_ACCUM,
             "MASK": E.DS_EPI_MASK, "STATS+pivot": E.DS_EPI_STATS}
 
     def tile_case(kern, combo, geom, mt=1):
         """geom: (N, H, W, Cin, Cout, k, ldz)"""
         N, H, W, K, Nc, k, ld = geom
-        path, dtype = {"lds": (1, E.DS_DTYPE_F32), "direct": (2, E.DS_DTYPE_F32), "glds": (3, E.DS_DTYPE_F32), "bf16t": (0, E.DS_DTYPE_BF16)}[kern]
+        path, dtype = {"lds": (1, E.DS_DTYPE_F32), "glds": (3, E.DS_DTYPE_F32), "bf16t": (0, E.DS_DTYPE_BF16)}[kern]
 
         def build():
             pin(path, 0, mt, 2)
@@ -238,14 +242,14 @@ def main():
     ROWD = {"bf16d": ["0", "STATS+pivot", "ACCUM", "ACCUM|BNSUMS", "m16", "z16"],
             "x3": ["0", "STATS+pivot", "ACCUM|BNSUMS", "ACCUM|BNSUMS+mask_rstd"],
             "fp8d": ["0", "STATS+pivot", "ACCUM", "ACCUM|BNSUMS", "m16", "z16"]}
-    TILES = {"lds": list(TILE) + ["BNR"], "direct": list(TILE), "glds": list(TILE) + ["BNR"], "bf16t": list(TILE)}
+    TILES = {"lds": list(TILE) + ["BNR"], "glds": list(TILE) + ["BNR"], "bf16t": list(TILE)}
     g3 = (1, 8, 8, 16, 40, 3, 48)
     M, K, Nc, ld = SMALL
     try:
         for kern, combos in TILES.items():
             for combo in combos:
                 record("small/%s/%s" % (kern, combo), False, tile_case(kern, combo, (M, 1, 1, K, Nc, 1, ld)))
-                if kern in ("lds", "direct") and combo != "BNR":          # the 256-row (64-row) tiles: the MT loop
+                if kern == "lds" and combo != "BNR":          # the 256-row tile: the MT loop
                     record("small/%s-mt2/%s" % (kern, combo), False, tile_case(kern, combo, (M, 1, 1, K, Nc, 1, ld), mt=2))
             record("3x3/%s/STATS+pivot" % kern, False, tile_case(kern, "STATS+pivot", g3))
         for combo in WIDE:

@@ -17,7 +17,7 @@ and what ds_conv_plan_enable_bnsums / _enable_pool3 / _enable_bn_relu / _norm_su
 partial counts they leave in the plan); through a raw ds_conv_desc: the five ds_conv_igemm_* answers without
 flags and with DS_EPI_STATS.  Of the product library the raw answers and the f32 plan are stored in full and the bf16 / fp8 /
 f32x3 plans as one sha256 prefix each.  The tuning library answers the same under ds_debug_conv_set_wide 0 / 1 / 2, set_path
-1 / 3 and set_tile (1,1) .. (2,6) -- not path 2, whose grid always comes from the occupancy query; of those, one sha256 prefix
+1 / 3 (the two families it pins) and set_tile (1,1) .. (2,6); of those, one sha256 prefix
 per shape (all its N) is stored, in the order of shapes().  That keeps the file under 200 KB."""
 import ctypes as C
 import hashlib

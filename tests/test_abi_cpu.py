@@ -35,7 +35,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     for n in names:
         assert hasattr(dll, n), "libds_kernels.so lacks %s" % n
     assert sorted(lib.SIGNATURES) == names, "ctypes table and header disagree"
-    assert lib.load().ds_version() >= 1
+    assert lib.load().ds_version() == 4
 
 
 def test_shipped_library_exports_only_the_contract_and_reads_no_environment(lib):
@@ -56,6 +56,11 @@ def test_shipped_library_exports_only_the_contract_and_reads_no_environment(lib)
     t = lib.load_tuning()
     assert t.ds_debug_conv_set_tile(3, 1) == -1 and t.ds_debug_conv_set_tile(0, 0) == 0
     assert not hasattr(ctypes.CDLL(lib.LIB_PATH), "ds_debug_conv_set_tile")
+    # the retired register-direct family: its number is refused, the two kept families and automatic are not
+    assert t.ds_debug_conv_set_path(2) != 0 and b"ds_debug_conv_set_path" in t.ds_last_error()
+    assert t.ds_debug_conv_set_path(1) == 0 and t.ds_debug_conv_set_path(3) == 0 and t.ds_debug_conv_set_path(0) == 0
+    for path in (lib.LIB_PATH, lib.TUNING_LIB_PATH):          # (retired with ds_version() 4)
+        assert not hasattr(ctypes.CDLL(path), "ds_maxpool3_bwd_dy16")
 
 
 def test_python_engine_switches_are_inert_beside_the_product_library(lib, monkeypatch):
@@ -79,6 +84,14 @@ def test_errors_are_reported_not_thrown(lib):
     l = lib.load()
     assert l.ds_gather_rows(None, None, None, 1, 1, 1, 1, 1, None) == -1          # DS_ERR_ARG
     assert b"ds_gather_rows" in l.ds_last_error()
+    # the max-pool gradients read dy as floats: another storage type is refused in Python, before any library call
+    import torch
+    from tumblr_emotions_amd import ops
+    dy, am, dx = torch.zeros(1, 1, 1, 4, dtype=torch.bfloat16), torch.zeros(1, 1, 1, 4, dtype=torch.uint8), torch.zeros(1, 1, 1, 4)
+    with pytest.raises(ValueError, match="fp32"):
+        ops.maxpool_bwd(dy, am, dx, False, 1, 1, 1, 4, 3, 1, "SAME")
+    with pytest.raises(ValueError, match="fp32"):
+        ops.maxpool3_bwd_sums(dy, am, dx, False, torch.zeros(1, 1, 1, 4), 1, 1, 1, 4, torch.zeros(2, 4, 1))
 
 
 def test_product_path_has_no_cpu_fallback(lib):

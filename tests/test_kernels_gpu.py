@@ -948,52 +948,6 @@ def test_max_pool_gradient_that_also_emits_the_batch_norm_sums(case):
         assert np.abs(q_got - q_ref).max() <= 2e-6 * scale_q, np.abs(q_got - q_ref).max() / scale_q
 
 
-@pytest.mark.parametrize("case", [(4, 14, 14, 480), (2, 28, 28, 192), (9, 7, 7, 832), (3, 6, 5, 12)])
-def test_max_pool_gradient_reading_bf16_storage_and_a_dgrad_writing_it(case):
-    """ds_maxpool3_bwd_dy16 + ds_conv_desc.z_dtype on a Conv2DBackpropInput launch (round 6, 16-bit labels, off in the engine:
-    no time gain): Branch_3's 1x1 dgrad writes its output rounded to bf16 and the 3x3 / 1 MaxPoolGrad reads that storage.  The
-    pool gradient (plain and accumulating, and with the BatchNorm sums) has the bits of ds_maxpool_bwd / ds_maxpool3_bwd_sums
-    on the same values in fp32; the dgrad's bf16 output is its fp32 output rounded to nearest even."""
-    ops = _ops()
-    N, H, W, Cc = case
-    rng = np.random.RandomState(N * 7 + Cc)
-    x = torch.from_numpy(rng.normal(size=(N, H, W, Cc)).astype(np.float32)).cuda()
-    pooled, am = torch.empty_like(x), torch.empty(N, H, W, Cc, dtype=torch.uint8, device="cuda")
-    ops.maxpool_fwd(x, pooled, am, N, H, W, Cc, 3, 1, "SAME")
-    dy16 = torch.from_numpy(rng.normal(size=(N, H, W, Cc)).astype(np.float32)).cuda().to(torch.bfloat16)
-    dy32 = dy16.float()
-    base = torch.from_numpy(rng.normal(size=(N, H, W, Cc)).astype(np.float32)).cuda()
-    y = torch.relu(torch.from_numpy(rng.normal(size=(N, H, W, Cc)).astype(np.float32)).cuda()).to(torch.bfloat16)
-    P = ops.maxpool3_bwd_sums_partials(N, W, Cc)
-    for acc in (True, False):
-        a, b = base.clone(), base.clone()
-        ops.maxpool_bwd(dy32, am, a, acc, N, H, W, Cc, 3, 1, "SAME")
-        ops.maxpool_bwd(dy16, am, b, acc, N, H, W, Cc, 3, 1, "SAME")
-        pa, pb = torch.zeros(2, Cc, P, device="cuda"), torch.zeros(2, Cc, P, device="cuda")
-        c, d = base.clone(), base.clone()
-        ops.maxpool3_bwd_sums(dy32, am, c, acc, y, N, H, W, Cc, pa)
-        ops.maxpool3_bwd_sums(dy16, am, d, acc, y, N, H, W, Cc, pb)
-        torch.cuda.synchronize()
-        assert torch.equal(a, b) and torch.equal(c, d) and torch.equal(a, c) and torch.equal(pa, pb)
-    if Cc % 16 == 0:
-        Ci = 64          # a 1x1 dgrad [M, Ci] -> [M, Cc] on the register-direct bf16 kernel, fp32 and bf16 output
-        M = N * H * W
-        w = torch.from_numpy((rng.normal(size=(1, 1, Cc, Ci)) * 0.05).astype(np.float32)).cuda()
-        dz = torch.from_numpy(rng.normal(size=(M, Ci)).astype(np.float32)).cuda()
-        outs = []
-        for o16 in (False, True):
-            pl = ops.LayerPlan(ops.DS_CONV_DGRAD, ops.DS_ARITH_BF16, ops.DS_PLAN_ACT16, N, H, W, Cc, Ci, 1, 1, Ci, Cc, 0)
-            assert pl.family == ops.DS_FAM_BF16D
-            pl.alloc_weights(x.device)
-            pl.prepare(ops._p(w))
-            out = torch.zeros(M, Cc, device="cuda", dtype=torch.bfloat16 if o16 else torch.float32)
-            pl.d.z_dtype = ops.DS_DTYPE_BF16 if o16 else ops.DS_DTYPE_F32
-            pl.run(ops._p(dz), ops._p(w), ops._p(out))
-            torch.cuda.synchronize()
-            outs.append(out)
-        assert torch.equal(outs[1], outs[0].to(torch.bfloat16)) and float(outs[0].abs().max()) > 0
-
-
 def _fp8_round(a, fmax, mant, emin):
     """saturating round-to-nearest-even to an OCP fp8 format (e4m3fn: 448, 3, -6; e5m2: 57344, 2, -14), as float64"""
     a = np.asarray(a, np.float64)
@@ -1493,6 +1447,31 @@ def test_conv_bf16_register_direct_forward_dgrad_match_oracle(case):
             g2.run(ops._p(dyd), ops._p(wbt), ops._p(out), stats=ops._p(sums), mask=ops._p(mask))
             return sums, P
         _check_accum_bnsums_epilogue(run, dref, g.M, Ci, rng, 2e-4)
+
+
+def test_a_dgrad_plan_refuses_bf16_output_storage():
+    """ds_conv_desc.z_dtype = DS_DTYPE_BF16 is a forward layer's centred storage: ds_conv_run refuses it on a
+    Conv2DBackpropInput plan before any launch, and the same plan with fp32 output is the fp64 dgrad of the bf16-rounded
+    operands."""
+    ops = _ops()
+    N, H, W, Ci, Co = 1, 4, 4, 16, 64
+    rng = np.random.RandomState(11)
+    w = rng.normal(size=(1, 1, Ci, Co)) * 0.1
+    dy = rng.normal(size=(N, H, W, Co))
+    wd, dyd = dev(w), dev(dy)
+    pl = ops.LayerPlan(ops.DS_CONV_DGRAD, ops.DS_ARITH_BF16, ops.DS_PLAN_ACT16, N, H, W, Ci, Co, 1, 1, Co, Ci)
+    pl.alloc_weights(wd.device)
+    pl.prepare(ops._p(wd))
+    dx = torch.zeros(pl.M, Ci, device="cuda")
+    pl.d.z_dtype = ops.DS_DTYPE_BF16
+    with pytest.raises(RuntimeError, match="ds_conv_run"):
+        pl.run(ops._p(dyd), ops._p(wd), ops._p(dx))
+    torch.cuda.synchronize()
+    assert float(dx.abs().max()) == 0          # nothing was launched
+    pl.d.z_dtype = ops.DS_DTYPE_F32
+    pl.run(ops._p(dyd), ops._p(wd), ops._p(dx))
+    torch.cuda.synchronize()
+    close(dx, S.conv2d_same_bwd_input(_bf16_round(dy), _bf16_round(w), (N, H, W, Ci), 1).reshape(-1, Ci), 2e-4)
 
 
 def test_conv_bf16_folded_stem_and_epilogues():
@@ -2179,8 +2158,8 @@ def test_softmax_ce_and_adam_and_reductions():
 
 
 def test_every_conv_instantiation_matches_the_oracle(tuning_lib):
-    """All tile shapes of the three kernel families (register-staged LDS: mt 1-2 x nt 1-6; register-direct:
-    mt 1-2 x nt 1-4; LDS-DMA with the 32-deep K-tile: nt 1-3), forward (n-contiguous weights, BN statistics) and dgrad (k-contiguous, flipped taps), on a
+    """All tile shapes of the two kernel families (register-staged LDS: mt 1-2 x nt 1-6; LDS-DMA with the 32-deep K-tile:
+    nt 1-3), forward (n-contiguous weights, BN statistics) and dgrad (k-contiguous, flipped taps), on a
     shape with ragged M, a K tail and a partial last column tile -- reached through the tuning knobs."""
     ops = _ops()
     from tumblr_emotions_amd import _lib
@@ -2194,7 +2173,7 @@ def test_every_conv_instantiation_matches_the_oracle(tuning_lib):
     dgr_ref = S.conv2d_same_bwd_input(dy, w, (N, H, W, Ci), 1).reshape(-1, Ci)
     xd, wd, dyd = dev(x), dev(w), dev(dy)
     try:
-        for path, nts in ((1, range(1, 7)), (2, range(1, 5)), (3, range(1, 4))):
+        for path, nts in ((1, range(1, 7)), (3, range(1, 4))):
             for mt in (1, 2):
                 for nt in nts:
                     assert lib.ds_debug_conv_set_path(path) == 0 and lib.ds_debug_conv_set_tile(mt, nt) == 0
@@ -2297,11 +2276,11 @@ def _epilogue_operands():
 
 
 @pytest.mark.parametrize("combo", ["BIAS", "BIAS|RELU", "ACCUM", "MASK", "STATS+pivot"])
-@pytest.mark.parametrize("path", [2, 3], ids=["direct", "glds"])
-def test_tile_epilogue_combinations_of_the_pinned_direct_and_lds_dma_kernels(path, combo, tuning_lib):
-    """conv_direct_kernel (path 2) and conv_glds_kernel (path 3), pinned at the 128 x 64 tile, with the epilogue flags the
+@pytest.mark.parametrize("path", [3], ids=["glds"])
+def test_tile_epilogue_combinations_of_the_pinned_lds_dma_kernel(path, combo, tuning_lib):
+    """conv_glds_kernel (path 3), pinned at the 128 x 64 tile, with the epilogue flags the
     sweeps above run on the register-staged kernel only.  Tolerances: those of test_every_conv_instantiation_matches_the_oracle,
-    the test that pins these two kernels -- z 2e-4 of max|ref|, column sums 1e-3 of max|sum| + 1e-3 (partials summed over P in
+    the test that pins this kernel -- z 2e-4 of max|ref|, column sums 1e-3 of max|sum| + 1e-3 (partials summed over P in
     fp64, about the pivot; the sum of squares against the same bound of its own reference)."""
     ops = _ops()
     from tumblr_emotions_amd import _lib

@@ -176,37 +176,30 @@ def test_max_pool_gradient_against_the_oracle_on_every_dispatch_branch(case, kin
 
 @pytest.mark.parametrize("case", POOL3S1, ids=_id)
 def test_max_pool_gradient_variants_equal_the_anchored_one_on_ties(case):
-    """ds_maxpool3_bwd_sums (fp32 and bf16 y) and ds_maxpool3_bwd_dy16 (plain and with the sums) are bit-identical to
-    ds_maxpool_bwd -- which the test above anchors -- on winners decided by ties."""
+    """ds_maxpool3_bwd_sums (fp32 and bf16 y) is bit-identical to ds_maxpool_bwd -- which the test above anchors -- on
+    winners decided by ties."""
     ops = _ops()
     k, s, mode, (N, H, W, Cc) = case
     x, _, arg_ref = plain_reference(case, "ties", "f32")
     pooled, am = run_fwd(ops, x, case, "f32")
     assert np.array_equal(am.cpu().numpy(), arg_ref)
     rng = np.random.RandomState(6)
-    dy16 = dev(rng.normal(size=x.shape)).to(torch.bfloat16)
-    dy32 = dy16.float()
+    dy = dev(rng.normal(size=x.shape))
     base = dev(rng.normal(size=x.shape))
     P = ops.maxpool3_bwd_sums_partials(N, W, Cc)
     assert P >= 1
     for acc in (False, True):
         want = base.clone()
-        ops.maxpool_bwd(dy32, am, want, acc, N, H, W, Cc, 3, 1, "SAME")
-        got16 = base.clone()
-        ops.maxpool_bwd(dy16, am, got16, acc, N, H, W, Cc, 3, 1, "SAME")
-        torch.cuda.synchronize()
-        assert torch.equal(want, got16)
+        ops.maxpool_bwd(dy, am, want, acc, N, H, W, Cc, 3, 1, "SAME")
         parts = []
         for y in (pooled, pooled.to(torch.bfloat16)):
-            for dy in (dy32, dy16):
-                got = base.clone()
-                part = torch.full((2, Cc, P), float("nan"), device="cuda")
-                ops.maxpool3_bwd_sums(dy, am, got, acc, y, N, H, W, Cc, part)
-                torch.cuda.synchronize()
-                assert torch.equal(want, got)
-                parts.append(part)
-        assert torch.equal(parts[0], parts[1]) and torch.equal(parts[2], parts[3])
-        assert torch.equal(parts[0], parts[2])              # the pooled ties are exact in bf16: same y, same sums
+            got = base.clone()
+            part = torch.full((2, Cc, P), float("nan"), device="cuda")
+            ops.maxpool3_bwd_sums(dy, am, got, acc, y, N, H, W, Cc, part)
+            torch.cuda.synchronize()
+            assert torch.equal(want, got)
+            parts.append(part)
+        assert torch.equal(parts[0], parts[1])              # the pooled ties are exact in bf16: same y, same sums
         g = (want.double() * (pooled.double() > 0)).reshape(-1, Cc)
         mag = g.abs().sum(0).cpu().numpy()
         # sum g over M = N H W cells in some fixed order, every partial sum below sum |g|: (M - 1) u sum |g|

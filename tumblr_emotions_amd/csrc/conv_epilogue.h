@@ -5,7 +5,7 @@
 //   * wave-row epilogue (one wave per 32 rows x NB * 32 columns, descriptor addressing, reads before stores): wave_row_epilogue,
 //     called by gemm_wide_kernel and conv_bf16d_kernel.
 // A difference between callers is either a compile-time option or an argument; the comment at each says which.
-// conv_direct_kernel, conv_bf16_kernel and conv_fp8d_kernel hold the same code in place: on the shared functions their schedule or
+// conv_bf16_kernel and conv_fp8d_kernel hold the same code in place: on the shared functions their schedule or
 // occupancy moved (profiles/conv_epilogue_notes.md).  Of the callers, conv_igemm_kernel<1, 1, false, false, *> gained a wave per
 // SIMD, so its persistent launches (more than 2048 row tiles) have a larger grid.
 #pragma once

@@ -393,220 +393,9 @@ __global__ __launch_bounds__(256, 4) void gemm_group_kernel(const GemmGroupParam
 }
 
 // ================================================================================================
-// Register-direct variant: no LDS, no barriers.
-//
-// In the kernel above a wave only ever reads ITS OWN 32*MT rows of the A tile back from LDS, and the
-// fp32 MFMA fragment layout (lane (i, kh) holds A[i][kh*8 .. kh*8+7]) is exactly two 16-byte loads of
-// a row's K-chunk -- so each wave can fetch its A fragments straight from global memory into the
-// registers the MFMA reads, and do the same for the weight fragments (two float4 per row when the
-// weights are k-contiguous, eight coalesced dwords when they are n-contiguous; co-resident waves hit
-// the same weight lines in L1/L2).  That removes every ds_read/ds_write and, more importantly, every
-// workgroup barrier: the four waves of a workgroup become independent pipelines (load K-tile t+1 ->
-// MFMAs of K-tile t), so a wave delayed by matrix-pipe contention on its SIMD no longer stalls its
-// three block-mates on the other SIMDs.  Registers double-buffer one K-tile; the loop is unrolled by
-// two so both buffers are statically indexed.
-// ================================================================================================
-template <int MT, int NT, bool BNMAJOR>
-struct Frag {
-    f32x4 alo[MT], ahi[MT];                  // A[row][kh*8 + 0..3], [.. + 4..7]
-    f32x4 blo[BNMAJOR ? 1 : NT], bhi[BNMAJOR ? 1 : NT];
-    float bs[BNMAJOR ? NT : 1][8];           // n-contiguous weights: B[kh*8 + s][col]
-};
-
-template <int MT, int NT, bool BNMAJOR, bool FOLD>
-__global__ __launch_bounds__(256) void conv_direct_kernel(const ConvParams p) {
-    const ds_conv_desc &d = p.d;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, lk = lane >> 5;
-    constexpr int BM = 32 * MT, BN = 32 * NT;
-    const int n0 = blockIdx.y * BN;
-    const int ohw = d.OH * d.OW;
-    const int chunks = (d.Cin + BK - 1) / BK;
-    const int KT_all = p.taps * chunks;
-    const int kts = (KT_all + (int)gridDim.z - 1) / (int)gridDim.z;
-    const int kt0 = (int)blockIdx.z * kts;
-    const int KT = (kt0 + kts < KT_all ? kt0 + kts : KT_all) - kt0;
-    float *const zout = p.z + (int64_t)blockIdx.z * p.d.z_split_stride;
-    const int flags = d.flags;
-    const __amdgpu_buffer_rsrc_t srd_x = make_srd(p.x, p.x_bytes);
-    const __amdgpu_buffer_rsrc_t srd_w = make_srd(p.w, p.w_bytes);
-    const int wave_id = blockIdx.x * 4 + wave, waves = gridDim.x * 4;
-
-    unsigned b_off[NT];
-    bool b_ok[NT];
-#pragma unroll
-    for (int b = 0; b < NT; ++b) {
-        const int n = n0 + b * 32 + li;
-        b_ok[b] = n < d.Cout;
-        b_off[b] = BNMAJOR ? (unsigned)n + (unsigned)(lk * 8) * (unsigned)d.w_k_stride
-                           : (unsigned)n * (unsigned)d.w_n_stride + (unsigned)(lk * 8);
-    }
-
-    int ih0[MT], iw0[MT];
-    unsigned xb[MT];
-    int tap, c0, dh, dw;
-    auto setup_tile = [&](int tile) {
-#pragma unroll
-        for (int a = 0; a < MT; ++a) {
-            const int m = tile * BM + a * 32 + li;
-            const bool rv = m < p.M;
-            const int mm = rv ? m : 0;
-            const int n = mm / ohw;
-            const int r = mm - n * ohw;
-            const int oh = r / d.OW;
-            const int ow = r - oh * d.OW;
-            ih0[a] = rv ? oh * d.stride - d.pad_t : -(1 << 20);
-            iw0[a] = ow * d.stride - d.pad_l;
-            xb[a] = (unsigned)n * (unsigned)(d.H * d.W) * (unsigned)d.ldx;
-        }
-        // K-tile order: channel chunk OUTER, tap INNER -- the KH*KW taps of one 16-channel chunk touch the
-        // same (tile + halo) pixels' 64-byte segments, ~15 KB per workgroup, which stays in the XCD's L2
-        // (tap-outer order streamed 9 x the whole tile through L2: measured 8x over-fetch on the 3x3 layers)
-        const int chunk = kt0 / p.taps;
-        tap = kt0 - chunk * p.taps;
-        c0 = chunk * BK;
-        dh = tap / d.KW;
-        dw = tap - dh * d.KW;
-    };
-
-    typedef Frag<MT, NT, BNMAJOR> F;
-    auto load = [&](F &f) {
-        const int k = c0 + lk * 8;
-#pragma unroll
-        for (int a = 0; a < MT; ++a) {
-            const int ih = ih0[a] + dh, iw = iw0[a] + dw;
-            const bool pix = (unsigned)ih < (unsigned)d.H;
-            const bool ok0 = pix && (unsigned)(FOLD ? iw + k / d.fold_cin : iw) < (unsigned)d.W && k < d.Cin;
-            const bool ok1 = pix && (unsigned)(FOLD ? iw + (k + 4) / d.fold_cin : iw) < (unsigned)d.W && k + 4 < d.Cin;
-            const unsigned off = (xb[a] + (unsigned)(ih * d.W + iw) * (unsigned)d.ldx + (unsigned)k) * 4u;
-            f.alo[a] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, ok0 ? off : kOOB, 0, 0));
-            f.ahi[a] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, ok1 ? off + 16u : kOOB, 0, 0));
-        }
-        const int tap_eff = d.flip ? p.taps - 1 - tap : tap;
-        const unsigned wt = (unsigned)tap_eff * (unsigned)d.w_tap_stride + (unsigned)c0 * (BNMAJOR ? (unsigned)d.w_k_stride : 1u);
-        if (BNMAJOR) {
-#pragma unroll
-            for (int b = 0; b < NT; ++b)
-#pragma unroll
-                for (int s = 0; s < 8; ++s) {
-                    const bool ok = b_ok[b] && k + s < d.Cin;
-                    const unsigned off = (wt + b_off[b] + (unsigned)s * (unsigned)d.w_k_stride) * 4u;
-                    f.bs[b][s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd_w, ok ? off : kOOB, 0, 0));
-                }
-        } else {
-#pragma unroll
-            for (int b = 0; b < NT; ++b) {
-                const unsigned off = (wt + b_off[b]) * 4u;
-                f.blo[b] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_w, (b_ok[b] && k < d.Cin) ? off : kOOB, 0, 0));
-                f.bhi[b] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_w, (b_ok[b] && k + 4 < d.Cin) ? off + 16u : kOOB, 0, 0));
-            }
-        }
-        ++tap;
-        if (++dw == d.KW) {
-            dw = 0;
-            if (++dh == d.KH) { dh = 0; tap = 0; c0 += BK; }
-        }
-    };
-
-    f32x16 acc[MT][NT];
-    auto mma = [&](const F &f) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int a = 0; a < MT; ++a) {
-                const float av = s < 4 ? f.alo[a][s & 3] : f.ahi[a][s & 3];
-#pragma unroll
-                for (int b = 0; b < NT; ++b) {
-                    const float bv = BNMAJOR ? f.bs[b][s] : (s < 4 ? f.blo[b][s & 3] : f.bhi[b][s & 3]);
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[a][b], 0, 0, 0);
-                }
-            }
-    };
-
-    float csum[NT], csq[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) csum[j] = csq[j] = 0.f;
-
-    F f0, f1;
-    if (wave_id < p.row_tiles) {
-        setup_tile(wave_id);
-        load(f0);
-    }
-    for (int tile = wave_id; tile < p.row_tiles; tile += waves) {
-        const int m0 = tile * BM;
-        const bool has_next = tile + waves < p.row_tiles;
-#pragma unroll
-        for (int a = 0; a < MT; ++a)
-#pragma unroll
-            for (int b = 0; b < NT; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-        int kt = 0;
-        for (; kt + 2 <= KT; kt += 2) {
-            load(f1);                                   // K-tile kt+1 (always inside this row tile)
-            mma(f0);
-            if (kt + 2 < KT) load(f0);                  // K-tile kt+2 ...
-            else if (has_next) { setup_tile(tile + waves); load(f0); }   // ... or the next row tile's first
-            mma(f1);
-        }
-        const bool odd = kt < KT;
-        if (odd) {                                      // odd K-tile count: one more step out of f0
-            if (has_next) { setup_tile(tile + waves); load(f1); }
-            mma(f0);
-        }
-
-        // ---- epilogue: ds::tile_store's store phase in place (on the shared function this kernel's schedule and occupancy, hence
-        // its grid and partial count, moved: profiles/conv_epilogue_notes.md) ------------------------------------------------
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            const int col = n0 + b * 32 + li;
-            const bool colok = col < d.Cout;
-            const float bv = ((flags & DS_EPI_BIAS) && colok) ? p.bias[col] : 0.f;
-            const float pv = (p.pivot && colok) ? p.pivot[col] : 0.f;      // statistics are taken about the pivot
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int a = 0; a < MT; ++a) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                    if (row < p.M && colok) {
-                        float v = acc[a][b][r] + bv;
-                        const int64_t off = (int64_t)row * d.ldz + col;
-                        if (flags & DS_EPI_ACCUM) v += zout[off];
-                        if (flags & DS_EPI_MASK) v = p.mask[(int64_t)row * d.ldmask + col] > 0.f ? v : 0.f;
-                        if (flags & DS_EPI_RELU) v = fmaxf(v, 0.f);
-                        zout[off] = v;
-                        const float u = v - pv;
-                        s += u;
-                        q += u * u;
-                    }
-                }
-            }
-            csum[b] += s;
-            csq[b] += q;
-        }
-        if (odd) f0 = f1;      // the next row tile's first K-tile was fetched into f1: move it (after the epilogue, so the loads had time to land)
-    }
-
-    if (flags & DS_EPI_STATS) {      // one partial per wave: [2][Cout][P], P = 4 * gridDim.x
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            const float s = csum[b] + __shfl_xor(csum[b], 32);
-            const float q = csq[b] + __shfl_xor(csq[b], 32);
-            const int col = n0 + b * 32 + li;
-            if (lk == 0 && col < d.Cout) {
-                p.stats[(int64_t)col * waves + wave_id] = s;
-                p.stats[((int64_t)d.Cout + col) * waves + wave_id] = q;
-            }
-        }
-    }
-}
-
-// ================================================================================================
 // LDS-DMA variant (gfx950): K-tile 32, operands go global -> LDS with buffer_load_dwordx4 ... lds.
 //
-// Same implicit GEMM, same epilogue, different staging.  The loop above moves every operand through
+// Same implicit GEMM, same epilogue, different staging.  conv_igemm_kernel's loop moves every operand through
 // VGPRs (buffer_load -> s_waitcnt -> ds_write_b128): 12 staging registers per thread, three 13-cycle
 // LDS stores per K-tile and a vmcnt(0) in the middle of every K-step.  Here each lane's 16 bytes land
 // directly in LDS (a wave-instruction fills 1 KiB at M0 + lane*16; out-of-range lanes write zeros --
@@ -1714,7 +1503,7 @@ struct Tuning {
     int wide_nb = 0;          // DS_WIDE_NB pins the wide kernel's column blocks per wave
     int wide_min_wgs = 128;   // DS_WIDE_MINWGS (see wide_nb)
     int mt = 0, nt = 0;       // DS_CONV_CFG="mt,nt" / ds_debug_conv_set_tile pin the tile
-    int path = 0;             // DS_CONV_PATH=lds|direct|glds / ds_debug_conv_set_path pin the kernel family: 1 / 2 / 3
+    int path = 0;             // DS_CONV_PATH=lds|glds / ds_debug_conv_set_path pin the kernel family: 1 / 3
     int prio = 0;             // DS_CONV_PRIO; opt-in: measured neutral-to-negative (profiles/r01_notes.md)
     int xcd_remap = 1;        // DS_CONV_XCD_REMAP, A/B aid; default on
     int bf16d_max_nb = 8;     // ds_debug_conv_bf16_set_max_nb
@@ -1733,7 +1522,7 @@ Tuning &tuning() {
         knob("DS_CONV_PRIO", &t.prio);
         knob("DS_CONV_XCD_REMAP", &t.xcd_remap);
         if (const char *e = ds::tune_env("DS_CONV_CFG")) sscanf(e, "%d,%d", &t.mt, &t.nt);
-        if (const char *e = ds::tune_env("DS_CONV_PATH")) t.path = e[0] == 'l' ? 1 : (e[0] == 'd' ? 2 : (e[0] == 'g' ? 3 : 0));
+        if (const char *e = ds::tune_env("DS_CONV_PATH")) t.path = e[0] == 'l' ? 1 : (e[0] == 'g' ? 3 : 0);
         return t;
     }();
     return tune;
@@ -1741,7 +1530,6 @@ Tuning &tuning() {
 
 struct TileCfg {
     int mt, nt;
-    bool direct;     // register-direct kernel (tile = per-WAVE 32*mt x 32*nt) instead of the LDS kernel
     bool glds;       // LDS-DMA kernel, K-tile 32 (128 x 32*nt tile)
     bool bf16;       // bf16-multiply kernel (128 x 32*nt tile, nt <= 4)
     int wide;        // > 0: wide 1x1 kernel, 128 rows x 32*wide columns per workgroup
@@ -1814,12 +1602,6 @@ KernelFn kernel_of(const Launch &L) {
         });
     return with_const<1, 2>(c.mt == 2 ? 2 : 1, [&](auto mt) {
         constexpr int MT = decltype(mt)::value;
-        if (c.direct)
-            return with_const<1, 4>(c.nt, [&](auto nt) {
-                constexpr int NT = decltype(nt)::value;
-                if (v.bnmajor) return v.fold ? conv_direct_kernel<MT, NT, true, true> : conv_direct_kernel<MT, NT, true, false>;
-                return conv_direct_kernel<MT, NT, false, false>;
-            });
         return with_const<1, 6>(c.nt, [&](auto nt) {
             constexpr int NT = decltype(nt)::value;
             if (v.bnmajor) {
@@ -1912,7 +1694,7 @@ TileCfg pick_cfg(const ds_conv_desc *d, bool vec, Ask ask) {
     const int64_t M = conv_M(d);
     const int N = d->Cout;
     const int pad32 = (N + 31) / 32 * 32, pad64 = (N + 63) / 64 * 64;
-    TileCfg c = {1, 1, false, false, false, 0};
+    TileCfg c = {1, 1, false, false, 0};
     if (int nb = wide_nb(d, vec, ask)) {
         c.wide = nb;
         c.nt = nb;
@@ -1931,29 +1713,18 @@ TileCfg pick_cfg(const ds_conv_desc *d, bool vec, Ask ask) {
         if (t.nt > 0) c.nt = t.nt > 4 ? 4 : t.nt;
         return c;
     }
-    // Measured (profiles/r01_lds_vs_direct_sweep.txt): the LDS-staged kernel wins on every shape of this
-    // model -- fragment-shaped global loads touch 32 cache lines per wave instruction and are TA-bound --
-    // so the register-direct family is opt-in only.
-    c.direct = vec && t.path == 2;
-    if (c.direct) {
-        // per-WAVE tile 32*mt x 32*nt
-        const int64_t row_tiles = (M + 31) / 32;
-        if (pad64 * 100 <= pad32 * 112 && row_tiles * (pad64 / 64) >= 12 * ds::kCUs) c.nt = 2;
-    } else {
-        // Measured on MI355X over every conv/GEMM shape of the joint step (profiles/r01_tile_sweep.txt):
-        // latency-bound per wave, so small tiles at 3-5 resident workgroups per CU beat wide ones.
-        const int64_t row_tiles = (M + 127) / 128;
-        if (pad64 * 100 <= pad32 * 112 && row_tiles * (pad64 / 64) >= 5 * ds::kCUs / 2) c.nt = 2;
-    }
-    if (d->tile_nt > 0 && !c.direct) c.nt = d->tile_nt > 6 ? 6 : d->tile_nt;     // per-layer choice (tuning table)
+    // Measured on MI355X over every conv/GEMM shape of the joint step (profiles/r01_tile_sweep.txt):
+    // latency-bound per wave, so small tiles at 3-5 resident workgroups per CU beat wide ones.
+    const int64_t row_tiles = (M + 127) / 128;
+    if (pad64 * 100 <= pad32 * 112 && row_tiles * (pad64 / 64) >= 5 * ds::kCUs / 2) c.nt = 2;
+    if (d->tile_nt > 0) c.nt = d->tile_nt > 6 ? 6 : d->tile_nt;     // per-layer choice (tuning table)
     if (t.mt > 0) c.mt = t.mt;
     if (t.nt > 0) c.nt = t.nt;
-    if (c.direct && c.nt > 4) c.nt = 4;
     // LDS-DMA kernel (K-tile 32): needs 16-byte aligned operands and no folded stem.  Automatic for the
     // multi-tap convs whose reduction the 32-deep K-tile pads by no more than ~12 % over the 16-deep one:
     // measured 3-10 % faster there (long K loops), 5-10 % slower on the 1x1 layers whose 9-26 K-tiles
     // leave the prologue/epilogue exposed (profiles/r01_glds_sweep.txt).
-    if (!c.direct && vec && d->fold_cin == 0 && t.path != 1) {
+    if (vec && d->fold_cin == 0 && t.path != 1) {
         const int k16 = (d->Cin + 15) / 16 * 16, k32 = (d->Cin + 31) / 32 * 32;
         if (t.path == 3 || (d->KH * d->KW >= 4 && k32 * 100 <= k16 * 112)) {
             c.glds = true;
@@ -1982,7 +1753,7 @@ Launch choose(const ds_conv_desc *d, bool aligned, Ask ask = kAsIs) {
     L.bnr = false;          // (a DS_EPI_BN_RELU launch keeps the grid the descriptor gets without the flag)
     L.pool = d->pool_argmax || ask == kBeforePool;
     L.bnb = d->bnb != nullptr;
-    const int bm = (c.direct ? 32 : 128) * (c.glds ? 1 : c.mt), bn = 32 * c.nt;
+    const int bm = 128 * (c.glds ? 1 : c.mt), bn = 32 * c.nt;
     L.row_tiles = (int)((conv_M(d) + bm - 1) / bm);
     if (c.wide && L.pool) {          // 32-row blocks of whole image rows, four per workgroup
         int rpb, bpi;
@@ -1990,29 +1761,28 @@ Launch choose(const ds_conv_desc *d, bool aligned, Ask ask = kAsIs) {
         L.row_tiles = (int)(((int64_t)d->N * bpi + 3) / 4);
     }
     L.gy = (d->Cout + bn - 1) / bn;
-    const int wg_tiles = c.direct ? (L.row_tiles + 3) / 4 : L.row_tiles;     // row tiles in units of workgroups
-    L.gx = wg_tiles;
+    L.gx = L.row_tiles;
     L.one = true;
     // (the wide 1x1 kernel: always one workgroup per (row group, column tile))
-    if (!c.wide && (wg_tiles > kOneTilePerWg || c.direct)) {
+    if (!c.wide && L.row_tiles > kOneTilePerWg) {
         int target = (resident_per_cu(kernel_of(L)) * ds::kCUs) / L.gy;             // one resident wave of workgroups
         if (target < 8) target = 8;
-        L.gx = wg_tiles < target ? wg_tiles : target;
+        L.gx = L.row_tiles < target ? L.row_tiles : target;
         if (L.gx >= 8) L.gx &= ~7;                  // multiple of 8: column tiles of a row tile share an XCD
         L.one = false;
     }
-    if (d->grid_x > 0 && !c.direct) {       // per-layer override
-        L.gx = d->grid_x < wg_tiles ? d->grid_x : wg_tiles;
-        L.one = L.gx == wg_tiles;
+    if (d->grid_x > 0) {       // per-layer override
+        L.gx = d->grid_x < L.row_tiles ? d->grid_x : L.row_tiles;
+        L.one = L.gx == L.row_tiles;
     }
     L.bnr = (d->flags & DS_EPI_BN_RELU) != 0;
     L.grid = dim3(L.gx, L.gy, d->splits > 1 ? d->splits : 1);
     L.col_tiles = 0;
-    if (L.one && (c.wide || (tuning().xcd_remap && L.gy > 1)) && !c.direct) {    // one workgroup per tile: 1-D XCD-aware launch (TileId)
+    if (L.one && (c.wide || (tuning().xcd_remap && L.gy > 1))) {    // one workgroup per tile: 1-D XCD-aware launch (TileId)
         L.col_tiles = L.gy;
         L.grid = dim3((L.row_tiles * L.gy + 7) / 8 * 8, 1, L.grid.z);
     }
-    L.partials = c.direct ? L.gx * 4 : L.gx;
+    L.partials = L.gx;
     return L;
 }
 
@@ -2020,7 +1790,7 @@ Launch choose(const ds_conv_desc *d, bool aligned, Ask ask = kAsIs) {
 // (pointer alignment is checked at launch), 128-row tiles of the LDS / LDS-DMA kernels or the wide 1x1 kernel.
 bool bnr_ok(const ds_conv_desc *d, const Launch &L) {
     if (d->dtype != DS_DTYPE_F32 || !L.v.bnmajor || !L.v.vec || L.v.fold || d->splits > 1 || d->bnb) return false;
-    return !L.c.bf16 && !L.c.direct && L.c.mt == 1;
+    return !L.c.bf16 && L.c.mt == 1;
 }
 
 // What the four launchers of this file fill alike: the operands, M, the taps and the extents of the two buffer descriptors
@@ -2132,7 +1902,8 @@ extern "C" int ds_debug_conv_set_wide(int mode) {
 }
 
 extern "C" int ds_debug_conv_set_path(int path) {
-    DS_REQUIRE(path >= 0 && path <= 3, "ds_debug_conv_set_path: 0 = automatic, 1 = register-staged LDS kernel, 2 = register-direct kernel, 3 = LDS-DMA kernel");
+    DS_REQUIRE(path == 0 || path == 1 || path == 3,
+               "ds_debug_conv_set_path: 0 = automatic, 1 = register-staged LDS kernel, 3 = LDS-DMA kernel (2, the register-direct kernel, is retired)");
     tuning().path = path;
     return DS_OK;
 }
@@ -2227,7 +1998,7 @@ extern "C" int ds_gemm_group(const ds_conv_desc *const *descs, const float *cons
                    "ds_gemm_group: problem %d: overlapping output slabs", i);
         const Launch L = choose(d, aligned16(x[i], w[i]));
         const TileCfg &c = L.c;
-        DS_REQUIRE(c.mt == 1 && c.nt == 1 && !c.direct && !c.glds && !c.bf16 && !c.wide,
+        DS_REQUIRE(c.mt == 1 && c.nt == 1 && !c.glds && !c.bf16 && !c.wide,
                    "ds_gemm_group: problem %d's own launch is not the 128 x 32 tile (run it through ds_conv_igemm)", i);
         ConvParams &p = g.p[i];
         if (int rc = fill_params(p, "ds_gemm_group", "", d, x[i], w[i], z[i], nullptr, nullptr, nullptr)) return rc;

@@ -327,6 +327,7 @@ extern "C" int ds_conv_run(const ds_conv_layer_plan *p, const void *x, const voi
     static const ds_conv_io none = {};
     if (io == nullptr) io = &none;
     const ds_conv_desc &d = p->d;
+    PLAN_REQUIRE(p->role != DS_CONV_DGRAD || d.z_dtype != DS_DTYPE_BF16, "ds_conv_run: z_dtype DS_DTYPE_BF16 is a forward layer's storage, not a dgrad's");
     if (d.flags & DS_EPI_BN_RELU) {
         PLAN_REQUIRE(io->scale && io->shift, "ds_conv_run: DS_EPI_BN_RELU needs io.scale and io.shift");
         PLAN_REQUIRE(d.flags == DS_EPI_BN_RELU, "ds_conv_run: DS_EPI_BN_RELU excludes every other epilogue flag");

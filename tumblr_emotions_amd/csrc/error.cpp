@@ -13,5 +13,5 @@ void set_error(const char *fmt, ...) {
 }
 }  // namespace ds
 
-extern "C" int ds_version(void) { return 3; }
+extern "C" int ds_version(void) { return 4; }
 extern "C" const char *ds_last_error(void) { return ds::g_err; }

@@ -296,8 +296,7 @@ struct WinRow {
     unsigned a[3];      // packed uchar4 arg-max of the three windows of one output row
 };
 
-template <typename TD>          // TD: storage of the pool's output gradient (float; __bf16: a dgrad wrote it rounded, ds_conv_desc.z_dtype)
-__device__ __forceinline__ WinRow load_win_row(const TD *dy, const uint8_t *am, int64_t row_base, int iw, int W, int C,
+__device__ __forceinline__ WinRow load_win_row(const float *dy, const uint8_t *am, int64_t row_base, int iw, int W, int C,
                                                int c, bool row_ok) {
     WinRow r;
 #pragma unroll
@@ -310,7 +309,7 @@ __device__ __forceinline__ WinRow load_win_row(const TD *dy, const uint8_t *am, 
         if (ok) {
             const int64_t o = (row_base + ow) * C + c;
             r.a[q] = *reinterpret_cast<const unsigned *>(am + o);
-            const float4 v = ld4<TD>(dy + o);
+            const float4 v = ld4<float>(dy + o);
             r.d[q][0] = v.x; r.d[q][1] = v.y; r.d[q][2] = v.z; r.d[q][3] = v.w;
         }
     }
@@ -328,8 +327,7 @@ __device__ __forceinline__ void win_row_grad(const WinRow &w, int p, float g[4])
     }
 }
 
-template <typename TD = float>
-__global__ __launch_bounds__(256) void maxpool3s1_bwd_rolling(const TD *dy, const uint8_t *am, float *dx,
+__global__ __launch_bounds__(256) void maxpool3s1_bwd_rolling(const float *dy, const uint8_t *am, float *dx,
                                                               int accumulate, int N, int H, int W, int C) {
     const int C4 = C >> 2;
     const int64_t total = (int64_t)N * W * C4;
@@ -370,8 +368,8 @@ __global__ __launch_bounds__(256) void maxpool3s1_bwd_rolling(const TD *dy, cons
 // picks the divisor that fills the 256 threads -- 528 channels: 6 chunks of 22 quads x 11 unit groups instead of 132 of 256 threads,
 // 832: 13 chunks of 16 x 16 instead of 208) and the units [ub * upb, (ub + 1) * upb), ub = blockIdx.x / chunks; partials [2][C][P] with
 // P = gridDim.x / chunks, summed per thread in unit order and over the unit groups in a fixed order (deterministic).
-template <typename TY, typename TD = float>
-__global__ __launch_bounds__(256) void maxpool3s1_bwd_sums_kernel(const TD *dy, const uint8_t *am, float *dx, int accumulate,
+template <typename TY>
+__global__ __launch_bounds__(256) void maxpool3s1_bwd_sums_kernel(const float *dy, const uint8_t *am, float *dx, int accumulate,
                                                                   const TY *y, int N, int H, int W, int C, float *partials,
                                                                   int upb, int CW, int chunks) {
     extern __shared__ __attribute__((aligned(16))) float sh[];   // [RG][CW][8]
@@ -875,7 +873,7 @@ extern "C" int ds_maxpool_bwd(const float *dy, const uint8_t *argmax, float *dx,
                               int32_t OH, int32_t OW, void *stream) {
     DS_REQUIRE(dy && argmax && dx && C % 4 == 0, "ds_maxpool_bwd: bad argument");
     if (k == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && OH == H && OW == W) {
-        hipLaunchKernelGGL(maxpool3s1_bwd_rolling<float>, dim3(ds::stream_grid((int64_t)N * W * (C / 4), 256)), dim3(256), 0,
+        hipLaunchKernelGGL(maxpool3s1_bwd_rolling, dim3(ds::stream_grid((int64_t)N * W * (C / 4), 256)), dim3(256), 0,
                            (hipStream_t)stream, dy, argmax, dx, accumulate, N, H, W, C);
         return ds::check_launch("ds_maxpool_bwd");
     }
@@ -902,31 +900,6 @@ extern "C" int ds_maxpool3_bwd_sums_partials(int32_t N, int32_t W, int32_t C) {
     return pool_sums_shape(N, W, C).P;
 }
 
-// The 3x3 / 1 MaxPoolGrad reading its output gradient from bf16 storage (a Conv2DBackpropInput wrote it rounded:
-// ds_conv_desc.z_dtype on the dgrad): partials == nullptr: the plain pass (ds_maxpool_bwd), else with the sums (ds_maxpool3_bwd_sums)
-extern "C" int ds_maxpool3_bwd_dy16(const void *dy16, const uint8_t *argmax, float *dx, int32_t accumulate, const void *y,
-                                    int32_t y_dtype, int32_t N, int32_t H, int32_t W, int32_t C, float *partials,
-                                    void *stream) {
-    DS_REQUIRE(dy16 && argmax && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && (((uintptr_t)dy16) & 7) == 0,
-               "ds_maxpool3_bwd_dy16: bad argument (C %% 4 == 0, 8-byte aligned dy)");
-    const __bf16 *dy = reinterpret_cast<const __bf16 *>(dy16);
-    if (!partials) {
-        hipLaunchKernelGGL(maxpool3s1_bwd_rolling<__bf16>, dim3(ds::stream_grid((int64_t)N * W * (C / 4), 256)), dim3(256), 0,
-                           (hipStream_t)stream, dy, argmax, dx, accumulate, N, H, W, C);
-        return ds::check_launch("ds_maxpool3_bwd_dy16");
-    }
-    DS_REQUIRE(y && C <= 1024 && (y_dtype == DS_DTYPE_F32 || y_dtype == DS_DTYPE_BF16), "ds_maxpool3_bwd_dy16: the sums need y (fp32 / bf16), C <= 1024");
-    const PoolSumsShape sh = pool_sums_shape(N, W, C);
-    const size_t shmem = (size_t)sh.RG * sh.CW * 8 * sizeof(float);
-    if (y_dtype == DS_DTYPE_BF16)
-        hipLaunchKernelGGL((maxpool3s1_bwd_sums_kernel<__bf16, __bf16>), dim3(sh.P * sh.chunks), dim3(256), shmem, (hipStream_t)stream, dy, argmax, dx,
-                           accumulate, (const __bf16 *)y, N, H, W, C, partials, sh.upb, sh.CW, sh.chunks);
-    else
-        hipLaunchKernelGGL((maxpool3s1_bwd_sums_kernel<float, __bf16>), dim3(sh.P * sh.chunks), dim3(256), shmem, (hipStream_t)stream, dy, argmax, dx,
-                           accumulate, (const float *)y, N, H, W, C, partials, sh.upb, sh.CW, sh.chunks);
-    return ds::check_launch("ds_maxpool3_bwd_dy16");
-}
-
 extern "C" int ds_maxpool3_bwd_sums(const float *dy, const uint8_t *argmax, float *dx, int32_t accumulate, const void *y,
                                     int32_t y_dtype, int32_t N, int32_t H, int32_t W, int32_t C, float *partials,
                                     void *stream) {
@@ -937,10 +910,10 @@ extern "C" int ds_maxpool3_bwd_sums(const float *dy, const uint8_t *argmax, floa
     const PoolSumsShape sh = pool_sums_shape(N, W, C);
     const size_t shmem = (size_t)sh.RG * sh.CW * 8 * sizeof(float);
     if (y_dtype == DS_DTYPE_BF16)
-        hipLaunchKernelGGL((maxpool3s1_bwd_sums_kernel<__bf16, float>), dim3(sh.P * sh.chunks), dim3(256), shmem, (hipStream_t)stream, dy, argmax, dx,
+        hipLaunchKernelGGL(maxpool3s1_bwd_sums_kernel<__bf16>, dim3(sh.P * sh.chunks), dim3(256), shmem, (hipStream_t)stream, dy, argmax, dx,
                            accumulate, (const __bf16 *)y, N, H, W, C, partials, sh.upb, sh.CW, sh.chunks);
     else
-        hipLaunchKernelGGL((maxpool3s1_bwd_sums_kernel<float, float>), dim3(sh.P * sh.chunks), dim3(256), shmem, (hipStream_t)stream, dy, argmax, dx,
+        hipLaunchKernelGGL(maxpool3s1_bwd_sums_kernel<float>, dim3(sh.P * sh.chunks), dim3(256), shmem, (hipStream_t)stream, dy, argmax, dx,
                            accumulate, (const float *)y, N, H, W, C, partials, sh.upb, sh.CW, sh.chunks);
     return ds::check_launch("ds_maxpool3_bwd_sums");
 }

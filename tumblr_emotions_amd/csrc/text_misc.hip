@@ -14,7 +14,7 @@ namespace {
 // per-element integer division.  Four rows are fetched before the first is stored (memory-level parallelism:
 // the 12 MB table is cache resident, the stores are the HBM stream) and the stores are non-temporal -- the
 // rows are next read by the projection GEMM, long after they left the caches at 2^20 tokens.
-template <int VEC, bool NT = true, bool OUTORDER = false>
+template <int VEC, bool OUTORDER = false>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float *table, const int64_t *ids, float *out, int B,
                                                           int T, int D, int64_t rows, int time_major, int rpw) {
     typedef float vec_t __attribute__((ext_vector_type(VEC)));
@@ -63,14 +63,8 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float *table, co
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (!dst[u]) continue;
-                if (lane < DV) {
-                    if (NT) __builtin_nontemporal_store(v0[u], reinterpret_cast<vec_t *>(dst[u] + lane * VEC));
-                    else *reinterpret_cast<vec_t *>(dst[u] + lane * VEC) = v0[u];
-                }
-                if (64 + lane < DV) {
-                    if (NT) __builtin_nontemporal_store(v1[u], reinterpret_cast<vec_t *>(dst[u] + (64 + lane) * VEC));
-                    else *reinterpret_cast<vec_t *>(dst[u] + (64 + lane) * VEC) = v1[u];
-                }
+                if (lane < DV) __builtin_nontemporal_store(v0[u], reinterpret_cast<vec_t *>(dst[u] + lane * VEC));
+                if (64 + lane < DV) __builtin_nontemporal_store(v1[u], reinterpret_cast<vec_t *>(dst[u] + (64 + lane) * VEC));
             }
         };
         fetch(r, srcA, dstA, okA, a0, a1);
@@ -107,10 +101,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float *table, co
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
-                if (v < DV && dst[u]) {
-                    if (NT) __builtin_nontemporal_store(val[u], reinterpret_cast<vec_t *>(dst[u] + v * VEC));
-                    else *reinterpret_cast<vec_t *>(dst[u] + v * VEC) = val[u];
-                }
+                if (v < DV && dst[u]) __builtin_nontemporal_store(val[u], reinterpret_cast<vec_t *>(dst[u] + v * VEC));
         }
     }
 }
@@ -625,22 +616,8 @@ extern "C" int ds_gather_rows(const float *table, const int64_t *ids, float *out
     rpw = rpw < 4 ? 4 : (rpw > 16 ? 16 : rpw);
     const int64_t waves = (total + rpw - 1) / rpw;
     const dim3 grid((unsigned)((waves + 3) / 4));
-    static int plain = -1;
-    if (plain < 0) {
-        const char *e = ds::tune_env("DS_GATHER_PLAIN_STORES");      // A/B aid
-        plain = e ? atoi(e) : 0;
-    }
-    static int outorder = -1;
-    if (outorder < 0) {
-        const char *e = ds::tune_env("DS_GATHER_OUTORDER");          // A/B aid
-        outorder = e ? atoi(e) : 1;
-    }
-    if (D % 4 == 0 && a16 && !plain && time_major && outorder == 1) {
-        hipLaunchKernelGGL((gather_rows_kernel<4, true, true>), grid, dim3(256), 0, s, table, ids, out, B, T, D, table_rows, time_major, rpw);
-    } else if (D % 4 == 0 && a16 && time_major && outorder == 2) {
-        hipLaunchKernelGGL((gather_rows_kernel<4, false, true>), grid, dim3(256), 0, s, table, ids, out, B, T, D, table_rows, time_major, rpw);
-    } else if (D % 4 == 0 && a16 && plain) {
-        hipLaunchKernelGGL((gather_rows_kernel<4, false>), grid, dim3(256), 0, s, table, ids, out, B, T, D, table_rows, time_major, rpw);
+    if (D % 4 == 0 && a16 && time_major) {
+        hipLaunchKernelGGL((gather_rows_kernel<4, true>), grid, dim3(256), 0, s, table, ids, out, B, T, D, table_rows, time_major, rpw);
     } else if (D % 4 == 0 && a16) {
         hipLaunchKernelGGL(gather_rows_kernel<4>, grid, dim3(256), 0, s, table, ids, out, B, T, D, table_rows, time_major, rpw);
     } else if (D % 2 == 0 && a8) {

@@ -897,11 +897,8 @@ def bn_pool_infer_bwd_apply_sums(z, dpool, argmax, N, H, W, C_, rstd, shift, dz,
 
 
 def maxpool_bwd(dy, argmax, dx, accumulate, N, H, W, C_, k, stride, mode="SAME"):
-    if dy.dtype == torch.bfloat16:          # (3x3 / 1 SAME only: Branch_3's pool behind a dgrad that writes bf16)
-        assert k == 3 and stride == 1 and mode == "SAME"
-        _lib.check(_lib.load().ds_maxpool3_bwd_dy16(_p(dy), _p(argmax), _p(dx), int(accumulate), None, DS_DTYPE_F32, N, H, W, C_,
-                                                    None, _stream()), "ds_maxpool3_bwd_dy16")
-        return
+    if dy.dtype != torch.float32:          # (the library reads dy as floats)
+        raise ValueError("maxpool_bwd: dy must be fp32, got %s" % dy.dtype)
     if mode == "SAME":
         OH, pt = same_pad(H, k, stride)
         OW, pl = same_pad(W, k, stride)
@@ -917,10 +914,8 @@ def maxpool3_bwd_sums_partials(N, W, C_):
 
 def maxpool3_bwd_sums(dy, argmax, dx, accumulate, y, N, H, W, C_, partials):
     """ds_maxpool_bwd of a 3x3 / 1 SAME pool + the BatchNorm-backward sums (sum g, sum g*y over y > 0) of the activation y."""
-    if dy.dtype == torch.bfloat16:          # the pool's output gradient in bf16 storage
-        _lib.check(_lib.load().ds_maxpool3_bwd_dy16(_p(dy), _p(argmax), _p(dx), int(accumulate), _p(y), act_dtype(y), N, H, W, C_,
-                                                    _p(partials), _stream()), "ds_maxpool3_bwd_dy16")
-        return
+    if dy.dtype != torch.float32:          # (the library reads dy as floats)
+        raise ValueError("maxpool3_bwd_sums: dy must be fp32, got %s" % dy.dtype)
     _lib.check(_lib.load().ds_maxpool3_bwd_sums(_p(dy), _p(argmax), _p(dx), int(accumulate), _p(y), act_dtype(y), N, H, W, C_,
                                                 _p(partials), _stream()), "ds_maxpool3_bwd_sums")
 
