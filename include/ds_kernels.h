@@ -150,6 +150,14 @@ int ds_debug_conv_set_path(int path);
 /* the wide-tile register-direct kernel for plain 1x1 / GEMM shapes (flags within DS_EPI_STATS):
  * 0 = never, 1 = automatic (default), 2 = wherever the shape allows.                                      */
 int ds_debug_conv_set_wide(int mode);
+/* the wide kernel's column blocks (of 32) per wave: 0 = the cost model (default), 1 .. 8 pins them (the field DS_WIDE_NB
+ * feeds).  The launch rules still hold: a pin above a launch's own cap (2 with ds_conv_desc.bnb) is ignored, and a
+ * pool_argmax launch keeps ceil(Cout / 32).  Anything else is DS_ERR_ARG.                                      */
+int ds_debug_conv_set_wide_nb(int nb);
+/* What ds_conv_igemm would launch for `d` with 16-byte aligned operands (the plan-time questions' assumption; host code,
+ * nothing is launched and no device is needed): out = {wide kernel's column blocks per wave or 0, n-contiguous weights,
+ * bnb, pool, DS_EPI_BN_RELU, mt, nt, LDS-DMA kernel, workgroups launched, statistics partials}.                */
+int ds_debug_conv_igemm_launch(const ds_conv_desc *d, int out[10]);
 /* ds_conv_wino's kernel carries four ablation bits in `flags` (256 / 512 / 1024 / 2048: skip the pixel loads, the weight
  * DMAs, the output stores ... -- garbage results, timing only).  They are refused (DS_ERR_ARG) unless switched on here. */
 int ds_debug_conv_wino_allow_ablation(int on);

@@ -320,6 +320,8 @@ DEBUG_SIGNATURES = {
     "ds_debug_conv_set_tile": (C.c_int, [C.c_int, C.c_int]),
     "ds_debug_conv_set_path": (C.c_int, [C.c_int]),
     "ds_debug_conv_set_wide": (C.c_int, [C.c_int]),
+    "ds_debug_conv_set_wide_nb": (C.c_int, [C.c_int]),
+    "ds_debug_conv_igemm_launch": (C.c_int, [_CD, C.POINTER(C.c_int)]),
     "ds_debug_conv_wino_allow_ablation": (C.c_int, [C.c_int]),
     "ds_debug_conv_wino4_set_nb": (C.c_int, [C.c_int]),
     "ds_debug_conv_bf16_set_max_nb": (C.c_int, [C.c_int]),

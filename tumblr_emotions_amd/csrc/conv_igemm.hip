@@ -1901,6 +1901,28 @@ extern "C" int ds_debug_conv_set_wide(int mode) {
     return DS_OK;
 }
 
+extern "C" int ds_debug_conv_set_wide_nb(int nb) {
+    DS_REQUIRE(nb >= 0 && nb <= 8, "ds_debug_conv_set_wide_nb: 0 = the cost model, 1 .. 8 column blocks per wave");
+    tuning().wide_nb = nb;          // (wide_nb: a pin above the launch's own cap is ignored; POOL keeps ceil(Cout / 32))
+    return DS_OK;
+}
+
+extern "C" int ds_debug_conv_igemm_launch(const ds_conv_desc *d, int out[10]) {
+    DS_REQUIRE(d && out, "ds_debug_conv_igemm_launch: null argument");
+    const Launch L = choose(d, true);
+    out[0] = L.c.wide;
+    out[1] = L.v.bnmajor ? 1 : 0;
+    out[2] = L.bnb ? 1 : 0;
+    out[3] = L.pool ? 1 : 0;
+    out[4] = L.bnr ? 1 : 0;
+    out[5] = L.c.mt;
+    out[6] = L.c.nt;
+    out[7] = L.c.glds ? 1 : 0;
+    out[8] = (int)(L.grid.x * L.grid.y * L.grid.z);
+    out[9] = L.partials;
+    return DS_OK;
+}
+
 extern "C" int ds_debug_conv_set_path(int path) {
     DS_REQUIRE(path == 0 || path == 1 || path == 3,
                "ds_debug_conv_set_path: 0 = automatic, 1 = register-staged LDS kernel, 3 = LDS-DMA kernel (2, the register-direct kernel, is retired)");
