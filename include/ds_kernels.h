@@ -814,6 +814,26 @@ int ds_adam_tf_clipped(float *theta, const float *g, float *m, float *v, int64_t
                        const int64_t *segments, int32_t nseg, const int64_t *chunks, int32_t nchunks, const float *factors,
                        int32_t *flags, void *stream);
 
+/* Moving averages of the trained variables in the optimiser pass: tf.train.ExponentialMovingAverage.apply behind
+ * apply_gradients (slim/train_image_classifier.py:497-524 builds it over the model variables).  TensorFlow is not in the
+ * reference tree; restated from TF 1.x (moving_averages.assign_moving_average, zero_debias off):
+ *   decay_t = min(decay, (1 + t) / (10 + t))        t = num_updates, formed by the host
+ *   shadow  = shadow - (shadow - variable) * (1 - decay_t)
+ * ds_adam_tf_ema / ds_adam_tf_clipped_ema are ds_adam_tf / ds_adam_tf_clipped (the same bits in theta, m and v: one shared
+ * per-element update) plus, for every element i of [0, n) and in the same pass, with w' = the theta[i] just written,
+ *   shadow[i] = shadow[i] - (shadow[i] - w') * ema_rate
+ * three fp32 operations, each rounded once, never contracted.  ema_rate = 1 - decay_t in [0, 1] (anything else, a NaN or a
+ * NULL shadow: DS_ERR_ARG before any launch); ema_rate_dev (nullable) overrides it from device memory (hipGraph replay), as
+ * lr_t_dev does lr_t.  ema_rate 0 leaves shadow bit for bit.  ds_adam_tf_clipped_ema with flags[1] != 0 leaves shadow
+ * untouched like theta, m and v.  shadow must not overlap the other buffers.  Plain vector stores only. */
+int ds_adam_tf_ema(float *theta, const float *g, float *m, float *v, float *shadow, int64_t n, int64_t n_wd, float wd,
+                   float grad_scale, float lr_t, const float *lr_t_dev, float ema_rate, const float *ema_rate_dev,
+                   float beta1, float beta2, float eps, void *stream);
+int ds_adam_tf_clipped_ema(float *theta, const float *g, float *m, float *v, float *shadow, int64_t n, int64_t n_wd, float wd,
+                           float grad_scale, float lr_t, const float *lr_t_dev, float ema_rate, const float *ema_rate_dev,
+                           float beta1, float beta2, float eps, const int64_t *segments, int32_t nseg, const int64_t *chunks,
+                           int32_t nchunks, const float *factors, int32_t *flags, void *stream);
+
 /* Clone-gradient accumulation over the flat gradient buffer (slim/deployment/model_deploy.py:414-444, _sum_clones_gradients).
  * mode 0: acc[i] = g[i]            (first clone)
  * mode 1: acc[i] = acc[i] + g[i]   (middle clones)

@@ -279,6 +279,9 @@ SIGNATURES = {
     "ds_grad_norms": (C.c_int, [_P, _P, _i64, _i64, _f32, _f32, _P, _i32, _P, _i32, _i32, C.c_double, _i32, _P, _P, _P, _P, _P]),
     "ds_adam_tf_clipped": (C.c_int, [_P, _P, _P, _P, _i64, _i64, _f32, _f32, _f32, _P, _f32, _f32, _f32, _P, _i32, _P, _i32, _P,
                                      _P, _P]),
+    "ds_adam_tf_ema": (C.c_int, [_P, _P, _P, _P, _P, _i64, _i64, _f32, _f32, _f32, _P, _f32, _P, _f32, _f32, _f32, _P]),
+    "ds_adam_tf_clipped_ema": (C.c_int, [_P, _P, _P, _P, _P, _i64, _i64, _f32, _f32, _f32, _P, _f32, _P, _f32, _f32, _f32, _P,
+                                         _i32, _P, _i32, _P, _P, _P]),
     "ds_grad_accumulate": (C.c_int, [_P, _P, _i64, _i32, _P]),
     "ds_sumsq": (C.c_int, [_P, _i64, _P, _P, _P]),
     "ds_colsum": (C.c_int, [_P, _i64, _i32, _i32, _P, _P, _P]),

@@ -270,24 +270,42 @@ __device__ __forceinline__ float adam_g_eff(const float *g, int64_t i, float w, 
     return gi;
 }
 
-// The update of element i from its effective gradient gi, shared by both Adam kernels.
-__device__ __forceinline__ void adam_tf_update(float *theta, float *m, float *v, int64_t i, float w, float gi, float lr_t,
-                                               float b1, float b2, float eps) {
+// The update of element i from its effective gradient gi, shared by every Adam kernel; returns the new theta[i].
+__device__ __forceinline__ float adam_tf_update(float *theta, float *m, float *v, int64_t i, float w, float gi, float lr_t,
+                                                float b1, float b2, float eps) {
 #pragma clang fp contract(off)
     const float mi = b1 * m[i] + (1.f - b1) * gi;
     const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
     m[i] = mi;
     v[i] = vi;
-    theta[i] = w - lr_t * mi / (sqrtf(vi) + eps);     // epsilon outside the bias correction (A10)
+    const float wn = w - lr_t * mi / (sqrtf(vi) + eps);     // epsilon outside the bias correction (A10)
+    theta[i] = wn;
+    return wn;
 }
 
-__global__ __launch_bounds__(256) void adam_tf_kernel(float *theta, const float *g, float *m, float *v, int64_t n,
-                                                      int64_t n_wd, float wd, float grad_scale, float lr_t,
-                                                      const float *lr_t_dev, float b1, float b2, float eps) {
+// tf.train.ExponentialMovingAverage's assign_moving_average on element i, wn = the variable after the update:
+// shadow -= (shadow - wn) * rate -- a difference, a product and a difference, each rounded once (the _ema kernels).
+__device__ __forceinline__ void ema_update(float *shadow, int64_t i, float wn, float rate) {
+#pragma clang fp contract(off)
+    const float s = shadow[i];
+    const float d = s - wn;
+    const float p = d * rate;
+    shadow[i] = s - p;
+}
+
+// EMA = false: ds_adam_tf (shadow, ema_rate and ema_rate_dev are not read).  EMA = true: ds_adam_tf_ema, the same pass with
+// the shadow update behind every element's Adam update.
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_tf_kernel(float *theta, const float *g, float *m, float *v, float *shadow,
+                                                      int64_t n, int64_t n_wd, float wd, float grad_scale, float lr_t,
+                                                      const float *lr_t_dev, float ema_rate, const float *ema_rate_dev,
+                                                      float b1, float b2, float eps) {
     if (lr_t_dev) lr_t = lr_t_dev[0];         // step size kept on device (hipGraph replay safe)
+    if (EMA && ema_rate_dev) ema_rate = ema_rate_dev[0];
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float w = theta[i];
-        adam_tf_update(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale), lr_t, b1, b2, eps);
+        const float wn = adam_tf_update(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale), lr_t, b1, b2, eps);
+        if (EMA) ema_update(shadow, i, wn, ema_rate);
     }
 }
 
@@ -426,10 +444,13 @@ __global__ __launch_bounds__(256) void grad_norms_stage2(const int64_t *segments
 }
 
 // The optimiser launch behind ds_grad_norms: chunk by chunk, g_eff * factors[seg] into adam_tf_update.  flags[1] set: nothing
-// is written but flags[2], the count of skipped steps, which workgroup 0 raises by one.
-__global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float *theta, const float *g, float *m, float *v, int64_t n,
-                                                              int64_t n_wd, float wd, float grad_scale, float lr_t,
-                                                              const float *lr_t_dev, float b1, float b2, float eps,
+// is written but flags[2], the count of skipped steps, which workgroup 0 raises by one.  EMA = true (ds_adam_tf_clipped_ema):
+// the shadow update behind every element's Adam update, pad elements included; a skipped step leaves the shadows alone too.
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float *theta, const float *g, float *m, float *v, float *shadow,
+                                                              int64_t n, int64_t n_wd, float wd, float grad_scale, float lr_t,
+                                                              const float *lr_t_dev, float ema_rate,
+                                                              const float *ema_rate_dev, float b1, float b2, float eps,
                                                               const int64_t *segments, int nseg, const int64_t *chunks,
                                                               int nchunks, const float *factors, int *flags) {
     if (flags[kFlagSkip]) {
@@ -437,6 +458,7 @@ __global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float *theta, cons
         return;
     }
     if (lr_t_dev) lr_t = lr_t_dev[0];
+    if (EMA && ema_rate_dev) ema_rate = ema_rate_dev[0];
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const ClipChunk q = clip_chunk(segments, nseg, chunks, c, n);
         if (!q.ok) continue;
@@ -445,7 +467,9 @@ __global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float *theta, cons
         for (int64_t j = threadIdx.x; j < q.count; j += 256) {
             const int64_t i = clip_flat(q, j);
             const float w = theta[i];
-            adam_tf_update(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale) * f, lr_t, b1, b2, eps);
+            const float wn = adam_tf_update(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale) * f, lr_t, b1, b2,
+                                            eps);
+            if (EMA) ema_update(shadow, i, wn, ema_rate);
         }
     }
 }
@@ -690,9 +714,21 @@ extern "C" int ds_adam_tf(float *theta, const float *g, float *m, float *v, int6
                           float grad_scale, float lr_t, const float *lr_t_dev, float beta1, float beta2, float eps,
                           void *stream) {
     DS_REQUIRE(theta && g && m && v && n > 0 && n_wd >= 0 && n_wd <= n, "ds_adam_tf: bad argument");
-    hipLaunchKernelGGL(adam_tf_kernel, dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
-                       n, n_wd, wd, grad_scale, lr_t, lr_t_dev, beta1, beta2, eps);
+    hipLaunchKernelGGL(adam_tf_kernel<false>, dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
+                       (float *)nullptr, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, 0.f, (const float *)nullptr, beta1, beta2,
+                       eps);
     return ds::check_launch("ds_adam_tf");
+}
+
+extern "C" int ds_adam_tf_ema(float *theta, const float *g, float *m, float *v, float *shadow, int64_t n, int64_t n_wd,
+                              float wd, float grad_scale, float lr_t, const float *lr_t_dev, float ema_rate,
+                              const float *ema_rate_dev, float beta1, float beta2, float eps, void *stream) {
+    DS_REQUIRE(theta && g && m && v && n > 0 && n_wd >= 0 && n_wd <= n, "ds_adam_tf_ema: bad argument");
+    DS_REQUIRE(shadow, "ds_adam_tf_ema: null shadow");
+    DS_REQUIRE(ema_rate >= 0.f && ema_rate <= 1.f, "ds_adam_tf_ema: ema_rate must lie in [0, 1] (got %g)", (double)ema_rate);
+    hipLaunchKernelGGL(adam_tf_kernel<true>, dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
+                       shadow, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, ema_rate, ema_rate_dev, beta1, beta2, eps);
+    return ds::check_launch("ds_adam_tf_ema");
 }
 
 extern "C" int ds_grad_norms(const float *theta, const float *g, int64_t n, int64_t n_wd, float wd, float grad_scale,
@@ -719,10 +755,27 @@ extern "C" int ds_adam_tf_clipped(float *theta, const float *g, float *m, float 
     DS_REQUIRE(theta && g && m && v && n > 0 && n_wd >= 0 && n_wd <= n, "ds_adam_tf_clipped: bad argument");
     DS_REQUIRE(segments && chunks && nseg > 0 && nchunks > 0, "ds_adam_tf_clipped: empty segment or chunk table");
     DS_REQUIRE(factors && flags, "ds_adam_tf_clipped: null factors or flags");
-    hipLaunchKernelGGL(adam_tf_clipped_kernel, dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream, theta, g,
-                       m, v, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, beta1, beta2, eps, segments, nseg, chunks, nchunks,
-                       factors, flags);
+    hipLaunchKernelGGL(adam_tf_clipped_kernel<false>, dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream,
+                       theta, g, m, v, (float *)nullptr, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, 0.f, (const float *)nullptr,
+                       beta1, beta2, eps, segments, nseg, chunks, nchunks, factors, flags);
     return ds::check_launch("ds_adam_tf_clipped");
+}
+
+extern "C" int ds_adam_tf_clipped_ema(float *theta, const float *g, float *m, float *v, float *shadow, int64_t n, int64_t n_wd,
+                                      float wd, float grad_scale, float lr_t, const float *lr_t_dev, float ema_rate,
+                                      const float *ema_rate_dev, float beta1, float beta2, float eps, const int64_t *segments,
+                                      int32_t nseg, const int64_t *chunks, int32_t nchunks, const float *factors,
+                                      int32_t *flags, void *stream) {
+    DS_REQUIRE(theta && g && m && v && n > 0 && n_wd >= 0 && n_wd <= n, "ds_adam_tf_clipped_ema: bad argument");
+    DS_REQUIRE(segments && chunks && nseg > 0 && nchunks > 0, "ds_adam_tf_clipped_ema: empty segment or chunk table");
+    DS_REQUIRE(factors && flags, "ds_adam_tf_clipped_ema: null factors or flags");
+    DS_REQUIRE(shadow, "ds_adam_tf_clipped_ema: null shadow");
+    DS_REQUIRE(ema_rate >= 0.f && ema_rate <= 1.f, "ds_adam_tf_clipped_ema: ema_rate must lie in [0, 1] (got %g)",
+               (double)ema_rate);
+    hipLaunchKernelGGL(adam_tf_clipped_kernel<true>, dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream,
+                       theta, g, m, v, shadow, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, ema_rate, ema_rate_dev, beta1, beta2,
+                       eps, segments, nseg, chunks, nchunks, factors, flags);
+    return ds::check_launch("ds_adam_tf_clipped_ema");
 }
 
 extern "C" int ds_grad_accumulate(float *acc, float *g, int64_t n, int32_t mode, void *stream) {

@@ -5,7 +5,7 @@ import numpy as np
 
 from ..net import SentimentNet
 from ..feature_cache import check_feature_cache_config
-from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, run_training
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, run_training
 
 _RANDOM_SEED = 0
 _CONFIG = {'mode': 'train',
@@ -53,6 +53,7 @@ def get_init_fn(checkpoints_dir, model_name=None):
 class ImageModel(SyntheticInput):
     def __init__(self, config, nb_emotions=15, device="cuda", **net_kw):
         self.config = config
+        ema_net_kwargs(config)      # (a bad moving_average_decay is refused before anything touches the device)
         if config.get('final_endpoint', 'Mixed_5c') != 'Mixed_5c':
             raise NotImplementedError("final_endpoint must be Mixed_5c")
         self.learning_rate = config['initial_lr']
@@ -64,6 +65,8 @@ class ImageModel(SyntheticInput):
         if "dtype" in config:
             net_kw.setdefault("dtype", config["dtype"])
         for key, value in clip_net_kwargs(config).items():      # gradient clipping / the non-finite guard (training.py)
+            net_kw.setdefault(key, value)
+        for key, value in ema_net_kwargs(config).items():      # moving averages of the trained variables (training.py)
             net_kw.setdefault(key, value)
         self.net = SentimentNet(mode="image", nb_emotions=self.nb_emotions, device=device, **net_kw)
         self.net.initialize(seed=config.get('seed', 1))

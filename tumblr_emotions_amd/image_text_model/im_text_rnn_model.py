@@ -8,7 +8,7 @@ from ..image_model.im_model import get_init_fn
 from ..net import SentimentNet
 from ..text_model.text_preprocessing import resolve_embedding
 from ..feature_cache import check_feature_cache_config
-from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, run_training
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, run_training
 
 _POST_SIZE = 50
 _CONFIG = {'mode': 'train',
@@ -28,6 +28,7 @@ _CONFIG = {'mode': 'train',
 class DeepSentiment(SyntheticInput):
     def __init__(self, config, nb_emotions=15, embedding=None, device="cuda", **net_kw):
         self.config = config
+        ema_net_kwargs(config)      # (a bad moving_average_decay is refused before anything touches the device)
         if config.get('final_endpoint', 'Mixed_5c') != 'Mixed_5c':
             raise NotImplementedError("final_endpoint must be Mixed_5c")
         self.learning_rate = config['initial_lr']
@@ -43,6 +44,8 @@ class DeepSentiment(SyntheticInput):
             net_kw.setdefault("dtype", config["dtype"])
         for key, value in clip_net_kwargs(config).items():      # gradient clipping / the non-finite guard (training.py)
             net_kw.setdefault(key, value)
+        for key, value in ema_net_kwargs(config).items():      # moving averages of the trained variables (training.py)
+            net_kw.setdefault(key, value)
         self.net = SentimentNet(mode="joint", nb_emotions=self.nb_emotions,
                                 im_features_size=config['im_features_size'], rnn_size=config['rnn_size'],
                                 fc_size=config['fc_size'], vocab_size=vocab, embedding_dim=dim, post_size=post,
@@ -50,6 +53,7 @@ class DeepSentiment(SyntheticInput):
         self.net.initialize(seed=config.get('seed', 1))
         if embedding is not None:
             self.net.store.view("Text/W_embedding").copy_(torch.from_numpy(embedding))
+            self.net.store.reset_ema()          # (a trainable table's moving average starts at the assigned table)
         self.embedding = self.net.store.view("Text/W_embedding")
         self.logits = None
 
@@ -97,7 +101,11 @@ def _restored_validation_model(checkpoint_dir, config):
     path = latest_checkpoint(checkpoint_dir)
     if path is None:
         raise FileNotFoundError("no checkpoint in %s" % checkpoint_dir)
-    load_checkpoint(model, path)
+    # config['moving_average_decay']: the analyses run on the averaged variables, as slim's eval does when its flag is set
+    if model.config.get('moving_average_decay') is not None:
+        load_checkpoint(model, path, averaged=True)
+    else:
+        load_checkpoint(model, path)
     return model
 
 

@@ -9,6 +9,7 @@ Data-parallel: gradients are summed over ranks with RCCL all-reduce 
 buckets of the flat gradient buffer and scaled by 1/world inside the Adam kernel; the L2 term is
 applied once, locally, after the reduction (slim/deployment/model_deploy.py:221-223,301-302).
 """
+import contextlib
 import math
 
 import numpy as np
@@ -40,15 +41,40 @@ def check_clip_config(clip_gradient_norm=None, clip_global_norm=None):
     return ops.CLIP_NONE, 0.0
 
 
+def check_ema_config(decay=None):
+    """moving_average_decay as a float, or None when it is not given; needs no device.  slim's --moving_average_decay
+    (train_image_classifier.py:157): a float with 0 < decay < 1.  ValueError for anything else (a bool is not a number)."""
+    if decay is None:
+        return None
+    if isinstance(decay, (bool, np.bool_)) or not isinstance(decay, (float, np.floating)) or not 0.0 < decay < 1.0:
+        raise ValueError("moving_average_decay must be a float with 0 < decay < 1, not %r" % (decay,))
+    return float(decay)
+
+
+def ema_decay(decay, t):
+    """decay_t of update t = 1, 2, ... as the fp32 number TF computes with: min(decay, (1 + t) / (10 + t)), what
+    tf.train.ExponentialMovingAverage(decay, num_updates=t) uses; the min is taken in double, then rounded once."""
+    return np.float32(min(float(decay), (1.0 + t) / (10.0 + t)))
+
+
+def ema_rate(decay, t):
+    """1 - decay_t, formed in fp32 as TF forms it: the factor of (shadow - variable) in update t."""
+    return np.float32(1.0) - ema_decay(decay, t)
+
+
 class SentimentNet:
     def __init__(self, mode="joint", nb_emotions=15, im_features_size=256, rnn_size=512, fc_size=512,
                  vocab_size=10000, embedding_dim=300, post_size=32, image_size=224, dropout_keep_prob=0.8,
                  trainable_bn_beta=True, device="cuda", process_group=None, overlap_comm=True,
                  concurrent_towers=True, train_all=False, trainable_embedding=False, dtype="f32",
                  force_dp_buckets=False, sync_bn=False, frozen_bn=False, clip_gradient_norm=None, clip_global_norm=None,
-                 skip_nonfinite_steps=False):
+                 skip_nonfinite_steps=False, moving_average_decay=None):
         assert mode in ("joint", "image", "text")
         self.dtype = dtype
+        # moving averages of the trained variables (opt-in, DESIGN.md 7.15); refused before anything touches the device
+        self.ema_decay = check_ema_config(moving_average_decay)
+        if self.ema_decay is not None and dtype != "f32":
+            raise NotImplementedError("moving_average_decay is implemented for the fp32 configuration, not %r" % dtype)
         # gradient clipping and the non-finite guard (opt-in, DESIGN.md 7.13); refused before anything touches the device
         self.clip_mode, self.clip_norm = check_clip_config(clip_gradient_norm, clip_global_norm)
         self.skip_nonfinite_steps = bool(skip_nonfinite_steps)
@@ -85,6 +111,11 @@ class SentimentNet:
             self.head = TextHeadEngine(self.store, rnn_size, nb_emotions, device)
         self.store.finalize()
         st = self.store
+        self.ema_rate_dev = None
+        self._averaged = False       # inside averaged_weights(): theta holds the averages, store.ema the variables
+        if self.ema_decay is not None:
+            st.enable_ema()
+            self.ema_rate_dev = torch.zeros(1, device=self.device)
         self.step = 0
         self.frozen_l2_sumsq = 0.0
         self.loss_buf = torch.zeros(1, device=self.device)
@@ -210,8 +241,78 @@ class SentimentNet:
             sd[k] = sd[k][:, :, :3, :].copy()
         return sd
 
+    # ---- moving averages of the trained variables -----------------------------------
+    def _need_averages(self, what):
+        if self.store.ema is None:
+            raise RuntimeError("%s needs moving_average_decay: this net keeps no moving averages" % what)
+
+    def averages_state_dict(self):
+        """{tf_name: array} of the moving averages of the TRAINABLE variables, split and trimmed as state_dict() does (the
+        block-input 1x1 convs under their own names, the stem with 3 inputs).  Inside averaged_weights() too these are the
+        averages, not the variables.  load_averages_state_dict is the inverse."""
+        self._need_averages("averages_state_dict()")
+        torch.cuda.synchronize()
+        if self._averaged:      # (exchanged: theta holds them)
+            names = self._trainable_tf_names()
+            sd = {n: v for n, v in self.store.state_dict().items() if n in names}
+        else:
+            sd = self.store.state_dict(which="ema")
+        k ="InceptionV1/Conv2d_1a_7x7/weights"
+        if k in sd:
+            sd[k] = sd[k][:, :, :3, :].copy()
+        return sd
+
+    def _trainable_tf_names(self):
+        out = set()
+        for e in self.store.entries.values():
+            if e.trainable:
+                out.update([n for (n, _, _) in e.columns] if e.columns else [e.name])
+        return out
+
+    def load_averages_state_dict(self, sd, strict=True):
+        """Moving averages from {tf_name: array} (what averages_state_dict returns; a checkpoint's 'moving_averages')."""
+        self._need_averages("load_averages_state_dict()")
+        if self._averaged:
+            raise RuntimeError("load_averages_state_dict inside averaged_weights()")
+        sd = dict(sd)
+        k = "InceptionV1/Conv2d_1a_7x7/weights"
+        if k in sd and k in self._trainable_tf_names() and np.asarray(sd[k]).shape[2] == 3:
+            w = np.zeros((7, 7, 4, 64), np.float32)
+            w[:, :, :3, :] = np.asarray(sd[k])
+            sd[k] = w
+        return self.store.load_state_dict(sd, strict, which="ema")
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """with net.averaged_weights(): predict, forward, eval_gradients, integrated_gradients, input_gradient and
+        image_features see the moving averages in place of the trainable variables (what slim's eval restores with
+        variables_to_restore).  The CONTENTS of store.theta and store.ema are exchanged -- the engines hold addresses into
+        theta, which stay -- and exchanged back on exit, so both buffers get their old bits back.  Around each exchange what
+        an optimiser step invalidates is invalidated (the fused forward's prepared statistics) and nothing more: the frozen
+        filters' prepared copies and a captured step stay valid.  train_step, capture_step and a nested averaged_weights()
+        raise RuntimeError inside."""
+        self._need_averages("averaged_weights()")
+        if self._averaged:
+            raise RuntimeError("averaged_weights() is already entered: it does not nest")
+        self._exchange_averages()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._exchange_averages()
+            self._averaged = False
+
+    def _exchange_averages(self):
+        st = self.store
+        tmp = st.theta.clone()
+        st.theta.copy_(st.ema)
+        st.ema.copy_(tmp)
+        if self.image is not None:
+            self.image.invalidate_fused()
+
     def after_load(self):
-        """L2 of the frozen conv weights is a constant of the run: sum it once."""
+        """L2 of the frozen conv weights is a constant of the run: sum it once.  The moving averages start at the variables."""
+        self.store.reset_ema()
         tot = 0.0
         for e in self.store.entries.values():
             if (not e.trainable) and e.name.endswith("/weights"):
@@ -537,6 +638,8 @@ class SentimentNet:
         is refused, before anything is enqueued or counted); the step is the image step's, bit for bit."""
         if "features" in batch:
             self.check_feature_batch(batch)
+        if self._averaged:
+            raise RuntimeError("train_step inside averaged_weights(): the variables are exchanged for their moving averages")
         if type(num_clones) is not int or num_clones != 1:
             return self._train_step_clones(batch, lr, dropout_mask, seed, num_clones, after_clone)
         self._clone_count = 1
@@ -549,6 +652,8 @@ class SentimentNet:
                 # replay of the captured step: only the two per-step scalars change, and they live on the device
                 self.seed_dev.fill_(seed)
                 self.lr_t_dev.fill_(lr_t)
+                if self.ema_rate_dev is not None:
+                    self.ema_rate_dev.fill_(float(ema_rate(self.ema_decay, self.step)))
                 self._graph.replay()
                 return self.loss_buf.view(())
             if self._graph_key[-2:] != self._batch_key(batch, dropout_mask)[-2:]:
@@ -559,14 +664,22 @@ class SentimentNet:
         self._optimise(grad_scale, lr_t)
         return self.loss_buf.view(())
 
-    def _optimise(self, grad_scale, lr_t, lr_t_dev=None):
+    def _optimise(self, grad_scale, lr_t, lr_t_dev=None, ema_rate_dev=None):
         """The optimiser behind a step's gradients (all-reduced and clone-summed in store.grad): one ds_adam_tf launch -- or,
         with clip_gradient_norm / clip_global_norm / skip_nonfinite_steps, the norm launches (ds_grad_norms) and the Adam launch
         that reads their factors and skip flag from device memory (ds_adam_tf_clipped).  Nothing synchronises; store.grad is
         only read.  Under data parallelism every rank reduces the same summed buffer with the same kernels, so the ranks
-        clip and skip alike."""
+        clip and skip alike.
+        With moving_average_decay the Adam launch is its _ema twin (ds_adam_tf_ema / ds_adam_tf_clipped_ema): the same bits in
+        theta, m and v, and store.ema moved towards the new theta by the rate of step `self.step` (ema_rate_dev: read from
+        device memory instead, the captured step) in the same pass."""
         st = self.store
+        rate = 0.0 if self.ema_decay is None else float(ema_rate(self.ema_decay, max(self.step, 1)))
         if not self.clip_active:
+            if self.ema_decay is not None:
+                ops.adam_tf_ema(st.theta, st.grad, st.m, st.v, st.ema, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale,
+                                lr_t, rate, ADAM_B1, ADAM_B2, ADAM_EPS, lr_t_dev=lr_t_dev, ema_rate_dev=ema_rate_dev)
+                return
             ops.adam_tf(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
                         ADAM_B1, ADAM_B2, ADAM_EPS, lr_t_dev=lr_t_dev)
             return
@@ -574,6 +687,11 @@ class SentimentNet:
         partials, sumsq, factors, flags = self.clip_state
         ops.grad_norms(st.theta, st.grad, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, seg, chunks, self.clip_mode,
                        self.clip_norm, self.skip_nonfinite_steps, partials, sumsq, factors, flags)
+        if self.ema_decay is not None:
+            ops.adam_tf_clipped_ema(st.theta, st.grad, st.m, st.v, st.ema, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY,
+                                    grad_scale, lr_t, rate, ADAM_B1, ADAM_B2, ADAM_EPS, seg, chunks, factors, flags,
+                                    lr_t_dev=lr_t_dev, ema_rate_dev=ema_rate_dev)
+            return
         ops.adam_tf_clipped(st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, lr_t,
                             ADAM_B1, ADAM_B2, ADAM_EPS, seg, chunks, factors, flags, lr_t_dev=lr_t_dev)
 
@@ -756,6 +874,8 @@ class SentimentNet:
         of ~900 kernel launches, which is what bounds the step below ~64 samples per GPU.  Per-step scalars (Adam's
         lr_t, the dropout seed) are read from device memory.  Single rank only: with data parallelism the RCCL
         all-reduce stays outside a graph and the eager step is used."""
+        if self._averaged:
+            raise RuntimeError("capture_step inside averaged_weights(): the variables are exchanged for their moving averages")
         if type(num_clones) is not int or num_clones != 1:
             if self.check_clones(num_clones) > 1:
                 raise NotImplementedError("capture_step with num_clones = %d: a step of several clones is not captured"
@@ -767,7 +887,8 @@ class SentimentNet:
         st = self.store
         # eager warm-up (allocates every buffer, builds every plan) on a snapshot of the optimiser state, so that
         # capturing has no side effect on the variables, the Adam slots or the BatchNorm moving statistics
-        state = (st.theta, st.m, st.v, st.frozen) + (() if self.clip_state is None else (self.clip_state[3],))
+        state = (st.theta, st.m, st.v, st.frozen) + (() if self.clip_state is None else (self.clip_state[3],)) + \
+            (() if st.ema is None else (st.ema,))      # (the warm-up's lr is 0, but its step would still move the averages)
         keep = [b.clone() for b in state]      # (the guard's count of skipped steps is state too)
         if self.image is not None and self.image.B != batch["images"].shape[0]:
             self.image.alloc(batch["images"].shape[0])
@@ -795,7 +916,7 @@ class SentimentNet:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._step_body(batch, dropout_mask, 0, self.loss_buf)      # (the seed of a replay is seed_dev's)
-            self._optimise(1.0, 0.0, lr_t_dev=self.lr_t_dev)
+            self._optimise(1.0, 0.0, lr_t_dev=self.lr_t_dev, ema_rate_dev=self.ema_rate_dev)
         self._graph, self._graph_key = g, self._batch_key(batch, dropout_mask)
         return True
 

@@ -1043,6 +1043,27 @@ def adam_tf_clipped(theta, g, m, v, n, n_wd, wd, grad_scale, lr_t, b1, b2, eps, 
                                               _stream()), "ds_adam_tf_clipped")
 
 
+def adam_tf_ema(theta, g, m, v, shadow, n, n_wd, wd, grad_scale, lr_t, ema_rate, b1, b2, eps, lr_t_dev=None,
+                ema_rate_dev=None):
+    """ds_adam_tf plus shadow -= (shadow - theta_new) * ema_rate in the same pass (ds_adam_tf_ema)."""
+    assert shadow.dtype == torch.float32 and shadow.numel() >= n
+    _lib.check(_lib.load().ds_adam_tf_ema(_p(theta), _p(g), _p(m), _p(v), _p(shadow), n, n_wd, wd, grad_scale, lr_t,
+                                          _p(lr_t_dev), ema_rate, _p(ema_rate_dev), b1, b2, eps, _stream()), "ds_adam_tf_ema")
+
+
+def adam_tf_clipped_ema(theta, g, m, v, shadow, n, n_wd, wd, grad_scale, lr_t, ema_rate, b1, b2, eps, segments, chunks,
+                        factors, flags, lr_t_dev=None, ema_rate_dev=None):
+    """ds_adam_tf_clipped plus the shadow update of ds_adam_tf_ema; a skipped step leaves the shadows alone too."""
+    nseg, nchunks = segments.shape[0], chunks.shape[0]
+    assert shadow.dtype == torch.float32 and shadow.numel() >= n
+    assert factors.dtype == torch.float32 and factors.numel() >= nseg + 1 and flags.dtype == torch.int32 and flags.numel() >= 4
+    assert segments.dtype == torch.int64 and chunks.dtype == torch.int64 and segments.shape[1] == 8 and chunks.shape[1] == 4
+    _lib.check(_lib.load().ds_adam_tf_clipped_ema(_p(theta), _p(g), _p(m), _p(v), _p(shadow), n, n_wd, wd, grad_scale, lr_t,
+                                                  _p(lr_t_dev), ema_rate, _p(ema_rate_dev), b1, b2, eps, _p(segments), nseg,
+                                                  _p(chunks), nchunks, _p(factors), _p(flags), _stream()),
+               "ds_adam_tf_clipped_ema")
+
+
 def grad_accumulate(acc, g, n, mode):
     """Clone-gradient accumulation over the first n floats of two flat buffers: mode 0 acc = g, 1 acc = acc + g,
     2 g = acc + g (the running sum is the left operand; n % 4 == 0, 16-byte aligned)."""

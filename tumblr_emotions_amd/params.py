@@ -111,7 +111,19 @@ class ParamStore:
         self.frozen = torch.zeros(max(off, 4), dtype=torch.float32, device=self.device)
         self.clip_names, self.clip_segments, self.clip_chunks = build_clip_tables(tr, n_tr)
         self._clip_dev = None
+        self.ema = None      # moving averages of the trainable range, laid out like theta (enable_ema: only when asked for)
         self.finalized = True
+
+    def enable_ema(self):
+        """Allocate the shadow buffer of the trainable variables (SentimentNet(moving_average_decay=...))."""
+        if self.ema is None:
+            self.ema = self.theta.clone()
+        return self.ema
+
+    def reset_ema(self):
+        """shadow = variable, what TF's initialiser of a shadow variable does."""
+        if self.ema is not None:
+            self.ema.copy_(self.theta)
 
     def clip_tables(self):
         """(segments, chunks) of the gradient-norm kernels as int64 tensors on the store's device (copied there once)."""
@@ -152,14 +164,17 @@ class ParamStore:
         return out
 
     def slot_view(self, name, which):
-        """View of an Adam slot ('m' / 'v') of a trainable variable."""
+        """View of an Adam slot ('m' / 'v') or of the moving average ('ema') of a trainable variable."""
         e = self.entries[name]
-        assert e.trainable
+        assert e.trainable and which in ("m", "v", "ema")
+        if which == "ema" and self.ema is None:
+            raise RuntimeError("this store keeps no moving averages (moving_average_decay is not set)")
         return getattr(self, which)[e.offset:e.offset + e.numel].view(e.shape)
 
     def load_state_dict(self, sd, strict=True, which="value"):
         """sd: {tf_name: array-like}.  Fused tensors are assembled from their column ranges.
-        which='value' loads variables; 'm' / 'v' load the Adam slots of the trainable ones."""
+        which='value' loads variables; 'm' / 'v' load the Adam slots of the trainable ones, 'ema' their moving averages
+        (the inverse of state_dict(which='ema'))."""
         seen = set()
         for e in self.entries.values():
             if which != "value" and not e.trainable:
@@ -181,12 +196,14 @@ class ParamStore:
                 raise KeyError(e.name)
         return seen
 
-    def state_dict(self, grads=False):
+    def state_dict(self, grads=False, which="value"):
+        """which='ema': the moving averages of the trainable variables in place of the variables (trainable names only)."""
         out = {}
         for e in self.entries.values():
-            if grads and not e.trainable:
+            if (grads or which != "value") and not e.trainable:
                 continue
-            t = (self.grad_view(e.name) if grads else self.view(e.name)).detach().cpu()
+            t = self.grad_view(e.name) if grads else (self.view(e.name) if which == "value" else self.slot_view(e.name, which))
+            t = t.detach().cpu()
             if e.columns:
                 for (n, c0, c1) in e.columns:
                     out[n] = t[..., c0:c1].contiguous().numpy()

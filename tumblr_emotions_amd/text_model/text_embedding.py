@@ -4,7 +4,7 @@ import torch
 
 from ..net import SentimentNet
 from .text_preprocessing import resolve_embedding
-from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, run_training
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, run_training
 
 _RANDOM_SEED = 0
 _CONFIG = {'mode': 'train',
@@ -22,6 +22,7 @@ _POST_SIZE = 50                                 # datasets/convert_to_dataset.py
 class TextModel(SyntheticInput):
     def __init__(self, config, nb_emotions=15, embedding=None, device="cuda", **net_kw):
         self.config = config
+        ema_net_kwargs(config)      # (a bad moving_average_decay is refused before anything touches the device)
         if config.get('frozen_bn'):
             raise ValueError("config['frozen_bn']: the text model has no BatchNorm")
         self.learning_rate = config['initial_lr']
@@ -37,11 +38,14 @@ class TextModel(SyntheticInput):
             net_kw.setdefault("dtype", config["dtype"])
         for key, value in clip_net_kwargs(config).items():      # gradient clipping / the non-finite guard (training.py)
             net_kw.setdefault(key, value)
+        for key, value in ema_net_kwargs(config).items():      # moving averages of the trained variables (training.py)
+            net_kw.setdefault(key, value)
         self.net = SentimentNet(mode="text", nb_emotions=self.nb_emotions, rnn_size=config['rnn_size'],
                                 vocab_size=vocab, embedding_dim=dim, post_size=post, device=device, **net_kw)
         self.net.initialize(seed=config.get('seed', 1))
         if embedding is not None:               # the step-0 embedding_init assign (:131-132)
             self.net.store.view("Text/W_embedding").copy_(torch.from_numpy(embedding))
+            self.net.store.reset_ema()          # (a trainable table's moving average starts at the assigned table)
         self.embedding = self.net.store.view("Text/W_embedding")
         self.logits = None
 

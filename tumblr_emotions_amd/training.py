@@ -10,6 +10,7 @@ Behaviour kept from the reference (image_text_model/im_text_rnn_model.py:107-169
   * prints `Finished training. Last batch loss {:.3f}`                                  :169
 The per-step work itself is SentimentNet.train_step (HIP kernels).
 """
+import contextlib
 import json
 import os
 import shutil
@@ -65,6 +66,22 @@ def clip_net_kwargs(config):
     return kw
 
 
+def ema_net_kwargs(config):
+    """config['moving_average_decay'] = d as a SentimentNet argument; needs no device.  slim's
+    --moving_average_decay: train_* keep moving averages of the trained variables (decay min(d, (1 + t) / (10 + t))) and
+    write them into every checkpoint; evaluate_*, the analyses and class_visualisation given the key restore the averages
+    in place of the variables, as slim's eval does when its flag is set.  ValueError unless d is a float with 0 < d < 1;
+    with a config['dtype'] other than 'f32' a NotImplementedError."""
+    from .net import check_ema_config
+    d = check_ema_config(config.get("moving_average_decay"))
+    if d is None:
+        return {}
+    if config.get("dtype", "f32") != "f32":
+        raise NotImplementedError("config['moving_average_decay'] with config['dtype'] = %r: moving averages are implemented "
+                                  "for the fp32 configuration" % (config["dtype"],))
+    return {"moving_average_decay": d}
+
+
 def _log_gradient_norms(net, train_dir, step):
     """One line of <train_dir>/gradients.jsonl: the step, the global norm, the factor(s), the skipped count, the norms."""
     gn = net.grad_norms()
@@ -88,9 +105,12 @@ def _write_checkpoint(model, path, step):
     net = model.net
     torch.cuda.synchronize()
     # plain tensors / numbers / strings only, so that the file loads with weights_only=True
-    torch.save({"variables": {k: torch.from_numpy(v) for k, v in net.state_dict().items()},
-                "adam_m": net.store.m.cpu(), "adam_v": net.store.v.cpu(), "global_step": int(step),
-                "config": json.dumps(model.config, default=str)}, path)
+    ck = {"variables": {k: torch.from_numpy(v) for k, v in net.state_dict().items()},
+          "adam_m": net.store.m.cpu(), "adam_v": net.store.v.cpu(), "global_step": int(step),
+          "config": json.dumps(model.config, default=str)}
+    if net.store.ema is not None:      # moving_average_decay: the averages of the trainable variables, under their TF names
+        ck["moving_averages"] = {k: torch.from_numpy(v) for k, v in net.averages_state_dict().items()}
+    torch.save(ck, path)
 
 
 def save_checkpoint(model, train_dir, step):
@@ -116,7 +136,10 @@ class Validator:
     False), which writes no variable, moving statistic, pivot or step counter, into a freshly reset StreamingMetrics, and
     appends result() + global_step + learning_rate to <train_dir>/validation.jsonl.  config['keep_best']: an accuracy strictly
     above the best so far also writes model.best.pt (what save_checkpoint writes; the `checkpoint` index is left alone, so
-    latest_checkpoint does not see it) and best.json."""
+    latest_checkpoint does not see it) and best.json.
+    A net with moving averages (config['moving_average_decay']) is validated inside net.averaged_weights(): on the averages,
+    what evaluate_* will score; every line then carries "weights": "averaged".  model.best.pt is written
+    outside the context and holds variables and averages like any other checkpoint."""
 
     def __init__(self, model, train_dir):
         from .metrics import DEFAULT_TOP_K, StreamingMetrics
@@ -135,12 +158,15 @@ class Validator:
     def run(self, step, lr, quiet=False):
         net = self.model.net
         self.metrics.reset()
-        for batch in self.model.validation_batches(self.batches):
-            self.metrics.update(net.predict(batch, is_training=False, fused=self.fused), batch["labels"])
+        averaged = net.store.ema is not None
+        with (net.averaged_weights() if averaged else contextlib.nullcontext()):
+            for batch in self.model.validation_batches(self.batches):
+                self.metrics.update(net.predict(batch, is_training=False, fused=self.fused), batch["labels"])
         res = self.metrics.result()
         _warn_uncounted(res, "validation at step %d" % step)
         with open(os.path.join(self.train_dir, "validation.jsonl"), "a") as f:
-            f.write(json.dumps(dict(res, global_step=step, learning_rate=lr)) + "\n")
+            f.write(json.dumps(dict(res, global_step=step, learning_rate=lr, **({"weights": "averaged"} if averaged else {})))
+                    + "\n")
         if not quiet:
             print("global step %d: validation accuracy = %.4f, loss = %.4f (%d samples)" % (step, res["accuracy"], res["loss"], res["n"]))
         if self.keep_best and (self.best is None or res["accuracy"] > self.best):
@@ -210,9 +236,21 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
     return loss_val
 
 
-def load_checkpoint(model, path):
+def load_checkpoint(model, path, averaged=False):
+    """Restore variables, Adam slots and step.  A net with moving averages also gets the file's 'moving_averages' (a file
+    without them leaves the averages at the variables, where load_state_dict puts them).  averaged=True: the averages are
+    loaded IN PLACE OF the trainable variables -- slim's variables_to_restore in eval_image_classifier.py:141-146; a net with
+    moving averages then starts them there as well -- and a file without them is a KeyError."""
     ck = torch.load(path, map_location="cpu", weights_only=True)       # never unpickles arbitrary objects
-    model.net.load_state_dict({k: v.numpy() for k, v in ck["variables"].items()})
+    variables = {k: v.numpy() for k, v in ck["variables"].items()}
+    averages = ck.get("moving_averages")
+    if averaged:
+        if averages is None:
+            raise KeyError("%s holds no moving averages: it was not trained with config['moving_average_decay']" % path)
+        variables.update({k: v.numpy() for k, v in averages.items()})
+    model.net.load_state_dict(variables)
+    if averages is not None and not averaged and model.net.store.ema is not None:
+        model.net.load_averages_state_dict({k: v.numpy() for k, v in averages.items()})
     model.net.store.m.copy_(ck["adam_m"])
     model.net.store.v.copy_(ck["adam_v"])
     model.net.step = int(ck["global_step"])
@@ -234,7 +272,11 @@ def run_evaluation(model, checkpoint_dir, log_dir, mode, num_evals, batch_fn=Non
     path = latest_checkpoint(checkpoint_dir)
     if path is None:
         raise FileNotFoundError("no checkpoint in %s" % checkpoint_dir)
-    step = load_checkpoint(model, path)
+    # config['moving_average_decay']: score the averaged variables, as slim's eval does when its flag is set
+    if getattr(model, "config", {}).get("moving_average_decay") is not None:
+        step = load_checkpoint(model, path, averaged=True)
+    else:
+        step = load_checkpoint(model, path)
     is_training = mode == "train"
     fused = bool(getattr(model, "config", {}).get("fused_inference", False)) and not is_training
     metrics = None
@@ -296,7 +338,9 @@ class SyntheticInput:
     config['num_clones'] = K (default 1): train_* run K clones per rank and step with config['batch_size'] rows each
     (check_clones_config; the trainers call use_clones() before the first batch); evaluate_* and the analyses ignore it.
     config['clip_gradient_norm'], config['clip_global_norm'], config['skip_nonfinite_steps'], config['log_gradient_norms']:
-    gradient clipping, the non-finite step guard and gradients.jsonl (clip_net_kwargs)."""
+    gradient clipping, the non-finite step guard and gradients.jsonl (clip_net_kwargs).
+    config['moving_average_decay'] = d: moving averages of the trained variables in train_*, restored in place of the
+    variables by evaluate_* and the analyses (ema_net_kwargs)."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
