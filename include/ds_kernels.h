@@ -834,6 +834,44 @@ int ds_adam_tf_clipped_ema(float *theta, const float *g, float *m, float *v, flo
                            float beta1, float beta2, float eps, const int64_t *segments, int32_t nseg, const int64_t *chunks,
                            int32_t nchunks, const float *factors, int32_t *flags, void *stream);
 
+/* slim's --optimizer (train_image_classifier.py) behind the same effective gradient: ONE entry point for kind x {plain,
+ * clipped + guard} x {no averages, averages}.  gi = the g_eff of ds_adam_tf (times factors[seg] in the clipped form), w =
+ * theta[i].  [TF-sem]: TF's training_ops CPU functors restated -- TensorFlow is not in the reference tree, parity unpinned.
+ * Every operation is one fp32 rounding, in this order, never contracted:
+ *   DS_OPT_SGD       ApplyGradientDescent         p = lr*gi; theta = w - p                   (no slot is read or written;
+ *                                                                                            slot0 / slot1 may be NULL)
+ *   DS_OPT_MOMENTUM  ApplyMomentum, no Nesterov   t = momentum*acc; a = t + gi; acc = a; p = lr*a; theta = w - p
+ *                                                 acc = slot0, initialised to 0 (slot1 may be NULL)
+ *   DS_OPT_RMSPROP   ApplyRMSProp                 q = gi*gi; d = q - ms; e = d*(1 - rho); ms' = ms + e; s = sqrtf(ms' + eps);
+ *                                                 nmr = gi*lr; r = nmr/s; t = mom*momentum; mom' = t + r; theta = w - mom'
+ *                                                 ms = slot1, initialised to 1.0; mom = slot0, initialised to 0
+ *   DS_OPT_ADAM      the update of ds_adam_tf with b1 / b2 / eps, slot0 = m, slot1 = v, lr = lr_t (bias-corrected by the
+ *                    host): the bits of the matching ds_adam_tf* call, the kernels are the same instantiations
+ * lr_dev (nullable) overrides lr from device memory, as lr_t_dev does.  shadow non-NULL: the shadow update of ds_adam_tf_ema
+ * behind every element's update, with ema_rate in [0, 1] / ema_rate_dev; theta and the slots keep the bits of the call
+ * without a shadow.  segments .. flags all NULL / 0: the unclipped pass of ds_adam_tf.  All set (the tables and the outputs of
+ * ds_grad_norms): the pass of ds_adam_tf_clipped -- pad elements with factor 1; flags[1] != 0 leaves theta, both slots and
+ * shadow untouched bit for bit and raises flags[2] by one, for every kind.  Some but not all of them set, a NULL theta / g /
+ * descriptor, n <= 0, n_wd outside [0, n], an unknown kind or a slot the kind reads being NULL: DS_ERR_ARG before any launch.
+ * Launch shapes are those of ds_adam_tf / ds_adam_tf_clipped.  Plain vector stores only. */
+enum { DS_OPT_ADAM = 0, DS_OPT_SGD = 1, DS_OPT_MOMENTUM = 2, DS_OPT_RMSPROP = 3 };
+typedef struct {
+    int32_t kind;
+    float lr;                        /* Adam: lr_t (bias-corrected); others: the learning rate */
+    const float *lr_dev;             /* non-NULL: read from device memory (captured step) */
+    float b1, b2, eps;               /* Adam; eps is RMSProp's too */
+    float momentum, rho;             /* Momentum / RMSProp */
+    float *shadow;                   /* NULL: no moving averages */
+    float ema_rate;
+    const float *ema_rate_dev;
+    const int64_t *segments, *chunks;   /* NULL / 0: unclipped */
+    int32_t nseg, nchunks;
+    const float *factors;
+    int32_t *flags;
+} ds_opt_desc;
+int ds_opt_step(const ds_opt_desc *d, float *theta, const float *g, float *slot0, float *slot1, int64_t n, int64_t n_wd,
+                float wd, float grad_scale, void *stream);
+
 /* Clone-gradient accumulation over the flat gradient buffer (slim/deployment/model_deploy.py:414-444, _sum_clones_gradients).
  * mode 0: acc[i] = g[i]            (first clone)
  * mode 1: acc[i] = acc[i] + g[i]   (middle clones)

@@ -159,6 +159,14 @@ class ExampleFields(C.Structure):
                 ("post_id", C.c_int64), ("day", C.c_int64), ("text_len", C.c_int32), ("reserved", C.c_int32)]
 
 
+class OptDesc(C.Structure):
+    """ds_opt_desc"""
+    _fields_ = [("kind", C.c_int32), ("lr", C.c_float), ("lr_dev", C.c_void_p), ("b1", C.c_float), ("b2", C.c_float),
+                ("eps", C.c_float), ("momentum", C.c_float), ("rho", C.c_float), ("shadow", C.c_void_p),
+                ("ema_rate", C.c_float), ("ema_rate_dev", C.c_void_p), ("segments", C.c_void_p), ("chunks", C.c_void_p),
+                ("nseg", C.c_int32), ("nchunks", C.c_int32), ("factors", C.c_void_p), ("flags", C.c_void_p)]
+
+
 _P = C.c_void_p
 _i32, _i64, _f32, _u64 = C.c_int32, C.c_int64, C.c_float, C.c_uint64
 _CD = C.POINTER(ConvDesc)
@@ -282,6 +290,7 @@ SIGNATURES = {
     "ds_adam_tf_ema": (C.c_int, [_P, _P, _P, _P, _P, _i64, _i64, _f32, _f32, _f32, _P, _f32, _P, _f32, _f32, _f32, _P]),
     "ds_adam_tf_clipped_ema": (C.c_int, [_P, _P, _P, _P, _P, _i64, _i64, _f32, _f32, _f32, _P, _f32, _P, _f32, _f32, _f32, _P,
                                          _i32, _P, _i32, _P, _P, _P]),
+    "ds_opt_step": (C.c_int, [C.POINTER(OptDesc), _P, _P, _P, _P, _i64, _i64, _f32, _f32, _P]),
     "ds_grad_accumulate": (C.c_int, [_P, _P, _i64, _i32, _P]),
     "ds_sumsq": (C.c_int, [_P, _i64, _P, _P, _P]),
     "ds_colsum": (C.c_int, [_P, _i64, _i32, _i32, _P, _P, _P]),

@@ -283,6 +283,64 @@ __device__ __forceinline__ float adam_tf_update(float *theta, float *m, float *v
     return wn;
 }
 
+// ---- the other optimisers of slim's --optimizer behind the same effective gradient (ds_opt_step) ---------------------------
+// [TF-sem] TF's training_ops CPU functors restated (TensorFlow is not in the reference tree; parity unpinned).  Every
+// operation below is one fp32 rounding, in this order; nothing is contracted.  slot0 / slot1 are the buffers Adam calls m / v.
+enum { kOptAdam = DS_OPT_ADAM, kOptSgd = DS_OPT_SGD, kOptMomentum = DS_OPT_MOMENTUM, kOptRmsprop = DS_OPT_RMSPROP };
+
+// ApplyGradientDescent: no slot is read or written.
+__device__ __forceinline__ float sgd_tf_update(float *theta, int64_t i, float w, float gi, float lr) {
+#pragma clang fp contract(off)
+    const float p = lr * gi;
+    const float wn = w - p;
+    theta[i] = wn;
+    return wn;
+}
+
+// ApplyMomentum, use_nesterov = False: acc (slot0, starts at 0) = mu * acc + g; theta -= lr * acc.
+__device__ __forceinline__ float momentum_tf_update(float *theta, float *acc, int64_t i, float w, float gi, float lr, float mu) {
+#pragma clang fp contract(off)
+    const float t = mu * acc[i];
+    const float a = t + gi;
+    acc[i] = a;
+    const float p = lr * a;
+    const float wn = w - p;
+    theta[i] = wn;
+    return wn;
+}
+
+// ApplyRMSProp: ms (slot1, starts at 1) += (g^2 - ms) (1 - rho); mom (slot0, starts at 0) = mom * mu + g lr / sqrt(ms + eps);
+// theta -= mom.
+__device__ __forceinline__ float rmsprop_tf_update(float *theta, float *mom, float *ms, int64_t i, float w, float gi, float lr,
+                                                   float mu, float rho, float eps) {
+#pragma clang fp contract(off)
+    const float q = gi * gi;
+    const float msi = ms[i];
+    const float d = q - msi;
+    const float e = d * (1.f - rho);
+    const float msn = msi + e;
+    ms[i] = msn;
+    const float s = sqrtf(msn + eps);
+    const float nmr = gi * lr;
+    const float r = nmr / s;
+    const float t = mom[i] * mu;
+    const float mn = t + r;
+    mom[i] = mn;
+    const float wn = w - mn;
+    theta[i] = wn;
+    return wn;
+}
+
+// The update of kind KIND on element i; lr is Adam's lr_t for kOptAdam, the learning rate otherwise.  Returns the new theta[i].
+template <int KIND>
+__device__ __forceinline__ float opt_update(float *theta, float *slot0, float *slot1, int64_t i, float w, float gi, float lr,
+                                            float b1, float b2, float eps, float mu, float rho) {
+    if (KIND == kOptSgd) return sgd_tf_update(theta, i, w, gi, lr);
+    if (KIND == kOptMomentum) return momentum_tf_update(theta, slot0, i, w, gi, lr, mu);
+    if (KIND == kOptRmsprop) return rmsprop_tf_update(theta, slot0, slot1, i, w, gi, lr, mu, rho, eps);
+    return adam_tf_update(theta, slot0, slot1, i, w, gi, lr, b1, b2, eps);
+}
+
 // tf.train.ExponentialMovingAverage's assign_moving_average on element i, wn = the variable after the update:
 // shadow -= (shadow - wn) * rate -- a difference, a product and a difference, each rounded once (the _ema kernels).
 __device__ __forceinline__ void ema_update(float *shadow, int64_t i, float wn, float rate) {
@@ -293,18 +351,20 @@ __device__ __forceinline__ void ema_update(float *shadow, int64_t i, float wn, f
     shadow[i] = s - p;
 }
 
-// EMA = false: ds_adam_tf (shadow, ema_rate and ema_rate_dev are not read).  EMA = true: ds_adam_tf_ema, the same pass with
-// the shadow update behind every element's Adam update.
-template <bool EMA>
+// The unclipped loop shape of every optimiser kind.  KIND = kOptAdam, EMA = false: ds_adam_tf (shadow, ema_rate and
+// ema_rate_dev are not read).  EMA = true: ds_adam_tf_ema, the same pass with the shadow update behind every element's update.
+// The other kinds (ds_opt_step) read lr_t as the learning rate and m / v as slot0 / slot1.
+template <int KIND, bool EMA>
 __global__ __launch_bounds__(256) void adam_tf_kernel(float *theta, const float *g, float *m, float *v, float *shadow,
                                                       int64_t n, int64_t n_wd, float wd, float grad_scale, float lr_t,
                                                       const float *lr_t_dev, float ema_rate, const float *ema_rate_dev,
-                                                      float b1, float b2, float eps) {
+                                                      float b1, float b2, float eps, float mu, float rho) {
     if (lr_t_dev) lr_t = lr_t_dev[0];         // step size kept on device (hipGraph replay safe)
     if (EMA && ema_rate_dev) ema_rate = ema_rate_dev[0];
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float w = theta[i];
-        const float wn = adam_tf_update(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale), lr_t, b1, b2, eps);
+        const float wn = opt_update<KIND>(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale), lr_t, b1, b2, eps, mu,
+                                          rho);
         if (EMA) ema_update(shadow, i, wn, ema_rate);
     }
 }
@@ -443,16 +503,18 @@ __global__ __launch_bounds__(256) void grad_norms_stage2(const int64_t *segments
         for (int s = threadIdx.x; s < nseg; s += 256) factors[s] = gfac;
 }
 
-// The optimiser launch behind ds_grad_norms: chunk by chunk, g_eff * factors[seg] into adam_tf_update.  flags[1] set: nothing
-// is written but flags[2], the count of skipped steps, which workgroup 0 raises by one.  EMA = true (ds_adam_tf_clipped_ema):
-// the shadow update behind every element's Adam update, pad elements included; a skipped step leaves the shadows alone too.
-template <bool EMA>
+// The optimiser launch behind ds_grad_norms, the clipped loop shape of every kind: chunk by chunk, g_eff * factors[seg] into
+// the per-element update.  flags[1] set: nothing is written but flags[2], the count of skipped steps, which workgroup 0 raises
+// by one.  EMA = true (ds_adam_tf_clipped_ema): the shadow update behind every element's update, pad elements included; a
+// skipped step leaves the shadows alone too.
+template <int KIND, bool EMA>
 __global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float *theta, const float *g, float *m, float *v, float *shadow,
                                                               int64_t n, int64_t n_wd, float wd, float grad_scale, float lr_t,
                                                               const float *lr_t_dev, float ema_rate,
                                                               const float *ema_rate_dev, float b1, float b2, float eps,
-                                                              const int64_t *segments, int nseg, const int64_t *chunks,
-                                                              int nchunks, const float *factors, int *flags) {
+                                                              float mu, float rho, const int64_t *segments, int nseg,
+                                                              const int64_t *chunks, int nchunks, const float *factors,
+                                                              int *flags) {
     if (flags[kFlagSkip]) {
         if (blockIdx.x == 0 && threadIdx.x == 0) flags[kFlagSkipped] = flags[kFlagSkipped] + 1;
         return;
@@ -467,8 +529,8 @@ __global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float *theta, cons
         for (int64_t j = threadIdx.x; j < q.count; j += 256) {
             const int64_t i = clip_flat(q, j);
             const float w = theta[i];
-            const float wn = adam_tf_update(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale) * f, lr_t, b1, b2,
-                                            eps);
+            const float wn = opt_update<KIND>(theta, m, v, i, w, adam_g_eff(g, i, w, n_wd, wd, grad_scale) * f, lr_t, b1, b2,
+                                              eps, mu, rho);
             if (EMA) ema_update(shadow, i, wn, ema_rate);
         }
     }
@@ -714,9 +776,9 @@ extern "C" int ds_adam_tf(float *theta, const float *g, float *m, float *v, int6
                           float grad_scale, float lr_t, const float *lr_t_dev, float beta1, float beta2, float eps,
                           void *stream) {
     DS_REQUIRE(theta && g && m && v && n > 0 && n_wd >= 0 && n_wd <= n, "ds_adam_tf: bad argument");
-    hipLaunchKernelGGL(adam_tf_kernel<false>, dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
+    hipLaunchKernelGGL((adam_tf_kernel<kOptAdam, false>), dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
                        (float *)nullptr, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, 0.f, (const float *)nullptr, beta1, beta2,
-                       eps);
+                       eps, 0.f, 0.f);
     return ds::check_launch("ds_adam_tf");
 }
 
@@ -726,8 +788,8 @@ extern "C" int ds_adam_tf_ema(float *theta, const float *g, float *m, float *v, 
     DS_REQUIRE(theta && g && m && v && n > 0 && n_wd >= 0 && n_wd <= n, "ds_adam_tf_ema: bad argument");
     DS_REQUIRE(shadow, "ds_adam_tf_ema: null shadow");
     DS_REQUIRE(ema_rate >= 0.f && ema_rate <= 1.f, "ds_adam_tf_ema: ema_rate must lie in [0, 1] (got %g)", (double)ema_rate);
-    hipLaunchKernelGGL(adam_tf_kernel<true>, dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
-                       shadow, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, ema_rate, ema_rate_dev, beta1, beta2, eps);
+    hipLaunchKernelGGL((adam_tf_kernel<kOptAdam, true>), dim3(ds::stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, theta, g, m, v,
+                       shadow, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, ema_rate, ema_rate_dev, beta1, beta2, eps, 0.f, 0.f);
     return ds::check_launch("ds_adam_tf_ema");
 }
 
@@ -755,9 +817,9 @@ extern "C" int ds_adam_tf_clipped(float *theta, const float *g, float *m, float 
     DS_REQUIRE(theta && g && m && v && n > 0 && n_wd >= 0 && n_wd <= n, "ds_adam_tf_clipped: bad argument");
     DS_REQUIRE(segments && chunks && nseg > 0 && nchunks > 0, "ds_adam_tf_clipped: empty segment or chunk table");
     DS_REQUIRE(factors && flags, "ds_adam_tf_clipped: null factors or flags");
-    hipLaunchKernelGGL(adam_tf_clipped_kernel<false>, dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((adam_tf_clipped_kernel<kOptAdam, false>), dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream,
                        theta, g, m, v, (float *)nullptr, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, 0.f, (const float *)nullptr,
-                       beta1, beta2, eps, segments, nseg, chunks, nchunks, factors, flags);
+                       beta1, beta2, eps, 0.f, 0.f, segments, nseg, chunks, nchunks, factors, flags);
     return ds::check_launch("ds_adam_tf_clipped");
 }
 
@@ -772,10 +834,67 @@ extern "C" int ds_adam_tf_clipped_ema(float *theta, const float *g, float *m, fl
     DS_REQUIRE(shadow, "ds_adam_tf_clipped_ema: null shadow");
     DS_REQUIRE(ema_rate >= 0.f && ema_rate <= 1.f, "ds_adam_tf_clipped_ema: ema_rate must lie in [0, 1] (got %g)",
                (double)ema_rate);
-    hipLaunchKernelGGL(adam_tf_clipped_kernel<true>, dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((adam_tf_clipped_kernel<kOptAdam, true>), dim3(ds::stream_grid(nchunks, 1)), dim3(256), 0, (hipStream_t)stream,
                        theta, g, m, v, shadow, n, n_wd, wd, grad_scale, lr_t, lr_t_dev, ema_rate, ema_rate_dev, beta1, beta2,
-                       eps, segments, nseg, chunks, nchunks, factors, flags);
+                       eps, 0.f, 0.f, segments, nseg, chunks, nchunks, factors, flags);
     return ds::check_launch("ds_adam_tf_clipped_ema");
+}
+
+// One launch of kind KIND: the clipped loop shape when the descriptor carries tables, the plain one otherwise; either with
+// the shadow update when it carries a shadow.
+template <int KIND>
+static void opt_step_launch(const ds_opt_desc *d, float *theta, const float *g, float *slot0, float *slot1, int64_t n,
+                            int64_t n_wd, float wd, float grad_scale, bool clipped, hipStream_t stream) {
+    const bool ema = d->shadow != nullptr;
+    const float rate = ema ? d->ema_rate : 0.f;
+    const float *rate_dev = ema ? d->ema_rate_dev : nullptr;
+    if (clipped) {
+        const dim3 grid(ds::stream_grid(d->nchunks, 1)), block(256);
+        if (ema)
+            hipLaunchKernelGGL((adam_tf_clipped_kernel<KIND, true>), grid, block, 0, stream, theta, g, slot0, slot1, d->shadow, n,
+                               n_wd, wd, grad_scale, d->lr, d->lr_dev, rate, rate_dev, d->b1, d->b2, d->eps, d->momentum, d->rho,
+                               d->segments, d->nseg, d->chunks, d->nchunks, d->factors, d->flags);
+        else
+            hipLaunchKernelGGL((adam_tf_clipped_kernel<KIND, false>), grid, block, 0, stream, theta, g, slot0, slot1,
+                               (float *)nullptr, n, n_wd, wd, grad_scale, d->lr, d->lr_dev, 0.f, (const float *)nullptr, d->b1,
+                               d->b2, d->eps, d->momentum, d->rho, d->segments, d->nseg, d->chunks, d->nchunks, d->factors,
+                               d->flags);
+        return;
+    }
+    const dim3 grid(ds::stream_grid(n, 256)), block(256);
+    if (ema)
+        hipLaunchKernelGGL((adam_tf_kernel<KIND, true>), grid, block, 0, stream, theta, g, slot0, slot1, d->shadow, n, n_wd, wd,
+                           grad_scale, d->lr, d->lr_dev, rate, rate_dev, d->b1, d->b2, d->eps, d->momentum, d->rho);
+    else
+        hipLaunchKernelGGL((adam_tf_kernel<KIND, false>), grid, block, 0, stream, theta, g, slot0, slot1, (float *)nullptr, n,
+                           n_wd, wd, grad_scale, d->lr, d->lr_dev, 0.f, (const float *)nullptr, d->b1, d->b2, d->eps,
+                           d->momentum, d->rho);
+}
+
+extern "C" int ds_opt_step(const ds_opt_desc *d, float *theta, const float *g, float *slot0, float *slot1, int64_t n,
+                           int64_t n_wd, float wd, float grad_scale, void *stream) {
+    DS_REQUIRE(d, "ds_opt_step: null descriptor");
+    DS_REQUIRE(theta && g && n > 0 && n_wd >= 0 && n_wd <= n, "ds_opt_step: bad argument");
+    DS_REQUIRE(d->kind >= DS_OPT_ADAM && d->kind <= DS_OPT_RMSPROP,
+               "ds_opt_step: kind must be 0 (adam), 1 (sgd), 2 (momentum) or 3 (rmsprop), not %d", (int)d->kind);
+    DS_REQUIRE(d->kind == DS_OPT_SGD || slot0, "ds_opt_step: kind %d needs slot0", (int)d->kind);
+    DS_REQUIRE((d->kind != DS_OPT_ADAM && d->kind != DS_OPT_RMSPROP) || slot1, "ds_opt_step: kind %d needs slot1", (int)d->kind);
+    const bool clipped = d->segments || d->chunks || d->nseg != 0 || d->nchunks != 0 || d->factors || d->flags;
+    if (clipped) {
+        DS_REQUIRE(d->segments && d->chunks && d->nseg > 0 && d->nchunks > 0, "ds_opt_step: empty segment or chunk table");
+        DS_REQUIRE(d->factors && d->flags, "ds_opt_step: null factors or flags");
+    }
+    if (d->shadow)
+        DS_REQUIRE(d->ema_rate >= 0.f && d->ema_rate <= 1.f, "ds_opt_step: ema_rate must lie in [0, 1] (got %g)",
+                   (double)d->ema_rate);
+    const hipStream_t s = (hipStream_t)stream;
+    switch (d->kind) {
+    case DS_OPT_ADAM: opt_step_launch<kOptAdam>(d, theta, g, slot0, slot1, n, n_wd, wd, grad_scale, clipped, s); break;
+    case DS_OPT_SGD: opt_step_launch<kOptSgd>(d, theta, g, slot0, slot1, n, n_wd, wd, grad_scale, clipped, s); break;
+    case DS_OPT_MOMENTUM: opt_step_launch<kOptMomentum>(d, theta, g, slot0, slot1, n, n_wd, wd, grad_scale, clipped, s); break;
+    default: opt_step_launch<kOptRmsprop>(d, theta, g, slot0, slot1, n, n_wd, wd, grad_scale, clipped, s); break;
+    }
+    return ds::check_launch("ds_opt_step");
 }
 
 extern "C" int ds_grad_accumulate(float *acc, float *g, int64_t n, int32_t mode, void *stream) {

@@ -51,6 +51,54 @@ def check_ema_config(decay=None):
     return float(decay)
 
 
+OPTIMIZERS = ("adam", "sgd", "momentum", "rmsprop")
+_SLIM_OPTIMIZERS_NOT_BUILT = ("adadelta", "adagrad", "ftrl")
+# hyper-parameter -> (default, the optimisers that read it); opt_epsilon's default depends on the optimiser (None)
+_OPT_HYPER = {"opt_epsilon": (None, ("adam", "rmsprop")), "momentum": (0.9, ("momentum", "rmsprop")),
+              "rmsprop_decay": (0.9, ("rmsprop",)), "adam_beta1": (ADAM_B1, ("adam",)), "adam_beta2": (ADAM_B2, ("adam",))}
+_OPT_EPSILON = {"adam": ADAM_EPS, "rmsprop": 1.0}
+
+
+def check_optimizer_config(optimizer="adam", opt_epsilon=None, momentum=0.9, rmsprop_decay=0.9, adam_beta1=ADAM_B1,
+                           adam_beta2=ADAM_B2):
+    """The optimiser arguments as {'optimizer': name, 'opt_epsilon', 'momentum', 'rmsprop_decay', 'adam_beta1', 'adam_beta2'}
+    (floats; a hyper-parameter the optimiser does not read is absent); needs no device.  slim's --optimizer block
+    (train_image_classifier.py): 'adam' (the reference's tf.train.AdamOptimizer and the default), 'sgd', 'momentum' (no
+    Nesterov), 'rmsprop' (whose momentum is `momentum`).  opt_epsilon=None is 1e-8 for adam (AdamOptimizer's default) and
+    1.0 for rmsprop (slim's flag default).  ValueError for an unknown name (the four valid ones are listed), for a value that
+    is not a finite number in its range -- 0 <= momentum < 1, 0 < rmsprop_decay < 1, 0 <= adam_beta < 1, opt_epsilon > 0; a
+    bool is not a number -- and for a hyper-parameter moved off its default for an optimiser that does not read it (silently
+    ignored, a sweep over it would measure nothing).  'adadelta', 'adagrad' and 'ftrl' are a NotImplementedError."""
+    if optimizer in _SLIM_OPTIMIZERS_NOT_BUILT:
+        raise NotImplementedError("optimizer %r is not implemented (nor are %s); implemented: %s"
+                                  % (optimizer, ", ".join(repr(o) for o in _SLIM_OPTIMIZERS_NOT_BUILT if o != optimizer),
+                                     ", ".join(OPTIMIZERS)))
+    if not isinstance(optimizer, str) or optimizer not in OPTIMIZERS:
+        raise ValueError("optimizer must be one of %s, not %r" % (", ".join(repr(o) for o in OPTIMIZERS), optimizer))
+    given = {"opt_epsilon": opt_epsilon, "momentum": momentum, "rmsprop_decay": rmsprop_decay, "adam_beta1": adam_beta1,
+             "adam_beta2": adam_beta2}
+    out = {"optimizer": optimizer}
+    for key, x in given.items():
+        default, readers = _OPT_HYPER[key]
+        if x is None and key == "opt_epsilon":
+            if optimizer in readers:
+                out[key] = _OPT_EPSILON[optimizer]
+            continue
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(x):
+            raise ValueError("%s must be a finite number, not %r" % (key, x))
+        if optimizer not in readers:
+            if default is None or float(x) != default:
+                raise ValueError("%s = %r is given, but optimizer %r does not read it (%s)"
+                                 % (key, x, optimizer, " and ".join(repr(o) for o in readers) + " do"))
+            continue
+        ok = x > 0 if key == "opt_epsilon" else 0 < x < 1 if key == "rmsprop_decay" else 0 <= x < 1
+        if not ok:
+            raise ValueError("%s must satisfy %s, not %r" % (key, {"opt_epsilon": "opt_epsilon > 0", "rmsprop_decay":
+                             "0 < rmsprop_decay < 1"}.get(key, "0 <= %s < 1" % key), x))
+        out[key] = float(x)
+    return out
+
+
 def ema_decay(decay, t):
     """decay_t of update t = 1, 2, ... as the fp32 number TF computes with: min(decay, (1 + t) / (10 + t)), what
     tf.train.ExponentialMovingAverage(decay, num_updates=t) uses; the min is taken in double, then rounded once."""
@@ -68,9 +116,17 @@ class SentimentNet:
                  trainable_bn_beta=True, device="cuda", process_group=None, overlap_comm=True,
                  concurrent_towers=True, train_all=False, trainable_embedding=False, dtype="f32",
                  force_dp_buckets=False, sync_bn=False, frozen_bn=False, clip_gradient_norm=None, clip_global_norm=None,
-                 skip_nonfinite_steps=False, moving_average_decay=None):
+                 skip_nonfinite_steps=False, moving_average_decay=None, optimizer="adam", opt_epsilon=None, momentum=0.9,
+                 rmsprop_decay=0.9, adam_beta1=ADAM_B1, adam_beta2=ADAM_B2):
         assert mode in ("joint", "image", "text")
         self.dtype = dtype
+        # the optimiser (slim's --optimizer); refused before anything touches the device.  opt_epsilon=None:
+        # 1e-8 for adam, 1.0 for rmsprop.  Every dtype keeps fp32 variables and steps through the one _optimise below.
+        self.opt = check_optimizer_config(optimizer, opt_epsilon, momentum, rmsprop_decay, adam_beta1, adam_beta2)
+        self.optimizer = self.opt["optimizer"]
+        # adam with AdamOptimizer's defaults: the ds_adam_tf* launches, as before the optimiser could be chosen
+        self._reference_adam = self.opt == {"optimizer": "adam", "opt_epsilon": ADAM_EPS, "adam_beta1": ADAM_B1,
+                                            "adam_beta2": ADAM_B2}
         # moving averages of the trained variables (opt-in); refused before anything touches the device
         self.ema_decay = check_ema_config(moving_average_decay)
         if self.ema_decay is not None and dtype != "f32":
@@ -111,6 +167,8 @@ class SentimentNet:
             self.head = TextHeadEngine(self.store, rnn_size, nb_emotions, device)
         self.store.finalize()
         st = self.store
+        if self.optimizer == "rmsprop":
+            st.v.fill_(1.0)      # RMSPropOptimizer's `rms` slot starts at ones (store.m is its `momentum` slot, at zero)
         self.ema_rate_dev = None
         self._averaged = False       # inside averaged_weights(): theta holds the averages, store.ema the variables
         if self.ema_decay is not None:
@@ -672,9 +730,28 @@ class SentimentNet:
         clip and skip alike.
         With moving_average_decay the Adam launch is its _ema twin (ds_adam_tf_ema / ds_adam_tf_clipped_ema): the same bits in
         theta, m and v, and store.ema moved towards the new theta by the rate of step `self.step` (ema_rate_dev: read from
-        device memory instead, the captured step) in the same pass."""
+        device memory instead, the captured step) in the same pass.
+        The one place that chooses the optimiser: any other `optimizer`, or adam with its own betas / epsilon, is the same
+        sequence with ONE ds_opt_step in place of the Adam launch (lr_t: _begin_step's step scalar; store.m / store.v are
+        slot0 / slot1)."""
         st = self.store
         rate = 0.0 if self.ema_decay is None else float(ema_rate(self.ema_decay, max(self.step, 1)))
+        if not self._reference_adam:
+            kw = {}
+            if self.clip_active:
+                seg, chunks = st.clip_tables()
+                partials, sumsq, factors, flags = self.clip_state
+                ops.grad_norms(st.theta, st.grad, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale, seg, chunks,
+                               self.clip_mode, self.clip_norm, self.skip_nonfinite_steps, partials, sumsq, factors, flags)
+                kw.update(segments=seg, chunks=chunks, factors=factors, flags=flags)
+            if self.ema_decay is not None:
+                kw.update(shadow=st.ema, ema_rate=rate, ema_rate_dev=ema_rate_dev)
+            o = self.opt
+            ops.opt_step(ops.OPT_KINDS[self.optimizer], st.theta, st.grad, st.m, st.v, st.n_trainable_padded, st.n_l2,
+                         WEIGHT_DECAY, grad_scale, lr_t, b1=o.get("adam_beta1", 0.0), b2=o.get("adam_beta2", 0.0),
+                         eps=o.get("opt_epsilon", 0.0), momentum=o.get("momentum", 0.0), rho=o.get("rmsprop_decay", 0.0),
+                         lr_dev=lr_t_dev, **kw)
+            return
         if not self.clip_active:
             if self.ema_decay is not None:
                 ops.adam_tf_ema(st.theta, st.grad, st.m, st.v, st.ema, st.n_trainable_padded, st.n_l2, WEIGHT_DECAY, grad_scale,
@@ -723,11 +800,15 @@ class SentimentNet:
         return out
 
     def _begin_step(self, lr):
-        """Count the step and return its Adam step size lr_t."""
+        """Count the step and return the optimiser's step scalar (what lr_t_dev carries in a captured step): Adam's
+        bias-corrected lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) with the configured betas, the learning rate for the others."""
         self.step += 1
         if self.image is not None:
             self.image.invalidate_fused()      # beta and the moving statistics move: predict(fused=True) prepares them again
-        return lr * math.sqrt(1.0 - ADAM_B2 ** self.step) / (1.0 - ADAM_B1 ** self.step)
+        if self.optimizer != "adam":
+            return lr
+        b1, b2 = self.opt["adam_beta1"], self.opt["adam_beta2"]
+        return lr * math.sqrt(1.0 - b2 ** self.step) / (1.0 - b1 ** self.step)
 
     def _l2_term(self):
         """sum(w^2) over the trainable weights under the L2 regulariser, before the update.  Only total_loss_value() reads it."""

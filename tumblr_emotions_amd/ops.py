@@ -1064,6 +1064,33 @@ def adam_tf_clipped_ema(theta, g, m, v, shadow, n, n_wd, wd, grad_scale, lr_t, e
                "ds_adam_tf_clipped_ema")
 
 
+OPT_ADAM, OPT_SGD, OPT_MOMENTUM, OPT_RMSPROP = 0, 1, 2, 3
+OPT_KINDS = {"adam": OPT_ADAM, "sgd": OPT_SGD, "momentum": OPT_MOMENTUM, "rmsprop": OPT_RMSPROP}
+
+
+def opt_step(kind, theta, g, slot0, slot1, n, n_wd, wd, grad_scale, lr, b1=0.0, b2=0.0, eps=0.0, momentum=0.0, rho=0.0,
+             lr_dev=None, shadow=None, ema_rate=0.0, ema_rate_dev=None, segments=None, chunks=None, factors=None, flags=None):
+    """One optimiser step of `kind` (OPT_*) over a flat buffer (ds_opt_step): lr is Adam's lr_t for OPT_ADAM and the learning
+    rate otherwise; slot0 / slot1 are Adam's m / v, momentum's accumulator / nothing, RMSProp's mom / ms (sgd reads neither).
+    shadow: the moving-average update of adam_tf_ema in the same pass.  segments, chunks, factors, flags (all four or none):
+    the clipped pass behind grad_norms, skipped as a whole when flags[1] is set."""
+    d = _lib.OptDesc()
+    d.kind, d.lr, d.lr_dev = int(kind), lr, _p(lr_dev)
+    d.b1, d.b2, d.eps, d.momentum, d.rho = b1, b2, eps, momentum, rho
+    if shadow is not None:
+        assert shadow.dtype == torch.float32 and shadow.numel() >= n
+    d.shadow, d.ema_rate, d.ema_rate_dev = _p(shadow), ema_rate, _p(ema_rate_dev)
+    if segments is not None or chunks is not None:
+        nseg, nchunks = segments.shape[0], chunks.shape[0]
+        assert segments.dtype == torch.int64 and chunks.dtype == torch.int64 and segments.shape[1] == 8 and chunks.shape[1] == 4
+        assert factors is None or (factors.dtype == torch.float32 and factors.numel() >= nseg + 1)
+        assert flags is None or (flags.dtype == torch.int32 and flags.numel() >= 4)
+        d.segments, d.chunks, d.nseg, d.nchunks = _p(segments), _p(chunks), nseg, nchunks
+    d.factors, d.flags = _p(factors), _p(flags)
+    _lib.check(_lib.load().ds_opt_step(C.byref(d), _p(theta), _p(g), _p(slot0), _p(slot1), n, n_wd, wd, grad_scale, _stream()),
+               "ds_opt_step")
+
+
 def grad_accumulate(acc, g, n, mode):
     """Clone-gradient accumulation over the first n floats of two flat buffers: mode 0 acc = g, 1 acc = acc + g,
     2 g = acc + g (the running sum is the left operand; n % 4 == 0, 16-byte aligned)."""

@@ -4,7 +4,8 @@ import torch
 
 from ..net import SentimentNet
 from .text_preprocessing import resolve_embedding
-from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, run_training
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, optimizer_net_kwargs, \
+    check_schedule_config, run_training
 
 _RANDOM_SEED = 0
 _CONFIG = {'mode': 'train',
@@ -54,7 +55,9 @@ def train_text_model(train_dir, num_steps, *, config=None, quiet=False):
     """Train rnn text model (text_embedding.py:89-150)."""
     config = dict(_CONFIG, **(config or {}))
     check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
-    model = TextModel(config)
+    check_schedule_config(config)
+    # slim's optimiser keys reach the net from the trainers only: evaluate_* and the analyses run no optimiser
+    model = TextModel(config, **optimizer_net_kwargs(config))
     model.use_clones()
     return run_training(model, train_dir, num_steps, quiet=quiet)
 

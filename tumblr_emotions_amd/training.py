@@ -82,6 +82,97 @@ def ema_net_kwargs(config):
     return {"moving_average_decay": d}
 
 
+_OPT_KEYS = ("opt_epsilon", "momentum", "rmsprop_decay", "adam_beta1", "adam_beta2")
+
+
+def optimizer_net_kwargs(config):
+    """The optimiser keys of a front-end config as SentimentNet arguments; needs no device.  slim's
+    --optimizer block: config['optimizer'] in 'adam' (default, the reference's), 'sgd', 'momentum', 'rmsprop';
+    config['opt_epsilon'], config['momentum'], config['rmsprop_decay'], config['adam_beta1'], config['adam_beta2'].  What
+    net.check_optimizer_config refuses is refused here, and so is ANY of the five keys present for an optimiser that does not
+    read it, default value or not.  train_* pass them to the net; evaluate_*, the analyses and class_visualisation build
+    their net without them (they run no optimiser and load any checkpoint)."""
+    from .net import _OPT_HYPER, check_optimizer_config
+    name = config.get("optimizer", "adam")
+    kw = {k: config[k] for k in _OPT_KEYS if k in config}
+    check_optimizer_config(name, **kw)
+    for k in kw:
+        if name not in _OPT_HYPER[k][1]:
+            raise ValueError("config[%r] is given, but config['optimizer'] = %r does not read it" % (k, name))
+    if "optimizer" in config:
+        kw["optimizer"] = name
+    return kw
+
+
+_SCHEDULE_KEYS = {"learning_rate_decay_factor": ("exponential",), "num_epochs_per_decay": ("exponential", "polynomial"),
+                  "end_learning_rate": ("polynomial",)}
+_SCHEDULE_DEFAULTS = {"learning_rate_decay_factor": 0.94, "num_epochs_per_decay": 2.0, "end_learning_rate": 1e-4}
+
+
+def check_schedule_config(config, num_samples=None):
+    """config['learning_rate_decay_type'] and its keys (slim's train_image_classifier.py:221-258); needs no device.  Returns
+    None when the type is absent -- the reference's per-epoch rule stays -- else (type, decay_steps or None).
+      'fixed'        initial_lr
+      'exponential'  initial_lr * learning_rate_decay_factor (0.94) ** floor(t / decay_steps), slim's staircase
+      'polynomial'   (initial_lr - end_learning_rate (1e-4)) * (1 - min(t, decay_steps) / decay_steps) + end_learning_rate
+    decay_steps = int(num_samples / batch_size * num_epochs_per_decay (2.0)), slim's formula taken literally: batch_size is ONE
+    clone's, so with num_clones or several ranks an "epoch" of the schedule is num_clones * world passes over the data (slim
+    has the same quirk).  ValueError for an unknown type, a schedule key without the type or for a type that does not read
+    it, a value out of range (factor > 0, epochs > 0, end >= 0; finite numbers, a bool is not one) and decay_steps == 0
+    (checked when num_samples is given)."""
+    kind = config.get("learning_rate_decay_type")
+    given = [k for k in _SCHEDULE_KEYS if k in config]
+    if kind is None:
+        if given:
+            raise ValueError("config[%r] needs config['learning_rate_decay_type']: without it the learning rate follows "
+                             "initial_lr * decay_factor ** epoch" % given[0])
+        return None
+    if kind not in ("fixed", "exponential", "polynomial"):
+        raise ValueError("config['learning_rate_decay_type'] must be 'fixed', 'exponential' or 'polynomial', not %r" % (kind,))
+    for k in given:
+        x = config[k]
+        if kind not in _SCHEDULE_KEYS[k]:
+            raise ValueError("config[%r] is given, but config['learning_rate_decay_type'] = %r does not read it" % (k, kind))
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) \
+                or (x < 0 if k == "end_learning_rate" else not x > 0):
+            raise ValueError("config[%r] must be a finite number %s, not %r" % (k, ">= 0" if k == "end_learning_rate" else "> 0", x))
+    if kind == "fixed" or num_samples is None:
+        return kind, None
+    decay_steps = int(num_samples / config["batch_size"] * config.get("num_epochs_per_decay", 2.0))
+    if decay_steps == 0:
+        raise ValueError("config['learning_rate_decay_type'] = %r: decay_steps = int(num_samples / batch_size * "
+                         "num_epochs_per_decay) = int(%d / %d * %r) is 0" % (kind, num_samples, config["batch_size"],
+                                                                              config.get("num_epochs_per_decay", 2.0)))
+    return kind, decay_steps
+
+
+def learning_rate_at(config, num_samples, t, world=1):
+    """The learning rate of the step that follows t completed steps (TF reads global_step before the increment, so a resumed
+    run continues the schedule from the checkpoint's step).  A pure function of its arguments; needs no device.
+    Without config['learning_rate_decay_type']: the reference's rule as run_training has always applied it, a Python float --
+    initial_lr * decay_factor ** (t // nb_batches), nb_batches = max(1, num_samples // (batch_size * num_clones * world)).
+    With it (check_schedule_config): an np.float32 formed the way tf.train.exponential_decay / polynomial_decay form theirs --
+    every hyper-parameter and the step cast to fp32, every operation rounded to fp32 once, in TF's order:
+      exponential  p = floor(t / decay_steps); initial_lr * pow(factor, p)          (the power: correctly rounded)
+      polynomial   p = min(t, decay_steps) / decay_steps; (initial_lr - end) * (1 - p) + end"""
+    sched = check_schedule_config(config, num_samples)
+    if sched is None:
+        nb_batches = max(1, num_samples // (config["batch_size"] * check_clones_config(config) * world))
+        return config["initial_lr"] * config["decay_factor"] ** (t // nb_batches)
+    f32 = np.float32
+    kind, decay_steps = sched
+    lr0 = f32(config["initial_lr"])
+    if kind == "fixed":
+        return lr0
+    gs, ds = f32(t), f32(decay_steps)
+    if kind == "exponential":
+        p = np.floor(f32(gs / ds))
+        return f32(lr0 * f32(float(f32(config.get("learning_rate_decay_factor", 0.94))) ** float(p)))
+    end = f32(config.get("end_learning_rate", 1e-4))
+    p = f32(min(gs, ds) / ds)
+    return f32(f32(f32(lr0 - end) * f32(f32(1.0) - p)) + end)
+
+
 def _log_gradient_norms(net, train_dir, step):
     """One line of <train_dir>/gradients.jsonl: the step, the global norm, the factor(s), the skipped count, the norms."""
     gn = net.grad_norms()
@@ -108,6 +199,8 @@ def _write_checkpoint(model, path, step):
     ck = {"variables": {k: torch.from_numpy(v) for k, v in net.state_dict().items()},
           "adam_m": net.store.m.cpu(), "adam_v": net.store.v.cpu(), "global_step": int(step),
           "config": json.dumps(model.config, default=str)}
+    if not net._reference_adam:      # the optimiser's name and hyper-parameters; a file without the key is the reference's adam
+        ck["optimizer"] = dict(net.opt)      # (the slots stay under adam_m / adam_v: slot0 / slot1 of every kind)
     if net.store.ema is not None:      # moving_average_decay: the averages of the trainable variables, under their TF names
         ck["moving_averages"] = {k: torch.from_numpy(v) for k, v in net.averages_state_dict().items()}
     torch.save(ck, path)
@@ -187,6 +280,10 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
                  dropout_mask=None, quiet=False):
     """model: ImageModel / TextModel / DeepSentiment front end (has .net, .config, .dataset)."""
     rank, world = _rank_world()
+    resume_from = model.config.get("resume_from")
+    if resume_from is not None and os.path.commonpath([os.path.abspath(train_dir), os.path.abspath(resume_from)]) == \
+            os.path.abspath(train_dir):
+        raise ValueError("config['resume_from'] = %r lies inside train_dir, which is deleted and re-created" % (resume_from,))
     if rank == 0:
         if os.path.exists(train_dir):
             shutil.rmtree(train_dir)           # "Delete old model", :116-118
@@ -199,12 +296,29 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
     nb_batches = max(1, model.dataset.num_samples // (batch_size * num_clones * world))
     net = model.net
     validator = Validator(model, train_dir) if rank == 0 and cfg.get("validate_every") is not None else None
-    epoch, lr = 0, initial_lr
+    # config['learning_rate_decay_type']: slim's schedules, a function of the steps completed (learning_rate_at); absent: the
+    # reference's per-epoch rule below, unchanged
+    schedule = check_schedule_config(cfg, model.dataset.num_samples)
+    # config['resume_from'] = a checkpoint file: variables, slots, averages and step are restored and steps
+    # global_step .. num_steps - 1 are run (the reference never resumes; without the key nothing changes)
+    start = 0
+    if cfg.get("resume_from") is not None:      # (train_dir has just been emptied: the file lies outside it)
+        start = int(load_checkpoint(model, cfg["resume_from"], resume=True))
+    epoch = -(-start // nb_batches)      # epochs begun before step `start`
+    lr = initial_lr * decay ** max(epoch - 1, 0)
     last_save = time.time()
     loss_val = float("nan")
     t0 = time.time()
-    for step in range(num_steps):
-        if step % nb_batches == 0:                                   # :143-147
+    for step in range(start, num_steps):
+        if schedule is not None:
+            new = float(learning_rate_at(cfg, model.dataset.num_samples, step))
+            if rank == 0 and not quiet and (step == start or new != lr):
+                print("New learning rate: {0}".format(new))
+            lr = new
+            if rank == 0:      # one line per step: what the schedule handed to the optimiser
+                with open(os.path.join(train_dir, "learning_rate.jsonl"), "a") as f:
+                    f.write(json.dumps({"global_step": step, "learning_rate": lr}) + "\n")
+        elif step % nb_batches == 0:                                 # :143-147
             lr = initial_lr * decay ** epoch
             if rank == 0 and not quiet:
                 print("New learning rate: {0}".format(lr))
@@ -236,12 +350,20 @@ def run_training(model, train_dir, num_steps, batch_fn=None, log_every=10, save_
     return loss_val
 
 
-def load_checkpoint(model, path, averaged=False):
-    """Restore variables, Adam slots and step.  A net with moving averages also gets the file's 'moving_averages' (a file
+def load_checkpoint(model, path, averaged=False, resume=False):
+    """Restore variables, optimiser slots and step.  resume=True (run_training's config['resume_from']): the file's optimiser
+    kind (its 'optimizer' entry; a file without one is adam) must be the net's -- the slots of one kind mean nothing to
+    another (slim fails the same way, on missing slot variables): ValueError naming both.  Every other load reads variables,
+    and averages when asked for them, and accepts any kind.  A net with moving averages also gets the file's 'moving_averages' (a file
     without them leaves the averages at the variables, where load_state_dict puts them).  averaged=True: the averages are
     loaded IN PLACE OF the trainable variables -- slim's variables_to_restore in eval_image_classifier.py:141-146; a net with
     moving averages then starts them there as well -- and a file without them is a KeyError."""
     ck = torch.load(path, map_location="cpu", weights_only=True)       # never unpickles arbitrary objects
+    if resume:
+        theirs = ck.get("optimizer", {"optimizer": "adam"})["optimizer"]
+        if theirs != model.net.optimizer:
+            raise ValueError("%s was written by optimizer %r and cannot resume a run with optimizer %r: the slots of one "
+                             "mean nothing to the other" % (path, theirs, model.net.optimizer))
     variables = {k: v.numpy() for k, v in ck["variables"].items()}
     averages = ck.get("moving_averages")
     if averaged:
@@ -340,7 +462,12 @@ class SyntheticInput:
     config['clip_gradient_norm'], config['clip_global_norm'], config['skip_nonfinite_steps'], config['log_gradient_norms']:
     gradient clipping, the non-finite step guard and gradients.jsonl (clip_net_kwargs).
     config['moving_average_decay'] = d: moving averages of the trained variables in train_*, restored in place of the
-    variables by evaluate_* and the analyses (ema_net_kwargs)."""
+    variables by evaluate_* and the analyses (ema_net_kwargs).
+    config['optimizer'] ('adam', 'sgd', 'momentum', 'rmsprop') with config['opt_epsilon'], ['momentum'], ['rmsprop_decay'],
+    ['adam_beta1'], ['adam_beta2'] (optimizer_net_kwargs) and config['learning_rate_decay_type'] ('fixed', 'exponential',
+    'polynomial') with ['learning_rate_decay_factor'], ['num_epochs_per_decay'], ['end_learning_rate'] (check_schedule_config):
+    slim's optimiser and learning-rate flags, read by train_* only; config['resume_from'] = a checkpoint file to continue
+    from (run_training)."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
