@@ -1719,6 +1719,10 @@ def test_text_tower_persistent_and_stepwise_paths_agree():
 
 
 def test_batch_norm_forward_backward_with_segments():
+    """One layer's BatchNorm + ReLU, forward and backward, chained against the oracle at model-level tolerances.  The forward
+    kernels on their own -- ds_bn_finalize at P up to 2048 with every pivot form, ds_bn_apply_relu through its multi-pass row
+    walk and every segment layout -- are anchored to fp64 with derived gates in tests/test_bn_fwd_gpu.py (reference:
+    tests/bn_fwd_ref.py); the backward kernels in tests/test_bn_bwd_gpu.py."""
     ops = _ops()
     rng = np.random.RandomState(7)
     M, Cc = 1000, 176                                       # fused 1x1 of Mixed_3b: 64 | 96 | 16
@@ -1727,7 +1731,8 @@ def test_batch_norm_forward_backward_with_segments():
     y_ref, mean, var, xhat, rstd = S.batch_norm_train(z, beta)
     y_ref = S.relu(y_ref)
     zd, bd = dev(z), dev(beta)
-    # forward statistics through the conv epilogue path is covered elsewhere; here feed exact partials
+    # the statistics of the conv epilogue are checked by the 50-sigma test below and tests/test_conv_layers_gpu.py, the
+    # finalize itself by tests/test_bn_fwd_gpu.py; here feed exact partials
     stats = torch.stack([zd.sum(0), (zd * zd).sum(0)]).reshape(2, Cc, 1).contiguous()
     mean_d, rstd_d, shift_d = (torch.empty(Cc, device="cuda") for _ in range(3))
     mm, mv = torch.zeros(Cc, device="cuda"), torch.ones(Cc, device="cuda")
@@ -1772,7 +1777,9 @@ def test_batch_norm_statistics_of_channels_with_mean_50_sigma(geometry):
     produce): mean / variance / rstd from the conv epilogue + ds_bn_finalize against the fp64 oracle, with the
     pivot the engine would pass (the previous step's batch mean: here the true mean off by 0.5 std), and the
     normalised activations and BN backward on top of those statistics.  The last geometry runs the persistent
-    launch path (one workgroup sums several row tiles)."""
+    launch path (one workgroup sums several row tiles).  This is the chain from the conv epilogue at whatever P
+    its plans return; ds_bn_finalize on its own (P up to 2048, 50-sigma / constant / clamped channels, every pivot
+    form, one-ulp gates) is anchored to fp64 in tests/test_bn_fwd_gpu.py."""
     ops = _ops()
     N, H, W, Ci, Co, k = geometry
     rng = np.random.RandomState(12)
