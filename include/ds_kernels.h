@@ -767,6 +767,22 @@ int ds_debug_lstm_seq_set_profile_bwd(void *buf);      /* the same for the ds_ls
  * loss / dlogits may each be NULL. */
 int ds_softmax_ce(const float *logits, const int64_t *labels, int32_t B, int32_t C, float grad_scale,
                   const float *grad_scale_dev, float *loss, float *dlogits, void *stream);
+/* The two other arguments of slim.losses.softmax_cross_entropy(logits, onehot, weights, label_smoothing), which the reference
+ * leaves at their defaults and slim's train_image_classifier.py sets (--label_smoothing, :138-139, :461-466) [TF-sem]:
+ *   q_bc = onehot(y_b)_c (1 - label_smoothing) + label_smoothing / C   (TF's form; a label outside [0, C): all label_smoothing / C)
+ *   l_b  = sum_c q_bc (lse_b - z_bc);   w_b = class_weights[y_b]  (1 when class_weights is NULL or y_b is outside [0, C):
+ *          the lookup never leaves the C floats);   P = #{b : w_b != 0}   (compute_weighted_loss, SUM_BY_NONZERO_WEIGHTS)
+ *   loss[0] = sum_b w_b l_b / P   (0 when P == 0; NaN when a label is outside [0, C), as ds_softmax_ce);
+ *   dlogits = (softmax - q) w_b grad_scale / P   (all 0 when P == 0; exactly 0 in a row of weight 0).
+ * class_weights: a DEVICE pointer to C floats (>= 0), or NULL.  The kernels read it and nothing else of the descriptor from
+ * memory, so a captured launch keeps no host pointer.  One workgroup, a first pass over the labels counts P, no atomics.
+ * ce == NULL or {0, NULL}: the bits of ds_softmax_ce (its own kernel is launched). */
+typedef struct ds_ce_desc {
+    float label_smoothing;
+    const float *class_weights;
+} ds_ce_desc;
+int ds_softmax_ce_opts(const ds_ce_desc *ce, const float *logits, const int64_t *labels, int32_t B, int32_t C, float grad_scale,
+                       const float *grad_scale_dev, float *loss, float *dlogits, void *stream);
 
 /* tf.train.AdamOptimizer.apply_gradients over one flat parameter buffer
  * (im_text_rnn_model.py:134-135).  g_eff = g*grad_scale + (i < n_wd ? wd*theta : 0): the first
@@ -936,6 +952,11 @@ int ds_slab_epilogue_group(const ds_slab_combine *ops, int32_t count, void *stre
 int ds_slab_epilogue_ce(const float *slabs, int32_t splits, int64_t slab_stride, int32_t lds, int32_t M, int32_t N,
                         float *logits, const float *bias, const int64_t *labels, float grad_scale,
                         const float *grad_scale_dev, float *loss, float *dlogits, void *stream);
+/* The same with the cross entropy's options: the bits of ds_slab_epilogue(flags = DS_EPI_BIAS) followed by
+ * ds_softmax_ce_opts(ce, logits, ...); the same limits (M <= 512, N <= 32); ce == NULL or {0, NULL}: ds_slab_epilogue_ce's bits. */
+int ds_slab_epilogue_ce_opts(const ds_ce_desc *ce, const float *slabs, int32_t splits, int64_t slab_stride, int32_t lds,
+                             int32_t M, int32_t N, float *logits, const float *bias, const int64_t *labels, float grad_scale,
+                             const float *grad_scale_dev, float *loss, float *dlogits, void *stream);
 int ds_copy2d(const float *src, int32_t lds, float *dst, int32_t ldd, int64_t rows, int32_t cols,
               void *stream);
 int ds_pad_channels(const float *src, int32_t cs, float *dst, int32_t cd, int64_t pixels, void *stream);

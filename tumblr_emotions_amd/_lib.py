@@ -167,6 +167,11 @@ class OptDesc(C.Structure):
                 ("nseg", C.c_int32), ("nchunks", C.c_int32), ("factors", C.c_void_p), ("flags", C.c_void_p)]
 
 
+class CeDesc(C.Structure):
+    """ds_ce_desc"""
+    _fields_ = [("label_smoothing", C.c_float), ("class_weights", C.c_void_p)]
+
+
 _P = C.c_void_p
 _i32, _i64, _f32, _u64 = C.c_int32, C.c_int64, C.c_float, C.c_uint64
 _CD = C.POINTER(ConvDesc)
@@ -283,6 +288,7 @@ SIGNATURES = {
     "ds_lstm_seq_bwd": (C.c_int, [_P, _P, _i32, _P, _P, _i32, _P, _i32, _i32, _i32, _P, _i32, _P, C.c_size_t, _P]),
     "ds_lstm_seq_status": (C.c_int, [_P, _i32]),
     "ds_softmax_ce": (C.c_int, [_P, _P, _i32, _i32, _f32, _P, _P, _P, _P]),
+    "ds_softmax_ce_opts": (C.c_int, [C.POINTER(CeDesc), _P, _P, _i32, _i32, _f32, _P, _P, _P, _P]),
     "ds_adam_tf": (C.c_int, [_P, _P, _P, _P, _i64, _i64, _f32, _f32, _f32, _P, _f32, _f32, _f32, _P]),
     "ds_grad_norms": (C.c_int, [_P, _P, _i64, _i64, _f32, _f32, _P, _i32, _P, _i32, _i32, C.c_double, _i32, _P, _P, _P, _P, _P]),
     "ds_adam_tf_clipped": (C.c_int, [_P, _P, _P, _P, _i64, _i64, _f32, _f32, _f32, _P, _f32, _f32, _f32, _P, _i32, _P, _i32, _P,
@@ -298,6 +304,8 @@ SIGNATURES = {
     "ds_gemm_group": (C.c_int, [C.POINTER(_CD), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _i32, _P]),
     "ds_slab_epilogue_group": (C.c_int, [C.POINTER(SlabCombine), _i32, _P]),
     "ds_slab_epilogue_ce": (C.c_int, [_P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _f32, _P, _P, _P, _P]),
+    "ds_slab_epilogue_ce_opts": (C.c_int, [C.POINTER(CeDesc), _P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _f32, _P, _P, _P,
+                                           _P]),
     "ds_copy2d": (C.c_int, [_P, _i32, _P, _i32, _i64, _i32, _P]),
     "ds_pad_channels": (C.c_int, [_P, _i32, _P, _i32, _i64, _P]),
     "ds_fill": (C.c_int, [_P, _i64, _f32, _P]),

@@ -218,10 +218,39 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float *acts, c
 // ---- softmax cross entropy (+ gradient), one workgroup, fixed summation order -----------------------
 // (the whole workgroup's work: softmax_ce_kernel, and slab_epilogue_ce_kernel behind its combine -- there thread t reads back
 // the rows t, t + 256 of `logits` that it has just stored itself)
+// OPTS = false is slim.losses.softmax_cross_entropy at its defaults, the text the two entry points have always run.
+// OPTS = true adds its two other arguments (ds_ce_desc): label_smoothing eps -- q = onehot (1 - eps) + eps / C, TF's own
+// form -- and per-class weights w_b = cw[y_b] under compute_weighted_loss's SUM_BY_NONZERO_WEIGHTS: loss = sum_b w_b l_b / P,
+// l_b = sum_c q_bc (lse_b - z_bc), dlogits = (softmax - q) w_b grad_scale / P, P = #{b: w_b != 0} counted by a first pass over
+// the labels (integers: exact in any order; reduced in the fixed order of the loss all the same).  P == 0: loss and dlogits
+// are 0.  With eps = 0 and w = 1 every product below is by 1 or 0 and P = B: the bits of OPTS = false (finite logits).
+template <bool OPTS>
 __device__ __forceinline__ void softmax_ce_workgroup(const float *logits, const int64_t *labels, int B, int C,
                                                      float grad_scale, const float *grad_scale_dev,
-                                                     float *loss, float *dlogits, float *red) {
+                                                     float *loss, float *dlogits, float *red, float eps = 0.f,
+                                                     const float *cw = nullptr) {
     if (grad_scale_dev) grad_scale *= grad_scale_dev[0];   // upstream d(loss) handed over on device
+    float denom = (float)B, sp = 1.f, sn = 0.f;
+    if constexpr (OPTS) {
+        int *cnt = reinterpret_cast<int *>(red);
+        int n = 0;
+        for (int b = threadIdx.x; b < B; b += 256) {
+            const int64_t yl = labels[b];
+            // (the lookup is guarded exactly as the row pass guards it: a label outside [0, C) weighs 1)
+            const float w = (cw && yl >= 0 && yl < C) ? cw[yl] : 1.f;
+            n += w != 0.f ? 1 : 0;
+        }
+        cnt[threadIdx.x] = n;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) cnt[threadIdx.x] += cnt[threadIdx.x + o];
+            __syncthreads();
+        }
+        denom = (float)cnt[0];
+        __syncthreads();                                   // `red` is the loss reduction's next
+        sp = 1.f - eps;
+        sn = eps / (float)C;
+    }
     float acc = 0.f;
     for (int b = threadIdx.x; b < B; b += 256) {
         const float *z = logits + (int64_t)b * C;
@@ -234,11 +263,27 @@ __device__ __forceinline__ void softmax_ce_workgroup(const float *logits, const 
         const int64_t yl = labels[b];
         const bool yok = yl >= 0 && yl < C;
         const int y = yok ? (int)yl : -1;
-        acc += yok ? (m + logf(s)) - z[y] : NAN;
-        if (dlogits) {
-            const float k = grad_scale / (float)B, inv = 1.f / s;
-            for (int c = 0; c < C; ++c)
-                dlogits[(int64_t)b * C + c] = (expf(z[c] - m) * inv - (c == y ? 1.f : 0.f)) * k;
+        if constexpr (OPTS) {
+            const float w = (cw && yok) ? cw[y] : 1.f;
+            if (w != 0.f) {                                // (a zero weight drops the row, whatever its logits)
+                const float lse = m + logf(s);
+                float l = 0.f;
+                for (int c = 0; c < C; ++c) l += ((c == y ? sp : 0.f) + sn) * (lse - z[c]);
+                acc += yok ? w * l : NAN;
+            }
+            if (dlogits) {
+                const float wk = denom > 0.f ? w * (grad_scale / denom) : 0.f, inv = 1.f / s;
+                for (int c = 0; c < C; ++c)
+                    dlogits[(int64_t)b * C + c] =
+                        wk == 0.f ? 0.f : (expf(z[c] - m) * inv - ((c == y ? sp : 0.f) + sn)) * wk;
+            }
+        } else {
+            acc += yok ? (m + logf(s)) - z[y] : NAN;
+            if (dlogits) {
+                const float k = grad_scale / (float)B, inv = 1.f / s;
+                for (int c = 0; c < C; ++c)
+                    dlogits[(int64_t)b * C + c] = (expf(z[c] - m) * inv - (c == y ? 1.f : 0.f)) * k;
+            }
         }
     }
     red[threadIdx.x] = acc;
@@ -247,14 +292,19 @@ __device__ __forceinline__ void softmax_ce_workgroup(const float *logits, const 
         if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0 && loss) loss[0] = red[0] / (float)B;
+    if constexpr (OPTS) {
+        if (threadIdx.x == 0 && loss) loss[0] = denom > 0.f ? red[0] / denom : 0.f;
+    } else {
+        if (threadIdx.x == 0 && loss) loss[0] = red[0] / (float)B;
+    }
 }
 
+template <bool OPTS>
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const float *logits, const int64_t *labels, int B, int C,
                                                          float grad_scale, const float *grad_scale_dev,
-                                                         float *loss, float *dlogits) {
+                                                         float *loss, float *dlogits, float eps, const float *cw) {
     __shared__ float red[256];
-    softmax_ce_workgroup(logits, labels, B, C, grad_scale, grad_scale_dev, loss, dlogits, red);
+    softmax_ce_workgroup<OPTS>(logits, labels, B, C, grad_scale, grad_scale_dev, loss, dlogits, red, eps, cw);
 }
 
 // ---- TF Adam over a flat buffer ------------------------------------------------------------------
@@ -764,12 +814,29 @@ extern "C" int ds_lstm_cell_bwd(const float *acts, const float *c_t, const float
     return ds::check_launch("ds_lstm_cell_bwd");
 }
 
+// Is the descriptor the keys-absent case (the existing entry points' arithmetic, run as their own instantiation)?
+static bool ce_desc_is_default(const ds_ce_desc *ce) { return !ce || (ce->label_smoothing == 0.f && !ce->class_weights); }
+static bool ce_desc_ok(const ds_ce_desc *ce) { return !ce || (ce->label_smoothing >= 0.f && ce->label_smoothing < 1.f); }
+
 extern "C" int ds_softmax_ce(const float *logits, const int64_t *labels, int32_t B, int32_t C, float grad_scale,
                              const float *grad_scale_dev, float *loss, float *dlogits, void *stream) {
     DS_REQUIRE(logits && labels && B > 0 && C > 0, "ds_softmax_ce: bad argument");
-    hipLaunchKernelGGL(softmax_ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, B, C, grad_scale,
-                       grad_scale_dev, loss, dlogits);
+    hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, B, C, grad_scale,
+                       grad_scale_dev, loss, dlogits, 0.f, (const float *)nullptr);
     return ds::check_launch("ds_softmax_ce");
+}
+
+extern "C" int ds_softmax_ce_opts(const ds_ce_desc *ce, const float *logits, const int64_t *labels, int32_t B, int32_t C,
+                                  float grad_scale, const float *grad_scale_dev, float *loss, float *dlogits, void *stream) {
+    DS_REQUIRE(logits && labels && B > 0 && C > 0, "ds_softmax_ce_opts: bad argument");
+    DS_REQUIRE(ce_desc_ok(ce), "ds_softmax_ce_opts: label_smoothing is a number in [0, 1)");
+    if (ce_desc_is_default(ce))
+        hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, B, C,
+                           grad_scale, grad_scale_dev, loss, dlogits, 0.f, (const float *)nullptr);
+    else
+        hipLaunchKernelGGL(softmax_ce_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, B, C,
+                           grad_scale, grad_scale_dev, loss, dlogits, ce->label_smoothing, ce->class_weights);
+    return ds::check_launch("ds_softmax_ce_opts");
 }
 
 extern "C" int ds_adam_tf(float *theta, const float *g, float *m, float *v, int64_t n, int64_t n_wd, float wd,
@@ -1095,10 +1162,12 @@ extern "C" int ds_slab_epilogue_group(const ds_slab_combine *ops, int32_t count,
 // The combine of the W_softmax GEMM's slabs (bias added: the logits) going straight on to the cross entropy and its gradient:
 // one workgroup, as ds_softmax_ce is -- thread t combines rows t and t + 256, stores them, and runs ds_softmax_ce's own
 // arithmetic on them (softmax_ce_workgroup), so logits, loss and dlogits are the bits of ds_slab_epilogue + ds_softmax_ce.
+template <bool OPTS>
 __global__ __launch_bounds__(256) void slab_epilogue_ce_kernel(const float *slabs, int splits, int64_t slab_stride, int lds,
                                                                int M, int N, float *logits, const float *bias,
                                                                const int64_t *labels, float grad_scale,
-                                                               const float *grad_scale_dev, float *loss, float *dlogits) {
+                                                               const float *grad_scale_dev, float *loss, float *dlogits,
+                                                               float eps, const float *cw) {
     __shared__ float red[256];
     for (int m = threadIdx.x; m < M; m += 256) {
         for (int n = 0; n < N; ++n) {
@@ -1108,7 +1177,7 @@ __global__ __launch_bounds__(256) void slab_epilogue_ce_kernel(const float *slab
             logits[(int64_t)m * N + n] = v;
         }
     }
-    softmax_ce_workgroup(logits, labels, M, N, grad_scale, grad_scale_dev, loss, dlogits, red);
+    softmax_ce_workgroup<OPTS>(logits, labels, M, N, grad_scale, grad_scale_dev, loss, dlogits, red, eps, cw);
 }
 
 extern "C" int ds_slab_epilogue_ce(const float *slabs, int32_t splits, int64_t slab_stride, int32_t lds, int32_t M, int32_t N,
@@ -1116,9 +1185,28 @@ extern "C" int ds_slab_epilogue_ce(const float *slabs, int32_t splits, int64_t s
                                    const float *grad_scale_dev, float *loss, float *dlogits, void *stream) {
     DS_REQUIRE(slabs && logits && labels && splits >= 1 && lds >= N, "ds_slab_epilogue_ce: bad argument");
     DS_REQUIRE(M > 0 && M <= 512 && N > 0 && N <= 32, "ds_slab_epilogue_ce: M <= 512 rows of N <= 32 logits (packed, row stride N)");
-    hipLaunchKernelGGL(slab_epilogue_ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, slabs, splits, slab_stride, lds, M, N,
-                       logits, bias, labels, grad_scale, grad_scale_dev, loss, dlogits);
+    hipLaunchKernelGGL(slab_epilogue_ce_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, slabs, splits, slab_stride, lds,
+                       M, N, logits, bias, labels, grad_scale, grad_scale_dev, loss, dlogits, 0.f, (const float *)nullptr);
     return ds::check_launch("ds_slab_epilogue_ce");
+}
+
+extern "C" int ds_slab_epilogue_ce_opts(const ds_ce_desc *ce, const float *slabs, int32_t splits, int64_t slab_stride,
+                                        int32_t lds, int32_t M, int32_t N, float *logits, const float *bias,
+                                        const int64_t *labels, float grad_scale, const float *grad_scale_dev, float *loss,
+                                        float *dlogits, void *stream) {
+    DS_REQUIRE(slabs && logits && labels && splits >= 1 && lds >= N, "ds_slab_epilogue_ce_opts: bad argument");
+    DS_REQUIRE(M > 0 && M <= 512 && N > 0 && N <= 32,
+               "ds_slab_epilogue_ce_opts: M <= 512 rows of N <= 32 logits (packed, row stride N)");
+    DS_REQUIRE(ce_desc_ok(ce), "ds_slab_epilogue_ce_opts: label_smoothing is a number in [0, 1)");
+    if (ce_desc_is_default(ce))
+        hipLaunchKernelGGL(slab_epilogue_ce_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, slabs, splits, slab_stride,
+                           lds, M, N, logits, bias, labels, grad_scale, grad_scale_dev, loss, dlogits, 0.f,
+                           (const float *)nullptr);
+    else
+        hipLaunchKernelGGL(slab_epilogue_ce_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, slabs, splits, slab_stride,
+                           lds, M, N, logits, bias, labels, grad_scale, grad_scale_dev, loss, dlogits, ce->label_smoothing,
+                           ce->class_weights);
+    return ds::check_launch("ds_slab_epilogue_ce_opts");
 }
 
 extern "C" int ds_copy2d(const float *src, int32_t lds, float *dst, int32_t ldd, int64_t rows, int32_t cols,

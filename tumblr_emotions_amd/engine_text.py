@@ -298,8 +298,9 @@ class JointHeadEngine:
         return bool(self.group) and self.fwd_group is not None
 
     def forward(self, im_feat, tx_feat, ce=None):
-        """ce: (labels, loss, dlogits) -- the cross entropy of the logits and its gradient (softmax_ce with grad_scale 1) from
-        the W_softmax combine's own launch (SentimentNet._step_body; the grouped chain only: see ce_fused)."""
+        """ce: (labels, loss, dlogits[, ce_desc]) -- the cross entropy of the logits and its gradient (softmax_ce with grad_scale
+        1; with an ops.ce_desc: softmax_ce_opts) from the W_softmax combine's own launch (SentimentNet._step_body; the grouped
+        chain only: see ce_fused)."""
         B = im_feat.shape[0]
         self.alloc(B)
         lds = (im_feat.stride(0), tx_feat.stride(0))

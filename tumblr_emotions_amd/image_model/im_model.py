@@ -5,7 +5,7 @@ import numpy as np
 
 from ..net import SentimentNet
 from ..feature_cache import check_feature_cache_config
-from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, optimizer_net_kwargs, \
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, loss_net_kwargs, optimizer_net_kwargs, \
     check_schedule_config, run_training
 
 _RANDOM_SEED = 0
@@ -80,8 +80,8 @@ def train_image_model(checkpoints_dir, train_dir, num_steps, *, config=None, qui
     check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
     check_feature_cache_config(config)
     check_schedule_config(config)
-    # slim's optimiser keys reach the net from the trainers only: evaluate_* and the analyses run no optimiser
-    model = ImageModel(config, **optimizer_net_kwargs(config))
+    # slim's optimiser and loss keys reach the net from the trainers only: evaluate_* and the analyses run no optimiser and no loss
+    model = ImageModel(config, **optimizer_net_kwargs(config), **loss_net_kwargs(config))
     model.use_clones()
     model.use_augmentation()
     model.use_feature_cache()        # config['feature_cache']: built at the first batch, behind the warm start

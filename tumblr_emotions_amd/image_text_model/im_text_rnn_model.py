@@ -8,7 +8,7 @@ from ..image_model.im_model import get_init_fn
 from ..net import SentimentNet
 from ..text_model.text_preprocessing import resolve_embedding
 from ..feature_cache import check_feature_cache_config
-from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, optimizer_net_kwargs, \
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, loss_net_kwargs, optimizer_net_kwargs, \
     check_schedule_config, run_training
 
 _POST_SIZE = 50
@@ -75,8 +75,8 @@ def train_deep_sentiment(checkpoints_dir, train_dir, num_steps, *, config=None, 
     check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
     check_feature_cache_config(config)
     check_schedule_config(config)
-    # slim's optimiser keys reach the net from the trainers only: evaluate_* and the analyses run no optimiser
-    model = DeepSentiment(config, **optimizer_net_kwargs(config))
+    # slim's optimiser and loss keys reach the net from the trainers only: evaluate_* and the analyses run no optimiser and no loss
+    model = DeepSentiment(config, **optimizer_net_kwargs(config), **loss_net_kwargs(config))
     model.use_clones()
     model.use_augmentation()
     model.use_feature_cache()        # config['feature_cache']: built at the first batch, behind the warm start

@@ -51,6 +51,37 @@ def check_ema_config(decay=None):
     return float(decay)
 
 
+def check_loss_config(label_smoothing=None, class_weights=None, nb_emotions=15):
+    """(label_smoothing as a float, class_weights as a tuple of floats or None) of the two other arguments of
+    slim.losses.softmax_cross_entropy(logits, onehot, weights, label_smoothing); needs no device.  label_smoothing (slim's
+    --label_smoothing, train_image_classifier.py:138-139): a finite float with 0 <= label_smoothing < 1 (None: 0).
+    class_weights: a sequence of exactly nb_emotions (None: any number of) finite numbers >= 0, not all zero -- the loss
+    weight of a row is its label's.  ValueError for anything else (a bool is not a number).  (0.0, None) is the keys-absent case."""
+    eps = 0.0
+    if label_smoothing is not None:
+        x = label_smoothing
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) \
+                or not math.isfinite(x) or not 0.0 <= x < 1.0:
+            raise ValueError("label_smoothing must be a finite float with 0 <= label_smoothing < 1, not %r" % (x,))
+        eps = float(x)
+    cw = None
+    if class_weights is not None:
+        if isinstance(class_weights, (str, bytes, dict)) or not hasattr(class_weights, "__len__") \
+                or not hasattr(class_weights, "__iter__"):
+            raise ValueError("class_weights must be a sequence of nb_emotions numbers, not %r" % (class_weights,))
+        ws = list(class_weights)
+        if nb_emotions is not None and len(ws) != nb_emotions:
+            raise ValueError("class_weights must have exactly nb_emotions = %d entries, not %d" % (nb_emotions, len(ws)))
+        for w in ws:
+            if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, float, np.integer, np.floating)) \
+                    or not math.isfinite(w) or w < 0:
+                raise ValueError("class_weights must be finite numbers >= 0, not %r" % (w,))
+        if not any(w > 0 for w in ws):
+            raise ValueError("class_weights are all zero: no row would count")
+        cw = tuple(float(w) for w in ws)
+    return eps, cw
+
+
 OPTIMIZERS = ("adam", "sgd", "momentum", "rmsprop")
 _SLIM_OPTIMIZERS_NOT_BUILT = ("adadelta", "adagrad", "ftrl")
 # hyper-parameter -> (default, the optimisers that read it); opt_epsilon's default depends on the optimiser (None)
@@ -117,9 +148,12 @@ class SentimentNet:
                  concurrent_towers=True, train_all=False, trainable_embedding=False, dtype="f32",
                  force_dp_buckets=False, sync_bn=False, frozen_bn=False, clip_gradient_norm=None, clip_global_norm=None,
                  skip_nonfinite_steps=False, moving_average_decay=None, optimizer="adam", opt_epsilon=None, momentum=0.9,
-                 rmsprop_decay=0.9, adam_beta1=ADAM_B1, adam_beta2=ADAM_B2):
+                 rmsprop_decay=0.9, adam_beta1=ADAM_B1, adam_beta2=ADAM_B2, label_smoothing=None, class_weights=None):
         assert mode in ("joint", "image", "text")
         self.dtype = dtype
+        # the cross entropy's options (opt-in); refused before anything touches the device.  The logits and
+        # dlogits are fp32 in every dtype configuration, so none is refused
+        self.label_smoothing, self.class_weights = check_loss_config(label_smoothing, class_weights, nb_emotions)
         # the optimiser (slim's --optimizer); refused before anything touches the device.  opt_epsilon=None:
         # 1e-8 for adam, 1.0 for rmsprop.  Every dtype keeps fp32 variables and steps through the one _optimise below.
         self.opt = check_optimizer_config(optimizer, opt_epsilon, momentum, rmsprop_decay, adam_beta1, adam_beta2)
@@ -174,6 +208,13 @@ class SentimentNet:
         if self.ema_decay is not None:
             st.enable_ema()
             self.ema_rate_dev = torch.zeros(1, device=self.device)
+        # label_smoothing = 0 and no weights: nothing is allocated and the step makes the ds_softmax_ce / ds_slab_epilogue_ce
+        # launches it has always made; otherwise the weights live on the device (uploaded once) under one descriptor
+        self.class_weights_dev = self.ce_desc = None
+        if self.label_smoothing != 0.0 or self.class_weights is not None:
+            if self.class_weights is not None:
+                self.class_weights_dev = torch.tensor(self.class_weights, dtype=torch.float32, device=self.device)
+            self.ce_desc = ops.ce_desc(self.label_smoothing, self.class_weights_dev)
         self.step = 0
         self.frozen_l2_sumsq = 0.0
         self.loss_buf = torch.zeros(1, device=self.device)
@@ -837,10 +878,16 @@ class SentimentNet:
                 # the head is asked about the plans of THIS batch size (none yet: forward builds them, one ds_softmax_ce below)
                 self.head.alloc(B)
                 ce_done = self.head.grouped() and self.head.ce_fused()
-                logits = self.head.forward(im, tx, ce=(labels, loss_out, self.dlogits) if ce_done else None)
+                ce = None
+                if ce_done:      # (with label_smoothing / class_weights: the descriptor rides along)
+                    ce = (labels, loss_out, self.dlogits) + (() if self.ce_desc is None else (self.ce_desc,))
+                logits = self.head.forward(im, tx, ce=ce)
             self.logits = logits
             if not ce_done:
-                ops.softmax_ce(logits, labels, B, C_, 1.0, None, loss_out, self.dlogits)
+                if self.ce_desc is None:
+                    ops.softmax_ce(logits, labels, B, C_, 1.0, None, loss_out, self.dlogits)
+                else:      # label_smoothing / class_weights: the same launch with the descriptor (read at enqueue time)
+                    ops.softmax_ce_opts(self.ce_desc, logits, labels, B, C_, 1.0, None, loss_out, self.dlogits)
             # The L2 term, on the pre-update weights: with the grouped head chain the engine whose backward() runs first runs it
             # behind its parameter gradients on the weight-gradient stream (joined before the optimiser); otherwise here
             job = self._l2_term if (l2 and self.store.n_l2 > 0) else None

@@ -244,9 +244,19 @@ class GemmGroup:
             t.end(self)
 
 
-def split_gemm_ce(gemm, x, w, logits, bias, labels, loss, dlogits):
+def ce_desc(label_smoothing=0.0, class_weights=None):
+    """ds_ce_desc: label_smoothing and the per-class weights (a float32 device tensor of C entries, or None).  The caller
+    keeps the tensor alive for as long as the descriptor is used."""
+    d = _lib.CeDesc()
+    d.label_smoothing = float(label_smoothing)
+    d.class_weights = None if class_weights is None else _p(class_weights).value
+    return d
+
+
+def split_gemm_ce(gemm, x, w, logits, bias, labels, loss, dlogits, ce=None):
     """SplitGemm.run of the W_softmax GEMM with DS_EPI_BIAS and softmax_ce(logits, labels, .., 1.0, None, loss, dlogits) behind
-    it, the combine and the cross entropy as ONE single-workgroup launch (ds_slab_epilogue_ce): the same bits."""
+    it, the combine and the cross entropy as ONE single-workgroup launch (ds_slab_epilogue_ce): the same bits.  ce: a ce_desc --
+    softmax_ce_opts behind the combine instead (ds_slab_epilogue_ce_opts)."""
     t = CONV_TIMER
     if t is not None:
         t.begin()
@@ -254,6 +264,11 @@ def split_gemm_ce(gemm, x, w, logits, bias, labels, loss, dlogits):
     _lib.check(lib.ds_conv_igemm(C.byref(gemm.plan.d), x, w, _p(gemm.slabs), None, None, None, None, _stream()), "ds_conv_igemm")
     if t is not None:
         t.end(gemm)
+    if ce is not None:
+        _lib.check(lib.ds_slab_epilogue_ce_opts(C.byref(ce), _p(gemm.slabs), gemm.splits, gemm.M * gemm.N, gemm.N, gemm.M, gemm.N,
+                                                _p(logits), bias, _p(labels), 1.0, None, _p(loss), _p(dlogits), _stream()),
+                   "ds_slab_epilogue_ce_opts")
+        return
     _lib.check(lib.ds_slab_epilogue_ce(_p(gemm.slabs), gemm.splits, gemm.M * gemm.N, gemm.N, gemm.M, gemm.N, _p(logits), bias,
                                        _p(labels), 1.0, None, _p(loss), _p(dlogits), _stream()), "ds_slab_epilogue_ce")
 
@@ -1006,6 +1021,12 @@ def lstm_seq_status(ws, B):
 def softmax_ce(logits, labels, B, C_, grad_scale, grad_scale_dev, loss, dlogits):
     _lib.check(_lib.load().ds_softmax_ce(_p(logits), _p(labels), B, C_, grad_scale, _p(grad_scale_dev), _p(loss),
                                          _p(dlogits), _stream()), "ds_softmax_ce")
+
+
+def softmax_ce_opts(ce, logits, labels, B, C_, grad_scale, grad_scale_dev, loss, dlogits):
+    """softmax_ce with label smoothing and per-class weights (ce: a ce_desc; None: softmax_ce's bits)."""
+    _lib.check(_lib.load().ds_softmax_ce_opts(None if ce is None else C.byref(ce), _p(logits), _p(labels), B, C_, grad_scale,
+                                              _p(grad_scale_dev), _p(loss), _p(dlogits), _stream()), "ds_softmax_ce_opts")
 
 
 def adam_tf(theta, g, m, v, n, n_wd, wd, grad_scale, lr_t, b1, b2, eps, lr_t_dev=None):

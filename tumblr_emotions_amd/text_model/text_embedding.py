@@ -4,7 +4,7 @@ import torch
 
 from ..net import SentimentNet
 from .text_preprocessing import resolve_embedding
-from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, optimizer_net_kwargs, \
+from ..training import SyntheticInput, check_clones_config, clip_net_kwargs, ema_net_kwargs, loss_net_kwargs, optimizer_net_kwargs, \
     check_schedule_config, run_training
 
 _RANDOM_SEED = 0
@@ -56,8 +56,8 @@ def train_text_model(train_dir, num_steps, *, config=None, quiet=False):
     config = dict(_CONFIG, **(config or {}))
     check_clones_config(config)      # (before the model is built: a bad num_clones needs no device to be refused)
     check_schedule_config(config)
-    # slim's optimiser keys reach the net from the trainers only: evaluate_* and the analyses run no optimiser
-    model = TextModel(config, **optimizer_net_kwargs(config))
+    # slim's optimiser and loss keys reach the net from the trainers only: evaluate_* and the analyses run no optimiser and no loss
+    model = TextModel(config, **optimizer_net_kwargs(config), **loss_net_kwargs(config))
     model.use_clones()
     return run_training(model, train_dir, num_steps, quiet=quiet)
 

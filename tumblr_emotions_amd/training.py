@@ -82,6 +82,24 @@ def ema_net_kwargs(config):
     return {"moving_average_decay": d}
 
 
+def loss_net_kwargs(config):
+    """config['label_smoothing'] and config['class_weights'] as SentimentNet arguments; needs no device.
+    slim's --label_smoothing and the `weights` of slim.losses.softmax_cross_entropy: label_smoothing = e trains on
+    onehot (1 - e) + e / C; class_weights = [w_0 .. w_{C-1}] weighs a row's loss by its label's weight and divides by the
+    number of rows whose weight is not zero.  What net.check_loss_config refuses is refused here (the number of weights is
+    held against the data set's classes when the net is built).  label_smoothing = 0 (or absent) without weights returns {}:
+    the step is the one without the keys.  train_* pass them to the net; evaluate_*, the analyses, explain_posts and
+    class_visualisation ignore them, and validation during training keeps the plain mean cross entropy."""
+    from .net import check_loss_config
+    eps, cw = check_loss_config(config.get("label_smoothing"), config.get("class_weights"), nb_emotions=None)
+    kw = {}
+    if eps != 0.0:
+        kw["label_smoothing"] = eps
+    if cw is not None:
+        kw["class_weights"] = list(cw)
+    return kw
+
+
 _OPT_KEYS = ("opt_epsilon", "momentum", "rmsprop_decay", "adam_beta1", "adam_beta2")
 
 
@@ -201,6 +219,9 @@ def _write_checkpoint(model, path, step):
           "config": json.dumps(model.config, default=str)}
     if not net._reference_adam:      # the optimiser's name and hyper-parameters; a file without the key is the reference's adam
         ck["optimizer"] = dict(net.opt)      # (the slots stay under adam_m / adam_v: slot0 / slot1 of every kind)
+    if net.ce_desc is not None:      # label_smoothing / class_weights, for the record: the loss has no state to restore
+        ck["loss"] = {"label_smoothing": float(net.label_smoothing),
+                      "class_weights": None if net.class_weights is None else [float(w) for w in net.class_weights]}
     if net.store.ema is not None:      # moving_average_decay: the averages of the trainable variables, under their TF names
         ck["moving_averages"] = {k: torch.from_numpy(v) for k, v in net.averages_state_dict().items()}
     torch.save(ck, path)
@@ -467,7 +488,9 @@ class SyntheticInput:
     ['adam_beta1'], ['adam_beta2'] (optimizer_net_kwargs) and config['learning_rate_decay_type'] ('fixed', 'exponential',
     'polynomial') with ['learning_rate_decay_factor'], ['num_epochs_per_decay'], ['end_learning_rate'] (check_schedule_config):
     slim's optimiser and learning-rate flags, read by train_* only; config['resume_from'] = a checkpoint file to continue
-    from (run_training)."""
+    from (run_training).
+    config['label_smoothing'] = e and config['class_weights'] = [w per emotion]: the other two arguments of
+    slim.losses.softmax_cross_entropy, read by train_* only (loss_net_kwargs)."""
 
     def _init_input(self, config, post_size, vocab_size, nb_emotions, with_images, device):
         from .synthetic import SyntheticDataset
